@@ -21,16 +21,23 @@ LAUNCH CONTRACT.  ``--gpus N`` ALWAYS means N ranks, one per GPU:
 share (256 ant x 4096/8 = 512 beams per GPU x 32768 chan); the name is in ``config.workload``.
 
 Rank 0 prints ONE JSON line.  ``roofline`` prices the dominant kernel against
-the 8 TB/s HBM peak with its ALGORITHMIC bytes (8 B per coefficient written);
+the 8 TB/s HBM peak with its ALGORITHMIC bytes (8 B per coefficient written).
+At N > 1 ``per_rank`` holds every rank's own kernel time and launch geometry, and ``rccl_world_size`` the communicator's size.
+
+A plain run measures the headline only: set-up (including the library's autotune), warm-up, the timed steps, the line.
+``--full`` (N = 1) adds the side measurements, each of which takes runs of its own:
 ``cpu_baseline`` times the CPU oracle (the restated reference verifier, one
 thread like the reference) on a bounded channel slab of the same workload.
-``also_measured`` (N = 1) carries what the headline's 50-step burst does not show: the SUSTAINED rate over >= 5 s of
+``also_measured`` carries what the headline's 50-step burst does not show: the SUSTAINED rate over >= 5 s of
 back-to-back steps, BASELINE configs[4] (streaming at a 200 us cadence: full-tensor period and the largest slab that
-keeps the cadence, model time advancing 200 us per tick), the fp16 output modes and the fused beamformer.  At N > 1
-``per_rank`` holds every rank's own kernel time and launch geometry, and ``rccl_world_size`` the communicator's size.
+keeps the cadence, model time advancing 200 us per tick), the fp16 output modes and the fused beamformer.
 The oracle is loaded only in that cpu_baseline leg (where it is also used to
-spot-check the last generated step), never inside the timed GPU region; with
---no-cpu-baseline bench.py does not touch oracle/ at all.
+spot-check the last generated step) and by the --check-all-ranks rehearsal flag, never inside the timed GPU region;
+without --full (or with --full --no-cpu-baseline) bench.py does not touch oracle/ at all.
+
+``--dump-outputs DIR`` writes what the timed path computed in its LAST timed step, after the timing: a fixed, seeded
+sample of channel rows of the coefficient tensor (the whole of it is 16 GiB), so that two builds can be compared
+output for output (dump_outputs below).
 """
 from __future__ import annotations
 
@@ -72,8 +79,13 @@ def parse():
                          "configs[3] and configs[4] composed; model time advances 200 us per step")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="--gpus N > 1 without a launcher: seconds the parent waits for its N rank processes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp16 / fused-beamformer side measurements (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the headline (N = 1): cpu_baseline with the oracle spot check, "
+                         "and also_measured (sustained rate, streaming, fp16, beamformers); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's coefficients to DIR/*.npy (24 MiB of fp32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the also_measured side measurements")
     ap.add_argument("--per-step-events", action="store_true",
                     help="record a HIP event after every timed step and report the per-step median / min / max "
                          "(each event is a marker packet that costs the stream ~6 us, so it is off by default)")
@@ -512,6 +524,37 @@ def pmc_traffic(bytes_algo: int):
     return None, None
 
 
+DUMP_BYTES = 24 << 20  # --dump-outputs: coefficient bytes written per run, over all ranks (with the index files < 64 MB)
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(dirname: str, d_out: int, bp, rank: int, n_ranks: int, device, sh) -> None:
+    """``--dump-outputs DIR``: the last timed step's coefficients as a caller receives them, (channel, antenna, beam,
+    {re, im}) fp32, at channel rows drawn with a fixed seed (the same rows for the same shape, run after run):
+    ``coefficients.npy`` (n_rows, ant, beam, 2) and ``coefficient_channels.npy`` (n_rows,) float64.  A channel row
+    larger than the budget is itself sampled at seeded (antenna, beam) pairs: then ``coefficients.npy`` is
+    (n_rows, n_pairs, 2) and ``coefficient_pairs.npy`` holds the flat pair indices.  At N > 1 every rank writes its own
+    beam slab's rows as ``coefficients_rank<r>.npy``; the index files come from rank 0."""
+    n_pairs = bp.NR_STATIONS * bp.NR_BEAMS
+    budget = DUMP_BYTES // n_ranks // 8  # complex fp32 values per rank
+    rng = np.random.default_rng(DUMP_SEED)
+    chans = np.sort(rng.choice(bp.NR_CHANNELS, size=min(bp.NR_CHANNELS, max(1, budget // n_pairs)), replace=False))
+    pairs = np.sort(rng.choice(n_pairs, size=budget, replace=False)) if n_pairs > budget else None
+    host = np.empty((len(chans), bp.NR_STATIONS, bp.NR_BEAMS, 2), dtype=np.float32)
+    device.stream_synchronize(sh)
+    for i, c in enumerate(chans):
+        device.memcpy_dtoh(host[i], d_out + int(c) * n_pairs * 8)
+    if pairs is not None:
+        host = np.ascontiguousarray(host.reshape(len(chans), n_pairs, 2)[:, pairs])
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / ("coefficients.npy" if n_ranks == 1 else f"coefficients_rank{rank}.npy"), host)
+    if rank == 0:
+        np.save(d / "coefficient_channels.npy", chans.astype(np.float64))
+        if pairs is not None:
+            np.save(d / "coefficient_pairs.npy", pairs.astype(np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -732,6 +775,8 @@ def main():
             mx_f, _, _ = orc.max_ulp(host, orc.generate_dt(orc.params_from(bp), local, dt_last, 0, nchk), 1)
         return int(mx), int(n_over), int(mx_f)
 
+    if args.dump_outputs:  # before anything below rewrites the output buffer
+        dump_outputs(args.dump_outputs, out.data_ptr(), bp, rank, N, device, sh)
     if args.check_all_ranks:
         mx, n_over, _ = spot_check()
         assert n_over == 0, f"rank {rank}: {n_over} elements over 1 ULP (max {mx})"
@@ -791,10 +836,11 @@ def main():
             },
         }
         check = None
-        if N == 1 and not args.no_cpu_baseline:
+        with_cpu_baseline = N == 1 and args.full and not args.no_cpu_baseline
+        if with_cpu_baseline:
             check = spot_check()  # before anything else rewrites the output buffer
         samples = []
-        if N == 1 and not args.no_extras:
+        if N == 1 and args.full and not args.no_extras:
             # the side measurements must not be able to take the headline line down with them: a failure there is REPORTED
             # (also_measured.error / extras_vs_oracle_all_ok), the line is still printed
             try:
@@ -804,7 +850,7 @@ def main():
 
                 traceback.print_exc()
                 result["also_measured"] = {"error": f"{type(e).__name__}: {e}"}
-        if N == 1 and not args.no_cpu_baseline:
+        if with_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(bp, np.ascontiguousarray(table_host), args.cpu_seconds)
             if samples:
                 try:

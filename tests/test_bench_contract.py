@@ -9,6 +9,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +62,7 @@ def _common(d, n_gpus=1):
 
 
 def test_single_gpu_line_with_cpu_baseline():
-    d = _run(["--cpu-seconds", "0.3", "--sustain-seconds", "0.4"])
+    d = _run(["--full", "--cpu-seconds", "0.3", "--sustain-seconds", "0.4"])
     _common(d)
     assert d["config"]["collective"] == "none" and d["rccl_world_size"] is None
     am = d["also_measured"]
@@ -85,6 +86,24 @@ def test_single_gpu_line_with_cpu_baseline():
     assert "error" not in am
     assert any("device memory" in x["item"] for x in xs) and any(x["item"].startswith("beamform_accumulated 256x") for x in xs)
     assert c["beamform_accumulated"]["value"] > 0 and c["beamform_accumulated"]["cores"] == 1
+
+
+def test_plain_line_is_the_headline_only_and_dumps_the_last_timed_step(tmp_path, oracle):
+    """Without --full the line carries no side measurement; --dump-outputs writes the LAST timed step's coefficients
+    (step k = warmup + steps - 1 generates time index 1 + k % 255), every dumped row within 1 ULP of the oracle.
+    The expectation comes from the oracle alone: this process must not load the HIP library before the tests that
+    import torch do (torch brings its own libamdhip64.so)."""
+    d = _run(["--dump-outputs", str(tmp_path)])
+    _common(d)
+    assert "also_measured" not in d and "cpu_baseline" not in d
+    coeff = np.load(tmp_path / "coefficients.npy")
+    chans = np.load(tmp_path / "coefficient_channels.npy")
+    assert coeff.dtype == np.float32 and chans.dtype == np.float64 and not (tmp_path / "coefficient_pairs.npy").exists()
+    assert coeff.shape == (len(chans), 16, 64, 2) and len(chans) == 2048  # the small shape fits the budget whole
+    op = oracle.params(2048, 16, 64)
+    exp = oracle.generate_dt(op, oracle.simulate_input(op), [oracle.delta_time(op, 1 + (2 + 5 - 1) % 255)], 0, 2048)
+    mx, n_over, _ = oracle.max_ulp(coeff, exp[0][chans.astype(np.int64)], 1)
+    assert n_over == 0, mx
 
 
 def test_collective_control_flow_over_rccl_world_of_one():

@@ -57,6 +57,53 @@ def test_gpus_n_without_ranks_is_an_error_not_a_one_gpu_line():
     assert res.returncode != 0 and res.stdout.strip() == "" and "WORLD_SIZE=2" in res.stderr
 
 
+class _HostDevice:
+    """The two calls bench.dump_outputs makes on dc_sand_amd.device, served from a host array standing for the output."""
+
+    def __init__(self, buf: np.ndarray):
+        self.buf, self.base = buf.view(np.uint8).ravel(), 1 << 40
+
+    def stream_synchronize(self, stream):
+        pass
+
+    def memcpy_dtoh(self, dst, src):
+        off = int(src) - self.base
+        assert 0 <= off and off + dst.nbytes <= self.buf.size
+        dst.view(np.uint8).ravel()[:] = self.buf[off:off + dst.nbytes]
+
+
+def test_dump_outputs_is_a_seeded_bounded_sample(tmp_path):
+    """--dump-outputs: the same rows for the same shape, the rows' values as the output holds them, at most the budget;
+    a channel row wider than the budget is sampled at seeded (antenna, beam) pairs; at N > 1 one file per rank."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from dc_sand_amd import BeamformerParameters
+
+    def dump(d, bp, rank=0, n_ranks=1):
+        out = np.random.default_rng(rank).standard_normal((bp.NR_CHANNELS, bp.NR_STATIONS, bp.NR_BEAMS, 2)).astype(np.float32)
+        dev = _HostDevice(out)
+        bench.dump_outputs(str(d), dev.base, bp, rank, n_ranks, dev, None)
+        return out
+
+    bp = BeamformerParameters(NR_CHANNELS=4096, NR_STATIONS=64, NR_BEAMS=256)  # 128 KiB per channel row
+    out = dump(tmp_path / "a", bp)
+    dump(tmp_path / "b", bp)
+    c, ch = np.load(tmp_path / "a" / "coefficients.npy"), np.load(tmp_path / "a" / "coefficient_channels.npy")
+    assert c.dtype == np.float32 and ch.dtype == np.float64 and c.nbytes == bench.DUMP_BYTES and len(np.unique(ch)) == len(ch)
+    assert np.array_equal(c, out[ch.astype(np.int64)])
+    assert np.array_equal(ch, np.load(tmp_path / "b" / "coefficient_channels.npy"))
+    wide = BeamformerParameters(NR_CHANNELS=2, NR_STATIONS=64, NR_BEAMS=65536)  # 32 MiB per channel row
+    out = dump(tmp_path / "w", wide)
+    c, ch, pr = (np.load(tmp_path / "w" / f) for f in ("coefficients.npy", "coefficient_channels.npy", "coefficient_pairs.npy"))
+    assert c.nbytes == bench.DUMP_BYTES and c.shape == (1, bench.DUMP_BYTES // 8, 2)
+    assert np.array_equal(c[0], out[int(ch[0])].reshape(-1, 2)[pr.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / "w").iterdir()) < 64e6
+    for r in range(2):
+        dump(tmp_path / "r", bp, r, 2)
+    assert sorted(f.name for f in (tmp_path / "r").iterdir()) == ["coefficient_channels.npy", "coefficients_rank0.npy", "coefficients_rank1.npy"]
+    assert np.load(tmp_path / "r" / "coefficients_rank1.npy").nbytes == bench.DUMP_BYTES // 2
+
+
 def test_named_configs_are_the_baseline_shapes():
     sys.path.insert(0, str(ROOT))
     import bench

@@ -1,14 +1,16 @@
-"""Turn a gpurun_out/<tag>_{kt,pmc_w,pmc_f} set + bench JSON into the committed profiles/ artefacts."""
+"""Turn a profile_out/<tag>_{kt,pmc_w,pmc_f} set + bench JSON (tools/profile_bench.sh) into the committed profiles/ artefacts."""
 import csv
 import glob
 import json
 import shutil
 import statistics as st
 import sys
+from pathlib import Path
 
-R = "/root/repo/"
+R = str(Path(__file__).resolve().parent.parent) + "/"
+O = R + "profile_out/"  # what tools/profile_bench.sh wrote
 tag, bench_json, rnd = sys.argv[1], sys.argv[2], sys.argv[3]  # e.g. prof5 bench5.json r01
-f = glob.glob(R + f"gpurun_out/{tag}_kt/**/*kernel_trace.csv", recursive=True)[0]
+f = glob.glob(O + f"{tag}_kt/**/*kernel_trace.csv", recursive=True)[0]
 import re
 
 # production symbol of the fp32 generator: bf_tiled_kernel<false, TPB, NT, ALIGNED, NOMATH=false, TAG=0, INL, TERMS, HALF>;
@@ -25,17 +27,17 @@ bench_rows = rows[-60:]  # 10 warm-up + 50 timed
 d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in bench_rows]
 timed = d[10:]
 vg = bench_rows[-1]
-shutil.copy(glob.glob(R + f"gpurun_out/{tag}_kt/**/*kernel_stats.csv", recursive=True)[0], R + f"profiles/{rnd}_bench_kernel_stats.csv")
-shutil.copy(R + "gpurun_out/" + bench_json, R + f"profiles/{rnd}_bench_n1.json")
+shutil.copy(glob.glob(O + f"{tag}_kt/**/*kernel_stats.csv", recursive=True)[0], R + f"profiles/{rnd}_bench_kernel_stats.csv")
+shutil.copy(O + bench_json, R + f"profiles/{rnd}_bench_n1.json")
 prof = None
-for l in open(R + f"gpurun_out/{tag}_kt.log"):
+for l in open(O + f"{tag}_kt.log"):
     if l.startswith('{"metric"'):
         prof = json.loads(l)
         open(R + f"profiles/{rnd}_bench_n1_under_rocprof.json", "w").write(l)
-b = json.loads(open(R + "gpurun_out/" + bench_json).read())
+b = json.loads(open(O + bench_json).read())
 res = {}
 for d_, name in ((f"{tag}_pmc_w", "WRITE_SIZE"), (f"{tag}_pmc_f", "FETCH_SIZE")):
-    ff = glob.glob(R + f"gpurun_out/{d_}/**/*counter_collection.csv", recursive=True)[0]
+    ff = glob.glob(O + f"{d_}/**/*counter_collection.csv", recursive=True)[0]
     v = [float(r["Counter_Value"]) for r in csv.DictReader(open(ff)) if is_prod(r["Kernel_Name"]) and r["Counter_Name"] == name]
     res[name] = (len(v), st.mean(v))
     shutil.copy(ff, R + f"profiles/{rnd}_pmc_{name.lower()}_counter_collection.csv")
@@ -69,14 +71,14 @@ md = f"""# {rnd} — bench.py under rocprofv3 (MI355X, ROCm 7.2; final build of 
 Commands (`bash tools/profile_bench.sh`; the profiler from /tmp with `TMPDIR=/tmp`, program directly after `--`):
 
 ```
-python bench.py                                                          -> {rnd}_bench_n1.json
-rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras
+python bench.py --full                                                   -> {rnd}_bench_n1.json
+rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py
                                                                          -> {rnd}_bench_kernel_stats.csv, {rnd}_bench_n1_under_rocprof.json
-rocprofv3 --pmc WRITE_SIZE --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras
-rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras
+rocprofv3 --pmc WRITE_SIZE --output-format csv -- python3 bench.py --steps 6 --warmup 2
+rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --steps 6 --warmup 2
                                                                          -> {rnd}_pmc_*_counter_collection.csv, pmc_write_size.json
 ```
-(`--no-extras`: without the side measurements of `also_measured`, so that the last 60 dispatches of the production kernel are the
+(plain runs: without the side measurements of `--full`, so that the last 60 dispatches of the production kernel are the
 10 warm-up + 50 timed steps.)
 
 Dominant kernel: `{vg['Kernel_Name'].split('(')[1] if False else vg['Kernel_Name'][:100]}` (fp32, 1 tile per workgroup, nontemporal stores,

@@ -7,4 +7,4 @@ tail -2 $O/pytest_all.log
 python tools/measure.py fp16 --modes 0 --form 3 --tpb 1 --wpc=4,5,6,-1 --cpb 16,24,32,48,64,96 > $O/fp16_mode0.log 2>&1
 python tools/measure.py fp16 --modes 4 --form 3 --tpb 1 --wpc=4,5,6,7,-1 --cpb 16,20,24,28,32 > $O/fp16_mode4.log 2>&1
 grep "^best\|^library" $O/fp16_mode0.log $O/fp16_mode4.log
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"
