@@ -8,16 +8,22 @@
 HIPCC   ?= /opt/rocm/bin/hipcc
 PYTHON  ?= python
 LIB     := dc_sand_amd/csrc/libdcs_beamformer.so
+STAGING := dc_sand_amd/csrc/libdcs_stream_staging.so
 SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_capi.hip
-HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h include/dcs_beamformer.h
+HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h dc_sand_amd/csrc/bf_stream_ext.h \
+           include/dcs_beamformer.h include/dcs_stream_staging.h
 # -ffp-contract=off is part of the numerical contract; keep in step with dc_sand_amd/build.py
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -fvisibility=hidden \
             -Wall -Wextra -Wno-unused-parameter
 
-all: $(LIB) probes oracle hosts
+all: $(LIB) $(STAGING) probes oracle hosts
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS)
+
+# staged delay tables (include/dcs_stream_staging.h): forwards to the product library's streams
+$(STAGING): dc_sand_amd/csrc/bf_stream_staging.cpp $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_stream_staging.cpp
 
 oracle:
 	$(MAKE) -C oracle
@@ -41,7 +47,7 @@ bench: $(LIB)
 	$(PYTHON) bench.py
 
 clean:
-	rm -f $(LIB) probes/libdcs_probes.so
+	rm -f $(LIB) $(STAGING) probes/libdcs_probes.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tests/cpp clean
 	rm -f tests/numerics/libnumerics_lab.so

@@ -32,6 +32,9 @@ COMBINED_COEFF_GEN_AND_BEAMFORMER_SINGLE_CHANNEL = 3
 B16 = 0
 B32 = 1
 
+# dcs_bf_stream_stage_table flags (include/dcs_stream_staging.h)
+DCS_BF_STAGE_CALLER_PINNED = 1
+
 
 class Timespec(ctypes.Structure):
     """``struct timespec`` (x86-64 Linux: two longs) -- the reference kernels' time arguments."""
@@ -133,6 +136,32 @@ def _lib() -> ctypes.CDLL:
 
 def lib() -> ctypes.CDLL:
     return _lib()
+
+
+# include/dcs_stream_staging.h: the companion library of staged delay tables, built with the product library; it takes
+# the stream handles of the library above
+STAGING_LIB_PATH = LIB_PATH.parent / "libdcs_stream_staging.so"
+STAGING_SIGNATURES = [
+    ("dcs_bf_stream_stage_table", c_int, [_VP, _VP, c_int]),
+    ("dcs_bf_stream_stage_table_from_global", c_int, [_VP, _VP, c_uint32, c_uint32, _VP]),
+]
+
+_STAGING = None
+
+
+def staging_lib() -> ctypes.CDLL:
+    global _STAGING
+    if _STAGING is None:
+        _lib()  # the product library first: its streams are what the companion works on
+        if not STAGING_LIB_PATH.exists():
+            raise ImportError(f"{STAGING_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
+        slib = ctypes.CDLL(str(STAGING_LIB_PATH))
+        for name, restype, argtypes in STAGING_SIGNATURES:
+            fn = getattr(slib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _STAGING = slib
+    return _STAGING
 
 
 def check(status: int, where: str) -> None:

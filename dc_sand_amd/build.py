@@ -1,6 +1,7 @@
 """Build driver: compiles the gfx950 kernels and the C-ABI into
-``dc_sand_amd/csrc/libdcs_beamformer.so`` with hipcc (in-tree, so the library
-travels with the source tree).  ``python -m dc_sand_amd.build [--force]``.
+``dc_sand_amd/csrc/libdcs_beamformer.so`` and its companion of staged delay tables
+(``include/dcs_stream_staging.h``) into ``libdcs_stream_staging.so``, with hipcc (in-tree, so the libraries
+travel with the source tree).  ``python -m dc_sand_amd.build [--force]``.
 
 Flags that are part of the numerical contract (DESIGN.md "numerics"):
   -ffp-contract=off   no fused multiply-add except where bf_math.h writes one;
@@ -19,7 +20,11 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libdcs_beamformer.so"
 SOURCES = ["bf_kernels.hip", "bf_beamform_mfma.hip", "bf_capi.hip"]
-HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "../../include/dcs_beamformer.h"]
+HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "bf_stream_ext.h", "../../include/dcs_beamformer.h",
+           "../../include/dcs_stream_staging.h"]
+# the companion library of include/dcs_stream_staging.h (staged delay tables for the streams of the product library)
+STAGING_LIB = CSRC / "libdcs_stream_staging.so"
+STAGING_SOURCES = ["bf_stream_staging.cpp"]
 ARCH = "gfx950"
 
 
@@ -48,11 +53,11 @@ def flags() -> list[str]:
     ]
 
 
-def needs_build() -> bool:
-    if not LIB.exists():
+def needs_build(lib: Path = LIB, sources=SOURCES) -> bool:
+    if not lib.exists():
         return True
-    t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES + HEADERS] + [Path(__file__)]
+    t = lib.stat().st_mtime
+    deps = [CSRC / s for s in sources + HEADERS] + [Path(__file__)]
     return any(d.resolve().stat().st_mtime > t for d in deps)
 
 
@@ -87,9 +92,11 @@ def compile_and_link(sources, extra_flags, out: Path, verbose: bool = False) -> 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    if not force and not needs_build():
-        return LIB
-    compile_and_link([CSRC / s for s in SOURCES], [], LIB, verbose)
+    """Both libraries; returns the product library's path."""
+    if force or needs_build():
+        compile_and_link([CSRC / s for s in SOURCES], [], LIB, verbose)
+    if force or needs_build(STAGING_LIB, STAGING_SOURCES):
+        compile_and_link([CSRC / s for s in STAGING_SOURCES], [], STAGING_LIB, verbose)
     return LIB
 
 

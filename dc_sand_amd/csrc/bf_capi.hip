@@ -15,7 +15,9 @@
 #include <cstring>
 #include <new>
 
+#include "../../include/dcs_stream_staging.h" // DCS_BF_STAGE_CALLER_PINNED
 #include "bf_kernels.h"
+#include "bf_stream_ext.h"
 
 static_assert(sizeof(dcs_delay_vals) == 16, "delay_vals must be 4 x fp32 (BeamformerParameters.h:61-66)");
 
@@ -147,6 +149,7 @@ struct dcs_bf_context {
 
 constexpr int kTableRing = 4;
 struct dcs_bf_stream {
+    bf_stream_ext_head ext; // FIRST: the staging calls of the companion library reach this library's through it
     dcs_bf_context *ctx;
     hipStream_t stream;
     hipGraph_t graph;
@@ -171,6 +174,15 @@ struct dcs_bf_stream {
     hipGraphExec_t gexec;
     hipGraphNode_t gnode_gather, gnode_terms, gnode_gen;
     bf_gather_launch gather;
+    // staged tables (dcs_bf_stream_stage_table*): the stream owns a THIRD table buffer, filled on an internal stream
+    // while the caller's stream runs; the consuming tick exchanges it with the context's current buffer, so the one it
+    // retires is read only by work queued before that tick (released_ev marks the point).  Created on first staging.
+    dcs_delay_vals *d_spare;
+    hipStream_t stage_stream; // non-blocking, highest priority: its own hardware queue, not behind the generator
+    hipEvent_t staged_ev;     // the staging copy / gather into d_spare has landed
+    hipEvent_t released_ev;   // recorded on the caller's stream in front of the last consuming tick
+    bool released_recorded;
+    bool staged;              // d_spare holds a table the next plain tick makes current
 };
 
 extern "C" {
@@ -1485,12 +1497,13 @@ int build_stream_graph(dcs_bf_stream *s, bool with_gather, hipGraph_t *graph, hi
     return DCS_OK;
 }
 
-// Rewrite the arguments of the generator (and pre-pass) node of `exec` for this tick and replay it.
-int replay(dcs_bf_stream *s, float dt, hipGraphExec_t exec, hipGraphNode_t n_gather, hipGraphNode_t n_terms, hipGraphNode_t n_gen)
+// Rewrite the arguments of the generator (and pre-pass) node of `exec` for this tick (fDeltaTime, the table buffer it
+// reads) and replay it.
+int replay(dcs_bf_stream *s, float dt, const dcs_delay_vals *delays, hipGraphExec_t exec, hipGraphNode_t n_gather,
+           hipGraphNode_t n_terms, hipGraphNode_t n_gen)
 {
-    dcs_bf_context *c = s->ctx;
     s->launch.args.a.dt0 = dt;
-    s->launch.args.a.delays = c->d_table[c->cur];
+    s->launch.args.a.delays = delays;
     if (n_gather) {
         void *gparams[6];
         hipKernelNodeParams gp;
@@ -1500,7 +1513,7 @@ int replay(dcs_bf_stream *s, float dt, hipGraphExec_t exec, hipGraphNode_t n_gat
     if (s->has_terms) {
         s->terms_args.dt0 = dt;
         s->terms_args.dt_inline[0] = dt;
-        s->terms_args.delays = c->d_table[c->cur];
+        s->terms_args.delays = delays;
         void *tparams[] = {&s->terms_args};
         hipKernelNodeParams tp;
         terms_node_params(s, tparams, &tp);
@@ -1512,6 +1525,102 @@ int replay(dcs_bf_stream *s, float dt, hipGraphExec_t exec, hipGraphNode_t n_gat
     DCS_TRY(hipGraphExecKernelNodeSetParams(exec, n_gen, &np));
     return (int)hipGraphLaunch(exec, s->stream);
 }
+
+// The staging machinery of a stream, created by its first dcs_bf_stream_stage_table* call (a stream that never stages
+// allocates nothing more).  What a failed call created stays and is completed by the next one; dcs_bf_stream_end frees it.
+int ensure_staging(dcs_bf_stream *s)
+{
+    if (!s->d_spare) DCS_TRY(hipMalloc((void **)&s->d_spare, (size_t)s->ctx->n_pairs * sizeof(dcs_delay_vals)));
+    if (!s->stage_stream) {
+        // the highest priority takes a hardware queue of its own pool: the gather must not queue behind the generator
+        // kernel of the running tick, as it would on a queue the caller's stream shares
+        int least = 0, greatest = 0;
+        DCS_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        DCS_TRY(hipStreamCreateWithPriority(&s->stage_stream, hipStreamNonBlocking, greatest));
+    }
+    if (!s->staged_ev) DCS_TRY(hipEventCreateWithFlags(&s->staged_ev, hipEventDisableTiming));
+    if (!s->released_ev) DCS_TRY(hipEventCreateWithFlags(&s->released_ev, hipEventDisableTiming));
+    return DCS_OK;
+}
+
+// Checks shared by both staging calls; on success the internal stream may write d_spare (it has waited until no work
+// queued on the caller's stream reads that buffer any more).
+int begin_staging(dcs_bf_stream *s)
+{
+    const int cap = refuse_if_capturing(s->stream); // a cross-stream wait on the internal stream would join the capture
+    if (cap != DCS_OK) return cap;
+    const int st = ensure_staging(s);
+    if (st != DCS_OK) return st;
+    if (s->released_recorded) DCS_TRY(hipStreamWaitEvent(s->stage_stream, s->released_ev, 0));
+    return DCS_OK;
+}
+
+// A tick with no table of its own while one is staged: the caller's stream waits (device side) for the staging, the
+// replay reads d_spare, and only once it is enqueued does d_spare become the context's current buffer.
+int consume_staged(dcs_bf_stream *s, float dt)
+{
+    dcs_bf_context *c = s->ctx;
+    DCS_TRY(hipStreamWaitEvent(s->stream, s->staged_ev, 0));
+    // everything queued so far may read the context's current buffer, nothing after this point will once it is retired
+    DCS_TRY(hipEventRecord(s->released_ev, s->stream));
+    s->released_recorded = true;
+    const int st = replay(s, dt, s->d_spare, s->exec, nullptr, s->terms_node, s->node);
+    if (st != DCS_OK) return st; // nothing committed: the context still reads its table, the staged one stays pending
+    dcs_delay_vals *retired = c->d_table[c->cur];
+    c->d_table[c->cur] = s->d_spare;
+    s->d_spare = retired;
+    s->staged = false;
+    return DCS_OK;
+}
+
+// include/dcs_stream_staging.h, reached through the table at the head of every stream (bf_stream_ext.h)
+int stage_table_impl(dcs_bf_stream *s, const dcs_delay_vals *table, int flags)
+{
+    if (!s || !table) return DCS_ERR_INVALID_ARGUMENT;
+    if (flags != 0 && flags != DCS_BF_STAGE_CALLER_PINNED) return DCS_ERR_INVALID_ARGUMENT;
+    dcs_bf_context *c = s->ctx;
+    DCS_CHECK_DEVICE(c);
+    const size_t tb = (size_t)c->n_pairs * sizeof(dcs_delay_vals);
+    const int st = begin_staging(s);
+    if (st != DCS_OK) return st;
+    const void *src = table;
+    int r = -1;
+    if (flags == 0) { // through the ring of pinned buffers the host-table ticks use: the caller's array is free on return
+        r = s->table_next;
+        s->table_next = (r + 1) % kTableRing;
+        if (s->table_pending[r]) DCS_TRY(hipEventSynchronize(s->table_copied[r])); // the copy of four stagings ago
+        std::memcpy(s->h_table[r], table, tb);
+        src = s->h_table[r];
+    }
+    DCS_TRY(hipMemcpyAsync(s->d_spare, src, tb, hipMemcpyHostToDevice, s->stage_stream));
+    if (r >= 0) {
+        DCS_TRY(hipEventRecord(s->table_copied[r], s->stage_stream));
+        s->table_pending[r] = true;
+    }
+    DCS_TRY(hipEventRecord(s->staged_ev, s->stage_stream));
+    s->staged = true;
+    return DCS_OK;
+}
+
+int stage_table_from_global_impl(dcs_bf_stream *s, const void *d_global, uint32_t nb_total, uint32_t beam_offset,
+                                 void *ready_event)
+{
+    if (!s || !d_global) return DCS_ERR_INVALID_ARGUMENT;
+    dcs_bf_context *c = s->ctx;
+    DCS_CHECK_DEVICE(c);
+    if ((uint64_t)beam_offset + (uint64_t)c->p.nr_beams > nb_total) return DCS_ERR_OUT_OF_RANGE;
+    if ((reinterpret_cast<uintptr_t>(d_global) & 15u) != 0) return DCS_ERR_INVALID_ARGUMENT;
+    const int st = begin_staging(s);
+    if (st != DCS_OK) return st;
+    if (ready_event) DCS_TRY(hipStreamWaitEvent(s->stage_stream, reinterpret_cast<hipEvent_t>(ready_event), 0));
+    DCS_TRY(bf_launch_gather_beams(s->d_spare, static_cast<const dcs_delay_vals *>(d_global), (uint32_t)c->p.nr_stations,
+                                   (uint32_t)c->p.nr_beams, nb_total, beam_offset, s->stage_stream));
+    DCS_TRY(hipEventRecord(s->staged_ev, s->stage_stream));
+    s->staged = true;
+    return DCS_OK;
+}
+
+const bf_stream_ext_ops kStagingOps = {BF_STREAM_EXT_VERSION, stage_table_impl, stage_table_from_global_impl};
 
 } // namespace
 
@@ -1534,6 +1643,7 @@ int dcs_bf_stream_begin(dcs_bf_context *c, int bitwidth, uint32_t c0, uint32_t n
     dcs_bf_stream *s = new (std::nothrow) dcs_bf_stream();
     if (!s) return (int)hipErrorOutOfMemory;
     std::memset(static_cast<void *>(s), 0, sizeof(*s));
+    s->ext.ops = &kStagingOps;
     s->ctx = c;
     s->stream = as_stream(stream);
     int st = DCS_OK;
@@ -1571,6 +1681,7 @@ int dcs_bf_stream_tick_dt(dcs_bf_stream *s, float dt, const dcs_delay_vals *new_
     if (!s) return DCS_ERR_INVALID_ARGUMENT;
     dcs_bf_context *c = s->ctx;
     DCS_CHECK_DEVICE(c);
+    if (s->staged) return new_table ? DCS_ERR_INVALID_ARGUMENT : consume_staged(s, dt);
     if (new_table) {
         // stage through pinned memory into the IDLE table buffer; replays already
         // queued keep reading the current one (their arguments are baked in)
@@ -1585,7 +1696,7 @@ int dcs_bf_stream_tick_dt(dcs_bf_stream *s, float dt, const dcs_delay_vals *new_
         s->table_pending[r] = true;
         c->cur = nxt;
     }
-    return replay(s, dt, s->exec, nullptr, s->terms_node, s->node);
+    return replay(s, dt, c->d_table[c->cur], s->exec, nullptr, s->terms_node, s->node);
 }
 
 int dcs_bf_stream_tick(dcs_bf_stream *s, uint64_t t, const dcs_delay_vals *new_table)
@@ -1614,6 +1725,7 @@ int dcs_bf_stream_tick_dt_from_global(dcs_bf_stream *s, float dt, const void *d_
     DCS_CHECK_DEVICE(c);
     if ((uint64_t)beam_offset + (uint64_t)c->p.nr_beams > nb_total) return DCS_ERR_OUT_OF_RANGE;
     if ((reinterpret_cast<uintptr_t>(d_global) & 15u) != 0) return DCS_ERR_INVALID_ARGUMENT;
+    if (s->staged) return DCS_ERR_INVALID_ARGUMENT; // a staged table is pending: the next plain tick takes it
     // the gather node writes the IDLE table buffer (replays already queued read the current one), the nodes
     // behind it read it: all inside one graph launch, ordered by the graph's edges
     const int nxt = c->cur ^ 1;
@@ -1622,7 +1734,7 @@ int dcs_bf_stream_tick_dt_from_global(dcs_bf_stream *s, float dt, const void *d_
     s->gather.nb_total = nb_total;
     s->gather.beam_offset = beam_offset;
     c->cur = nxt;
-    return replay(s, dt, s->gexec, s->gnode_gather, s->gnode_terms, s->gnode_gen);
+    return replay(s, dt, c->d_table[c->cur], s->gexec, s->gnode_gather, s->gnode_terms, s->gnode_gen);
 }
 
 int dcs_bf_stream_tick_from_global(dcs_bf_stream *s, uint64_t t, const void *d_global, uint32_t nb_total, uint32_t beam_offset)
@@ -1648,6 +1760,15 @@ int dcs_bf_stream_end(dcs_bf_stream *s)
 {
     if (!s) return DCS_OK;
     (void)hipStreamSynchronize(s->stream);
+    // the staging machinery: a table staged but never consumed is dropped with the buffer that holds it -- the one buffer
+    // the stream owns now (the context's two, whichever they are after exchanges, stay the context's)
+    if (s->stage_stream) {
+        (void)hipStreamSynchronize(s->stage_stream);
+        (void)hipStreamDestroy(s->stage_stream);
+    }
+    if (s->staged_ev) (void)hipEventDestroy(s->staged_ev);
+    if (s->released_ev) (void)hipEventDestroy(s->released_ev);
+    if (s->d_spare) (void)hipFree(s->d_spare);
     if (s->exec) (void)hipGraphExecDestroy(s->exec);
     if (s->graph) (void)hipGraphDestroy(s->graph);
     if (s->gexec) (void)hipGraphExecDestroy(s->gexec);

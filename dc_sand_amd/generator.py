@@ -247,6 +247,7 @@ class CoefficientStream:
     def __init__(self, gen: SteeringCoefficientGenerator, handle: int):
         self._gen = gen
         self._h = handle
+        self._pinned_staged = None
 
     def tick(self, t: int, new_table: np.ndarray | None = None) -> None:
         ptr = c_void_p(None)
@@ -300,10 +301,39 @@ class CoefficientStream:
                                                            *self._global_args(d_global_table, nr_beams_total, beam_offset)),
               "dcs_bf_stream_tick_at_from_global")
 
+    # -- staged tables: the NEXT tick's table lands while the current tick runs (``dcs_bf_stream_stage_table*``); the
+    #    next tick without a table of its own makes it current
+    def stage_table(self, table: np.ndarray, pinned: bool = False) -> None:
+        """Stage ``table`` for the next tick that brings no table.  ``pinned=False``: copied through the stream's pinned
+        ring, ``table`` is free again on return.  ``pinned=True``: ``table`` is a :func:`device.pagelocked_empty` array,
+        copied from where it is; keep it unchanged until the consuming tick has run on the stream."""
+        if pinned:
+            if not isinstance(table, np.ndarray) or not table.flags["C_CONTIGUOUS"]:
+                raise ValueError("pinned=True needs a C-contiguous pagelocked_empty array")
+        else:
+            table = np.ascontiguousarray(table)
+        if table.dtype != delay_vals_dtype or table.size != self._gen.params.n_pairs:
+            raise ValueError("bad delay table")
+        check(_lib.staging_lib().dcs_bf_stream_stage_table(c_void_p(self._h), c_void_p(table.ctypes.data),
+                                                   _lib.DCS_BF_STAGE_CALLER_PINNED if pinned else 0),
+              "dcs_bf_stream_stage_table")
+        if pinned:
+            self._pinned_staged = table  # the copy reads it asynchronously: keep the allocation alive
+
+    def stage_table_from_global(self, d_global_table, nr_beams_total: int | None = None, beam_offset: int = 0,
+                                ready_event=None) -> None:
+        """Stage this context's beam slice of a device-resident global table; the gather waits (on the device) for
+        ``ready_event`` -- a :class:`device.Event` or a raw ``hipEvent_t`` the producer recorded -- when given."""
+        ev = ready_event.handle if hasattr(ready_event, "handle") else ready_event
+        check(_lib.staging_lib().dcs_bf_stream_stage_table_from_global(c_void_p(self._h), *self._global_args(d_global_table, nr_beams_total, beam_offset),
+                                                               c_void_p(None if ev is None else int(ev))),
+              "dcs_bf_stream_stage_table_from_global")
+
     def end(self) -> None:
         if self._h:
             _lib.lib().dcs_bf_stream_end(c_void_p(self._h))
             self._h = None
+        self._pinned_staged = None
 
     def __del__(self):
         try:

@@ -358,6 +358,11 @@ int dcs_bf_stream_tick_dt_from_global(dcs_bf_stream *s, float dt, const void *d_
                                       uint32_t nr_beams_total, uint32_t beam_offset);
 int dcs_bf_stream_tick_at_from_global(dcs_bf_stream *s, const struct timespec *cur, const struct timespec *ref,
                                       const void *d_global_table, uint32_t nr_beams_total, uint32_t beam_offset);
+
+/* Staged tables -- the next tick's table lands while the current tick runs -- are the entry points of the companion
+ * library libdcs_stream_staging.so (include/dcs_stream_staging.h), which work on the streams of this library; this
+ * library's own ABI stays version 3.  While a table is staged on a stream, the ticks above follow that header's rules: one
+ * with new_table == NULL makes it current, one that brings a table of its own returns DCS_ERR_INVALID_ARGUMENT. */
 int dcs_bf_stream_end(dcs_bf_stream *s);
 
 #pragma GCC visibility pop

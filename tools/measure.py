@@ -15,6 +15,8 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         fused generate + beamform rate on several shapes                            -> profiles/r0N_fused.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
+    python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
+        the same per way of bringing a new delay table to EVERY tick (after autotune)  -> profiles/r04_streaming_staged.md
     python tools/measure.py pmc
         a few launches of each hot kernel, for `rocprofv3 --pmc ... -- python3 tools/measure.py pmc`
     python tools/measure.py sustained [--seconds 6]
@@ -280,7 +282,91 @@ def cmd_mfma(args):
             print(f"{name}, {blocks} workgroups ({blocks * 4 / 1024:.0f} waves per SIMD): {n * flop / ms / 1e9:.1f} TFLOP/s", flush=True)
 
 
+TABLE_MODES = ("unchanged", "host", "device", "staged-host", "staged-host-pinned", "staged-device")
+
+
+def stream_table_modes(args):
+    """Per table mode: the period of a tick when EVERY tick brings a new table (two tables alternating), for the full
+    tensor and a range of slabs.  host / device: the table comes with the tick (tick_dt(new_table) /
+    tick_dt_from_global: copy or gather in front of the generator); staged-*: the table of tick k + 1 is staged right
+    after tick k is enqueued (stage_table, pinned=True, stage_table_from_global) and the next tick consumes it."""
+    from dc_sand_amd.parameters import delay_vals_dtype
+
+    bp, g, _, full, buf = make(SHAPES["cfg3"], 32)
+    stream = device.Stream()
+    step_s = args.model_step_us * 1e-6
+    tables = [simulate_input(bp), simulate_input(bp)]
+    tables[1]["fPhase_rad"] += np.float32(0.25)
+    pinned = []
+    d_tables = []
+    for t in tables:
+        p = device.pagelocked_empty(bp.n_pairs, delay_vals_dtype)
+        p[:] = t
+        pinned.append(p)
+        d = device.mem_alloc(t.nbytes)
+        device.memcpy_htod(d, t)
+        d_tables.append(d)
+    g.autotune(buf, full, stream=stream)  # as bench.py: the full tensor, then the cadence slab (the other kernel variant)
+    g.autotune(buf, min(full, 2560 * bp.n_pairs * 8), stream=stream)
+
+    def tick_fn(st, mode):
+        if mode == "unchanged":
+            return lambda i: st.tick_dt(i * step_s)
+        if mode == "host":
+            return lambda i: st.tick_dt(i * step_s, tables[i % 2])
+        if mode == "device":
+            return lambda i: st.tick_dt_from_global(i * step_s, d_tables[i % 2])
+
+        def staged(i):
+            st.tick_dt(i * step_s)
+            if mode == "staged-host":
+                st.stage_table(tables[(i + 1) % 2])
+            elif mode == "staged-host-pinned":
+                st.stage_table(pinned[(i + 1) % 2], pinned=True)  # the two arrays never change: no reuse hazard
+            else:
+                st.stage_table_from_global(d_tables[(i + 1) % 2])
+        return staged
+
+    def period_us(fn, ticks, warm=20):
+        for i in range(warm):
+            fn(i)
+        stream.synchronize()
+        e0, e1 = device.Event(), device.Event()
+        t0 = time.perf_counter()
+        e0.record(stream)
+        for i in range(ticks):
+            fn(warm + i)
+        e1.record(stream)
+        e1.synchronize()
+        return e1.elapsed_ms_since(e0) / ticks * 1e3, (time.perf_counter() - t0) / ticks * 1e6
+
+    slabs = [int(x) for x in args.slabs.split(",")] if args.slabs else [2048, 2304, 2432, 2560, 2688, 2816, 3072]
+    out = {"config": "64ant x 1024beam x 32768chan, fp32, one time step per tick, a new table on every tick (two alternating); "
+                     f"model time advances {args.model_step_us} us per tick", "cadence_target_us": 200.0, "modes": {}}
+    for mode in args.table_mode:
+        res = {"slabs": []}
+        for nc in ([] if args.skip_full else [bp.NR_CHANNELS]) + slabs:
+            nbytes = nc * bp.n_pairs * 8
+            g.upload_delays(tables[0], stream=stream)
+            st = g.stream_begin(buf, nbytes, 0, nc, stream)
+            dev_us, wall_us = period_us(tick_fn(st, mode), ticks=args.ticks if nc < bp.NR_CHANNELS else 60)
+            st.end()
+            r = dict(channels=nc, bytes=nbytes, period_us=dev_us, wall_us=wall_us, TBps=nbytes / dev_us / 1e6)
+            if nc == bp.NR_CHANNELS:
+                res["full_tensor"] = r
+            else:
+                res["slabs"].append(r)
+            print(mode, json.dumps(r), flush=True)
+        ok = [s for s in res["slabs"] if max(s["period_us"], s["wall_us"]) <= 200.0]
+        res["largest_slab_at_200us"] = max(ok, key=lambda s: s["channels"]) if ok else None
+        out["modes"][mode] = res
+    print("SUMMARY", json.dumps(out), flush=True)
+    g.close()
+
+
 def cmd_stream(args):
+    if args.table_mode:
+        return stream_table_modes(args)
     bp, g, _, full, buf = make(SHAPES["cfg3"], 32)
     table = simulate_input(bp)
     stream = device.Stream()
@@ -455,6 +541,11 @@ def main():
     p.add_argument("--random", action="store_true", help="noise-like int8 samples instead of a constant byte (the matrix pipe's power depends on the data)")
     p = sub.add_parser("stream")
     p.add_argument("--model-step-us", type=float, default=200.0)
+    p.add_argument("--table-mode", action="append", choices=TABLE_MODES,
+                   help="measure per way of bringing a new table to every tick (repeatable); without it: the round-3 report")
+    p.add_argument("--slabs", default="", help="with --table-mode: comma-separated slab widths in channels")
+    p.add_argument("--skip-full", action="store_true", help="with --table-mode: no full-tensor run")
+    p.add_argument("--ticks", type=int, default=200, help="with --table-mode: timed ticks per slab")
     sub.add_parser("pmc")
     p = sub.add_parser("sustained")
     p.add_argument("--seconds", type=float, default=6.0)
