@@ -164,6 +164,35 @@ def staging_lib() -> ctypes.CDLL:
     return _STAGING
 
 
+# include/dcs_beam_weights.h: the companion library of per-input beam weights, built with the product library; it takes
+# the context handles of the library above
+WEIGHTS_LIB_PATH = LIB_PATH.parent / "libdcs_beam_weights.so"
+BEAM_WEIGHTS_SIGNATURES = [
+    ("dcs_bf_generate_and_beamform_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ("dcs_bf_generate_and_beamform_weighted_dt", c_int,
+     [_VP, POINTER(c_float), c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ("dcs_bf_beamform_accumulated_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ("dcs_bf_beamform_accumulated_weighted_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+]
+
+_WEIGHTS = None
+
+
+def beam_weights_lib() -> ctypes.CDLL:
+    global _WEIGHTS
+    if _WEIGHTS is None:
+        _lib()  # the product library first: its contexts are what the companion works on
+        if not WEIGHTS_LIB_PATH.exists():
+            raise ImportError(f"{WEIGHTS_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
+        wlib = ctypes.CDLL(str(WEIGHTS_LIB_PATH))
+        for name, restype, argtypes in BEAM_WEIGHTS_SIGNATURES:
+            fn = getattr(wlib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _WEIGHTS = wlib
+    return _WEIGHTS
+
+
 def check(status: int, where: str) -> None:
     if status != DCS_OK:
         raise DcsError(status, where)

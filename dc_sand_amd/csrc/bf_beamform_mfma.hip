@@ -289,479 +289,17 @@ constexpr int kChainWaves = 4;
 
 // NW: waves per workgroup -- 4; 8 (kStaged, eight beam tiles per workgroup) is instantiated in the probes build only: an A/B
 // that measured no gain over four tiles (profiles/r03_fused.md)
-template <int FORM, bool FULL, int NW = 4>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(FORM == kSplit ? (FULL ? 3 : 2) : (FORM == kChain ? kChainWaves : (FULL || FORM == kStaged ? 4 : 3)))))
-bf_beamform_i8_kernel(const bf_bacc_args a)
+constexpr int i8_waves_per_eu(int form, bool full)
 {
-    static_assert(NW == 4 || ((NW == 8 || NW == 16) && FORM == kStaged), "8- and 16-wave workgroups exist for the staged form only");
-    constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
-    extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
-    uint32_t bid = BACC_LOGICAL_ID(a);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t bg = bid % a.n_bgroups;
-    bid /= a.n_bgroups;
-    const uint32_t tg = bid % a.n_tgroups;
-    const uint32_t c = bid / a.n_tgroups;
-    // beam tiles per workgroup, sample blocks per round (kSplit: one tile, every wave takes every block)
-    const uint32_t nbt_log2 = SPLIT || CHAIN ? 0u : a.nbt_log2;
-    const uint32_t nbt = 1u << nbt_log2, tpr = SPLIT ? 1u : (uint32_t)NW >> nbt_log2;
-    const uint32_t bt = SPLIT ? 0u : wave & (nbt - 1u), slot = SPLIT ? 0u : wave >> nbt_log2;
-    const uint32_t kc = SPLIT || CHAIN ? wave : 0u; // the 64-antenna chunk whose coefficients this wave makes (and, kSplit, contracts)
-    const uint32_t lm = lane & 15u, lg = lane >> 4;
-    const uint32_t bw = (bg * nbt + bt) * 16u;     // first beam of this wave's tile
-    const uint32_t tt0 = tg * a.tiles_per_wg;      // first 16-sample block of the workgroup
-    const uint32_t tt1 = min(tt0 + a.tiles_per_wg, a.nT16);
-    const uint32_t n_blocks = tt1 > tt0 + slot ? (tt1 - tt0 - slot + tpr - 1u) / tpr : 0u; // this wave's sample blocks
-    const bool idle = bw >= a.B || n_blocks == 0u; // wave-uniform (kSplit: workgroup-uniform)
-    if (!STAGED && !CHAIN && idle) return;         // (no barrier behind this in the direct form; all waves alike in kSplit)
-    const bool has_chunk = !(SPLIT || CHAIN) || 64u * kc < a.A; // kSplit / kChain with <= 192 antennas: the last wave(s) have no chunk of their own
-    if (STAGED) { // this wave's share of the workgroup's blocks: global -> LDS, 1 KiB per instruction, same byte order
-        typedef __attribute__((address_space(3))) void lds_void;
-        typedef const __attribute__((address_space(1))) void glb_void;
-        const uint32_t bytes = (tt1 - tt0) * a.A * 32u; // a multiple of 32
-        const char *src = reinterpret_cast<const char *>(a.ant) + ((uint64_t)c * a.nT16 + tt0) * a.A * 32u;
-        for (uint32_t k = wave; k * 1024u < bytes; k += (uint32_t)NW) // a piece that overhangs the end re-reads the last 16 bytes
-            __builtin_amdgcn_global_load_lds((glb_void *)(src + min(k * 1024u + lane * 16u, bytes - 16u)), (lds_void *)(staged + k * 1024u),
-                                             16, 0, 0);
-    }
-
-    const uint32_t fw = a.flags[0]; // (epoch << 2) | highest pair class of the table (bf_bform_terms_kernel)
-    const uint32_t cls = (fw >> 2) == a.epoch ? (fw & 3u) : DCS_CLASS_FAST_LOW;
-    const float fChan = (float)c;
-    const float D = a.k.fDenominator, y = a.k.fRcpDenominator;
-
-    // ---- coefficients: lane (row lm, group lg) holds, in byte p of each of its six operands (3 digits x {re, im}),
-    //      antenna 64 kc + 4 p + lg.  16 terms loads in flight together; the fast classes fully unrolled (16 copies of
-    //      ~34 instructions, nothing moves), the slow class in four rolled trips.
-    // kStaged, fewer than four beam tiles per workgroup: the 4 / nbt waves that own the same tile make a quarter (half)
-    // of its coefficient registers each and exchange them through LDS behind the staging barrier (the slow class makes
-    // everything everywhere: its rolled loop does not split)
-    const bool shared_w = STAGED && a.share_off != 0u && tpr > 1u && cls != DCS_CLASS_SLOW;
-    intx4 wre[3], wim[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) wre[d] = wim[d] = intx4{0, 0, 0, 0};
-    // A coefficient that is not finite (an infinite or NaN delay value: the slow class) has no fixed-point digits; the
-    // verifier's sum for that beam and plane is NaN whatever the samples are (NaN * 0 = NaN), and so it is here: the lanes
-    // note it, the wave folds the notes into one bit per result row and plane, and the rows are stored as NaN.
-    bool bad_re = false, bad_im = false;
-    auto make_coefficients = [&]() {
-        // row i of the result tile is beam 4 (i & 3) + (i >> 2): the four lane groups of a store instruction then
-        // hold four CONSECUTIVE beams (512 contiguous bytes per block) instead of every fourth
-        const uint32_t beam = bw + 4u * (lm & 3u) + (lm >> 2);
-        const bool beam_live = beam < a.B;
-        const float *tp = a.terms + 2u * (uint64_t)min(beam, a.B - 1u);
-        // four antennas' words -> one register of each digit plane (a 4 x 4 byte transpose; byte z = antenna z)
-        auto planes = [](const uint32_t (&g)[4], uint32_t (&out)[3]) {
-            const uint32_t t0 = __builtin_amdgcn_perm(g[1], g[0], 0x05010400u), t1 = __builtin_amdgcn_perm(g[1], g[0], 0x07030602u);
-            const uint32_t t2 = __builtin_amdgcn_perm(g[3], g[2], 0x05010400u), t3 = __builtin_amdgcn_perm(g[3], g[2], 0x07030602u);
-            out[2] = __builtin_amdgcn_perm(t2, t0, 0x05040100u); // bytes 0: d3
-            out[1] = __builtin_amdgcn_perm(t2, t0, 0x07060302u); // bytes 1: d2
-            out[0] = __builtin_amdgcn_perm(t3, t1, 0x05040100u); // bytes 2: d1
-        };
-        // antennas 64 kc + 4 (4 q + z) + lg, z = 0..3, from their terms: one register of each of the six operands
-        auto four = [&](auto gen, auto track, uint32_t q, const floatx2 (&k4)[4], uint32_t (&nr)[3], uint32_t (&ni)[3]) {
-            uint32_t gr[4], gi[4];
-#pragma unroll
-            for (uint32_t z = 0; z < 4; z++) {
-                float re, im;
-                gen(k4[z].x, k4[z].y, re, im);
-                if (decltype(track)::value) { // the slow class only: infinite or NaN delay values end here
-                    bad_re |= !(fabsf(re) <= 2.0f);
-                    bad_im |= !(fabsf(im) <= 2.0f);
-                }
-                gr[z] = fixed_word(re), gi[z] = fixed_word(im);
-            }
-            planes(gr, nr), planes(gi, ni);
-            if (!FULL) { // antennas beyond nr_stations: zero digits, byte by byte
-                uint32_t mask = 0;
-#pragma unroll
-                for (uint32_t z = 0; z < 4; z++) mask |= 64u * kc + 4u * (4u * q + z) + lg < a.A ? 0xffu << (8u * z) : 0u;
-#pragma unroll
-                for (int d = 0; d < 3; d++) nr[d] &= mask, ni[d] &= mask;
-            }
-        };
-        auto generate = [&](auto gen, auto unrolled) {
-            floatx2 kp[16];
-#pragma unroll
-            for (uint32_t z = 0; z < 16; z++) {
-                const uint32_t ant = 64u * kc + 4u * z + lg;
-                kp[z] = *reinterpret_cast<const floatx2 *>(tp + 2u * (uint64_t)min(ant, a.A - 1u) * a.B);
-            }
-            if (decltype(unrolled)::value) {
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    if (shared_w && (q & (tpr - 1u)) != slot) continue; // a wave sharing its tile makes its own registers only
-                    const floatx2 k4[4] = {kp[4 * q], kp[4 * q + 1], kp[4 * q + 2], kp[4 * q + 3]};
-                    uint32_t nr[3], ni[3];
-                    four(gen, std::false_type{}, q, k4, nr, ni);
-                    if constexpr (CHAIN) { // straight to the LDS image (component q of the chunk's six operands): the 24 registers are never held
-                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * 6u * 64u + lane) * 4u + q;
-#pragma unroll
-                        for (int d = 0; d < 3; d++) cw[(uint32_t)d * 256u] = beam_live ? nr[d] : 0u, cw[(3u + (uint32_t)d) * 256u] = beam_live ? ni[d] : 0u;
-                    } else {
-#pragma unroll
-                        for (int d = 0; d < 3; d++) wre[d][q] = (int)nr[d], wim[d][q] = (int)ni[d];
-                    }
-                }
-            } else { // the new register enters at the top while the others, and the loaded terms, move down -- no
-                     // register is indexed by a loop variable
-#pragma unroll 1
-                for (uint32_t q = 0; q < 4; q++) {
-                    const floatx2 k4[4] = {kp[0], kp[1], kp[2], kp[3]};
-                    uint32_t nr[3], ni[3];
-                    four(gen, std::true_type{}, q, k4, nr, ni);
-                    if constexpr (CHAIN) {
-                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * 6u * 64u + lane) * 4u + q;
-#pragma unroll
-                        for (int d = 0; d < 3; d++) cw[(uint32_t)d * 256u] = beam_live ? nr[d] : 0u, cw[(3u + (uint32_t)d) * 256u] = beam_live ? ni[d] : 0u;
-                    } else {
-#pragma unroll
-                        for (int d = 0; d < 3; d++) {
-                            wre[d] = intx4{wre[d][1], wre[d][2], wre[d][3], (int)nr[d]};
-                            wim[d] = intx4{wim[d][1], wim[d][2], wim[d][3], (int)ni[d]};
-                        }
-                    }
-#pragma unroll
-                    for (uint32_t z = 0; z < 12; z++) kp[z] = kp[z + 4];
-                }
-            }
-            if (!CHAIN && !beam_live) { // beams beyond nr_beams: zero coefficients (their results are not stored either)
-#pragma unroll
-                for (int d = 0; d < 3; d++) wre[d] = wim[d] = intx4{0, 0, 0, 0};
-            }
-        };
-        if (cls == DCS_CLASS_SLOW) {
-            generate([&](float kx, float ky, float &re, float &im) { coeff_slow(kx, ky, fChan, D, re, im); }, std::false_type{});
-        } else {
-            dispatch_fast(a.k.uDiv3Exact != 0u, cls == DCS_CLASS_FAST_LOW, [&](auto div3, auto lowdeg) {
-                generate([&](float kx, float ky, float &re, float &im) {
-                    coeff_fast<decltype(div3)::value, decltype(lowdeg)::value>(kx, ky, fChan, D, y, re, im);
-                }, std::true_type{});
-            });
-        }
-    };
-
-    // ---- sample blocks, two at a time.  Column n of the B operand is NOT "sample n of one block": a lane loads the
-    //      4 bytes {re, im} x samples (2 m, 2 m + 1), m = n & 7, of block A (n < 8) or block B (n >= 8) of its pair, so
-    //      one 4-byte load per antenna serves FOUR contractions -- (even samples, odd samples) x (re, im) -- whose
-    //      16 columns are 8 sample pairs of block A and 8 of block B.  A 4 x 4 byte transpose (8 v_perm_b32 per 4
-    //      antennas) turns 16 loaded registers into the 4 K = 64 operands; a result lane holds samples 2 m and 2 m + 1 of
-    //      its 4 beams: one 16-byte store each.  Half the load and store instructions of a per-block scheme and no
-    //      half-word merging (d16 loads do not keep the other half with SRAM-ECC on).
-    //      Global addresses (kDirect, kSplit): a wave-uniform base (scalar registers) plus a per-lane byte offset; with
-    //      whole chunks (FULL) ONE offset register and the instruction's immediate (antenna 4 p + lg is 128 p bytes
-    //      further), otherwise offsets clamped to the last antenna (the coefficient digits are 0 beyond nr_stations).
-    //      Two load sets are in flight per wave.  hipcc waits for ALL memory operations at the head of a loop whose
-    //      loads cross the back-edge, stores included, so the order inside a trip is: wait, transpose, MFMAs, STORES,
-    //      then the next trip's LOADS -- one memory latency per trip, shared by loads and stores (with the loads issued
-    //      first, each trip paid the load and the store latency one after the other: 3.2 us per block and wave).
-    const char *ant8 = reinterpret_cast<const char *>(a.ant);
-    const uint32_t blk_bytes = a.A * 32u;            // one 16-sample block of one channel: <= 8 KiB
-    const uint32_t m = lm & 7u;
-    const bool second = lm >= 8u;                    // this lane's columns belong to block B of the pair
-    const uint32_t last = n_blocks - 1u;
-    const uint32_t voff = lg * 32u + m * 4u;
-    uint32_t cur[2][16];
-    // "every loaded register is needed HERE": keeps the compiler from sinking a load set into the trip that consumes it
-    auto arrived = [&](uint32_t (&v)[16]) {
-        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-        asm volatile("" : "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
-    };
-    auto fetch = [&](uint32_t (&dst)[16], uint32_t blk, uint32_t kc) { // pair (blk, min(blk + 1, last)), antenna chunk kc
-        const uint32_t blkA = min(blk, last), blkB = min(blk + 1u, last);
-        if (STAGED) { // from the LDS image: block j of the workgroup at j * blk_bytes
-            const uint32_t at = ((second ? blkB : blkA) * tpr + slot) * blk_bytes + m * 4u;
-#pragma unroll
-            for (uint32_t p = 0; p < 16; p++)
-                dst[p] = *reinterpret_cast<const uint32_t *>(staged + at + (FULL ? lg + 4u * p : min(lg + 4u * p, a.A - 1u)) * 32u);
-            return;
-        }
-        const char *base = ant8 + ((uint64_t)c * a.nT16 + tt0 + blkA * tpr + slot) * blk_bytes; // wave-uniform
-        const uint32_t hop = second ? (blkB - blkA) * tpr * blk_bytes : 0u;
-        if (FULL) {
-            const char *b2 = base + 2048u * kc;
-            const uint32_t vo = hop + voff;
-#pragma unroll
-            for (uint32_t p = 0; p < 16; p++) dst[p] = *reinterpret_cast<const uint32_t *>(b2 + vo + 128u * p);
-        } else {
-#pragma unroll
-            for (uint32_t p = 0; p < 16; p++)
-                dst[p] = *reinterpret_cast<const uint32_t *>(base + (hop + min(64u * kc + lg + 4u * p, a.A - 1u) * 32u + m * 4u));
-        }
-    };
-    // x[0] = re of the even samples, x[1] = im even, x[2] = re odd, x[3] = im odd; byte p of each = antenna 4 p + lg
-    auto transpose = [&](const uint32_t (&v)[16], intx4 (&x)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t t0 = __builtin_amdgcn_perm(v[4 * q + 1], v[4 * q], 0x05010400u);     // {a0.b0, a1.b0, a0.b1, a1.b1}
-            const uint32_t t1 = __builtin_amdgcn_perm(v[4 * q + 1], v[4 * q], 0x07030602u);     // {a0.b2, a1.b2, a0.b3, a1.b3}
-            const uint32_t t2 = __builtin_amdgcn_perm(v[4 * q + 3], v[4 * q + 2], 0x05010400u);
-            const uint32_t t3 = __builtin_amdgcn_perm(v[4 * q + 3], v[4 * q + 2], 0x07030602u);
-            x[0][q] = (int)__builtin_amdgcn_perm(t2, t0, 0x05040100u);
-            x[1][q] = (int)__builtin_amdgcn_perm(t2, t0, 0x07060302u);
-            x[2][q] = (int)__builtin_amdgcn_perm(t3, t1, 0x05040100u);
-            x[3][q] = (int)__builtin_amdgcn_perm(t3, t1, 0x07060302u);
-        }
-    };
-    // One load set (64 antennas of a pair of blocks) as fp32 sums f[v], plane v = (re even, im even, re odd, im odd):
-    // three integer contractions from zero per plane, each exact (|sum| <= 2^20); the two low digits are combined in
-    // integers (s2 * 256 + s3 < 2^29: exact), converted (one rounding, far below the result's last place), and the
-    // high digit enters with one fma.
-    const intx4 zero = {0, 0, 0, 0};
-    auto contract = [&](const intx4 (&x)[4], floatx4 (&f)[4]) {
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const intx4 s3 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[2] : wre[2], x[v], zero, 0, 0, 0);
-            const intx4 s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[1] : wre[1], x[v], zero, 0, 0, 0);
-            const intx4 s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[0] : wre[0], x[v], zero, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; r++) f[v][r] = fmaf((float)s1[r], 65536.0f, (float)(s2[r] * 256 + s3[r]));
-        }
-    };
-    const float inv = 1.0f / kFixScale;
-    uint32_t nan_re = 0, nan_im = 0;     // wave-uniform: rows whose re / im plane is NaN (set once the coefficients are made)
-    const float fNaN = __builtin_nanf("");
-    // register r of this lane is result row 4 lg + r
-    auto poison = [&](int r, floatx4 &o) { // o = {re even, im even, re odd, im odd}
-        if ((nan_re >> (4u * lg + (uint32_t)r)) & 1u) o[0] = fNaN, o[2] = fNaN;
-        if ((nan_im >> (4u * lg + (uint32_t)r)) & 1u) o[1] = fNaN, o[3] = fNaN;
-    };
-    const uint32_t bb = bw + lg;         // register r of this lane: beam bb + 4 r
-    const uint32_t out_blk = a.B * 128u; // bytes per 16-sample block of one channel
-    char *out8 = reinterpret_cast<char *>(a.beams);
-    // where this lane's 16 bytes {re, im} x samples (2 m, 2 m + 1) of beam bb + 4 r go, pair (blk, blk + 1)
-    auto out_of = [&](uint32_t blk, int r) {
-        const uint32_t blkA = min(blk, last), blkB = min(blk + 1u, last);
-        char *base = out8 + ((uint64_t)c * a.nT16 + tt0 + blkA * tpr + slot) * out_blk; // wave-uniform
-        return reinterpret_cast<floatx4 *>(base + ((second ? (blkB - blkA) * tpr * out_blk : 0u) + bb * 128u + m * 16u + 512u * r));
-    };
-    auto store = [&](floatx4 *dst, const floatx4 o) {
-#ifdef DCS_PROBES
-        if (a.plain_stores) { // probes build only: the A/B of profiles/r02_fused.md
-            *dst = o;
-            return;
-        }
-#endif
-        __builtin_nontemporal_store(o, dst); // written once, read by another kernel: do not keep it in L2
-    };
-    // scale and store: lane l, register r = beam bw + (l >> 4) + 4 r, samples 2 m, 2 m + 1
-    auto finish = [&](auto whole, uint32_t blk, const floatx4 (&f)[4]) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) { // beam bb + 4 r
-            floatx4 o = {f[0][r] * inv, f[1][r] * inv, f[2][r] * inv, f[3][r] * inv};
-            if (nan_re | nan_im) poison(r, o);
-            if (decltype(whole)::value || bb + 4u * r < a.B) {
-                floatx4 *dst = out_of(blk, r);
-#ifdef DCS_PROBES
-                if (a.probe == 4u) { // same bytes, but each instruction writes ONE contiguous KiB (values land in the wrong places)
-                    const uint32_t blkA = min(blk, last), blkB = min(blk + 1u, last);
-                    dst = reinterpret_cast<floatx4 *>(out8 + ((uint64_t)c * a.nT16 + tt0 + blkA * tpr + slot) * out_blk +
-                                                      ((r >= 2 ? (blkB - blkA) * tpr * out_blk : 0u) + bw * 128u + (r & 1) * 1024u + lane * 16u));
-                }
-#endif
-                store(dst, o);
-            }
-        }
-    };
-    // kSplit: the partial sums of two pairs meet in LDS -- [pair h][register r][chunk][lane] x 16 bytes -- and wave w
-    // adds up (in chunk order), scales and stores register r = w
-    floatx4 *part = reinterpret_cast<floatx4 *>(staged);
-    const uint32_t n_chunks = (a.A + 63u) / 64u;
-    auto park = [&](int h, const floatx4 (&f)[4]) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            floatx4 o = {f[0][r], f[1][r], f[2][r], f[3][r]};
-            if (nan_re | nan_im) poison(r, o); // the chunk's NaN rows reach the sum through its partial sums
-            part[((h * 4 + r) * 4 + kc) * 64u + lane] = o;
-        }
-    };
-    auto gather = [&](auto whole, int h, uint32_t blk) {
-        floatx4 o = part[((h * 4 + wave) * 4 + 0) * 64u + lane];
-        for (uint32_t k = 1; k < n_chunks; k++) o = o + part[((h * 4 + wave) * 4 + k) * 64u + lane];
-        o = o * inv;
-        if (decltype(whole)::value || bb + 4u * wave < a.B) store(out_of(blk, (int)wave), o);
-    };
-    auto run = [&](auto whole) {
-#ifdef DCS_PROBES
-        if (!SPLIT && (a.probe == 1u || a.probe == 3u || a.probe == 4u)) { // stores only: what does the memory system make of this store pattern alone?
-            floatx4 f[4];
-#pragma unroll
-            for (int v = 0; v < 4; v++) f[v] = floatx4{(float)wre[0][0], (float)wre[1][1], (float)wim[0][2], (float)wim[2][3]};
-            for (uint32_t blk = 0; blk < n_blocks; blk += 2) finish(whole, blk, f);
-            return;
-        }
-        if (FORM == kDirect && a.probe == 2u) { // loads and stores, no arithmetic between them
-            for (uint32_t blk = 0; blk < n_blocks; blk += 4) {
-                arrived(cur[0]);
-                arrived(cur[1]);
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    floatx4 f[4];
-#pragma unroll
-                    for (int v = 0; v < 4; v++)
-                        f[v] = floatx4{(float)cur[h][4 * v], (float)cur[h][4 * v + 1], (float)cur[h][4 * v + 2], (float)cur[h][4 * v + 3]};
-                    finish(whole, blk + 2u * h, f);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                fetch(cur[0], blk + 4u, kc);
-                fetch(cur[1], blk + 6u, kc);
-            }
-            return;
-        }
-#endif
-        if (STAGED) { // operands from LDS: nothing to wait for but the LDS itself
-            for (uint32_t blk = 0; blk < n_blocks; blk += 2) {
-                intx4 x[4];
-                floatx4 f[4];
-                fetch(cur[0], blk, 0u);
-                transpose(cur[0], x);
-                contract(x, f);
-                finish(whole, blk, f);
-            }
-        } else { // a trip = two pairs of sample blocks (a pair past the end repeats the last block)
-            for (uint32_t blk = 0; blk < n_blocks; blk += 4) {
-                if (has_chunk) {
-                    arrived(cur[0]);
-                    arrived(cur[1]);
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        intx4 x[4];
-                        floatx4 f[4];
-                        transpose(cur[h], x);
-                        contract(x, f);
-                        if (SPLIT)
-                            park(h, f);
-                        else
-                            finish(whole, blk + 2u * h, f);
-                    }
-                }
-                if (SPLIT) {
-                    __syncthreads(); // every chunk's partial sums are in LDS
-                    gather(whole, 0, blk);
-                    gather(whole, 1, blk + 2u);
-                    __syncthreads(); // ... and read, before the next trip overwrites them
-                }
-                __builtin_amdgcn_sched_barrier(0); // the loads stay behind the stores (see above)
-                if (has_chunk) {
-                    fetch(cur[0], blk + 4u, kc);
-                    fetch(cur[1], blk + 6u, kc);
-                }
-            }
-        }
-    };
-    // the first trip's samples (kStaged: all of them, above) travel while the coefficients are made
-    if (!STAGED && !CHAIN && has_chunk) fetch(cur[0], 0, kc);
-    if (CHAIN && !idle) fetch(cur[0], 0, 0u); // the first (pair, chunk) of this wave's own blocks
-    __builtin_amdgcn_sched_barrier(0);
-#ifdef DCS_PROBES
-    if (a.probe == 3u || a.probe == 4u) { // no coefficients either: the store pattern alone
-#pragma unroll
-        for (int d = 0; d < 3; d++) wre[d] = wim[d] = intx4{(int)lane, d, 2, 1};
-    } else
-#endif
-    if ((shared_w || CHAIN ? bw < a.B : !idle) && has_chunk) make_coefficients(); // (kChain: a wave without blocks still makes its chunk)
-    if (cls == DCS_CLASS_SLOW) { // bit i: result row i (lanes i, i + 16, i + 32, i + 48 hold its antennas) has a non-finite coefficient
-        const uint64_t br = __builtin_amdgcn_ballot_w64(bad_re), bi = __builtin_amdgcn_ballot_w64(bad_im);
-        nan_re = (uint32_t)((br | (br >> 16) | (br >> 32) | (br >> 48)) & 0xffffu);
-        nan_im = (uint32_t)((bi | (bi >> 16) | (bi >> 32) | (bi >> 48)) & 0xffffu);
-    }
-    if constexpr (STAGED) {
-        uint32_t *wx = reinterpret_cast<uint32_t *>(staged + a.share_off) + bt * (4u * 6u * 64u) + lane; // [tile][q][plane][lane]
-        if (shared_w && bw < a.B) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-                if ((q & (tpr - 1u)) == slot) {
-#pragma unroll
-                    for (int d = 0; d < 3; d++) wx[(q * 6u + d) * 64u] = (uint32_t)wre[d][q], wx[(q * 6u + 3u + d) * 64u] = (uint32_t)wim[d][q];
-                }
-        }
-        __syncthreads(); // hipcc drains the LDS-DMA (vmcnt(0)) in front of it
-        if (idle) return;
-        if (shared_w) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-                if ((q & (tpr - 1u)) != slot) {
-#pragma unroll
-                    for (int d = 0; d < 3; d++) wre[d][q] = (int)wx[(q * 6u + d) * 64u], wim[d][q] = (int)wx[(q * 6u + 3u + d) * 64u];
-                }
-        }
-    } else if constexpr (CHAIN) {
-        // ---- the coefficients of this wave's chunk to LDS: [chunk][operand: re d1, d2, d3, im d1, d2, d3][lane] x 16 bytes
-        intx4 *coef = reinterpret_cast<intx4 *>(staged);
-        uint32_t *nanw = reinterpret_cast<uint32_t *>(staged + 4u * 6u * 64u * 16u); // [chunk][re, im]
-        // (make_coefficients has written this wave's chunk: operand o of chunk k at coef[(k * 6 + o) * 64 + lane])
-        if (lane == 0u) nanw[2u * wave] = has_chunk ? nan_re : 0u, nanw[2u * wave + 1u] = has_chunk ? nan_im : 0u;
-        __syncthreads(); // the kernel's only barrier
-        if (idle) return;
-        nan_re = nanw[0] | nanw[2] | nanw[4] | nanw[6]; // a non-finite coefficient in ANY chunk poisons the row
-        nan_im = nanw[1] | nanw[3] | nanw[5] | nanw[7];
-        const uint32_t n_chunks = (a.A + 63u) / 64u;
-        auto run_chain = [&](auto whole) {
-            // a step = (pair of this wave's blocks, antenna chunk), pair-major; two sample buffers in turn: the samples of step
-            // s + 1 are requested before step s is worked on (step 0 was requested before the coefficient making)
-            const uint32_t n_steps = ((n_blocks + 1u) >> 1) * n_chunks;
-            intx4 acc[4][3];
-            uint32_t s = 0, chunk = 0, blk = 0;
-            uint32_t f_s = 1u, f_chunk = 1u % n_chunks, f_blk = 2u * (1u / n_chunks); // next step to request
-            auto step = [&](uint32_t (&now)[16], uint32_t (&ahead)[16]) {
-                arrived(now);
-                if (f_s < n_steps) fetch(ahead, f_blk, f_chunk);
-                f_s++;
-                if (++f_chunk == n_chunks) f_chunk = 0u, f_blk += 2u;
-                intx4 x[4];
-                transpose(now, x);
-                if (chunk == 0u) {
-#pragma unroll
-                    for (int v = 0; v < 4; v++)
-#pragma unroll
-                        for (int d = 0; d < 3; d++) acc[v][d] = zero;
-                }
-#pragma unroll
-                for (int half = 0; half < 2; half++) { // re planes (v = 0, 2), then im planes (v = 1, 3)
-#pragma unroll
-                    for (int d = 0; d < 3; d++) {
-                        const intx4 w = coef[(chunk * 6u + 3u * (uint32_t)half + (uint32_t)d) * 64u + lane];
-#pragma unroll
-                        for (int v = half; v < 4; v += 2) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v], acc[v][d], 0, 0, 0);
-                    }
-                }
-                if (chunk + 1u == n_chunks) { // all antennas in: digits d1 = acc[v][0], d2 = acc[v][1], d3 = acc[v][2]
-                    // one result register (four beams' sixteen bytes) at a time: recombined, scaled, stored -- the sixteen floats
-                    // are never all alive beside the accumulators
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        floatx4 o;
-#pragma unroll
-                        for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * inv;
-                        if (nan_re | nan_im) poison(r, o);
-                        if (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B) store(out_of(blk, r), o);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    chunk = 0u, blk += 2u;
-                } else {
-                    chunk++;
-                }
-                s++;
-            };
-            while (s < n_steps) {
-                step(cur[0], cur[1]);
-                if (s < n_steps) step(cur[1], cur[0]);
-            }
-        };
-        if (bw + 16u <= a.B)
-            run_chain(std::true_type{});
-        else
-            run_chain(std::false_type{});
-        return;
-    } else if (has_chunk) {
-        fetch(cur[1], 2, kc);
-    }
-    if (bw + 16u <= a.B)
-        run(std::true_type{});
-    else
-        run(std::false_type{});
+    return form == kSplit ? (full ? 3 : 2) : (form == kChain ? kChainWaves : (full || form == kStaged ? 4 : 3));
 }
+
+#define BF_I8_WEIGHTED 0
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
 
 } // namespace
 
@@ -780,12 +318,15 @@ hipError_t bf_warm_module_mfma()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_beamform_i8_kernel<kStaged, true>));
 }
 
-hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, hipStream_t stream)
+namespace {
+// w: nullptr, or the weights (the int8 form's kStaged and kChain only)
+hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, hipStream_t stream)
 {
     bf_bacc_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nT16 == 0) return hipSuccess;
     if (a.A > 256u) return hipErrorInvalidValue; // not built
     const bool chain = a.fp32_chain != 0u;
+    if (w && chain) return hipErrorInvalidValue;
     // beam tiles per workgroup: as many as the beams need; the fp32 form keeps its coefficient planes in LDS and
     // takes as many as still admit 6 workgroups per CU (26 KiB each), one tile whatever it takes beyond
     // more than 64 antennas, int8 form: one beam tile per workgroup; kChain (the product's form) or, probes build only, kSplit
@@ -830,6 +371,27 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, hipStream_t stream)
     const uint64_t blocks = (uint64_t)a.C * a.n_bgroups * a.n_tgroups;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)blocks), block(64u * nw);
+    if (w) { // the product's forms only
+        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
+        if (staged_form) {
+            size_t stage_bytes = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
+            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
+                a.share_off = (uint32_t)stage_bytes;
+                stage_bytes += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
+            }
+            if (a.A == 64u)
+                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kStaged, true>), grid, block, stage_bytes, stream, a, *w);
+            else
+                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kStaged, false>), grid, block, stage_bytes, stream, a, *w);
+        } else { // kChain: as below, + the 16 beams' scale factors
+            const size_t coef_bytes = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + 16u * sizeof(float);
+            if (a.A % 64u == 0u)
+                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kChain, true>), grid, block, coef_bytes, stream, a, *w);
+            else
+                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kChain, false>), grid, block, coef_bytes, stream, a, *w);
+        }
+        return hipGetLastError();
+    }
     if (chain) {
         if (nbt == 4)
             hipLaunchKernelGGL(bf_beamform_acc_kernel<4>, grid, block, lds, stream, a);
@@ -887,4 +449,12 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, hipStream_t stream)
             hipLaunchKernelGGL((bf_beamform_i8_kernel<kChain, false>), grid, block, coef_bytes, stream, a);
     }
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream) { return launch_beamform_acc(a, nullptr, stream); }
+
+hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream)
+{
+    return launch_beamform_acc(a, &w, stream);
 }

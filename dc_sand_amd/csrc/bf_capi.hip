@@ -17,6 +17,7 @@
 
 #include "../../include/dcs_stream_staging.h" // DCS_BF_STAGE_CALLER_PINNED
 #include "bf_kernels.h"
+#include "bf_ctx_ext.h"
 #include "bf_stream_ext.h"
 
 static_assert(sizeof(dcs_delay_vals) == 16, "delay_vals must be 4 x fp32 (BeamformerParameters.h:61-66)");
@@ -98,6 +99,7 @@ int verify_div3(dcs_bf_consts *k)
 
 constexpr int kSideStreams = 4;
 struct dcs_bf_context {
+    bf_ctx_ext_head ext; // FIRST: the weighted beamformer calls of the companion library reach this library's through it
     dcs_bf_params p;
     dcs_bf_consts k;
     uint32_t n_pairs;
@@ -122,6 +124,10 @@ struct dcs_bf_context {
     float *d_terms;         // [terms_steps][pairs_pad][2]; allocated on first use (ensure_terms)
     uint32_t *d_flags;      // [terms_steps][pairs_pad/64]
     uint32_t flag_epoch;    // the beamformers' class words are tagged with the call's number instead of being zeroed per call
+    // per-input beam weights (include/dcs_beam_weights.h): what the weighted terms pre-pass makes from the caller's weights
+    // for the beamformers; allocated on the first weighted call (ensure_weights)
+    float *d_wnorm;         // [A][B]: ghat = g / s_b
+    float *d_wscale;        // [B]: s_b
     // the terms-table variant of the tiled form (large launches of <= kTermsInline time steps): its own small
     // table, allocated with the context so that those launches stay capturable
     float *d_tt_terms;      // [kTermsInline][pairs_pad][2]
@@ -377,6 +383,14 @@ int dcs_event_elapsed_ms(void *start, void *stop, float *ms)
 namespace {
 int prepare_tiled(dcs_bf_context *c, bool out16, const float *dt_dev, float dt0, uint32_t nt, uint32_t c0, uint32_t nc, void *d_out,
                   bf_kernel_launch *l, const float *dt_host, bool terms_table);
+// the weighted beamformer calls (bf_ctx_ext.h; defined with the beamformers below)
+int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
+                                        size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
+                                        void *stream);
+int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                       const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, float *d_beams,
+                                       size_t beams_bytes, void *stream);
+const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl};
 }
 
 int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
@@ -389,6 +403,7 @@ int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
     dcs_bf_context *c = new (std::nothrow) dcs_bf_context();
     if (!c) return (int)hipErrorOutOfMemory;
     std::memset(c, 0, sizeof(*c));
+    c->ext.ops = &kWeightsOps;
     c->p = *p;
     c->k = make_consts(p);
     c->n_pairs = (uint32_t)p->nr_stations * (uint32_t)p->nr_beams;
@@ -458,6 +473,8 @@ int dcs_bf_destroy(dcs_bf_context *c)
     (void)hipFree(c->d_dt);
     (void)hipFree(c->d_terms);
     (void)hipFree(c->d_flags);
+    (void)hipFree(c->d_wnorm);
+    (void)hipFree(c->d_wscale);
     (void)hipFree(c->d_tt_terms);
     (void)hipFree(c->d_tt_flags);
     if (c->h_dt) (void)hipHostFree(c->h_dt);
@@ -1062,8 +1079,25 @@ int dcs_bf_generate_at(dcs_bf_context *c, int kernel, int bitwidth, const struct
 }
 
 namespace {
+// Per-input beam weights: the normalised weights and scales of the pre-pass (bf_weights_args).  Not capturable (hipMalloc):
+// a first weighted call on a capturing stream is refused up front, as ensure_terms does.
+int ensure_weights(dcs_bf_context *c, hipStream_t stream)
+{
+    if (c->d_wnorm && c->d_wscale) return DCS_OK;
+    {
+        const int cap = refuse_if_capturing(stream);
+        if (cap != DCS_OK) return cap;
+    }
+    if (!c->d_wnorm) DCS_TRY(hipMalloc((void **)&c->d_wnorm, (size_t)c->n_pairs * sizeof(float)));
+    if (!c->d_wscale) DCS_TRY(hipMalloc((void **)&c->d_wscale, (size_t)c->p.nr_beams * sizeof(float)));
+    return DCS_OK;
+}
+
+bool weights_ok(const float *d_weights) { return d_weights && !(reinterpret_cast<uintptr_t>(d_weights) & 3u); }
+
+// d_weights: nullptr (the unweighted call) or [B][A] fp32 weights in device memory (include/dcs_beam_weights.h)
 int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna,
-                  size_t antenna_bytes, float *d_beams, size_t beams_bytes, void *stream)
+                  size_t antenna_bytes, float *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr)
 {
     if (!c || (nt && (!d_antenna || !d_beams))) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
@@ -1078,8 +1112,10 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
     hipStream_t s = as_stream(stream);
     {
         int st_alloc = ensure_terms(c, s);
+        if (st_alloc == DCS_OK && d_weights) st_alloc = ensure_weights(c, s);
         if (st_alloc != DCS_OK) return st_alloc;
     }
+    const bf_weights_args wa = {d_weights, c->d_wnorm, c->d_wscale};
     uint32_t chunk = c->terms_steps & ~15u; // time steps per launch: what the terms table holds
     if (chunk > kDtSlotFloats) chunk = kDtSlotFloats;
     if (chunk == 0) return DCS_ERR_UNSUPPORTED;
@@ -1113,7 +1149,10 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
         ta.B = B;
         ta.nt = n;
         ta.k = c->k;
-        DCS_TRY(bf_launch_bform_terms(ta, inl ? dt_val : nullptr, s));
+        if (d_weights)
+            DCS_TRY(bf_launch_bform_terms_weighted(ta, wa, inl ? dt_val : nullptr, s));
+        else
+            DCS_TRY(bf_launch_bform_terms(ta, inl ? dt_val : nullptr, s));
         bf_beamform_args a;
         std::memset(&a, 0, sizeof(a));
         a.terms = c->d_terms;
@@ -1133,7 +1172,10 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
         while (cpb > 1 && (uint64_t)((B + 15u) / 16u) * ((C + cpb - 1) / cpb) * a.nt16 < 2048u) cpb >>= 1;
         a.chan_per_block = cpb;
         a.k = c->k;
-        DCS_TRY(bf_launch_beamform(a, s));
+        if (d_weights)
+            DCS_TRY(bf_launch_beamform_weighted(a, wa, s));
+        else
+            DCS_TRY(bf_launch_beamform(a, s));
         done += n;
     }
     return DCS_OK;
@@ -1156,7 +1198,7 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *c, const float *dt, uint32_t
 
 namespace {
 int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes,
-                      float *d_beams, size_t beams_bytes, void *stream)
+                      float *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr)
 {
     if (!c || (nt && (!d_antenna || !d_beams))) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
@@ -1168,12 +1210,15 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     if (beams_bytes < (size_t)B * C * nt * 2u * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & 7u))
         return DCS_ERR_INVALID_ARGUMENT;
+    if (d_weights && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights
     if (nt == 0) return DCS_OK;
     hipStream_t s = as_stream(stream);
     {
         int st_alloc = ensure_terms(c, s);
+        if (st_alloc == DCS_OK && d_weights) st_alloc = ensure_weights(c, s);
         if (st_alloc != DCS_OK) return st_alloc;
     }
+    const bf_weights_args wa = {d_weights, c->d_wnorm, c->d_wscale};
     float dt_coeff = 0.0f; // ONE coefficient time for the whole block of samples: by value, in the kernel arguments
     int st = fill_dt(c, src, 0, 1, &dt_coeff);
     if (st != DCS_OK) return st;
@@ -1195,7 +1240,10 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     ta.B = B;
     ta.nt = 1;
     ta.k = c->k;
-    DCS_TRY(bf_launch_bform_terms(ta, nullptr, s));
+    if (d_weights)
+        DCS_TRY(bf_launch_bform_terms_weighted(ta, wa, nullptr, s));
+    else
+        DCS_TRY(bf_launch_bform_terms(ta, nullptr, s));
     bf_bacc_args a;
     std::memset(&a, 0, sizeof(a));
     a.terms = c->d_terms;
@@ -1223,7 +1271,26 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     a.nbt_force = knob(c->probe.bacc_nbt, "DCS_BACC_NBT");
     a.nw_force = knob(c->probe.bacc_waves, "DCS_BACC_WAVES");
 #endif
-    return (int)bf_launch_beamform_acc(a, s);
+    return (int)(d_weights ? bf_launch_beamform_acc_weighted(a, wa, s) : bf_launch_beamform_acc(a, s));
+}
+
+// include/dcs_beam_weights.h, reached through the table at the head of every context (bf_ctx_ext.h)
+int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
+                                        size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
+                                        void *stream)
+{
+    if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!dt && t0 % 16u) return DCS_ERR_INVALID_ARGUMENT; // whole 16-sample blocks
+    return beamform_impl(c, dt_source{dt, dt ? 0 : t0}, nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream, d_weights);
+}
+
+int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                       const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, float *d_beams,
+                                       size_t beams_bytes, void *stream)
+{
+    if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
+    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams, beams_bytes,
+                             stream, d_weights);
 }
 } // namespace
 

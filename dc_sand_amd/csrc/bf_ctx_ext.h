@@ -1,0 +1,33 @@
+// bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companion libdcs_beam_weights.so
+// (include/dcs_beam_weights.h).  Both are built from this tree together.  Every dcs_bf_context begins with a
+// bf_ctx_ext_head whose table points at the product library's implementation of the weighted beamformer calls; the
+// companion checks the arguments it can check without a device, then the table's version, and forwards.  Not a public
+// interface.
+#ifndef BF_CTX_EXT_H
+#define BF_CTX_EXT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/dcs_beamformer.h"
+
+#define BF_CTX_EXT_VERSION 1u
+
+struct bf_ctx_ext_ops {
+    uint32_t version; // BF_CTX_EXT_VERSION
+    // dt: nt fDeltaTime values, or nullptr for the times of samples t0 .. t0 + nt - 1
+    int (*generate_and_beamform_weighted)(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt,
+                                          const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                          float *d_beams, size_t beams_bytes, void *stream);
+    // dt_coeff: the coefficients' fDeltaTime, or nullptr for that of sample t_coeff
+    int (*beamform_accumulated_weighted)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                         const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                         float *d_beams, size_t beams_bytes, void *stream);
+};
+
+// the first member of struct dcs_bf_context
+struct bf_ctx_ext_head {
+    const bf_ctx_ext_ops *ops;
+};
+
+#endif // BF_CTX_EXT_H

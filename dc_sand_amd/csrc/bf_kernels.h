@@ -113,6 +113,19 @@ struct bf_bform_terms_args_inl {
 // kernel arguments
 hipError_t bf_launch_bform_terms(const bf_bform_terms_args &a, const float *dt_inline, hipStream_t stream);
 
+// Per-input beam weights (include/dcs_beam_weights.h).  The weighted pre-pass reads the caller's
+// g[b][a] and, besides the terms, writes for the beamformers ghat[a][b] = g[b][a] / s_b (the terms table's [A][B] order)
+// and s_b = max_a |g[b][a]| per beam (NaN when a weight of the beam is not finite); the terms of a pair whose weight is 0
+// are written as (0, 0), so that antenna's coefficient is finite (1, 0) whatever its delay values are.
+struct bf_weights_args {
+    const float *g; // [B][A], the caller's weights (device)
+    float *gn;      // [A][B]: ghat
+    float *gs;      // [B]: s_b
+};
+// The weighted form of bf_launch_bform_terms: one more row of workgroups makes gn and gs
+hipError_t bf_launch_bform_terms_weighted(const bf_bform_terms_args &a, const bf_weights_args &w, const float *dt_inline,
+                                          hipStream_t stream);
+
 struct bf_beamform_args {
     const float *terms;    // [nt16*16][A][B][2] for this launch's time steps
     const uint32_t *flags; // [nt16*16], epoch-tagged (bf_bform_terms_args)
@@ -128,6 +141,8 @@ struct bf_beamform_args {
     dcs_bf_consts k;
 };
 hipError_t bf_launch_beamform(const bf_beamform_args &a, hipStream_t stream);
+// The same with weights: w.gn, w.gs as bf_launch_bform_terms_weighted wrote them (w.g unused)
+hipError_t bf_launch_beamform_weighted(const bf_beamform_args &a, const bf_weights_args &w, hipStream_t stream);
 
 // Beamformer with coefficient reuse on the matrix cores (bf_beamform_mfma.hip): the coefficients of ONE time
 // (terms table [A][B] from bf_launch_bform_terms with nt = 1) applied to nT16 blocks of 16 samples.
@@ -176,6 +191,8 @@ __host__ __device__ inline uint32_t bf_xcd_grouped(uint32_t w, uint32_t total, u
 #define BACC_KNOB(a, f) 0u
 #endif
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream);
+// The same with weights (int8 form only: kStaged and kChain; a.fp32_chain must be 0)
+hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
 // One coefficient per lane, one time step (reference kernel a1's shape).

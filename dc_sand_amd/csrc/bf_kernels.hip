@@ -481,8 +481,59 @@ __global__ void __launch_bounds__(kBlock) bf_terms_kernel(const bf_terms_args a)
 // lines per antenna (L2-resident, reused by every channel); the int8 samples of
 // one (channel, 16 times) block are staged in LDS once per channel.
 // ---------------------------------------------------------------------------
-template <bool INL> // INL: fDeltaTime of up to kDtInline time steps by value, behind the arguments proper
-__global__ void __launch_bounds__(kBlock) bf_bform_terms_kernel(const std::conditional_t<INL, bf_bform_terms_args_inl, bf_bform_terms_args> args)
+//
+// WEIGHTED (include/dcs_beam_weights.h): the terms of a pair whose weight g[b][a] is 0 are written as (0, 0), whose
+// coefficient (1, 0) is finite and of the lowest class whatever the delay values are; and one more row of workgroups
+// (blockIdx.y == 0, dispatched first: its chain of dependent steps is the longest; time step t is row t + 1) makes the
+// normalised weights: a wave per beam finds s_b = max_a |g[b][a]| (NaN when a weight is
+// not finite; max is exact, so the order does not matter) and writes ghat[a][b] = RN(g[b][a] / s_b) (0 for s_b == 0)
+// and s_b.  The beamformers read both after this launch.
+template <bool INL>
+using bf_bform_terms_param = std::conditional_t<INL, bf_bform_terms_args_inl, bf_bform_terms_args>;
+template <bool INL>
+struct bf_bform_terms_wargs {
+    bf_bform_terms_param<INL> t;
+    bf_weights_args w;
+};
+
+__device__ __forceinline__ void bform_weights_row(const bf_bform_terms_args &a, const bf_weights_args &w)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = gridDim.x * (kBlock / 64u);
+    for (uint32_t beam = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); beam < a.B; beam += waves) {
+        const float *g = w.g + (uint64_t)beam * a.A;
+        float m = 0.0f;
+        bool bad = false;
+        float v[4]; // the first 256 antennas' weights stay in registers for the second pass
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t ant = lane + 64u * k;
+            v[k] = ant < a.A ? g[ant] : 0.0f;
+        }
+        auto note = [&](float x) {
+            x = fabsf(x);
+            m = fmaxf(m, x);
+            bad |= !(x <= 3.40282347e38f);
+        };
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) note(v[k]);
+        for (uint32_t ant = lane + 256u; ant < a.A; ant += 64u) note(g[ant]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        const float s = __builtin_amdgcn_ballot_w64(bad) != 0u ? __builtin_nanf("") : m;
+        auto ghat = [&](float x) { return s == 0.0f ? 0.0f : __fdiv_rn(x, s); };
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t ant = lane + 64u * k;
+            if (ant < a.A) w.gn[(uint64_t)ant * a.B + beam] = ghat(v[k]);
+        }
+        for (uint32_t ant = lane + 256u; ant < a.A; ant += 64u) w.gn[(uint64_t)ant * a.B + beam] = ghat(g[ant]);
+        if (lane == 0u) w.gs[beam] = s;
+    }
+}
+
+template <bool INL, bool WEIGHTED> // INL: fDeltaTime of up to kDtInline time steps by value, behind the arguments proper
+__device__ __forceinline__ void bform_terms_body(const bf_bform_terms_param<INL> &args, const bf_weights_args &w)
 {
     const bf_bform_terms_args &a = [&]() -> const bf_bform_terms_args & {
         if constexpr (INL)
@@ -490,8 +541,14 @@ __global__ void __launch_bounds__(kBlock) bf_bform_terms_kernel(const std::condi
         else
             return args;
     }();
+    if constexpr (WEIGHTED) {
+        if (blockIdx.y == 0u) {
+            bform_weights_row(a, w);
+            return;
+        }
+    }
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x; // table index b*A + a
-    const uint32_t t = blockIdx.y;
+    const uint32_t t = WEIGHTED ? blockIdx.y - 1u : blockIdx.y;
     uint32_t cls = DCS_CLASS_FAST_LOW;
     if (p < a.n_pairs) {
         const floatx4 raw = *reinterpret_cast<const floatx4 *>(&a.delays[p]);
@@ -507,6 +564,9 @@ __global__ void __launch_bounds__(kBlock) bf_bform_terms_kernel(const std::condi
         else
             dt = a.dt_dev ? a.dt_dev[t] : a.dt0;
         dcs_pair_terms(d, dt, a.k.dHalfChannels, a.k.dDenominator, &fRate, &fPhase0);
+        if constexpr (WEIGHTED) {
+            if (w.g[p] == 0.0f) fRate = 0.0f, fPhase0 = 0.0f; // a flagged antenna: finite, lowest class
+        }
         cls = dcs_pair_class(fRate, fPhase0, a.k.fRotBoundScale, a.k.fLowDegLimit);
         const uint32_t b = p / a.A, ant = p - b * a.A;
         *reinterpret_cast<floatx2 *>(a.terms + 2u * ((uint64_t)t * a.n_pairs + (uint64_t)ant * a.B + b)) =
@@ -517,137 +577,27 @@ __global__ void __launch_bounds__(kBlock) bf_bform_terms_kernel(const std::condi
     if (cls != DCS_CLASS_FAST_LOW) atomicMax(&a.flags[t], (a.epoch << 2) | cls);
 }
 
+template <bool INL>
+__global__ void __launch_bounds__(kBlock) bf_bform_terms_kernel(const bf_bform_terms_param<INL> args)
+{
+    bform_terms_body<INL, false>(args, bf_weights_args{});
+}
+
+template <bool INL>
+__global__ void __launch_bounds__(kBlock) bf_bform_terms_w_kernel(const bf_bform_terms_wargs<INL> args)
+{
+    bform_terms_body<INL, true>(args.t, args.w);
+}
+
 // CH channels per pass: a lane's terms load and the LDS sample reads are shared by CH
 // independent coefficient chains (more ILP, fewer loads per product).
 constexpr uint32_t kAntChunk = 128; // antennas staged in LDS at a time (as fp32: 16 KiB per channel)
-template <int CH>
-__global__ void __launch_bounds__(kBlock) bf_beamform_kernel(const bf_beamform_args a)
-{
-    extern __shared__ __attribute__((aligned(16))) float s_ant[]; // [CH][A][16][2], int8 samples converted once
-
-    const uint32_t bid = blockIdx.x;
-    const uint32_t bg = bid % a.n_bgroups;
-    const uint32_t rest = bid / a.n_bgroups;
-    const uint32_t cb = rest % a.n_cblocks;
-    const uint32_t tex = rest / a.n_cblocks; // 16-sample block within this launch
-
-    const uint32_t b_local = threadIdx.x & 15u, t_in = threadIdx.x >> 4;
-    const uint32_t b = bg * 16u + b_local;
-    const uint32_t t = tex * 16u + t_in; // time index within this launch's terms table
-    const bool live = b < a.B;
-
-    // highest pair class over these 16 time steps (bf_bform_terms_kernel)
-    const uint32_t fw = a.flags[tex * 16u + (threadIdx.x & 15u)];
-    const uint32_t fl = (fw >> 2) == a.epoch ? (fw & 3u) : DCS_CLASS_FAST_LOW; // bf_bform_terms_kernel's epoch-tagged word
-    const int slow = __syncthreads_or((int)(fl == DCS_CLASS_SLOW));
-    const int high = __syncthreads_or((int)(fl != DCS_CLASS_FAST_LOW));
-
-    const float D = a.k.fDenominator, y = a.k.fRcpDenominator;
-    const float *tp = a.terms + 2u * ((uint64_t)t * a.A * a.B + (live ? b : 0u));
-    const uint32_t cbeg = cb * a.chan_per_block;
-    const uint32_t cend = min(cbeg + a.chan_per_block, a.C);
-    const uint32_t tex_g = a.tex0 + tex; // 16-sample block within the whole tensor
-    const uint32_t words = a.A * 8u;     // dwords of one [A][16][2] int8 block
-    const uint32_t sa = min(kAntChunk, a.A); // antennas per staged chunk = stride of a channel's LDS region
-
-    for (uint32_t c = cbeg; c < cend; c += CH) {
-        float fChan[CH], acc_re[CH], acc_im[CH];
-#pragma unroll
-        for (int h = 0; h < CH; h++) {
-            fChan[h] = (float)(c + h);
-            acc_re[h] = 0.0f;
-            acc_im[h] = 0.0f;
-        }
-        // antennas in chunks of kAntChunk (the LDS staging buffer); the running sums carry
-        // across chunks, so the summation order stays the verifier's (a = 0, 1, 2, ...)
-        for (uint32_t a0 = 0; a0 < a.A; a0 += kAntChunk) {
-            const uint32_t na = min(kAntChunk, a.A - a0);
-            const uint32_t cw = na * 8u; // dwords of this chunk's [na][16][2] int8 block
-            __syncthreads();             // previous chunk's readers are done
-#pragma unroll
-            for (int h = 0; h < CH; h++) {
-                if (c + h < cend) {
-                    const uint32_t *src = reinterpret_cast<const uint32_t *>(a.ant) +
-                                          ((uint64_t)(c + h) * a.nt16_total + tex_g) * words + (uint64_t)a0 * 8u;
-                    for (uint32_t i = threadIdx.x; i < cw; i += kBlock) {
-                        const uint32_t w = src[i]; // {re, im, re, im} of two consecutive (antenna, time) samples
-                        const floatx4 f = {(float)(int8_t)(w & 0xffu), (float)(int8_t)((w >> 8) & 0xffu),
-                                           (float)(int8_t)((w >> 16) & 0xffu), (float)(int8_t)(w >> 24)};
-                        *reinterpret_cast<floatx4 *>(&s_ant[((size_t)h * sa * 8u + i) * 4u]) = f;
-                    }
-                }
-            }
-            __syncthreads();
-
-            auto sample = [&](int h, uint32_t al, float &sre, float &sim) {
-                const floatx2 v = *reinterpret_cast<const floatx2 *>(&s_ant[(((size_t)h * sa + al) * 16u + t_in) * 2u]);
-                sre = v.x;
-                sim = v.y;
-            };
-            if (!slow) {
-                dispatch_fast(a.k.uDiv3Exact != 0u, !high, [&](auto div3, auto lowdeg) {
-                    // terms of antenna al+2 are requested while al is computed (L2 latency >> one step)
-                    auto terms_of = [&](uint32_t al) {
-                        return *reinterpret_cast<const floatx2 *>(tp + 2u * (uint64_t)(a0 + min(al, na - 1u)) * a.B);
-                    };
-                    auto products = [&](uint32_t al, const floatx2 kp) {
-#pragma unroll
-                        for (int h = 0; h < CH; h++) {
-                            float re, im, sre, sim;
-                            coeff_fast<decltype(div3)::value, decltype(lowdeg)::value>(kp.x, kp.y, fChan[h], D, y, re, im);
-                            sample(h, al, sre, sim);
-                            const float pr = re * sre, pi = im * sim; // product, then sum: two roundings each
-                            acc_re[h] = acc_re[h] + pr;
-                            acc_im[h] = acc_im[h] + pi;
-                        }
-                    };
-                    // three registers in rotation: step al uses one while al+2 is loaded into the one
-                    // step al-1 has just finished with
-                    floatx2 qa = terms_of(0), qb = terms_of(1), qc;
-                    uint32_t al = 0;
-                    for (; al + 2 < na; al += 3) {
-                        qc = terms_of(al + 2);
-                        products(al, qa);
-                        qa = terms_of(al + 3);
-                        products(al + 1, qb);
-                        qb = terms_of(al + 4);
-                        products(al + 2, qc);
-                    }
-                    if (al < na) products(al, qa);
-                    if (al + 1 < na) products(al + 1, qb);
-                });
-            } else {
-                // channel outermost and unrolled (h is a compile-time index: the accumulators stay in
-                // registers, nothing goes to scratch), antennas in order inside -- the same sums
-#pragma unroll
-                for (int h = 0; h < CH; h++) {
-                    float are = acc_re[h], aim = acc_im[h];
-                    for (uint32_t al = 0; al < na; al++) {
-                        const floatx2 kp = *reinterpret_cast<const floatx2 *>(tp + 2u * (uint64_t)(a0 + al) * a.B);
-                        float re, im, sre, sim;
-                        coeff_slow(kp.x, kp.y, fChan[h], D, re, im);
-                        sample(h, al, sre, sim);
-                        const float pr = re * sre, pi = im * sim;
-                        are = are + pr;
-                        aim = aim + pi;
-                    }
-                    acc_re[h] = are;
-                    acc_im[h] = aim;
-                }
-            }
-        }
-        if (live) {
-#pragma unroll
-            for (int h = 0; h < CH; h++) {
-                if (c + h < cend) {
-                    floatx2 *dst = reinterpret_cast<floatx2 *>(a.beams) +
-                                   (((uint64_t)(c + h) * a.nt16_total + tex_g) * a.B + b) * 16u + t_in;
-                    *dst = floatx2{acc_re[h], acc_im[h]};
-                }
-            }
-        }
-    }
-}
+#define BF_FUSED_WEIGHTED 0
+#include "bf_beamform_kernel.inc"
+#undef BF_FUSED_WEIGHTED
+#define BF_FUSED_WEIGHTED 1
+#include "bf_beamform_kernel.inc"
+#undef BF_FUSED_WEIGHTED
 
 // ---------------------------------------------------------------------------
 // One coefficient per lane (the launch shape of the reference's
@@ -964,7 +914,36 @@ hipError_t bf_launch_bform_terms(const bf_bform_terms_args &a, const float *dt_i
     return hipGetLastError();
 }
 
-hipError_t bf_launch_beamform(const bf_beamform_args &a_in, hipStream_t stream)
+hipError_t bf_launch_bform_terms_weighted(const bf_bform_terms_args &a, const bf_weights_args &w, const float *dt_inline,
+                                          hipStream_t stream)
+{
+    if (a.nt == 0 || a.n_pairs == 0) return hipSuccess;
+    if (a.nt > 65534u) return hipErrorInvalidValue;
+    const dim3 grid((a.n_pairs + kBlock - 1) / kBlock, a.nt + 1u); // row 0: the normalised weights
+    if (dt_inline != nullptr && a.nt > 1u) {
+        if (a.nt > kDtInline) return hipErrorInvalidValue;
+        bf_bform_terms_wargs<true> ai;
+        ai.t.a = a;
+        std::memcpy(ai.t.dt_inline, dt_inline, (size_t)a.nt * sizeof(float));
+        ai.w = w;
+        hipLaunchKernelGGL(bf_bform_terms_w_kernel<true>, grid, dim3(kBlock), 0, stream, ai);
+        return hipGetLastError();
+    }
+    bf_bform_terms_wargs<false> b;
+    b.t = a;
+    b.w = w;
+    if (dt_inline != nullptr) {
+        b.t.dt_dev = nullptr;
+        b.t.dt0 = dt_inline[0];
+    } else if (a.dt_dev == nullptr && a.nt != 1u) {
+        return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(bf_bform_terms_w_kernel<false>, grid, dim3(kBlock), 0, stream, b);
+    return hipGetLastError();
+}
+
+namespace {
+hipError_t launch_beamform(const bf_beamform_args &a_in, const bf_weights_args *w, hipStream_t stream)
 {
     bf_beamform_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nt16 == 0) return hipSuccess;
@@ -978,12 +957,27 @@ hipError_t bf_launch_beamform(const bf_beamform_args &a_in, hipStream_t stream)
     const int ch = (a.chan_per_block >= 4 && na <= 64u) ? 4 : (a.chan_per_block >= 2 ? 2 : 1);
     const size_t lds = (size_t)na * 32u * sizeof(float) * (size_t)ch;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (ch == 4)
+    if (w) {
+        if (ch == 4)
+            hipLaunchKernelGGL(bf_beamform_w_kernel<4>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
+        else if (ch == 2)
+            hipLaunchKernelGGL(bf_beamform_w_kernel<2>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
+        else
+            hipLaunchKernelGGL(bf_beamform_w_kernel<1>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
+    } else if (ch == 4)
         hipLaunchKernelGGL(bf_beamform_kernel<4>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
     else if (ch == 2)
         hipLaunchKernelGGL(bf_beamform_kernel<2>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
     else
         hipLaunchKernelGGL(bf_beamform_kernel<1>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t bf_launch_beamform(const bf_beamform_args &a, hipStream_t stream) { return launch_beamform(a, nullptr, stream); }
+
+hipError_t bf_launch_beamform_weighted(const bf_beamform_args &a, const bf_weights_args &w, hipStream_t stream)
+{
+    return launch_beamform(a, &w, stream);
 }
 

@@ -188,6 +188,42 @@ class SteeringCoefficientGenerator:
                 "dcs_bf_beamform_accumulated_dt",
             )
 
+    # -- per-input beam weights (include/dcs_beam_weights.h, companion library libdcs_beam_weights.so): d_weights is a
+    #    device [nr_beams][nr_stations] fp32 array (:class:`dc_sand_amd.beam_weights.BeamWeights.device_ptr`), read when
+    #    the work runs on the stream
+    def generate_and_beamform_weighted(self, d_antenna, antenna_bytes: int, d_weights, d_beams, beams_bytes: int,
+                                       t0: int = 0, nt: int | None = None, dt=None, stream=None) -> None:
+        """:meth:`generate_and_beamform` (or, with ``dt``, :meth:`generate_and_beamform_dt`) with per-input beam weights."""
+        wl = _lib.beam_weights_lib()
+        if dt is not None:
+            a = _dt_array(dt)
+            check(wl.dcs_bf_generate_and_beamform_weighted_dt(c_void_p(self._h), a.ctypes.data_as(ctypes.POINTER(c_float)), a.size,
+                                                             c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_weights)),
+                                                             c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
+                  "dcs_bf_generate_and_beamform_weighted_dt")
+            return
+        nt = self.params.NR_SAMPLES_PER_CHANNEL if nt is None else nt
+        check(wl.dcs_bf_generate_and_beamform_weighted(c_void_p(self._h), int(t0), int(nt), c_void_p(int(d_antenna)), int(antenna_bytes),
+                                                       c_void_p(int(d_weights)), c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
+              "dcs_bf_generate_and_beamform_weighted")
+
+    def beamform_accumulated_weighted(self, d_antenna, antenna_bytes: int, d_weights, d_beams, beams_bytes: int, nt: int,
+                                      t_coeff: int | None = None, dt_coeff: float | None = None, stream=None) -> None:
+        """:meth:`beamform_accumulated` with per-input beam weights."""
+        if (t_coeff is None) == (dt_coeff is None):
+            raise ValueError("give exactly one of t_coeff / dt_coeff")
+        wl = _lib.beam_weights_lib()
+        if dt_coeff is None:
+            check(wl.dcs_bf_beamform_accumulated_weighted(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
+                                                          int(antenna_bytes), c_void_p(int(d_weights)), c_void_p(int(d_beams)),
+                                                          int(beams_bytes), _s(stream)),
+                  "dcs_bf_beamform_accumulated_weighted")
+        else:
+            check(wl.dcs_bf_beamform_accumulated_weighted_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
+                                                             c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_weights)),
+                                                             c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
+                  "dcs_bf_beamform_accumulated_weighted_dt")
+
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")
     _TUNING_DEFAULTS = (0, -1, 0, 0, 0, 0, -1, -1, 0, 0)

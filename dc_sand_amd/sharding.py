@@ -51,6 +51,14 @@ def slice_table(global_table: np.ndarray, global_params: BeamformerParameters, s
     return np.ascontiguousarray(t[:, shard.beam_lo:shard.beam_hi]).ravel()
 
 
+def slice_weights(global_weights: np.ndarray, global_params: BeamformerParameters, shard: BeamShard) -> np.ndarray:
+    """The ``[B_local][A]`` beam weights of a shard (include/dcs_beam_weights.h): the rows ``beam_lo:beam_hi`` of the
+    global ``[B][A]`` array, the beams :func:`slice_table` gives the shard.  On the device the same rows start at
+    ``d_global_weights + beam_lo * A`` (:meth:`dc_sand_amd.beam_weights.BeamWeights.device_ptr`)."""
+    w = np.asarray(global_weights, dtype=np.float32).reshape(global_params.NR_BEAMS, global_params.NR_STATIONS)
+    return np.ascontiguousarray(w[shard.beam_lo:shard.beam_hi])
+
+
 def broadcast_table(table_bytes, src: int = 0, group=None):
     """Broadcast the table (a ``torch.uint8`` tensor of A*B*16 bytes, CPU for
     gloo or CUDA for RCCL) from ``src`` in place; returns the tensor."""

@@ -1,0 +1,388 @@
+"""Per-input beam weights on the GPU (include/dcs_beam_weights.h): both beamformers against the
+numerical contract -- unit weights bit-identical to the unweighted calls, 2^k weights exactly scaled, flagged antennas
+(weight 0) contributing nothing even with non-finite delay values, all-zero beams 0, a non-finite weight poisoning its
+own beam only, random weights within the derived bounds -- and the calls' plumbing: the fp32-chain refusal, capture
+with weights changed between replays, beam shards.  Every weighted call writes into a buffer with a canary behind the
+output tensor, which must stay untouched."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from conftest import rand_table
+
+pytestmark = pytest.mark.gpu
+
+# test_beamform_accumulated_on_the_matrix_cores's shapes: staged and kChain, ragged antennas / beams, several beam groups
+# and several workgroups per channel
+ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 48), (8, 4, 5, 16), (37, 21, 9, 48),
+              (130, 3, 4, 16), (4, 40, 7, 32), (9, 5, 3, 16), (129, 33, 2, 32), (256, 17, 2, 16), (1, 1, 1, 16),
+              (66, 70, 2, 80), (128, 16, 3, 64), (192, 48, 2, 32), (200, 20, 2, 32), (64, 1024, 1, 32),
+              (64, 32, 3, 112), (64, 24, 2, 272), (64, 16, 2, 592), (48, 16, 3, 48), (64, 64, 2, 272),
+              (256, 64, 2, 272), (100, 20, 3, 112), (256, 16, 1, 1600), (65, 16, 2, 48),
+              (64, 1024, 9, 32), (130, 20, 9, 32), (256, 64, 9, 16), (192, 48, 11, 48),
+              (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
+FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
+                (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
+T_COEFF = 9
+CANARY = 64
+
+
+class Case:
+    """One context, its samples and output buffer (with a canary), and both beamformers with and without weights."""
+
+    def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None):
+        from dc_sand_amd import BeamformerParameters
+        from dc_sand_amd.generator import SteeringCoefficientGenerator
+
+        self.gpu, self.oracle = gpu, oracle
+        self.A, self.B, self.C, self.nt = A, B, C, nt
+        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        self.op = oracle.params_from(self.bp)
+        self.table = rand_table(self.bp.n_pairs, seed=A + B + seed) if table is None else table  # [b*A + a]
+        self.ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+        self.g = SteeringCoefficientGenerator(self.bp)
+        self.g.upload_delays(self.table)
+        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
+        gpu.memcpy_htod(self.d_ant, self.ant)
+        self.shape = (C, nt // 16, B, 16, 2)
+        self.nbytes = int(np.prod(self.shape)) * 4
+        self.d_beams = gpu.mem_alloc(self.nbytes + CANARY)
+        self.d_w = gpu.mem_alloc(B * A * 4)
+
+    def set_ant(self, ant):
+        self.ant = ant
+        self.gpu.memcpy_htod(self.d_ant, ant)
+
+    def set_table(self, table):
+        self.table = table
+        self.g.upload_delays(table)
+
+    def run(self, kind, w=None, stream=None):
+        """kind 'acc' / 'fused'; w: None (unweighted) or a [B][A] array (copied to the device first)."""
+        gpu = self.gpu
+        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
+        if w is not None:
+            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
+        if kind == "acc":
+            if w is None:
+                self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, t_coeff=T_COEFF)
+            else:
+                self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt,
+                                                     t_coeff=T_COEFF)
+        else:
+            if w is None:
+                self.g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, t0=0, nt=self.nt)
+            else:
+                self.g.generate_and_beamform_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, t0=0,
+                                                      nt=self.nt)
+        return self.read()
+
+    def read(self):
+        host = np.empty(self.nbytes + CANARY, dtype=np.uint8)
+        self.gpu.memcpy_dtoh(host, self.d_beams)
+        assert np.all(host[self.nbytes:] == 0xFF), "written past the output tensor"
+        return host[:self.nbytes].view(np.float32).reshape(self.shape).copy()
+
+    def coefficients(self, dts):
+        """The oracle's fp32 coefficients [t][c][a][b][2] (the table turned to the generator's [a*B + b])."""
+        t_ab = np.ascontiguousarray(self.table.reshape(self.B, self.A).T).ravel()
+        return self.oracle.generate_dt(self.op, t_ab, dts)
+
+    def close(self):
+        self.g.close()
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.uint32)
+
+
+def normalise(w):
+    """s_b and ghat as the contract defines them (fp32, correctly rounded)."""
+    w = np.asarray(w, dtype=np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = np.abs(w).max(axis=1)
+        s = np.where(np.all(np.isfinite(w), axis=1), s, np.float32(np.nan)).astype(np.float32)
+        gh = np.where(s[:, None] == 0, np.float32(0), w / s[:, None]).astype(np.float32)
+    return s, gh
+
+
+def acc_bound_check(case, w, got):
+    """Fixed-point form: within 3.7e-7 * s_b * sum_a |x_a| + 3e-7 * |exact| of the fp64 sum of g * c * x over the
+    oracle's fp32 coefficients."""
+    from dc_sand_amd.generator import delta_times
+
+    A, B, C, nt = case.A, case.B, case.C, case.nt
+    s, _ = normalise(w)
+    coef = case.coefficients(delta_times(case.bp, T_COEFF, 1)[0])[0].astype(np.float64)  # [c][a][b][2]
+    x = case.ant.astype(np.float64)
+    gw = np.asarray(w, dtype=np.float64).T  # [a][b]
+    exact = np.einsum("cabk,ctaik->ctbik", coef * gw[None, :, :, None], x)
+    mag = np.abs(x).sum(axis=2)[:, :, None, :, :] * s.astype(np.float64)[None, None, :, None, None]
+    err = np.abs(got.astype(np.float64) - exact)
+    assert np.all(err <= 3.7e-7 * mag + 3e-7 * np.abs(exact) + 1e-30), float((err - 3.7e-7 * mag - 3e-7 * np.abs(exact)).max())
+
+
+def fused_expected(case, w):
+    """The per-sample rule restated in fp32 over the oracle's coefficients: sum += RN(RN(ghat * w) * x) in antenna order,
+    then RN(s_b * sum)."""
+    from dc_sand_amd.generator import delta_times
+
+    A, B, C, nt = case.A, case.B, case.C, case.nt
+    s, gh = normalise(w)
+    coef = case.coefficients(delta_times(case.bp, 0, nt))  # [t][c][a][b][2]
+    x = case.ant.astype(np.float32).transpose(0, 1, 3, 2, 4).reshape(C, nt, A, 2)  # [c][t][a][2]
+    acc = np.zeros((nt, C, B, 2), dtype=np.float32)
+    for a in range(A):
+        wp = (gh[:, a][None, None, :, None] * coef[:, :, a, :, :]).astype(np.float32)  # [t][c][b][2]
+        xa = x[:, :, a, :].transpose(1, 0, 2)[:, :, None, :]  # [t][c][1][2]
+        acc = (acc + (wp * xa).astype(np.float32)).astype(np.float32)
+    out = (s[None, None, :, None] * acc).astype(np.float32)  # [t][c][b][2]
+    return out.reshape(nt // 16, 16, C, B, 2).transpose(2, 0, 3, 1, 4)
+
+
+def random_weights(rng, B, A, zero_beam=True):
+    w = (rng.choice([-1.0, 1.0], size=(B, A)) * 10.0 ** rng.uniform(-3, 3, size=(B, A))).astype(np.float32)
+    if zero_beam:
+        w[rng.integers(0, B)] = 0.0
+    return w
+
+
+@pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
+def test_unit_and_power_of_two_weights_on_the_matrix_cores(gpu, oracle, A, B, C, nt):
+    c = Case(gpu, oracle, A, B, C, nt)
+    base = c.run("acc")
+    ones = c.run("acc", np.ones((B, A), np.float32))
+    assert np.array_equal(bits(ones), bits(base))
+    for k in (0.25, 8.0):
+        got = c.run("acc", np.full((B, A), k, np.float32))
+        assert np.array_equal(bits(got), bits((base * np.float32(k)).astype(np.float32))), k
+    c.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt", FUSED_SHAPES)
+def test_unit_and_power_of_two_weights_in_the_fused_kernel(gpu, oracle, A, B, C, nt):
+    c = Case(gpu, oracle, A, B, C, nt)
+    base = c.run("fused")
+    ones = c.run("fused", np.ones((B, A), np.float32))
+    assert np.array_equal(bits(ones), bits(base))
+    for k in (0.25, 8.0):
+        got = c.run("fused", np.full((B, A), k, np.float32))
+        assert np.array_equal(bits(got), bits((base * np.float32(k)).astype(np.float32))), k
+    # per beam: beam b weighted 2^(b % 5 - 2)
+    kb = (2.0 ** (np.arange(B) % 5 - 2)).astype(np.float32)
+    got = c.run("fused", np.repeat(kb[:, None], A, axis=1))
+    assert np.array_equal(bits(got), bits((base * kb[None, None, :, None, None]).astype(np.float32)))
+    c.close()
+
+
+@pytest.mark.parametrize("kind", ["acc", "fused"])
+@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (37, 21, 4, 48), (130, 20, 2, 32), (256, 17, 2, 16), (4, 40, 3, 32)])
+def test_flagged_antennas_contribute_nothing(gpu, oracle, kind, A, B, C, nt):
+    rng = np.random.default_rng(A * B)
+    c = Case(gpu, oracle, A, B, C, nt)
+    w = (rng.random((B, A)) < 0.7).astype(np.float32)
+    w[0, :] = 0.0   # an all-zero beam
+    w[-1, :] = 1.0  # a beam with every antenna
+    if A > 1:
+        w[min(1, B - 1), 0] = -0.0
+    got = c.run(kind, w)
+    assert np.all(got[:, :, 0] == 0)
+    ant = c.ant.copy()
+    for b in range(B):  # per beam, the samples with that beam's flagged antennas zeroed
+        z = ant.copy()
+        z[:, :, w[b] == 0] = 0
+        c.set_ant(z)
+        ref = c.run(kind)
+        assert np.all(got[:, :, b] == ref[:, :, b]), b
+        if b >= 3:
+            break
+    c.set_ant(ant)
+    # a flagged antenna (all beams) whose delay values are NaN or infinite: the beams stay finite and are the bits of the
+    # same call with finite delay values there
+    flag = A // 2
+    w2 = np.ones((B, A), np.float32)
+    w2[:, flag] = 0.0
+    finite = c.run(kind, w2)
+    assert np.all(np.isfinite(finite))
+    bad = c.table.copy().reshape(B, A)
+    bad["fDelay_s"][:, flag] = np.nan
+    bad["fDelayRate_sps"][:, flag] = np.inf
+    bad["fPhase_rad"][:, flag] = np.nan
+    c.set_table(bad.ravel())
+    got = c.run(kind, w2)
+    assert np.array_equal(bits(got), bits(finite))
+    # ... while unflagged, such an antenna turns every beam to NaN (what the weights are there to prevent)
+    assert np.all(np.isnan(c.run(kind, np.ones((B, A), np.float32))))
+    c.close()
+
+
+@pytest.mark.parametrize("kind", ["acc", "fused"])
+def test_a_non_finite_weight_poisons_its_beam_only(gpu, oracle, kind):
+    A, B, C, nt = 70, 20, 3, 32
+    c = Case(gpu, oracle, A, B, C, nt)
+    w = random_weights(np.random.default_rng(5), B, A, zero_beam=False)
+    ref = c.run(kind, w)
+    assert np.all(np.isfinite(ref))
+    for b, v in ((3, np.inf), (17, np.nan), (0, -np.inf)):
+        w2 = w.copy()
+        w2[b, A // 3] = v
+        got = c.run(kind, w2)
+        assert np.all(np.isnan(got[:, :, b])), (b, v)
+        others = [i for i in range(B) if i != b]
+        assert np.array_equal(bits(got[:, :, others]), bits(ref[:, :, others]))
+    c.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 4, 64), (37, 21, 3, 48), (129, 33, 2, 32), (256, 64, 2, 32), (1, 1, 1, 16),
+                                      (64, 128, 2, 48), (192, 48, 2, 32)])
+def test_random_weights_on_the_matrix_cores_within_the_bound(gpu, oracle, A, B, C, nt):
+    c = Case(gpu, oracle, A, B, C, nt)
+    w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=B > 1)
+    got = c.run("acc", w)
+    assert np.all(np.isfinite(got))
+    acc_bound_check(c, w, got)
+    c.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 32), (37, 21, 2, 48), (130, 3, 2, 16), (258, 2, 2, 16), (1, 1, 1, 16)])
+def test_random_weights_in_the_fused_kernel_within_the_bound(gpu, oracle, A, B, C, nt):
+    c = Case(gpu, oracle, A, B, C, nt)
+    w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=B > 1)
+    got = c.run("fused", w)
+    exp = fused_expected(c, w)
+    s, _ = normalise(w)
+    assert np.all(np.isfinite(got))
+    assert np.all(np.abs(got - exp) <= 2e-5 * A * s[None, None, :, None, None] + 1e-6)
+    c.close()
+
+
+def test_random_weights_seeded_fuzz(gpu, oracle):
+    """40 seeded cases over antennas <= 256, beams, channels and sample blocks, both beamformers, each within its bound."""
+    rng = np.random.default_rng(20261016)
+    for case in range(40):
+        A = int(rng.choice([1, 3, 17, 63, 64, 65, 128, 129, 192, 200, 256])) if case % 2 else int(rng.integers(1, 257))
+        B = int(rng.integers(1, 80))
+        C = int(rng.integers(1, 4))
+        nt = 16 * int(rng.integers(1, 6))
+        c = Case(gpu, oracle, A, B, C, nt, seed=case)
+        w = random_weights(rng, B, A, zero_beam=B > 1)
+        got = c.run("acc", w)
+        acc_bound_check(c, w, got)
+        if case % 4 == 0:
+            got = c.run("fused", w)
+            s, _ = normalise(w)
+            assert np.all(np.abs(got - fused_expected(c, w)) <= 2e-5 * A * s[None, None, :, None, None] + 1e-6), (A, B, C, nt)
+        c.close()
+
+
+def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle):
+    from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
+
+    c = Case(gpu, oracle, 64, 16, 2, 32)
+    c.g.set_tuning(math_mode=8)
+    gpu.memcpy_htod(c.d_w, np.ones((16, 64), np.float32))
+    gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
+    for kw in ({"t_coeff": T_COEFF}, {"dt_coeff": 0.0}):
+        with pytest.raises(DcsError) as e:
+            c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, c.nt, **kw)
+        assert e.value.status == DCS_ERR_UNSUPPORTED
+    gpu.synchronize()
+    assert np.all(c.read().view(np.uint32) == 0xFFFFFFFF)
+    c.close()
+
+
+@pytest.mark.parametrize("kind", ["acc", "fused"])
+def test_captured_call_picks_up_new_weights_on_replay(gpu, oracle, kind):
+    A, B, C, nt = 130, 20, 3, 64
+    c = Case(gpu, oracle, A, B, C, nt)
+    rng = np.random.default_rng(3)
+    w1 = random_weights(rng, B, A)
+    w2 = random_weights(rng, B, A)
+    ref2 = c.run(kind, w2)  # (also the plain call the capture rule asks for first)
+    ref1 = c.run(kind, w1)
+    s = gpu.Stream()
+    hip = ctypes.CDLL("libamdhip64.so")
+    V = ctypes.c_void_p
+    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
+    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
+    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
+    hip.hipGraphLaunch.argtypes = [V, V]
+    hip.hipGraphExecDestroy.argtypes = [V]
+    hip.hipGraphDestroy.argtypes = [V]
+    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
+    if kind == "acc":
+        c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
+    else:
+        c.g.generate_and_beamform_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, t0=0, nt=nt, stream=s.handle)
+    graph = V()
+    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
+    ex = V()
+    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    for w, ref in ((w1, ref1), (w2, ref2)):
+        gpu.memcpy_htod(c.d_w, w, stream=s.handle, sync=False)
+        gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY, stream=s.handle)
+        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        s.synchronize()
+        assert np.array_equal(bits(c.read()), bits(ref))
+    hip.hipGraphExecDestroy(ex)
+    hip.hipGraphDestroy(graph)
+    c.close()
+
+
+@pytest.mark.parametrize("kind", ["acc", "fused"])
+def test_beam_shards_reproduce_the_full_call(gpu, oracle, kind):
+    from dc_sand_amd.beam_weights import BeamWeights
+    from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
+
+    A, B, C, nt = 65, 37, 3, 48
+    full = Case(gpu, oracle, A, B, C, nt)
+    bw = BeamWeights(full.bp)
+    rng = np.random.default_rng(9)
+    for b in range(B):
+        bw.set(b, *random_weights(rng, 1, A, zero_beam=False)[0])
+    bw.set(4, *([0.0] * A))
+    bw.upload()
+    ref = full.run(kind, bw.host)
+    table_ab = np.ascontiguousarray(full.table.reshape(B, A).T).ravel()  # slice_table's [a][b] layout
+    for rank in range(2):
+        sh = beam_range(B, 2, rank)
+        lp = local_parameters(full.bp, sh)
+        local_ab = slice_table(table_ab, full.bp, sh).reshape(A, sh.n_beams)
+        part = Case(gpu, oracle, A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
+        assert part.bp.NR_BEAMS == lp.NR_BEAMS
+        part.set_ant(full.ant)
+        gpu.memset(part.d_beams, 0xFF, part.nbytes + CANARY)
+        if kind == "acc":
+            part.g.beamform_accumulated_weighted(part.d_ant, part.ant.nbytes, bw.device_ptr(sh.beam_lo), part.d_beams, part.nbytes,
+                                                 nt, t_coeff=T_COEFF)
+        else:
+            part.g.generate_and_beamform_weighted(part.d_ant, part.ant.nbytes, bw.device_ptr(sh.beam_lo), part.d_beams,
+                                                  part.nbytes, t0=0, nt=nt)
+        got = part.read()
+        assert np.array_equal(bits(got), bits(ref[:, :, sh.beam_lo:sh.beam_hi]))
+        part.close()
+    bw.free()
+    full.close()
+
+
+def test_weights_change_between_calls_on_one_stream(gpu, oracle):
+    """d_weights is read when the work runs: a copy queued between two calls on the stream applies to the second."""
+    A, B, C, nt = 64, 32, 2, 32
+    c = Case(gpu, oracle, A, B, C, nt)
+    rng = np.random.default_rng(1)
+    w1, w2 = random_weights(rng, B, A), random_weights(rng, B, A)
+    ref2 = c.run("acc", w2)
+    s = gpu.Stream()
+    d_out2 = gpu.mem_alloc(c.nbytes)
+    gpu.memcpy_htod(c.d_w, w1, stream=s.handle, sync=False)
+    c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
+    gpu.memcpy_htod(c.d_w, w2, stream=s.handle, sync=False)
+    c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, d_out2, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
+    s.synchronize()
+    got2 = np.empty(c.shape, np.float32)
+    gpu.memcpy_dtoh(got2, d_out2)
+    assert np.array_equal(bits(got2), bits(ref2))
+    acc_bound_check(c, w1, c.read())
+    d_out2.free()
+    c.close()

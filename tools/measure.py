@@ -13,6 +13,9 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         fp16 generator rate per arithmetic form                                     -> profiles/r02_fp16.md
     python tools/measure.py fused
         fused generate + beamform rate on several shapes                            -> profiles/r0N_fused.md
+    python tools/measure.py bfweights [--rounds 5]
+        per-input beam weights: weighted against unweighted beamformer calls, alternating, in one process
+                                                                                    -> profiles/r04_beam_weights.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -248,6 +251,66 @@ def cmd_bfacc(args):
         g.close()
         d_ant.free()
         d_beams.free()
+
+
+def _noise(d_ant, nbytes):
+    """Noise-like int8 samples (a 32 MiB seeded block repeated): the matrix pipe's power depends on the data."""
+    blk = min(nbytes, 32 << 20)
+    device.memcpy_htod(d_ant, np.random.default_rng(0xA17).integers(-128, 128, size=blk, dtype=np.int8))
+    off = blk
+    while off < nbytes:
+        n = min(off, nbytes - off)
+        device.memcpy_dtod(int(d_ant) + off, d_ant, n)
+        off += n
+    device.synchronize()
+
+
+def cmd_bfweights(args):
+    """Per-input beam weights (include/dcs_beam_weights.h): each shape's weighted and unweighted calls timed in turn,
+    ``--rounds`` times each, in the same process on the same buffers; the median of each and their ratio."""
+    from dc_sand_amd.beam_weights import BeamWeights
+
+    cases = [("acc", s) for s in ((64, 16, 4096, 256), (64, 256, 4096, 256), (256, 64, 4096, 256))]
+    cases += [("fused", s) for s in ((64, 16, 64, 256), (64, 16, 4096, 256), (64, 64, 4096, 64), (64, 256, 4096, 16), (256, 64, 1024, 64))]
+    if args.shape:  # one shape (counter passes): AxBxCxNT, of --kind
+        cases = [(args.kind, tuple(int(v) for v in args.shape.split("x")))]
+    rows = []
+    for kind, (A, B, C, nt) in cases:
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        ab, bb = A * C * nt * 2, B * C * nt * 8
+        d_ant, d_beams = device.mem_alloc(ab), device.mem_alloc(bb)
+        _noise(d_ant, ab)
+        w = BeamWeights(bp)  # a taper with every eighth antenna flagged
+        rng = np.random.default_rng(7)
+        w.host[:] = rng.uniform(0.25, 1.0, size=w.host.shape).astype(np.float32)
+        w.host[:, ::8] = 0.0
+        w.upload()
+        if kind == "acc":
+            plain = lambda: g.beamform_accumulated(d_ant, ab, d_beams, bb, nt, t_coeff=1)  # noqa: E731
+            weighted = lambda: g.beamform_accumulated_weighted(d_ant, ab, w.device_ptr(), d_beams, bb, nt, t_coeff=1)  # noqa: E731
+            form = "staged" if A <= 64 else "kChain"
+        else:
+            plain = lambda: g.generate_and_beamform(d_ant, ab, d_beams, bb, 0, nt)  # noqa: E731
+            weighted = lambda: g.generate_and_beamform_weighted(d_ant, ab, w.device_ptr(), d_beams, bb, 0, nt)  # noqa: E731
+            form = "per-sample fused"
+        t_plain, t_w = [], []
+        for _ in range(args.rounds):
+            t_plain.append(per_launch_ms(plain))
+            t_w.append(per_launch_ms(weighted))
+        mp, mw = float(np.median(t_plain)), float(np.median(t_w))
+        row = {"kind": kind, "form": form, "shape": f"{A}x{B}x{C}x{nt}", "unweighted_us": round(mp * 1e3, 2),
+               "weighted_us": round(mw * 1e3, 2), "ratio": round(mw / mp, 4),
+               "spread_unweighted": round((max(t_plain) - min(t_plain)) / mp, 4), "spread_weighted": round((max(t_w) - min(t_w)) / mw, 4)}
+        rows.append(row)
+        print(f"{form:17s} {A}ant x {B}beam x {C}chan x {nt}t: unweighted {mp * 1e3:.1f} us, weighted {mw * 1e3:.1f} us, "
+              f"ratio {mw / mp:.4f} (spread {row['spread_unweighted'] * 100:.1f} % / {row['spread_weighted'] * 100:.1f} %)", flush=True)
+        w.free()
+        g.close()
+        d_ant.free()
+        d_beams.free()
+    print(json.dumps({"bfweights": rows}), flush=True)
 
 
 def cmd_copy(args):
@@ -533,6 +596,10 @@ def main():
     p.add_argument("--form", type=int, default=1, help="1 = per-workgroup terms, 3 = terms table, 0 = library's choice")
     p.add_argument("--bits", type=int, default=16, choices=[16, 32])
     sub.add_parser("fused")
+    p = sub.add_parser("bfweights")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of unweighted and weighted timings per shape")
+    p.add_argument("--shape", default="", help="AxBxCxNT: one shape only (counter passes)")
+    p.add_argument("--kind", default="acc", choices=["acc", "fused"], help="with --shape: which beamformer")
     sub.add_parser("mfma")
     sub.add_parser("copy")
     p = sub.add_parser("bfacc")
@@ -567,7 +634,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
