@@ -232,8 +232,10 @@ __global__ void __launch_bounds__(kBlock) bf_beamform_acc_kernel(const bf_bacc_a
 // the chunks of more than 64 antennas) are scaled by exact powers of two and added in fp32.  What differs from the
 // verifier's fp32 "sum += coeff * sample" is the quantisation of each coefficient (|F / 8355711 - w| <=
 // 0.75 / 8355711 = 9e-8: the size of the fp32 coefficient's own last place) and the verifier's OWN accumulation
-// roundings; against an exact-arithmetic sum of the fp32 coefficients the result is within 9e-8 * sum_a |x_a| + a
-// few ulp (tests/test_gpu_parity.py holds it to that).
+// roundings; against an exact-arithmetic sum of the fp32 coefficients the result is within 9e-8 * sum_a |x_a| +
+// 1.8e-7 * |sum| (three roundings of 2^-24 relative each -- the low part's conversion apart, which is far below:
+// tests/test_beamformer_model.py derives it term by term; tests/test_gpu_beamformer_exact.py holds the kernels to
+// this arithmetic bit for bit, tests/test_gpu_parity.py to a bound over the oracle's coefficients).
 //
 // A wave owns one 16-beam tile of one channel and some of the workgroup's 16-sample blocks.  Its coefficients
 // (64 antennas = 6 operands of 4 registers: 3 digits x {re, im}) are made once, in registers (waves that own the

@@ -881,6 +881,21 @@ int fill_dt(const dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_
     return dcs_bf_delta_times(&c->p, src.t0 + off, n, dst);
 }
 
+// Can every fDeltaTime of a call's nt time steps be worked out?  The multi-launch calls ask BEFORE anything else happens
+// on the context or the stream (allocation, the capture check, the first enqueue), so that a time index which overflows
+// the verifier's nanosecond step (dcs_bf_delta_times: DCS_ERR_OUT_OF_RANGE) costs nothing but the status -- not a tensor
+// written up to the chunk that holds it.  The step RN(RN(RN((float)t * SAMPLING_PERIOD) * 1e9f) * FFT_SIZE) does not decrease
+// as t grows (the conversion rounds monotonically, and so does every product by a positive constant: params_ok), and
+// nothing else in the recipe can fail, so the LAST index decides; a range that wraps round 2^64 is out of range by itself.
+int check_dt_range(const dcs_bf_context *c, const dt_source &src, uint32_t nt)
+{
+    if (src.values || nt == 0) return DCS_OK;
+    const uint64_t t_last = src.t0 + (uint64_t)(nt - 1u);
+    if (t_last < src.t0) return DCS_ERR_OUT_OF_RANGE;
+    float dt;
+    return dcs_bf_delta_times(&c->p, t_last, 1, &dt);
+}
+
 // Stage n fDeltaTime values through a pinned slot into device memory on `stream`.  Not capturable: callers check
 // refuse_if_capturing() before their first launch.
 int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, hipStream_t stream, const float **dt_dev)
@@ -911,6 +926,10 @@ int generate_slab_impl(dcs_bf_context *c, int bitwidth, const dt_source &src, ui
     const size_t eb = out16 ? 4 : 8;
     const size_t step_bytes = (size_t)nc * c->n_pairs * eb;
     if (out_bytes < step_bytes * nt) return DCS_ERR_INVALID_ARGUMENT;
+    {
+        const int st_range = check_dt_range(c, src, nt); // the whole call's time indices, before the first chunk is launched
+        if (st_range != DCS_OK) return st_range;
+    }
     hipStream_t s = as_stream(stream);
     if (nt > 1 && (c->tune.form == 2 || nt > kDtInline)) { // the fDeltaTime values will be staged through pinned memory
         const int cap = refuse_if_capturing(s);
@@ -1109,6 +1128,10 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
     if (beams_bytes < (size_t)B * C * nt * 2u * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(d_antenna) & 3u) || (reinterpret_cast<uintptr_t>(d_beams) & 7u))
         return DCS_ERR_INVALID_ARGUMENT;
+    {
+        const int st_range = check_dt_range(c, src, nt); // the whole call's time indices, before the first chunk is launched
+        if (st_range != DCS_OK) return st_range;
+    }
     hipStream_t s = as_stream(stream);
     {
         int st_alloc = ensure_terms(c, s);
@@ -1212,6 +1235,10 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
         return DCS_ERR_INVALID_ARGUMENT;
     if (d_weights && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights
     if (nt == 0) return DCS_OK;
+    {
+        const int st_range = check_dt_range(c, src, 1); // the one coefficient time, before anything is allocated
+        if (st_range != DCS_OK) return st_range;
+    }
     hipStream_t s = as_stream(stream);
     {
         int st_alloc = ensure_terms(c, s);

@@ -44,7 +44,7 @@ extern "C" {
 #define DCS_ERR_INVALID_ARGUMENT (-1)
 #define DCS_ERR_UNSUPPORTED (-2)   /* the reference `throw`s here: BCT.cu:40-50 */
 #define DCS_ERR_NOT_READY (-3)     /* e.g. generate before a delay table is set */
-#define DCS_ERR_OUT_OF_RANGE (-4)
+#define DCS_ERR_OUT_OF_RANGE (-4) /* e.g. a time index of [t0, t0+nt) beyond dcs_bf_delta_times' range: returned before anything is enqueued */
 #define DCS_ERR_NO_DEVICE (-5)
 #define DCS_ERR_WRONG_DEVICE (-6) /* the context lives on another device than the calling thread's current one */
 
@@ -237,7 +237,9 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *ctx, const float *dt, uint32
  * taken as the 24-bit fixed-point number rint(w * 8355711) = three signed 8-bit digits, so a plane is three
  * integer contractions whose sums are exact and independent of the antenna order, recombined and divided by
  * 8355711 in fp32 at the end.  Against the exact sum of the fp32 coefficients times the samples the result is
- * within 9e-8 * sum_a |sample_a| + 1.5 ulp -- closer than the verifier's own fp32 loop (BCT.cu:363-414 with the
+ * within 9e-8 * sum_a |sample_a| + 1.8e-7 * |sum| (the quantisation, 0.75 / 8355711 per unit of sample, and three fp32
+ * roundings of 2^-24 relative each: up to 3 ulp of the result, 1.5 typically; derived term by term in
+ * tests/test_beamformer_model.py) -- closer than the verifier's own fp32 loop (BCT.cu:363-414 with the
  * coefficient held: sum += coeff * sample, whose partial sums round at every antenna) -- and within
  * 4e-5 * nr_stations of that loop in the worst case (every sample at full scale and every error aligned: 1 ulp of
  * the coefficient + the quantisation + the roundings of either side, 3e-7 * 128 per antenna; typically 10 x less),

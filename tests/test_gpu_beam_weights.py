@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
+from helpers.beamformer_model import fused_model, normalise
 
 pytestmark = pytest.mark.gpu
 
@@ -97,16 +98,6 @@ def bits(x):
     return np.ascontiguousarray(x).view(np.uint32)
 
 
-def normalise(w):
-    """s_b and ghat as the contract defines them (fp32, correctly rounded)."""
-    w = np.asarray(w, dtype=np.float32)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        s = np.abs(w).max(axis=1)
-        s = np.where(np.all(np.isfinite(w), axis=1), s, np.float32(np.nan)).astype(np.float32)
-        gh = np.where(s[:, None] == 0, np.float32(0), w / s[:, None]).astype(np.float32)
-    return s, gh
-
-
 def acc_bound_check(case, w, got):
     """Fixed-point form: within 3.7e-7 * s_b * sum_a |x_a| + 3e-7 * |exact| of the fp64 sum of g * c * x over the
     oracle's fp32 coefficients."""
@@ -124,21 +115,11 @@ def acc_bound_check(case, w, got):
 
 
 def fused_expected(case, w):
-    """The per-sample rule restated in fp32 over the oracle's coefficients: sum += RN(RN(ghat * w) * x) in antenna order,
-    then RN(s_b * sum)."""
+    """The per-sample rule restated in fp32 (helpers/beamformer_model.py: fused_model) over the oracle's coefficients."""
     from dc_sand_amd.generator import delta_times
 
-    A, B, C, nt = case.A, case.B, case.C, case.nt
     s, gh = normalise(w)
-    coef = case.coefficients(delta_times(case.bp, 0, nt))  # [t][c][a][b][2]
-    x = case.ant.astype(np.float32).transpose(0, 1, 3, 2, 4).reshape(C, nt, A, 2)  # [c][t][a][2]
-    acc = np.zeros((nt, C, B, 2), dtype=np.float32)
-    for a in range(A):
-        wp = (gh[:, a][None, None, :, None] * coef[:, :, a, :, :]).astype(np.float32)  # [t][c][b][2]
-        xa = x[:, :, a, :].transpose(1, 0, 2)[:, :, None, :]  # [t][c][1][2]
-        acc = (acc + (wp * xa).astype(np.float32)).astype(np.float32)
-    out = (s[None, None, :, None] * acc).astype(np.float32)  # [t][c][b][2]
-    return out.reshape(nt // 16, 16, C, B, 2).transpose(2, 0, 3, 1, 4)
+    return fused_model(case.coefficients(delta_times(case.bp, 0, case.nt)), case.ant, ghat=gh, scale=s)
 
 
 def random_weights(rng, B, A, zero_beam=True):

@@ -101,50 +101,91 @@ def test_non_capturable_calls_are_refused_up_front_and_the_capture_survives(gpu,
         b.free()
 
 
-@pytest.mark.parametrize("kernel", [0, 1])
+def _first_failing_time_index(bp):
+    """The first time index whose nanosecond step (BCT.cu:299: t * 1e-7f * 1e9f * 8192 in fp32) no longer fits a long."""
+    from dc_sand_amd import _lib
+    from dc_sand_amd.generator import delta_times
+
+    def valid(t):
+        try:
+            delta_times(bp, t, 1)
+            return True
+        except _lib.DcsError as e:
+            assert e.status == _lib.DCS_ERR_OUT_OF_RANGE
+            return False
+
+    t_edge = int(9.2e18 / (1e-7 * 1e9 * 8192))
+    while not valid(t_edge):
+        t_edge -= 1 << 20
+    lo, hi = t_edge, t_edge + (1 << 22)
+    while valid(hi):
+        hi += 1 << 22
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if valid(mid):
+            lo = mid
+        else:
+            hi = mid
+    assert valid(hi - 1) and not valid(hi)
+    return hi
+
+
+@pytest.mark.parametrize("kernel", [0, 1, 2, "slab", "fused", "fused_weighted"])
 def test_time_index_out_of_range_mid_loop_launches_nothing(gpu, kernel):
-    """A per-time-step loop whose LATER time indices overflow the verifier's nanosecond step (BCT.cu:299: the fp32
-    product no longer fits a long) returns DCS_ERR_OUT_OF_RANGE before the first launch and before the fork: the
-    output buffer is untouched and the stream carries on."""
+    """A multi-launch call whose LATER time indices overflow the verifier's nanosecond step (BCT.cu:299: the fp32
+    product no longer fits a long) returns DCS_ERR_OUT_OF_RANGE before the first launch (and before the fork of the
+    per-time-step loops): the output buffer is untouched and the stream carries on.  Kernels 0 and 1 launch per time step
+    (steps 0 .. 4 valid); kernel 2, generate_slab and the fused beamformer (weighted or not) launch per chunk of 4096 time
+    steps at this shape: 4096 + 32 steps whose first chunk is valid and whose second is not."""
     from dc_sand_amd import BeamformerParameters, _lib
-    from dc_sand_amd.generator import SteeringCoefficientGenerator, delta_times
+    from dc_sand_amd.generator import SteeringCoefficientGenerator
 
     bp = BeamformerParameters(NR_CHANNELS=8, NR_STATIONS=2, NR_BEAMS=3)
-    # the largest valid time index: the step in ns is t * 1e-7f * 1e9f * 8192 (fp32) and must stay below 9.2e18
-    t_edge = int(9.2e18 / (1e-7 * 1e9 * 8192))
-    while True:
-        try:
-            delta_times(bp, t_edge, 1)
-            break
-        except _lib.DcsError:
-            t_edge -= 1 << 20
-    lo, hi = t_edge, t_edge + (1 << 22)
-    while hi - lo > 1:  # first failing index
-        mid = (lo + hi) // 2
-        try:
-            delta_times(bp, mid, 1)
-            lo = mid
-        except _lib.DcsError:
-            hi = mid
-    nt = 16
-    t0 = hi - 5  # steps 0..4 are valid, 5.. are not
+    A, B, C = 2, 3, 8
+    hi = _first_failing_time_index(bp)
+    per_step = kernel in (0, 1)
+    nt = 16 if per_step else 4096 + 32
+    # per-step loops: steps 0..4 are valid, 5.. are not; chunked loops: t0 a multiple of 16 (the beamformers' rule), the first
+    # invalid step among the 32 of the second chunk
+    t0 = hi - 5 if per_step else (hi - 4097) // 16 * 16
+    assert t0 < hi and (per_step or 4096 < hi - t0 < nt)
     g = SteeringCoefficientGenerator(bp)
     g.upload_delays(rand_table(bp.n_pairs))
-    nbytes = g.output_bytes(1, nt)
-    buf = gpu.mem_alloc(nbytes)
     s = gpu.Stream()
+    extra = []
+    if kernel in ("fused", "fused_weighted"):
+        d_ant = gpu.mem_alloc(C * nt * A * 2)
+        gpu.memset(d_ant, 1, d_ant.nbytes)
+        d_w = gpu.mem_alloc(B * A * 4)
+        gpu.memcpy_htod(d_w, np.ones((B, A), np.float32))
+        extra = [d_ant, d_w]
+        nbytes = C * nt * B * 8
+        if kernel == "fused":
+            call = lambda buf, t: g.generate_and_beamform(d_ant, d_ant.nbytes, buf, nbytes, t0=t, nt=nt, stream=s)
+        else:
+            call = lambda buf, t: g.generate_and_beamform_weighted(d_ant, d_ant.nbytes, d_w, buf, nbytes, t0=t, nt=nt, stream=s)
+    elif kernel == "slab":
+        nbytes = nt * 3 * bp.n_pairs * 8
+        call = lambda buf, t: g.generate_slab(buf, nbytes, 2, 3, t0=t, nt=nt, stream=s)
+    else:
+        nbytes = g.output_bytes(1, nt)
+        call = lambda buf, t: g.generate(buf, nbytes, t0=t, nt=nt, kernel=kernel, stream=s)
+    buf = gpu.mem_alloc(nbytes)
     gpu.memset(buf, 0xFF, nbytes, stream=s)
     with pytest.raises(_lib.DcsError) as e:
-        g.generate(buf, nbytes, t0=t0, nt=nt, kernel=kernel, stream=s)
+        call(buf, t0)
     assert e.value.status == _lib.DCS_ERR_OUT_OF_RANGE
     s.synchronize()
     host = np.empty(nbytes, dtype=np.uint8)
     gpu.memcpy_dtoh(host, buf)
-    assert np.all(host == 0xFF), "a launch was made before the range check"
-    g.generate(buf, nbytes, t0=0, nt=nt, kernel=kernel, stream=s)  # the stream is fine
+    assert np.all(host == 0xFF), f"a launch was made before the range check: {int(np.count_nonzero(host != 0xFF))} of {nbytes} bytes written"
+    call(buf, 0)  # the stream is fine
     s.synchronize()
+    gpu.memcpy_dtoh(host, buf)
+    assert not np.all(host == 0xFF)
     g.close()
-    buf.free()
+    for b in [buf] + extra:
+        b.free()
 
 
 def test_launch_failure_in_the_fan_out_loop_joins_the_side_streams(gpu):
