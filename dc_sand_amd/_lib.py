@@ -193,6 +193,32 @@ def beam_weights_lib() -> ctypes.CDLL:
     return _WEIGHTS
 
 
+# include/dcs_beam_quant.h: the companion library of quantised int8 beam output, built with the product library; it
+# takes the context handles of the library above
+QUANT_LIB_PATH = LIB_PATH.parent / "libdcs_beam_quant.so"
+BEAM_QUANT_SIGNATURES = [
+    ("dcs_bf_beamform_accumulated_q8", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
+    ("dcs_bf_beamform_accumulated_q8_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
+]
+
+_QUANT = None
+
+
+def beam_quant_lib() -> ctypes.CDLL:
+    global _QUANT
+    if _QUANT is None:
+        _lib()  # the product library first: its contexts are what the companion works on
+        if not QUANT_LIB_PATH.exists():
+            raise ImportError(f"{QUANT_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
+        qlib = ctypes.CDLL(str(QUANT_LIB_PATH))
+        for name, restype, argtypes in BEAM_QUANT_SIGNATURES:
+            fn = getattr(qlib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _QUANT = qlib
+    return _QUANT
+
+
 def check(status: int, where: str) -> None:
     if status != DCS_OK:
         raise DcsError(status, where)

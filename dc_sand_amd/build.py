@@ -1,7 +1,8 @@
 """Build driver: compiles the gfx950 kernels and the C-ABI into
 ``dc_sand_amd/csrc/libdcs_beamformer.so`` and its companions -- staged delay tables
 (``include/dcs_stream_staging.h``) into ``libdcs_stream_staging.so``, per-input beam weights
-(``include/dcs_beam_weights.h``) into ``libdcs_beam_weights.so`` -- with hipcc (in-tree, so the libraries
+(``include/dcs_beam_weights.h``) into ``libdcs_beam_weights.so``, quantised int8 beam output
+(``include/dcs_beam_quant.h``) into ``libdcs_beam_quant.so`` -- with hipcc (in-tree, so the libraries
 travel with the source tree).  ``python -m dc_sand_amd.build [--force]``.
 
 Flags that are part of the numerical contract (DESIGN.md "numerics"):
@@ -23,13 +24,16 @@ LIB = CSRC / "libdcs_beamformer.so"
 SOURCES = ["bf_kernels.hip", "bf_beamform_mfma.hip", "bf_capi.hip"]
 HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "bf_stream_ext.h", "bf_ctx_ext.h", "bf_beamform_kernel.inc",
            "bf_beamform_i8_kernel.inc", "../../include/dcs_beamformer.h", "../../include/dcs_stream_staging.h",
-           "../../include/dcs_beam_weights.h"]
+           "../../include/dcs_beam_weights.h", "../../include/dcs_beam_quant.h"]
 # the companion library of include/dcs_stream_staging.h (staged delay tables for the streams of the product library)
 STAGING_LIB = CSRC / "libdcs_stream_staging.so"
 STAGING_SOURCES = ["bf_stream_staging.cpp"]
 # the companion library of include/dcs_beam_weights.h (per-input beam weights for the product library's beamformers)
 WEIGHTS_LIB = CSRC / "libdcs_beam_weights.so"
 WEIGHTS_SOURCES = ["bf_beam_weights.cpp"]
+# the companion library of include/dcs_beam_quant.h (quantised int8 beam output of the product library's matrix-core beamformer)
+QUANT_LIB = CSRC / "libdcs_beam_quant.so"
+QUANT_SOURCES = ["bf_beam_quant.cpp"]
 ARCH = "gfx950"
 
 
@@ -97,13 +101,15 @@ def compile_and_link(sources, extra_flags, out: Path, verbose: bool = False) -> 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """All three libraries; returns the product library's path."""
+    """All four libraries; returns the product library's path."""
     if force or needs_build():
         compile_and_link([CSRC / s for s in SOURCES], [], LIB, verbose)
     if force or needs_build(STAGING_LIB, STAGING_SOURCES):
         compile_and_link([CSRC / s for s in STAGING_SOURCES], [], STAGING_LIB, verbose)
     if force or needs_build(WEIGHTS_LIB, WEIGHTS_SOURCES):
         compile_and_link([CSRC / s for s in WEIGHTS_SOURCES], [], WEIGHTS_LIB, verbose)
+    if force or needs_build(QUANT_LIB, QUANT_SOURCES):
+        compile_and_link([CSRC / s for s in QUANT_SOURCES], [], QUANT_LIB, verbose)
     return LIB
 
 

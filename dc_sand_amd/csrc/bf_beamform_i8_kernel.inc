@@ -1,27 +1,43 @@
-// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included twice by bf_beamform_mfma.hip:
-// BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights).  One text, two
+// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included four times by bf_beamform_mfma.hip:
+// BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights); with
+// BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output).  One text, four
 // kernels: a WEIGHTED template parameter would rename the unweighted kernels' symbols, and a body shared through an inline
 // function changes their code; compiled from this file, the unweighted kernels are, instruction for instruction, what
-// they were before weights existed.
+// they were before weights existed, and the float kernels what they were before the quantiser.
 // WEIGHTED (kStaged and kChain; include/dcs_beam_weights.h, DESIGN.md section 5.7): every coefficient w is made into
 // w' = RN(ghat * w) before its digits are taken (ghat[a][b] beside the terms, same addressing), and the integer sums of a
 // beam are scaled by RN(s_b / 8355711) instead of 1 / 8355711 -- the same one multiply.  kStaged keeps its four factors in
 // registers; kChain, with no register to spare, reads them from LDS (16 floats behind the coefficients) one register
 // ahead inside its recombine loop.
+// QUANT (kStaged and kChain; include/dcs_beam_quant.h, DESIGN.md section 5.8): a result register's four floats -- the very
+// floats the float kernel stores -- are multiplied by the beam's gain, rounded and clamped to int8 (q8_pack), which makes
+// one dword per beam: 4 consecutive bytes of the int8 tensor [c][t/16][b][t%16][{re, im}].  A 4 x 4 dword transpose inside
+// each quad of lanes then leaves a lane with SIXTEEN consecutive bytes of one beam (samples 8 h .. 8 h + 7 of beam
+// bw + (lane >> 4) + 4 (lane & 3), h = (lane >> 2) & 1), and the wave writes its pair of blocks with one 16-byte store
+// per lane: 2 x 512 contiguous bytes.  kStaged keeps its four gains in registers, kChain reads them from LDS behind the
+// weighted form's factors, one register ahead.  Clipped components are counted per lane and tallied once, at the end.
 template <int FORM, bool FULL, int NW = 4>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL))))
-#if BF_I8_WEIGHTED
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT))))
+#if BF_I8_WEIGHTED && BF_I8_QUANT
+bf_beamform_i8_wq_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_quant_args qa)
+#elif BF_I8_QUANT
+bf_beamform_i8_q_kernel(const bf_bacc_args a, const bf_quant_args qa)
+#elif BF_I8_WEIGHTED
 bf_beamform_i8_w_kernel(const bf_bacc_args a, const bf_weights_args w)
 #else
 bf_beamform_i8_kernel(const bf_bacc_args a)
 #endif
 {
-    constexpr bool WEIGHTED = BF_I8_WEIGHTED;
+    constexpr bool WEIGHTED = BF_I8_WEIGHTED, QUANT = BF_I8_QUANT;
 #if !BF_I8_WEIGHTED
     const bf_weights_args w{}; // named by the (discarded) weighted branches only
 #endif
+#if !BF_I8_QUANT
+    const bf_quant_args qa{};  // named by the (discarded) quantised branches only
+#endif
     static_assert(NW == 4 || ((NW == 8 || NW == 16) && FORM == kStaged), "8- and 16-wave workgroups exist for the staged form only");
     static_assert(!WEIGHTED || FORM == kStaged || FORM == kChain, "weights exist for the product's forms only");
+    static_assert(!QUANT || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the quantiser exists for the product's forms only");
     constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
     extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
     uint32_t bid = BACC_LOGICAL_ID(a);
@@ -67,6 +83,14 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         for (int r = 0; r < 4; r++) fac[r] = w.gs[min(bw + (lane >> 4) + 4u * (uint32_t)r, a.B - 1u)] * inv;
     } else if constexpr (WEIGHTED && CHAIN) {
         fac[0] = w.gs[min(bw + (lane & 15u), a.B - 1u)] * inv;
+    }
+    // quantised: the gains of this lane's result registers (kStaged; kChain keeps them in LDS), and this lane's clipped
+    // components, byte r for register r
+    float kq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t n_clip = 0u;
+    if constexpr (QUANT && STAGED) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) kq[r] = qa.gains[min(bw + (lane >> 4) + 4u * (uint32_t)r, a.B - 1u)];
     }
 
     // ---- coefficients: lane (row lm, group lg) holds, in byte p of each of its six operands (3 digits x {re, im}),
@@ -312,6 +336,33 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     };
     // scale and store: lane l, register r = beam bw + (l >> 4) + 4 r, samples 2 m, 2 m + 1
     auto finish = [&](auto whole, uint32_t blk, const floatx4 (&f)[4]) {
+        if constexpr (QUANT) { // the same floats, quantised: one dword per register, transposed, one store
+            const bool pair_live = !second || blk + 1u <= last; // a pair past the end repeats the last block: neither stored nor counted twice
+            uint32_t pk[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) { // beam bb + 4 r
+                const float sc = WEIGHTED ? fac[r] : inv;
+                floatx4 o = {f[0][r] * sc, f[1][r] * sc, f[2][r] * sc, f[3][r] * sc};
+                if (nan_re | nan_im) poison(r, o);
+                pk[r] = q8_pack(o, kq[r], qa.clips != nullptr, pair_live && (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B), r, n_clip);
+            }
+            const uint32_t blkA = min(blk, last), blkB = min(blk + 1u, last);
+            char *base = out8 + ((uint64_t)c * a.nT16 + tt0 + blkA * tpr + slot) * (a.B * 32u); // wave-uniform
+            const uint32_t hop = second ? (blkB - blkA) * tpr * (a.B * 32u) : 0u;
+#ifdef DCS_Q8_DWORD_STORES // the A/B of profiles/r05_beam_quant.md: four dword stores per lane, 128-byte runs
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (pair_live && (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B))
+                    __builtin_nontemporal_store(pk[r], reinterpret_cast<uint32_t *>(base + (hop + (bb + 4u * (uint32_t)r) * 32u + m * 4u)));
+#else
+            q8_quad_transpose(pk, lane);
+            const uint32_t qbeam = bb + 4u * (lane & 3u); // this lane's sixteen bytes: samples 8 h .. 8 h + 7 of beam qbeam, h = (lane >> 2) & 1
+            if (pair_live && (decltype(whole)::value || qbeam < a.B))
+                __builtin_nontemporal_store(intx4{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]},
+                                            reinterpret_cast<intx4 *>(base + (hop + qbeam * 32u + ((lane >> 2) & 1u) * 16u)));
+#endif
+            return;
+        }
 #pragma unroll
         for (int r = 0; r < 4; r++) { // beam bb + 4 r
             const float sc = WEIGHTED ? fac[r] : inv; // beam bb + 4 r's factor
@@ -462,6 +513,9 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         if constexpr (WEIGHTED) {
             if (wave == 0u && lane < 16u) facw[lane] = fac[0];
         }
+        if constexpr (QUANT) { // behind the factors: [16] = the gain of beam bw + i
+            if (wave == 0u && lane < 16u) facw[16u + lane] = qa.gains[min(bw + lane, a.B - 1u)];
+        }
         __syncthreads(); // the kernel's only barrier
         if (idle) return;
         nan_re = nanw[0] | nanw[2] | nanw[4] | nanw[6]; // a non-finite coefficient in ANY chunk poisons the row
@@ -496,6 +550,45 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                         for (int v = half; v < 4; v += 2) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v], acc[v][d], 0, 0, 0);
                     }
                 }
+                if constexpr (QUANT) {
+                    if (chunk + 1u == n_chunks) { // as below, each register quantised to one dword as it is recombined; then one store
+                        const bool pair_live = !second || blk + 1u <= last;
+                        uint32_t pk[4];
+                        float sc_next = WEIGHTED ? facw[lg] : inv, k_next = facw[16u + lg]; // beam bb + 4 r's factor and gain, one register ahead
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const float sc = sc_next, k = k_next;
+                            if (r < 3) {
+                                if constexpr (WEIGHTED) sc_next = facw[4u * (uint32_t)r + 4u + lg];
+                                k_next = facw[16u + 4u * (uint32_t)r + 4u + lg];
+                            }
+                            floatx4 o;
+#pragma unroll
+                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * sc;
+                            if (nan_re | nan_im) poison(r, o);
+                            pk[r] = q8_pack(o, k, qa.clips != nullptr, pair_live && (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B), r, n_clip);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        const uint32_t blkB = min(blk + 1u, last); // (blk <= last)
+                        char *base = out8 + ((uint64_t)c * a.nT16 + tt0 + blk * tpr + slot) * (a.B * 32u); // wave-uniform
+                        const uint32_t hop = second ? (blkB - blk) * tpr * (a.B * 32u) : 0u;
+#ifdef DCS_Q8_DWORD_STORES
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+                            if (pair_live && (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B))
+                                __builtin_nontemporal_store(pk[r], reinterpret_cast<uint32_t *>(base + (hop + (bb + 4u * (uint32_t)r) * 32u + m * 4u)));
+#else
+                        q8_quad_transpose(pk, lane);
+                        const uint32_t qbeam = bb + 4u * (lane & 3u);
+                        if (pair_live && (decltype(whole)::value || qbeam < a.B))
+                            __builtin_nontemporal_store(intx4{(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3]},
+                                                        reinterpret_cast<intx4 *>(base + (hop + qbeam * 32u + ((lane >> 2) & 1u) * 16u)));
+#endif
+                        chunk = 0u, blk += 2u;
+                    } else {
+                        chunk++;
+                    }
+                } else
                 if (chunk + 1u == n_chunks) { // all antennas in: digits d1 = acc[v][0], d2 = acc[v][1], d3 = acc[v][2]
                     // one result register (four beams' sixteen bytes) at a time: recombined, scaled, stored -- the sixteen floats
                     // are never all alive beside the accumulators
@@ -528,6 +621,9 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
             run_chain(std::true_type{});
         else
             run_chain(std::false_type{});
+        if constexpr (QUANT) {
+            if (qa.clips) q8_tally(qa.clips, n_clip, bb, lm, a.B);
+        }
         return;
     } else if (has_chunk) {
         fetch(cur[1], 2, kc);
@@ -536,5 +632,8 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         run(std::true_type{});
     else
         run(std::false_type{});
+    if constexpr (QUANT) {
+        if (qa.clips) q8_tally(qa.clips, n_clip, bb, lm, a.B);
+    }
 }
 

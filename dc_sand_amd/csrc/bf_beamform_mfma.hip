@@ -291,17 +291,90 @@ constexpr int kChainWaves = 4;
 
 // NW: waves per workgroup -- 4; 8 (kStaged, eight beam tiles per workgroup) is instantiated in the probes build only: an A/B
 // that measured no gain over four tiles (profiles/r03_fused.md)
-constexpr int i8_waves_per_eu(int form, bool full)
+// quant: the quantised kChain kernels take 3 -- their epilogue (four packed results held for the quad transpose, the gains, the
+// clip counts) wants 144 registers and spills 16 of them at 128, and scratch is not an option (the first launch of a
+// process would pay for it); kChain measured the same at 3 waves as at 4
+constexpr int i8_waves_per_eu(int form, bool full, bool quant = false)
 {
-    return form == kSplit ? (full ? 3 : 2) : (form == kChain ? kChainWaves : (full || form == kStaged ? 4 : 3));
+    return form == kSplit ? (full ? 3 : 2) : (form == kChain ? kChainWaves - (quant ? 1 : 0) : (full || form == kStaged ? 4 : 3));
 }
 
+// ---- the quantised epilogue (include/dcs_beam_quant.h): what bf_beamform_i8_q_kernel and
+// bf_beamform_i8_wq_kernel do with a result register instead of storing its four floats.
+// o = {re even, im even, re odd, im odd} of one beam and one pair of samples, exactly the floats the unquantised kernel
+// stores; k the beam's gain.  Per component y = RN(o * k) (one multiply of its own), NaN -> -128, otherwise
+// clamp(rint(y), -127, 127); the four bytes are, in this order, four consecutive bytes of the int8 tensor.  Counting
+// (count: wave-uniform; live: this lane's register is stored at all) costs a compare per component and one wave-uniform
+// branch: the lanes' counts of register r pile up in byte r of n_clip -- at most 4 per pair of blocks, and the launcher
+// gives a wave fewer than 64 pairs.
+__device__ __forceinline__ uint32_t q8_pack(const floatx4 o, float k, bool count, bool live, int r, uint32_t &n_clip)
+{
+    uint32_t word = 0u, n = 0u;
+    bool any = false;
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        const float y = o[v] * k;
+        const float ry = rintf(y);
+        const bool clip = !(fabsf(ry) <= 127.0f); // NaN included
+        const float q = y != y ? -128.0f : __builtin_amdgcn_fmed3f(ry, -127.0f, 127.0f);
+        word |= ((uint32_t)(int)q & 0xffu) << (8 * v);
+        any |= clip;
+        n += clip ? 1u : 0u;
+    }
+    if (count && __builtin_amdgcn_ballot_w64(any && live) != 0ull) n_clip += live ? n << (8 * r) : 0u;
+    return word;
+}
+
+// 4 x 4 dword transpose inside every quad of lanes (lanes 4 j .. 4 j + 3), on the DPP quad permutes -- no LDS: afterwards
+// register j of lane i is what register i of lane j was.  Two exchanges of 2 x 2 blocks (lane ^ 1, then lane ^ 2); every
+// lane of the wave must be active.
+__device__ __forceinline__ void q8_quad_transpose(uint32_t (&d)[4], uint32_t lane)
+{
+    const bool b0 = (lane & 1u) != 0u, b1 = (lane & 2u) != 0u;
+#pragma unroll
+    for (int p = 0; p < 4; p += 2) { // registers (p, p + 1) with lane ^ 1: quad_perm [1, 0, 3, 2]
+        const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(b0 ? d[p] : d[p + 1]), 0xB1, 0xf, 0xf, false);
+        d[p] = b0 ? recv : d[p];
+        d[p + 1] = b0 ? d[p + 1] : recv;
+    }
+#pragma unroll
+    for (int p = 0; p < 2; p++) { // registers (p, p + 2) with lane ^ 2: quad_perm [2, 3, 0, 1]
+        const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(b1 ? d[p] : d[p + 2]), 0x4E, 0xf, 0xf, false);
+        d[p] = b1 ? recv : d[p];
+        d[p + 2] = b1 ? d[p + 2] : recv;
+    }
+}
+
+// The wave's clip counts to the caller's counters: n_clip's byte r is this lane's count for beam bb + 4 r, and the sixteen
+// lanes of a row (same lane >> 4) hold the same four beams.  Only a wave that clipped gets past the first line; it adds
+// up each row and issues at most sixteen atomics.
+__device__ __forceinline__ void q8_tally(unsigned long long *clips, uint32_t n_clip, uint32_t bb, uint32_t lm, uint32_t B)
+{
+    if (__builtin_amdgcn_ballot_w64(n_clip != 0u) == 0ull) return;
+    uint32_t even = n_clip & 0x00ff00ffu, odd = (n_clip >> 8) & 0x00ff00ffu; // registers (0, 2) and (1, 3) in 16-bit fields: <= 16 x 255
+    for (int s = 1; s < 16; s <<= 1) even += (uint32_t)__shfl_xor((int)even, s), odd += (uint32_t)__shfl_xor((int)odd, s);
+    if (lm < 4u) { // lane lm of the row: register r = lm
+        const uint32_t n = (((lm & 1u) ? odd : even) >> (16u * (lm >> 1))) & 0xffffu, beam = bb + 4u * lm;
+        if (n != 0u && beam < B) atomicAdd(clips + beam, (unsigned long long)n);
+    }
+}
+
+#define BF_I8_QUANT 0
 #define BF_I8_WEIGHTED 0
 #include "bf_beamform_i8_kernel.inc"
 #undef BF_I8_WEIGHTED
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
 #undef BF_I8_WEIGHTED
+#undef BF_I8_QUANT
+#define BF_I8_QUANT 1
+#define BF_I8_WEIGHTED 0
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
+#undef BF_I8_QUANT
 
 } // namespace
 
@@ -321,14 +394,15 @@ hipError_t bf_warm_module_mfma()
 }
 
 namespace {
-// w: nullptr, or the weights (the int8 form's kStaged and kChain only)
-hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, hipStream_t stream)
+// w: nullptr, or the weights (the int8 form's kStaged and kChain only); q: nullptr, or the quantiser's gains and counters
+// (the same two forms; a.beams is then the int8 tensor)
+hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, hipStream_t stream)
 {
     bf_bacc_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nT16 == 0) return hipSuccess;
     if (a.A > 256u) return hipErrorInvalidValue; // not built
     const bool chain = a.fp32_chain != 0u;
-    if (w && chain) return hipErrorInvalidValue;
+    if ((w || q) && chain) return hipErrorInvalidValue;
     // beam tiles per workgroup: as many as the beams need; the fp32 form keeps its coefficient planes in LDS and
     // takes as many as still admit 6 workgroups per CU (26 KiB each), one tile whatever it takes beyond
     // more than 64 antennas, int8 form: one beam tile per workgroup; kChain (the product's form) or, probes build only, kSplit
@@ -373,6 +447,41 @@ hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *
     const uint64_t blocks = (uint64_t)a.C * a.n_bgroups * a.n_tgroups;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)blocks), block(64u * nw);
+    if (q) { // the product's forms only; as the branch below, with the quantised kernels
+        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
+        if (a.tiles_per_wg / tpr > 126u) return hipErrorInvalidValue; // a lane counts its clips in bytes, 4 per pair of blocks
+        const bf_weights_args w0 = w ? *w : bf_weights_args{};
+        size_t lds_q;
+        if (staged_form) {
+            lds_q = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
+            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
+                a.share_off = (uint32_t)lds_q;
+                lds_q += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
+            }
+        } else { // kChain: the coefficients, the NaN-row words, the 16 beams' scale factors and their 16 gains
+            lds_q = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + 32u * sizeof(float);
+        }
+#define BF_LAUNCH_Q8(FORM, FULL)                                                                                       \
+    do {                                                                                                               \
+        if (w)                                                                                                         \
+            hipLaunchKernelGGL((bf_beamform_i8_wq_kernel<FORM, FULL>), grid, block, lds_q, stream, a, w0, *q);         \
+        else                                                                                                           \
+            hipLaunchKernelGGL((bf_beamform_i8_q_kernel<FORM, FULL>), grid, block, lds_q, stream, a, *q);              \
+    } while (0)
+        if (staged_form) {
+            if (a.A == 64u)
+                BF_LAUNCH_Q8(kStaged, true);
+            else
+                BF_LAUNCH_Q8(kStaged, false);
+        } else {
+            if (a.A % 64u == 0u)
+                BF_LAUNCH_Q8(kChain, true);
+            else
+                BF_LAUNCH_Q8(kChain, false);
+        }
+#undef BF_LAUNCH_Q8
+        return hipGetLastError();
+    }
     if (w) { // the product's forms only
         if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
         if (staged_form) {
@@ -454,9 +563,14 @@ hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *
 }
 } // namespace
 
-hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream) { return launch_beamform_acc(a, nullptr, stream); }
+hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream) { return launch_beamform_acc(a, nullptr, nullptr, stream); }
 
 hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream)
 {
-    return launch_beamform_acc(a, &w, stream);
+    return launch_beamform_acc(a, &w, nullptr, stream);
+}
+
+hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream)
+{
+    return launch_beamform_acc(a, w, &q, stream);
 }

@@ -390,7 +390,11 @@ int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint
 int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
                                        const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, float *d_beams,
                                        size_t beams_bytes, void *stream);
-const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl};
+int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                 size_t antenna_bytes, const float *d_weights, const float *d_quant_gains, int8_t *d_beams_q8,
+                                 size_t beams_bytes, unsigned long long *d_clip_count, void *stream);
+const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl,
+                                    beamform_accumulated_q8_impl};
 }
 
 int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
@@ -1220,8 +1224,10 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *c, const float *dt, uint32_t
 }
 
 namespace {
+// quant: nullptr, or the quantiser's gains and counters (include/dcs_beam_quant.h): d_beams is then the int8 tensor, a quarter the size
 int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes,
-                      float *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr)
+                      void *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr,
+                      const bf_quant_args *quant = nullptr)
 {
     if (!c || (nt && (!d_antenna || !d_beams))) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
@@ -1230,10 +1236,10 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     const uint32_t A = (uint32_t)c->p.nr_stations, B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     if (A > 256u) return DCS_ERR_UNSUPPORTED; // the coefficient planes of one workgroup must fit 64 KiB of LDS
     if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
-    if (beams_bytes < (size_t)B * C * nt * 2u * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    if (beams_bytes < (size_t)B * C * nt * 2u * (quant ? sizeof(int8_t) : sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & 7u))
         return DCS_ERR_INVALID_ARGUMENT;
-    if (d_weights && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights
+    if ((d_weights || quant) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights and no quantiser
     if (nt == 0) return DCS_OK;
     {
         const int st_range = check_dt_range(c, src, 1); // the one coefficient time, before anything is allocated
@@ -1277,7 +1283,7 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     a.flags = c->d_flags;
     a.epoch = epoch;
     a.ant = d_antenna;
-    a.beams = d_beams;
+    a.beams = static_cast<float *>(d_beams);
     a.A = A;
     a.B = B;
     a.C = C;
@@ -1298,6 +1304,7 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     a.nbt_force = knob(c->probe.bacc_nbt, "DCS_BACC_NBT");
     a.nw_force = knob(c->probe.bacc_waves, "DCS_BACC_WAVES");
 #endif
+    if (quant) return (int)bf_launch_beamform_acc_q8(a, d_weights ? &wa : nullptr, *quant, s);
     return (int)(d_weights ? bf_launch_beamform_acc_weighted(a, wa, s) : bf_launch_beamform_acc(a, s));
 }
 
@@ -1318,6 +1325,18 @@ int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff,
     if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
     return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams, beams_bytes,
                              stream, d_weights);
+}
+
+// include/dcs_beam_quant.h, reached the same way
+int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                 size_t antenna_bytes, const float *d_weights, const float *d_quant_gains, int8_t *d_beams_q8,
+                                 size_t beams_bytes, unsigned long long *d_clip_count, void *stream)
+{
+    if (!c || !weights_ok(d_quant_gains) || (d_weights && !weights_ok(d_weights)) || (reinterpret_cast<uintptr_t>(d_clip_count) & 7u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    const bf_quant_args quant = {d_quant_gains, d_clip_count};
+    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes,
+                             stream, d_weights, &quant);
 }
 } // namespace
 

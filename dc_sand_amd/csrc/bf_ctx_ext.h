@@ -1,8 +1,8 @@
-// bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companion libdcs_beam_weights.so
-// (include/dcs_beam_weights.h).  Both are built from this tree together.  Every dcs_bf_context begins with a
-// bf_ctx_ext_head whose table points at the product library's implementation of the weighted beamformer calls; the
-// companion checks the arguments it can check without a device, then the table's version, and forwards.  Not a public
-// interface.
+// bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
+// (include/dcs_beam_weights.h) and libdcs_beam_quant.so (include/dcs_beam_quant.h).  All are built from this tree
+// together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
+// implementation of the weighted and the quantised beamformer calls; a companion checks the arguments it can check
+// without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
 
@@ -11,7 +11,7 @@
 
 #include "../../include/dcs_beamformer.h"
 
-#define BF_CTX_EXT_VERSION 1u
+#define BF_CTX_EXT_VERSION 2u // 2: beamform_accumulated_q8 appended
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -23,6 +23,11 @@ struct bf_ctx_ext_ops {
     int (*beamform_accumulated_weighted)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
                                          const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
                                          float *d_beams, size_t beams_bytes, void *stream);
+    // the same with int8 output (include/dcs_beam_quant.h); d_weights: nullptr = unweighted; d_clip_count: nullptr = no counting
+    int (*beamform_accumulated_q8)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                   const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                   const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
+                                   unsigned long long *d_clip_count, void *stream);
 };
 
 // the first member of struct dcs_bf_context

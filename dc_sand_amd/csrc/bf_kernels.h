@@ -193,6 +193,14 @@ __host__ __device__ inline uint32_t bf_xcd_grouped(uint32_t w, uint32_t total, u
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream);
 // The same with weights (int8 form only: kStaged and kChain; a.fp32_chain must be 0)
 hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream);
+// Quantised int8 beam output (include/dcs_beam_quant.h): a.beams is then the int8 tensor
+// [C][nT16][B][16][2], written by the quantised kernels' epilogue from the floats the calls above would have stored
+struct bf_quant_args {
+    const float *gains;        // [B]: the beams' quantisation gains (device)
+    unsigned long long *clips; // [B]: clipped components per beam, added to; or nullptr: no counting
+};
+// w: nullptr (unweighted) or the weights, as bf_launch_beamform_acc_weighted (int8 form only: kStaged and kChain)
+hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
 // One coefficient per lane, one time step (reference kernel a1's shape).

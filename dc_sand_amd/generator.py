@@ -65,6 +65,11 @@ def output_bytes(params: BeamformerParameters, bitwidth: int, nt: int) -> int:
     return int(n.value)
 
 
+def quantised_beams_bytes(params: BeamformerParameters, nt: int) -> int:
+    """Size of the int8 beam tensor ``[C][nt / 16][B][16][{re, im}]`` of :meth:`SteeringCoefficientGenerator.beamform_accumulated_q8`."""
+    return int(params.NR_CHANNELS) * int(nt) * int(params.NR_BEAMS) * 2
+
+
 def gpu_utilisation(params: BeamformerParameters, kernel_ms: float) -> tuple[float, float]:
     """``BeamformerCoeffTest::get_time`` model (``BeamformerCoefficientTest.cu:426-448``)."""
     out = (c_float * 2)()
@@ -223,6 +228,31 @@ class SteeringCoefficientGenerator:
                                                              c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_weights)),
                                                              c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
                   "dcs_bf_beamform_accumulated_weighted_dt")
+
+    # -- quantised int8 beam output (include/dcs_beam_quant.h, companion library libdcs_beam_quant.so): d_quant_gains is a
+    #    device [nr_beams] fp32 array, d_clip_count a device [nr_beams] uint64 array or None
+    #    (:class:`dc_sand_amd.beam_quant.BeamQuantGains`), both read and written when the work runs on the stream
+    def beamform_accumulated_q8(self, d_antenna, antenna_bytes: int, d_quant_gains, d_beams_q8, beams_bytes: int, nt: int,
+                                t_coeff: int | None = None, dt_coeff: float | None = None, d_weights=None, d_clip_count=None,
+                                stream=None) -> None:
+        """:meth:`beamform_accumulated` (with ``d_weights``: :meth:`beamform_accumulated_weighted`) whose epilogue
+        requantises every beam to int8 with its gain: ``q = clamp(rint(v * k_b), -127, 127)``, NaN -> -128; the int8
+        tensor is ``[C][nt / 16][B][16][{re, im}]`` (:func:`quantised_beams_bytes`)."""
+        if (t_coeff is None) == (dt_coeff is None):
+            raise ValueError("give exactly one of t_coeff / dt_coeff")
+        ql = _lib.beam_quant_lib()
+        w = c_void_p(None if d_weights is None else int(d_weights))
+        clips = c_void_p(None if d_clip_count is None else int(d_clip_count))
+        if dt_coeff is None:
+            check(ql.dcs_bf_beamform_accumulated_q8(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
+                                                    int(antenna_bytes), w, c_void_p(int(d_quant_gains)), c_void_p(int(d_beams_q8)),
+                                                    int(beams_bytes), clips, _s(stream)),
+                  "dcs_bf_beamform_accumulated_q8")
+        else:
+            check(ql.dcs_bf_beamform_accumulated_q8_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
+                                                       c_void_p(int(d_antenna)), int(antenna_bytes), w, c_void_p(int(d_quant_gains)),
+                                                       c_void_p(int(d_beams_q8)), int(beams_bytes), clips, _s(stream)),
+                  "dcs_bf_beamform_accumulated_q8_dt")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

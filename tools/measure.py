@@ -16,6 +16,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py bfweights [--rounds 5]
         per-input beam weights: weighted against unweighted beamformer calls, alternating, in one process
                                                                                     -> profiles/r04_beam_weights.md
+    python tools/measure.py bfq8 [--rounds 5] [--shape AxBxCxNT --variant float|q8|q8c]
+        quantised int8 beam output: the float call against the int8 call (clip rate 0 and ~1 %, with and without
+        counters), alternating, in one process; with DCS_LIB_PATH pointing at a -DDCS_Q8_DWORD_STORES build beside its
+        companions, the other store form                                            -> profiles/r05_beam_quant.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -313,6 +317,80 @@ def cmd_bfweights(args):
     print(json.dumps({"bfweights": rows}), flush=True)
 
 
+def cmd_bfq8(args):
+    """Quantised int8 beam output (include/dcs_beam_quant.h): per shape the float call (twice: its own spread) and the int8
+    call at a clip rate of 0 and of about 1 %, each with and without counters, timed in turn ``--rounds`` times in the same
+    process on the same buffers.  The gains come from the float output of the first channels; the clip rates printed are
+    the counters' own.  ``--shape`` with ``--variant``: a few launches of one call only (counter passes)."""
+    from dc_sand_amd.beam_quant import BeamQuantGains
+    from dc_sand_amd.generator import quantised_beams_bytes
+
+    shapes = [(64, 16, 32768, 256), (64, 256, 4096, 256), (256, 64, 4096, 256), (256, 64, 1024, 256)]
+    if args.shape:
+        shapes = [tuple(int(v) for v in args.shape.split("x"))]
+    rows = []
+    for A, B, C, nt in shapes:
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        ab, fb, qb = A * C * nt * 2, B * C * nt * 8, quantised_beams_bytes(bp, nt)
+        d_ant, d_beams = device.mem_alloc(ab), device.mem_alloc(fb)
+        d_q = device.mem_alloc(qb)
+        _noise(d_ant, ab)
+        f32 = lambda: g.beamform_accumulated(d_ant, ab, d_beams, fb, nt, t_coeff=1)  # noqa: E731
+        f32()
+        nc = min(C, 8)  # the gains: from the first channels' float beams
+        v = np.empty((nc, nt // 16, B, 16, 2), dtype=np.float32)
+        device.memcpy_dtoh(v, d_beams)
+        mag = np.abs(np.moveaxis(v, 2, 0).reshape(B, -1)).astype(np.float64)
+        sets = {}
+        for name, k in (("0", 40.0 / mag.max(axis=1)), ("1pc", 127.5 / np.quantile(mag, 0.99, axis=1))):
+            qg = BeamQuantGains(bp)
+            qg.host[:] = k.astype(np.float32)
+            qg.upload()
+            sets[name] = qg
+
+        def q8(name, count):
+            qg = sets[name]
+            return lambda: g.beamform_accumulated_q8(d_ant, ab, qg.device_ptr(), d_q, qb, nt, t_coeff=1,
+                                                     d_clip_count=qg.clip_count_ptr() if count else None)
+        rates = {}
+        for name, qg in sets.items():  # the clip rate each gain set really gives, from one counted call
+            q8(name, True)()
+            rates[name] = float(qg.clip_counts(reset=True).sum()) / qb
+        if args.shape:
+            fn = {"float": f32, "q8": q8("1pc", False), "q8c": q8("1pc", True)}[args.variant]
+            for _ in range(5):
+                fn()
+            device.synchronize()
+            print(f"{args.variant} {A}x{B}x{C}x{nt}: algorithmic output bytes {fb if args.variant == 'float' else qb}", flush=True)
+            return
+        calls = [("float", f32), ("float_again", f32), ("q8_0", q8("0", False)), ("q8_0_counted", q8("0", True)),
+                 ("q8_1pc", q8("1pc", False)), ("q8_1pc_counted", q8("1pc", True))]
+        t = {name: [] for name, _ in calls}
+        for _ in range(args.rounds):
+            for name, fn in calls:
+                t[name].append(per_launch_ms(fn))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        spread = max(max(t["float"] + t["float_again"]) / min(t["float"] + t["float_again"]) - 1.0, abs(med["float_again"] / med["float"] - 1.0))
+        row = {"shape": f"{A}x{B}x{C}x{nt}", "form": "staged" if A <= 64 else "kChain", "byte_ratio": round((2 * A + 2 * B) / (2 * A + 8 * B), 3),
+               "float_us": round(med["float"] * 1e3, 1), "float_again_us": round(med["float_again"] * 1e3, 1), "float_spread": round(spread, 4),
+               "float_frac_8TBps": round((2 * A + 8 * B) * C * nt / (med["float"] * 1e-3) / 8e12, 3),
+               "clip_rate_0": rates["0"], "clip_rate_1pc": round(rates["1pc"], 5)}
+        for name in ("q8_0", "q8_0_counted", "q8_1pc", "q8_1pc_counted"):
+            row[name + "_us"] = round(med[name] * 1e3, 1)
+            row[name + "_ratio"] = round(med[name] / med["float"], 4)
+            row[name + "_frac_8TBps"] = round((2 * A + 2 * B) * C * nt / (med[name] * 1e-3) / 8e12, 3)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        for qg in sets.values():
+            qg.free()
+        g.close()
+        for d in (d_ant, d_beams, d_q):
+            d.free()
+    print(json.dumps({"bfq8": rows}), flush=True)
+
+
 def cmd_copy(args):
     """Mixed read + write ceiling: device-to-device copies (lean kernel in address order; hipMemcpyDtoD)."""
     from probes import dcs_probes as pr
@@ -600,6 +678,10 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="alternations of unweighted and weighted timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape only (counter passes)")
     p.add_argument("--kind", default="acc", choices=["acc", "fused"], help="with --shape: which beamformer")
+    p = sub.add_parser("bfq8")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the float and the int8 timings per shape")
+    p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
+    p.add_argument("--variant", default="q8", choices=["float", "q8", "q8c"], help="with --shape: float call, int8 call, int8 call with counters")
     sub.add_parser("mfma")
     sub.add_parser("copy")
     p = sub.add_parser("bfacc")
@@ -634,7 +716,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
