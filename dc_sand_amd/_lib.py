@@ -219,6 +219,33 @@ def beam_quant_lib() -> ctypes.CDLL:
     return _QUANT
 
 
+# include/dcs_beam_power.h: the companion library of detected, time-integrated beam power, built with the product
+# library; it takes the context handles of the library above
+POWER_LIB_PATH = LIB_PATH.parent / "libdcs_beam_power.so"
+BEAM_POWER_SIGNATURES = [
+    ("dcs_bf_beamform_accumulated_power", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ("dcs_bf_beamform_accumulated_power_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ("dcs_bf_integrate_block_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+]
+
+_POWER = None
+
+
+def beam_power_lib() -> ctypes.CDLL:
+    global _POWER
+    if _POWER is None:
+        _lib()  # the product library first: its contexts are what the companion works on
+        if not POWER_LIB_PATH.exists():
+            raise ImportError(f"{POWER_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
+        plib = ctypes.CDLL(str(POWER_LIB_PATH))
+        for name, restype, argtypes in BEAM_POWER_SIGNATURES:
+            fn = getattr(plib, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _POWER = plib
+    return _POWER
+
+
 def check(status: int, where: str) -> None:
     if status != DCS_OK:
         raise DcsError(status, where)

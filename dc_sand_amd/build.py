@@ -2,7 +2,8 @@
 ``dc_sand_amd/csrc/libdcs_beamformer.so`` and its companions -- staged delay tables
 (``include/dcs_stream_staging.h``) into ``libdcs_stream_staging.so``, per-input beam weights
 (``include/dcs_beam_weights.h``) into ``libdcs_beam_weights.so``, quantised int8 beam output
-(``include/dcs_beam_quant.h``) into ``libdcs_beam_quant.so`` -- with hipcc (in-tree, so the libraries
+(``include/dcs_beam_quant.h``) into ``libdcs_beam_quant.so``, detected beam power
+(``include/dcs_beam_power.h``) into ``libdcs_beam_power.so`` -- with hipcc (in-tree, so the libraries
 travel with the source tree).  ``python -m dc_sand_amd.build [--force]``.
 
 Flags that are part of the numerical contract (DESIGN.md "numerics"):
@@ -24,7 +25,7 @@ LIB = CSRC / "libdcs_beamformer.so"
 SOURCES = ["bf_kernels.hip", "bf_beamform_mfma.hip", "bf_capi.hip"]
 HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "bf_stream_ext.h", "bf_ctx_ext.h", "bf_beamform_kernel.inc",
            "bf_beamform_i8_kernel.inc", "../../include/dcs_beamformer.h", "../../include/dcs_stream_staging.h",
-           "../../include/dcs_beam_weights.h", "../../include/dcs_beam_quant.h"]
+           "../../include/dcs_beam_weights.h", "../../include/dcs_beam_quant.h", "../../include/dcs_beam_power.h"]
 # the companion library of include/dcs_stream_staging.h (staged delay tables for the streams of the product library)
 STAGING_LIB = CSRC / "libdcs_stream_staging.so"
 STAGING_SOURCES = ["bf_stream_staging.cpp"]
@@ -34,6 +35,9 @@ WEIGHTS_SOURCES = ["bf_beam_weights.cpp"]
 # the companion library of include/dcs_beam_quant.h (quantised int8 beam output of the product library's matrix-core beamformer)
 QUANT_LIB = CSRC / "libdcs_beam_quant.so"
 QUANT_SOURCES = ["bf_beam_quant.cpp"]
+# the companion library of include/dcs_beam_power.h (detected, time-integrated beam power of the same beamformer)
+POWER_LIB = CSRC / "libdcs_beam_power.so"
+POWER_SOURCES = ["bf_beam_power.cpp"]
 ARCH = "gfx950"
 
 
@@ -101,7 +105,7 @@ def compile_and_link(sources, extra_flags, out: Path, verbose: bool = False) -> 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """All four libraries; returns the product library's path."""
+    """All five libraries; returns the product library's path."""
     if force or needs_build():
         compile_and_link([CSRC / s for s in SOURCES], [], LIB, verbose)
     if force or needs_build(STAGING_LIB, STAGING_SOURCES):
@@ -110,6 +114,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         compile_and_link([CSRC / s for s in WEIGHTS_SOURCES], [], WEIGHTS_LIB, verbose)
     if force or needs_build(QUANT_LIB, QUANT_SOURCES):
         compile_and_link([CSRC / s for s in QUANT_SOURCES], [], QUANT_LIB, verbose)
+    if force or needs_build(POWER_LIB, POWER_SOURCES):
+        compile_and_link([CSRC / s for s in POWER_SOURCES], [], POWER_LIB, verbose)
     return LIB
 
 

@@ -1,6 +1,7 @@
-// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included four times by bf_beamform_mfma.hip:
+// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included six times by bf_beamform_mfma.hip:
 // BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights); with
-// BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output).  One text, four
+// BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output), with BF_I8_POWER 1
+// bf_beamform_i8_p_kernel and bf_beamform_i8_wp_kernel (detected block power).  One text, six
 // kernels: a WEIGHTED template parameter would rename the unweighted kernels' symbols, and a body shared through an inline
 // function changes their code; compiled from this file, the unweighted kernels are, instruction for instruction, what
 // they were before weights existed, and the float kernels what they were before the quantiser.
@@ -16,9 +17,19 @@
 // bw + (lane >> 4) + 4 (lane & 3), h = (lane >> 2) & 1), and the wave writes its pair of blocks with one 16-byte store
 // per lane: 2 x 512 contiguous bytes.  kStaged keeps its four gains in registers, kChain reads them from LDS behind the
 // weighted form's factors, one register ahead.  Clipped components are counted per lane and tallied once, at the end.
+// POWER (kStaged and kChain; include/dcs_beam_power.h, DESIGN.md section 5.9): a result register's four floats -- again
+// the very floats the float kernel stores -- become |.|^2 of its two samples and their sum; three exchanges inside each
+// group of 8 lanes (power_block_sum) finish the 16-sample block's balanced pairwise sum, the same bits in all 8 lanes.
+// Lane m < 4 of a group keeps register m's sum and writes that one dword: beam bw + (lane >> 4) + 4 m of its block of the
+// tensor [c][t/16][b] -- 2 x 64 contiguous bytes per wave and pair of blocks.  The weighted form's factors as in the
+// float kernels.
 template <int FORM, bool FULL, int NW = 4>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT))))
-#if BF_I8_WEIGHTED && BF_I8_QUANT
+#if BF_I8_WEIGHTED && BF_I8_POWER
+bf_beamform_i8_wp_kernel(const bf_bacc_args a, const bf_weights_args w)
+#elif BF_I8_POWER
+bf_beamform_i8_p_kernel(const bf_bacc_args a)
+#elif BF_I8_WEIGHTED && BF_I8_QUANT
 bf_beamform_i8_wq_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_quant_args qa)
 #elif BF_I8_QUANT
 bf_beamform_i8_q_kernel(const bf_bacc_args a, const bf_quant_args qa)
@@ -38,6 +49,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     static_assert(NW == 4 || ((NW == 8 || NW == 16) && FORM == kStaged), "8- and 16-wave workgroups exist for the staged form only");
     static_assert(!WEIGHTED || FORM == kStaged || FORM == kChain, "weights exist for the product's forms only");
     static_assert(!QUANT || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the quantiser exists for the product's forms only");
+    static_assert(!BF_I8_POWER || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the detector exists for the product's forms only");
     constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
     extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
     uint32_t bid = BACC_LOGICAL_ID(a);
@@ -336,6 +348,25 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     };
     // scale and store: lane l, register r = beam bw + (l >> 4) + 4 r, samples 2 m, 2 m + 1
     auto finish = [&](auto whole, uint32_t blk, const floatx4 (&f)[4]) {
+        if constexpr (BF_I8_POWER) { // the same floats, detected: the block sum of register m stays with lane m < 4 of each 8
+            float mine = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; r++) { // beam bb + 4 r
+                const float sc = WEIGHTED ? fac[r] : inv;
+                floatx4 o = {f[0][r] * sc, f[1][r] * sc, f[2][r] * sc, f[3][r] * sc};
+                if (nan_re | nan_im) poison(r, o);
+                const float P = power_block_sum(o);
+                mine = m == (uint32_t)r ? P : mine;
+            }
+            const uint32_t blkA = min(blk, last), blkB = min(blk + 1u, last);
+            char *base = out8 + ((uint64_t)c * a.nT16 + tt0 + blkA * tpr + slot) * (a.B * 4u); // wave-uniform
+            const uint32_t hop = second ? (blkB - blkA) * tpr * (a.B * 4u) : 0u;
+            const uint32_t pbeam = bb + 4u * m; // (m < 4) this lane's dword: beam pbeam of block A (lanes 0 - 7 of 16) or B
+            // a pair past the end repeats the last block: not stored
+            if (m < 4u && (!second || blk + 1u <= last) && (decltype(whole)::value || pbeam < a.B))
+                *reinterpret_cast<float *>(base + (hop + pbeam * 4u)) = mine;
+            return;
+        }
         if constexpr (QUANT) { // the same floats, quantised: one dword per register, transposed, one store
             const bool pair_live = !second || blk + 1u <= last; // a pair past the end repeats the last block: neither stored nor counted twice
             uint32_t pk[4];
@@ -550,6 +581,35 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                         for (int v = half; v < 4; v += 2) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v], acc[v][d], 0, 0, 0);
                     }
                 }
+                if constexpr (BF_I8_POWER) {
+                    if (chunk + 1u == n_chunks) { // as the float form below, each register detected and summed as it is recombined; then one dword
+                        float sc_next = WEIGHTED ? facw[lg] : inv; // beam bb + 4 r's factor, one register ahead
+                        float mine = 0.0f;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const float sc = sc_next;
+                            if constexpr (WEIGHTED) {
+                                if (r < 3) sc_next = facw[4u * (uint32_t)r + 4u + lg];
+                            }
+                            floatx4 o;
+#pragma unroll
+                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * sc;
+                            if (nan_re | nan_im) poison(r, o);
+                            const float P = power_block_sum(o);
+                            mine = m == (uint32_t)r ? P : mine;
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        const uint32_t blkB = min(blk + 1u, last); // (blk <= last)
+                        char *base = out8 + ((uint64_t)c * a.nT16 + tt0 + blk * tpr + slot) * (a.B * 4u); // wave-uniform
+                        const uint32_t hop = second ? (blkB - blk) * tpr * (a.B * 4u) : 0u;
+                        const uint32_t pbeam = bb + 4u * m;
+                        if (m < 4u && (!second || blk + 1u <= last) && (decltype(whole)::value || pbeam < a.B))
+                            *reinterpret_cast<float *>(base + (hop + pbeam * 4u)) = mine;
+                        chunk = 0u, blk += 2u;
+                    } else {
+                        chunk++;
+                    }
+                } else
                 if constexpr (QUANT) {
                     if (chunk + 1u == n_chunks) { // as below, each register quantised to one dword as it is recombined; then one store
                         const bool pair_live = !second || blk + 1u <= last;

@@ -359,6 +359,24 @@ __device__ __forceinline__ void q8_tally(unsigned long long *clips, uint32_t n_c
     }
 }
 
+// ---- the detecting epilogue (include/dcs_beam_power.h): what bf_beamform_i8_p_kernel and
+// bf_beamform_i8_wp_kernel do with a result register instead of storing its four floats.
+// o = {re even, im even, re odd, im odd} of one beam and samples 2 m, 2 m + 1 (m = lane & 7), exactly the floats the float
+// kernel stores.  p_t = RN(RN(re re) + RN(im im)) per sample (no fma: -ffp-contract=off), level 1 of the block's pairwise sum
+// in the lane, levels 2 - 4 with lane ^ 1, lane ^ 2 (the DPP quad permutes of q8_quad_transpose) and the other quad of the
+// 8-lane group (row_half_mirror: lane 7 - i of the group, whose quad holds one value by then).  fp32 addition commutes, so
+// all 8 lanes end with the same bits; every lane of the wave must be active.
+__device__ __forceinline__ float power_block_sum(const floatx4 o)
+{
+    const float p_even = o[0] * o[0] + o[1] * o[1], p_odd = o[2] * o[2] + o[3] * o[3];
+    float s = p_even + p_odd;
+    s = s + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0xB1, 0xf, 0xf, false));  // quad_perm [1, 0, 3, 2]
+    s = s + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x4E, 0xf, 0xf, false));  // quad_perm [2, 3, 0, 1]
+    s = s + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x141, 0xf, 0xf, false)); // row_half_mirror
+    return s;
+}
+
+#define BF_I8_POWER 0
 #define BF_I8_QUANT 0
 #define BF_I8_WEIGHTED 0
 #include "bf_beamform_i8_kernel.inc"
@@ -375,6 +393,35 @@ __device__ __forceinline__ void q8_tally(unsigned long long *clips, uint32_t n_c
 #include "bf_beamform_i8_kernel.inc"
 #undef BF_I8_WEIGHTED
 #undef BF_I8_QUANT
+#undef BF_I8_POWER
+#define BF_I8_POWER 1
+#define BF_I8_QUANT 0
+#define BF_I8_WEIGHTED 0
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
+#undef BF_I8_WEIGHTED
+#undef BF_I8_QUANT
+#undef BF_I8_POWER
+
+// Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
+// beam), beam fastest, adding its n blocks in order -- one rounded add each, no atomics, the same sum whatever the launch
+// geometry.  A wave reads and writes runs of consecutive beams (and, where B < 64, of consecutive channels' runs).
+__global__ void __launch_bounds__(256) bf_power_integrate_kernel(const bf_pint_args a)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // (i * C + c) * B + b
+    if (g >= a.total) return;
+    const uint32_t b = (uint32_t)(g % a.B);
+    const uint64_t ic = g / a.B;
+    const uint32_t c = (uint32_t)(ic % a.C);
+    const uint64_t i = ic / a.C;
+    const float *p = a.block_power + (((uint64_t)c * a.nr_blocks + i * a.n) * a.B + b);
+    float acc = a.accumulate ? a.spectra[g] : p[0];
+#pragma unroll 4
+    for (uint32_t j = a.accumulate ? 0u : 1u; j < a.n; j++) acc = acc + p[(uint64_t)j * a.B];
+    a.spectra[g] = acc;
+}
 
 } // namespace
 
@@ -396,13 +443,16 @@ hipError_t bf_warm_module_mfma()
 namespace {
 // w: nullptr, or the weights (the int8 form's kStaged and kChain only); q: nullptr, or the quantiser's gains and counters
 // (the same two forms; a.beams is then the int8 tensor)
-hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, hipStream_t stream)
+// power: a.beams is the block power tensor [C][nT16][B], written by the detecting kernels (the same two forms)
+hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, hipStream_t stream,
+                               bool power = false)
 {
     bf_bacc_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nT16 == 0) return hipSuccess;
     if (a.A > 256u) return hipErrorInvalidValue; // not built
     const bool chain = a.fp32_chain != 0u;
-    if ((w || q) && chain) return hipErrorInvalidValue;
+    if ((w || q || power) && chain) return hipErrorInvalidValue;
+    if (q && power) return hipErrorInvalidValue;
     // beam tiles per workgroup: as many as the beams need; the fp32 form keeps its coefficient planes in LDS and
     // takes as many as still admit 6 workgroups per CU (26 KiB each), one tile whatever it takes beyond
     // more than 64 antennas, int8 form: one beam tile per workgroup; kChain (the product's form) or, probes build only, kSplit
@@ -447,6 +497,40 @@ hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *
     const uint64_t blocks = (uint64_t)a.C * a.n_bgroups * a.n_tgroups;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)blocks), block(64u * nw);
+    if (power) { // the product's forms only; the geometry and the LDS of the float kernels' branches below
+        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
+        const bf_weights_args w0 = w ? *w : bf_weights_args{};
+        size_t lds_p;
+        if (staged_form) {
+            lds_p = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
+            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
+                a.share_off = (uint32_t)lds_p;
+                lds_p += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
+            }
+        } else { // kChain: the coefficients, the NaN-row words and (weighted) the 16 beams' scale factors
+            lds_p = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + (w ? 16u * sizeof(float) : 0u);
+        }
+#define BF_LAUNCH_POWER(FORM, FULL)                                                                                    \
+    do {                                                                                                               \
+        if (w)                                                                                                         \
+            hipLaunchKernelGGL((bf_beamform_i8_wp_kernel<FORM, FULL>), grid, block, lds_p, stream, a, w0);             \
+        else                                                                                                           \
+            hipLaunchKernelGGL((bf_beamform_i8_p_kernel<FORM, FULL>), grid, block, lds_p, stream, a);                  \
+    } while (0)
+        if (staged_form) {
+            if (a.A == 64u)
+                BF_LAUNCH_POWER(kStaged, true);
+            else
+                BF_LAUNCH_POWER(kStaged, false);
+        } else {
+            if (a.A % 64u == 0u)
+                BF_LAUNCH_POWER(kChain, true);
+            else
+                BF_LAUNCH_POWER(kChain, false);
+        }
+#undef BF_LAUNCH_POWER
+        return hipGetLastError();
+    }
     if (q) { // the product's forms only; as the branch below, with the quantised kernels
         if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
         if (a.tiles_per_wg / tpr > 126u) return hipErrorInvalidValue; // a lane counts its clips in bytes, 4 per pair of blocks
@@ -573,4 +657,18 @@ hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weigh
 hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream)
 {
     return launch_beamform_acc(a, w, &q, stream);
+}
+
+hipError_t bf_launch_beamform_acc_power(const bf_bacc_args &a, const bf_weights_args *w, hipStream_t stream)
+{
+    return launch_beamform_acc(a, w, nullptr, stream, true);
+}
+
+hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream)
+{
+    if (a.total == 0u) return hipSuccess;
+    const uint64_t blocks = (a.total + 255u) / 256u;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bf_power_integrate_kernel, dim3((uint32_t)blocks), dim3(256u), 0, stream, a);
+    return hipGetLastError();
 }

@@ -393,8 +393,13 @@ int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff,
 int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
                                  size_t antenna_bytes, const float *d_weights, const float *d_quant_gains, int8_t *d_beams_q8,
                                  size_t beams_bytes, unsigned long long *d_clip_count, void *stream);
+int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                    size_t antenna_bytes, const float *d_weights, float *d_block_power, size_t power_bytes,
+                                    void *stream);
+int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                               uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream);
 const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl,
-                                    beamform_accumulated_q8_impl};
+                                    beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl};
 }
 
 int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
@@ -1225,9 +1230,10 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *c, const float *dt, uint32_t
 
 namespace {
 // quant: nullptr, or the quantiser's gains and counters (include/dcs_beam_quant.h): d_beams is then the int8 tensor, a quarter the size
+// power: d_beams is the block power tensor (include/dcs_beam_power.h): one float per beam and 16-sample block, 4-byte aligned
 int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes,
                       void *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr,
-                      const bf_quant_args *quant = nullptr)
+                      const bf_quant_args *quant = nullptr, bool power = false)
 {
     if (!c || (nt && (!d_antenna || !d_beams))) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
@@ -1236,10 +1242,11 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     const uint32_t A = (uint32_t)c->p.nr_stations, B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     if (A > 256u) return DCS_ERR_UNSUPPORTED; // the coefficient planes of one workgroup must fit 64 KiB of LDS
     if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
-    if (beams_bytes < (size_t)B * C * nt * 2u * (quant ? sizeof(int8_t) : sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & 7u))
+    if (beams_bytes < (power ? (size_t)B * C * (nt / 16u) * sizeof(float) : (size_t)B * C * nt * 2u * (quant ? sizeof(int8_t) : sizeof(float))))
         return DCS_ERR_INVALID_ARGUMENT;
-    if ((d_weights || quant) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights and no quantiser
+    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & (power ? 3u : 7u)))
+        return DCS_ERR_INVALID_ARGUMENT;
+    if ((d_weights || quant || power) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights, no quantiser, no detector
     if (nt == 0) return DCS_OK;
     {
         const int st_range = check_dt_range(c, src, 1); // the one coefficient time, before anything is allocated
@@ -1305,6 +1312,7 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     a.nw_force = knob(c->probe.bacc_waves, "DCS_BACC_WAVES");
 #endif
     if (quant) return (int)bf_launch_beamform_acc_q8(a, d_weights ? &wa : nullptr, *quant, s);
+    if (power) return (int)bf_launch_beamform_acc_power(a, d_weights ? &wa : nullptr, s);
     return (int)(d_weights ? bf_launch_beamform_acc_weighted(a, wa, s) : bf_launch_beamform_acc(a, s));
 }
 
@@ -1337,6 +1345,39 @@ int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint6
     const bf_quant_args quant = {d_quant_gains, d_clip_count};
     return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes,
                              stream, d_weights, &quant);
+}
+
+// include/dcs_beam_power.h, reached the same way
+int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                    size_t antenna_bytes, const float *d_weights, float *d_block_power, size_t power_bytes,
+                                    void *stream)
+{
+    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights))) return DCS_ERR_INVALID_ARGUMENT;
+    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_block_power, power_bytes,
+                             stream, d_weights, nullptr, true);
+}
+
+int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                               uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream)
+{
+    if (!c || !weights_ok(d_block_power) || !weights_ok(d_spectra)) return DCS_ERR_INVALID_ARGUMENT;
+    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
+    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
+    if (power_bytes < (size_t)C * nr_blocks * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    if (spectra_bytes < (size_t)n_spectra * C * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_pint_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_power = d_block_power;
+    a.spectra = d_spectra;
+    a.total = n_spectra * C * B;
+    a.B = B;
+    a.C = C;
+    a.nr_blocks = nr_blocks;
+    a.n = blocks_per_spectrum;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_power_integrate(a, as_stream(stream));
 }
 } // namespace
 

@@ -1,7 +1,8 @@
 // bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
-// (include/dcs_beam_weights.h) and libdcs_beam_quant.so (include/dcs_beam_quant.h).  All are built from this tree
+// (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h) and libdcs_beam_power.so
+// (include/dcs_beam_power.h).  All are built from this tree
 // together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
-// implementation of the weighted and the quantised beamformer calls; a companion checks the arguments it can check
+// implementation of the weighted, the quantised and the detecting beamformer calls; a companion checks the arguments it can check
 // without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
@@ -11,7 +12,7 @@
 
 #include "../../include/dcs_beamformer.h"
 
-#define BF_CTX_EXT_VERSION 2u // 2: beamform_accumulated_q8 appended
+#define BF_CTX_EXT_VERSION 3u // 2: beamform_accumulated_q8 appended; 3: beamform_accumulated_power, integrate_block_power appended
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -28,6 +29,14 @@ struct bf_ctx_ext_ops {
                                    const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
                                    const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
                                    unsigned long long *d_clip_count, void *stream);
+    // the same with detected block power out (include/dcs_beam_power.h): float [C][nt / 16][B]; d_weights: nullptr = unweighted
+    int (*beamform_accumulated_power)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                      const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                      float *d_block_power, size_t power_bytes, void *stream);
+    // block powers [C][nr_blocks][B] -> spectra [nr_blocks / blocks_per_spectrum][C][B]
+    int (*integrate_block_power)(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                                 uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
+                                 void *stream);
 };
 
 // the first member of struct dcs_bf_context

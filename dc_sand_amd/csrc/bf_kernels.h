@@ -201,6 +201,21 @@ struct bf_quant_args {
 };
 // w: nullptr (unweighted) or the weights, as bf_launch_beamform_acc_weighted (int8 form only: kStaged and kChain)
 hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream);
+// Detected beam power (include/dcs_beam_power.h): a.beams is then the block power tensor
+// [C][nT16][B], one float per beam and 16-sample block, written by the detecting kernels' epilogue from the floats the
+// float calls would have stored.  w as above.
+hipError_t bf_launch_beamform_acc_power(const bf_bacc_args &a, const bf_weights_args *w, hipStream_t stream);
+// Block powers [C][nr_blocks][B] summed n at a time, in order, into spectra [nr_blocks / n][C][B]
+struct bf_pint_args {
+    const float *block_power;
+    float *spectra;
+    uint64_t total;      // (nr_blocks / n) * C * B
+    uint32_t B, C;
+    uint32_t nr_blocks;  // a multiple of n
+    uint32_t n;          // blocks per spectrum, >= 1
+    uint32_t accumulate; // non-zero: the sums start from what spectra holds
+};
+hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
 // One coefficient per lane, one time step (reference kernel a1's shape).

@@ -70,6 +70,19 @@ def quantised_beams_bytes(params: BeamformerParameters, nt: int) -> int:
     return int(params.NR_CHANNELS) * int(nt) * int(params.NR_BEAMS) * 2
 
 
+def block_power_bytes(params: BeamformerParameters, nt: int) -> int:
+    """Size of the block power tensor ``float [C][nt / 16][B]`` of :meth:`SteeringCoefficientGenerator.beamform_accumulated_power`."""
+    return int(params.NR_CHANNELS) * (int(nt) // 16) * int(params.NR_BEAMS) * 4
+
+
+def power_spectra_bytes(params: BeamformerParameters, nr_blocks: int, blocks_per_spectrum: int) -> int:
+    """Size of the spectra ``float [nr_blocks / blocks_per_spectrum][C][B]`` of
+    :meth:`SteeringCoefficientGenerator.integrate_block_power`."""
+    if blocks_per_spectrum <= 0 or nr_blocks % blocks_per_spectrum:
+        raise ValueError("nr_blocks must be a multiple of blocks_per_spectrum >= 1")
+    return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * int(params.NR_BEAMS) * 4
+
+
 def gpu_utilisation(params: BeamformerParameters, kernel_ms: float) -> tuple[float, float]:
     """``BeamformerCoeffTest::get_time`` model (``BeamformerCoefficientTest.cu:426-448``)."""
     out = (c_float * 2)()
@@ -253,6 +266,39 @@ class SteeringCoefficientGenerator:
                                                        c_void_p(int(d_antenna)), int(antenna_bytes), w, c_void_p(int(d_quant_gains)),
                                                        c_void_p(int(d_beams_q8)), int(beams_bytes), clips, _s(stream)),
                   "dcs_bf_beamform_accumulated_q8_dt")
+
+    # -- detected beam power (include/dcs_beam_power.h, companion library libdcs_beam_power.so): d_block_power is a device
+    #    float [C][nt / 16][B] array, d_spectra a device float [nr_blocks / blocks_per_spectrum][C][B] array
+    def beamform_accumulated_power(self, d_antenna, antenna_bytes: int, d_block_power, power_bytes: int, nt: int,
+                                   t_coeff: int | None = None, dt_coeff: float | None = None, d_weights=None, stream=None) -> None:
+        """:meth:`beamform_accumulated` (with ``d_weights``: :meth:`beamform_accumulated_weighted`) whose epilogue
+        detects: ``|v|^2`` of every sample, summed pairwise over each 16-sample block, one float per (channel, block,
+        beam) (:func:`block_power_bytes`)."""
+        if (t_coeff is None) == (dt_coeff is None):
+            raise ValueError("give exactly one of t_coeff / dt_coeff")
+        pl = _lib.beam_power_lib()
+        w = c_void_p(None if d_weights is None else int(d_weights))
+        if dt_coeff is None:
+            check(pl.dcs_bf_beamform_accumulated_power(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
+                                                       int(antenna_bytes), w, c_void_p(int(d_block_power)), int(power_bytes),
+                                                       _s(stream)),
+                  "dcs_bf_beamform_accumulated_power")
+        else:
+            check(pl.dcs_bf_beamform_accumulated_power_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
+                                                          c_void_p(int(d_antenna)), int(antenna_bytes), w,
+                                                          c_void_p(int(d_block_power)), int(power_bytes), _s(stream)),
+                  "dcs_bf_beamform_accumulated_power_dt")
+
+    def integrate_block_power(self, d_block_power, power_bytes: int, nr_blocks: int, blocks_per_spectrum: int, d_spectra,
+                              spectra_bytes: int, accumulate: bool = False, stream=None) -> None:
+        """Sums the block powers ``[C][nr_blocks][B]`` ``blocks_per_spectrum`` at a time, in order, into the spectra
+        ``[nr_blocks / blocks_per_spectrum][C][B]`` (:func:`power_spectra_bytes`); with ``accumulate`` the sums start
+        from what ``d_spectra`` holds, so an integration can span calls."""
+        pl = _lib.beam_power_lib()
+        check(pl.dcs_bf_integrate_block_power(c_void_p(self._h), c_void_p(int(d_block_power)), int(power_bytes), int(nr_blocks),
+                                              int(blocks_per_spectrum), 1 if accumulate else 0, c_void_p(int(d_spectra)),
+                                              int(spectra_bytes), _s(stream)),
+              "dcs_bf_integrate_block_power")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -20,6 +20,9 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         quantised int8 beam output: the float call against the int8 call (clip rate 0 and ~1 %, with and without
         counters), alternating, in one process; with DCS_LIB_PATH pointing at a -DDCS_Q8_DWORD_STORES build beside its
         companions, the other store form                                            -> profiles/r05_beam_quant.md
+    python tools/measure.py bfpower [--rounds 5] [--shape AxBxCxNT --variant float|power|power+int]
+        detected beam power: the float call (twice: its own spread) against the detecting call and the detecting call plus
+        the integration, alternating, in one process                              -> profiles/r06_beam_power.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -391,6 +394,67 @@ def cmd_bfq8(args):
     print(json.dumps({"bfq8": rows}), flush=True)
 
 
+def cmd_bfpower(args):
+    """Detected beam power (include/dcs_beam_power.h): per shape the float call (twice: its own spread), the detecting call,
+    the detecting call followed by the integration of all its blocks into one spectrum, and the integration alone, timed in
+    turn ``--rounds`` times in the same process on the same noise-like samples.  Bytes under the roofline's model: 2 A in
+    and 8 B (float) or B / 4 (power) out per sample and channel.  ``--shape`` with ``--variant``: a few launches of one
+    call only (counter passes)."""
+    from dc_sand_amd.generator import block_power_bytes, power_spectra_bytes
+
+    shapes = [(64, 16, 32768, 256), (64, 256, 4096, 256), (256, 64, 4096, 256), (256, 64, 1024, 256)]
+    if args.shape:
+        shapes = [tuple(int(v) for v in args.shape.split("x"))]
+    rows = []
+    for A, B, C, nt in shapes:
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        nblk = nt // 16
+        ab, fb, pb, sb = A * C * nt * 2, B * C * nt * 8, block_power_bytes(bp, nt), power_spectra_bytes(bp, nblk, nblk)
+        d_ant, d_beams, d_p, d_s = device.mem_alloc(ab), device.mem_alloc(fb), device.mem_alloc(pb), device.mem_alloc(sb)
+        _noise(d_ant, ab)
+        f32 = lambda: g.beamform_accumulated(d_ant, ab, d_beams, fb, nt, t_coeff=1)  # noqa: E731
+        power = lambda: g.beamform_accumulated_power(d_ant, ab, d_p, pb, nt, t_coeff=1)  # noqa: E731
+        integ = lambda: g.integrate_block_power(d_p, pb, nblk, nblk, d_s, sb)  # noqa: E731
+
+        def both():
+            power()
+            integ()
+        f32()
+        both()
+        if args.shape:
+            fn = {"float": f32, "power": power, "power+int": both}[args.variant]
+            for _ in range(5):
+                fn()
+            device.synchronize()
+            print(f"{args.variant} {A}x{B}x{C}x{nt}: algorithmic output bytes {fb if args.variant == 'float' else pb + (sb if args.variant == 'power+int' else 0)}",
+                  flush=True)
+            return
+        calls = [("float", f32), ("float_again", f32), ("power", power), ("power_int", both), ("int", integ)]
+        t = {name: [] for name, _ in calls}
+        for _ in range(args.rounds):
+            for name, fn in calls:
+                t[name].append(per_launch_ms(fn))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        spread = max(max(t["float"] + t["float_again"]) / min(t["float"] + t["float_again"]) - 1.0, abs(med["float_again"] / med["float"] - 1.0))
+        bytes_f, bytes_p = (2 * A + 8 * B) * C * nt, (2 * A * 16 + 4 * B) * C * nblk
+        row = {"shape": f"{A}x{B}x{C}x{nt}", "form": "staged" if A <= 64 else "kChain", "byte_ratio": round(bytes_p / bytes_f, 3),
+               "float_us": round(med["float"] * 1e3, 1), "float_again_us": round(med["float_again"] * 1e3, 1), "float_spread": round(spread, 4),
+               "float_frac_8TBps": round(bytes_f / (med["float"] * 1e-3) / 8e12, 3),
+               "power_us": round(med["power"] * 1e3, 1), "power_ratio": round(med["power"] / med["float"], 4),
+               "power_frac_8TBps": round(bytes_p / (med["power"] * 1e-3) / 8e12, 3),
+               "power_int_us": round(med["power_int"] * 1e3, 1), "power_int_ratio": round(med["power_int"] / med["float"], 4),
+               "int_us": round(med["int"] * 1e3, 1), "int_frac_8TBps": round((pb + sb) / (med["int"] * 1e-3) / 8e12, 3),
+               "power_within_spread": bool(med["power"] <= med["float"] * (1.0 + spread))}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        for d in (d_ant, d_beams, d_p, d_s):
+            d.free()
+    print(json.dumps({"bfpower": rows}), flush=True)
+
+
 def cmd_copy(args):
     """Mixed read + write ceiling: device-to-device copies (lean kernel in address order; hipMemcpyDtoD)."""
     from probes import dcs_probes as pr
@@ -678,6 +742,11 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="alternations of unweighted and weighted timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape only (counter passes)")
     p.add_argument("--kind", default="acc", choices=["acc", "fused"], help="with --shape: which beamformer")
+    p = sub.add_parser("bfpower")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the float and the power timings per shape")
+    p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
+    p.add_argument("--variant", default="power", choices=["float", "power", "power+int"],
+                   help="with --shape: float call, detecting call, detecting call + integration")
     p = sub.add_parser("bfq8")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the float and the int8 timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
@@ -716,7 +785,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
