@@ -8,12 +8,6 @@
 
 namespace {
 
-const bf_ctx_ext_ops *ops_of(dcs_bf_context *c)
-{
-    const bf_ctx_ext_ops *ops = reinterpret_cast<const bf_ctx_ext_head *>(c)->ops;
-    return ops && ops->version == BF_CTX_EXT_VERSION ? ops : nullptr;
-}
-
 bool aligned4(const void *p) { return !(reinterpret_cast<uintptr_t>(p) & 3u); }
 
 bool args_ok(dcs_bf_context *c, uint32_t nt, const float *d_weights, const float *d_block_power)

@@ -8,12 +8,6 @@
 
 namespace {
 
-const bf_ctx_ext_ops *ops_of(dcs_bf_context *c)
-{
-    const bf_ctx_ext_ops *ops = reinterpret_cast<const bf_ctx_ext_head *>(c)->ops;
-    return ops && ops->version == BF_CTX_EXT_VERSION ? ops : nullptr;
-}
-
 bool args_ok(dcs_bf_context *c, uint32_t nt, const float *d_weights, const float *d_quant_gains,
              const unsigned long long *d_clip_count)
 {

@@ -23,6 +23,16 @@
 // Lane m < 4 of a group keeps register m's sum and writes that one dword: beam bw + (lane >> 4) + 4 m of its block of the
 // tensor [c][t/16][b] -- 2 x 64 contiguous bytes per wave and pair of blocks.  The weighted form's factors as in the
 // float kernels.
+// An inclusion defines the switches it wants as 1; the others read as 0, and all three are gone again at the end.
+#ifndef BF_I8_WEIGHTED
+#define BF_I8_WEIGHTED 0
+#endif
+#ifndef BF_I8_QUANT
+#define BF_I8_QUANT 0
+#endif
+#ifndef BF_I8_POWER
+#define BF_I8_POWER 0
+#endif
 template <int FORM, bool FULL, int NW = 4>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT))))
 #if BF_I8_WEIGHTED && BF_I8_POWER
@@ -696,4 +706,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         if (qa.clips) q8_tally(qa.clips, n_clip, bb, lm, a.B);
     }
 }
+#undef BF_I8_WEIGHTED
+#undef BF_I8_QUANT
+#undef BF_I8_POWER
 

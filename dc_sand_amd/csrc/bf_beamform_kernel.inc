@@ -3,6 +3,9 @@
 // bf_beamform_i8_kernel.inc gives: the unweighted kernels keep their symbols and, instruction for instruction, their code.
 // WEIGHTED: each coefficient w becomes w' = RN(ghat * w) (ghat[a][b] beside the terms, same addressing), the products
 // and the sums are those described in bf_kernels.hip, and the beam's sums are multiplied by s_b once, at the store.
+#ifndef BF_FUSED_WEIGHTED
+#define BF_FUSED_WEIGHTED 0
+#endif
 template <int CH>
 #if BF_FUSED_WEIGHTED
 __global__ void __launch_bounds__(kBlock) bf_beamform_w_kernel(const bf_beamform_args a, const bf_weights_args w)
@@ -157,4 +160,5 @@ __global__ void __launch_bounds__(kBlock) bf_beamform_kernel(const bf_beamform_a
         }
     }
 }
+#undef BF_FUSED_WEIGHTED
 

@@ -376,34 +376,19 @@ __device__ __forceinline__ float power_block_sum(const floatx4 o)
     return s;
 }
 
-#define BF_I8_POWER 0
-#define BF_I8_QUANT 0
-#define BF_I8_WEIGHTED 0
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
-#undef BF_I8_QUANT
 #define BF_I8_QUANT 1
-#define BF_I8_WEIGHTED 0
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
+#define BF_I8_QUANT 1
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
-#undef BF_I8_QUANT
-#undef BF_I8_POWER
 #define BF_I8_POWER 1
-#define BF_I8_QUANT 0
-#define BF_I8_WEIGHTED 0
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
+#define BF_I8_POWER 1
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
-#undef BF_I8_WEIGHTED
-#undef BF_I8_QUANT
-#undef BF_I8_POWER
 
 // Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
 // beam), beam fastest, adding its n blocks in order -- one rounded add each, no atomics, the same sum whatever the launch
@@ -441,11 +426,41 @@ hipError_t bf_warm_module_mfma()
 }
 
 namespace {
-// w: nullptr, or the weights (the int8 form's kStaged and kChain only); q: nullptr, or the quantiser's gains and counters
-// (the same two forms; a.beams is then the int8 tensor)
-// power: a.beams is the block power tensor [C][nT16][B], written by the detecting kernels (the same two forms)
-hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, hipStream_t stream,
-                               bool power = false)
+// One launch for the six inclusions of bf_beamform_i8_kernel.inc.  w, q, power: nullptr / false = not asked for; those
+// kernels exist for the product's forms (kStaged, kChain; four waves) only, every other instantiation is the plain kernel's.
+template <int FORM, bool FULL, int NW>
+void launch_i8(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a, const bf_weights_args *w,
+               const bf_quant_args *q, bool power)
+{
+    if constexpr (NW == 4 && (FORM == kStaged || FORM == kChain)) {
+        if (power && w)
+            hipLaunchKernelGGL((bf_beamform_i8_wp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w);
+        else if (power)
+            hipLaunchKernelGGL((bf_beamform_i8_p_kernel<FORM, FULL>), grid, block, lds, stream, a);
+        else if (q && w)
+            hipLaunchKernelGGL((bf_beamform_i8_wq_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *q);
+        else if (q)
+            hipLaunchKernelGGL((bf_beamform_i8_q_kernel<FORM, FULL>), grid, block, lds, stream, a, *q);
+        else if (w)
+            hipLaunchKernelGGL((bf_beamform_i8_w_kernel<FORM, FULL>), grid, block, lds, stream, a, *w);
+        if (power || q || w) return;
+    }
+    hipLaunchKernelGGL((bf_beamform_i8_kernel<FORM, FULL, NW>), grid, block, lds, stream, a);
+}
+
+template <int FORM, int NW = 4>
+void launch_i8_form(bool full, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a,
+                    const bf_weights_args *w, const bf_quant_args *q, bool power)
+{
+    if (full)
+        launch_i8<FORM, true, NW>(grid, block, lds, stream, a, w, q, power);
+    else
+        launch_i8<FORM, false, NW>(grid, block, lds, stream, a, w, q, power);
+}
+} // namespace
+
+hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, bool power,
+                                  hipStream_t stream)
 {
     bf_bacc_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nT16 == 0) return hipSuccess;
@@ -497,96 +512,6 @@ hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *
     const uint64_t blocks = (uint64_t)a.C * a.n_bgroups * a.n_tgroups;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)blocks), block(64u * nw);
-    if (power) { // the product's forms only; the geometry and the LDS of the float kernels' branches below
-        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
-        const bf_weights_args w0 = w ? *w : bf_weights_args{};
-        size_t lds_p;
-        if (staged_form) {
-            lds_p = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
-            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
-                a.share_off = (uint32_t)lds_p;
-                lds_p += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
-            }
-        } else { // kChain: the coefficients, the NaN-row words and (weighted) the 16 beams' scale factors
-            lds_p = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + (w ? 16u * sizeof(float) : 0u);
-        }
-#define BF_LAUNCH_POWER(FORM, FULL)                                                                                    \
-    do {                                                                                                               \
-        if (w)                                                                                                         \
-            hipLaunchKernelGGL((bf_beamform_i8_wp_kernel<FORM, FULL>), grid, block, lds_p, stream, a, w0);             \
-        else                                                                                                           \
-            hipLaunchKernelGGL((bf_beamform_i8_p_kernel<FORM, FULL>), grid, block, lds_p, stream, a);                  \
-    } while (0)
-        if (staged_form) {
-            if (a.A == 64u)
-                BF_LAUNCH_POWER(kStaged, true);
-            else
-                BF_LAUNCH_POWER(kStaged, false);
-        } else {
-            if (a.A % 64u == 0u)
-                BF_LAUNCH_POWER(kChain, true);
-            else
-                BF_LAUNCH_POWER(kChain, false);
-        }
-#undef BF_LAUNCH_POWER
-        return hipGetLastError();
-    }
-    if (q) { // the product's forms only; as the branch below, with the quantised kernels
-        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
-        if (a.tiles_per_wg / tpr > 126u) return hipErrorInvalidValue; // a lane counts its clips in bytes, 4 per pair of blocks
-        const bf_weights_args w0 = w ? *w : bf_weights_args{};
-        size_t lds_q;
-        if (staged_form) {
-            lds_q = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
-            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
-                a.share_off = (uint32_t)lds_q;
-                lds_q += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
-            }
-        } else { // kChain: the coefficients, the NaN-row words, the 16 beams' scale factors and their 16 gains
-            lds_q = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + 32u * sizeof(float);
-        }
-#define BF_LAUNCH_Q8(FORM, FULL)                                                                                       \
-    do {                                                                                                               \
-        if (w)                                                                                                         \
-            hipLaunchKernelGGL((bf_beamform_i8_wq_kernel<FORM, FULL>), grid, block, lds_q, stream, a, w0, *q);         \
-        else                                                                                                           \
-            hipLaunchKernelGGL((bf_beamform_i8_q_kernel<FORM, FULL>), grid, block, lds_q, stream, a, *q);              \
-    } while (0)
-        if (staged_form) {
-            if (a.A == 64u)
-                BF_LAUNCH_Q8(kStaged, true);
-            else
-                BF_LAUNCH_Q8(kStaged, false);
-        } else {
-            if (a.A % 64u == 0u)
-                BF_LAUNCH_Q8(kChain, true);
-            else
-                BF_LAUNCH_Q8(kChain, false);
-        }
-#undef BF_LAUNCH_Q8
-        return hipGetLastError();
-    }
-    if (w) { // the product's forms only
-        if (nw != 4u || (!staged_form && (!wide || split))) return hipErrorInvalidValue;
-        if (staged_form) {
-            size_t stage_bytes = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
-            if (tpr > 1u && !BACC_KNOB(a, no_share)) {
-                a.share_off = (uint32_t)stage_bytes;
-                stage_bytes += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
-            }
-            if (a.A == 64u)
-                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kStaged, true>), grid, block, stage_bytes, stream, a, *w);
-            else
-                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kStaged, false>), grid, block, stage_bytes, stream, a, *w);
-        } else { // kChain: as below, + the 16 beams' scale factors
-            const size_t coef_bytes = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + 16u * sizeof(float);
-            if (a.A % 64u == 0u)
-                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kChain, true>), grid, block, coef_bytes, stream, a, *w);
-            else
-                hipLaunchKernelGGL((bf_beamform_i8_w_kernel<kChain, false>), grid, block, coef_bytes, stream, a, *w);
-        }
-        return hipGetLastError();
-    }
     if (chain) {
         if (nbt == 4)
             hipLaunchKernelGGL(bf_beamform_acc_kernel<4>, grid, block, lds, stream, a);
@@ -594,74 +519,40 @@ hipError_t launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *
             hipLaunchKernelGGL(bf_beamform_acc_kernel<2>, grid, block, lds, stream, a);
         else
             hipLaunchKernelGGL(bf_beamform_acc_kernel<1>, grid, block, lds, stream, a);
-    } else if (staged_form) {
+        return hipGetLastError();
+    }
+    const bool plain = !w && !q && !power;
+    if (!plain && (nw != 4u || (!staged_form && (!wide || split)))) return hipErrorInvalidValue; // the product's forms only
+    if (q && a.tiles_per_wg / tpr > 126u) return hipErrorInvalidValue; // a lane counts its clips in bytes, 4 per pair of blocks
+    const bool full = a.A % 64u == 0u; // (kStaged, kDirect: 64 antennas exactly)
+    if (staged_form) {
         size_t stage_bytes = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
         if (tpr > 1u && !BACC_KNOB(a, no_share)) { // waves that own the same tile share the making of its coefficients
             a.share_off = (uint32_t)stage_bytes;
             stage_bytes += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
         }
 #ifdef DCS_PROBES
-        if (a.wg_per_cu >= 1u && a.wg_per_cu <= 5u && stage_bytes < 160u * 1024u / a.wg_per_cu) // residency cap: unused LDS
+        if (plain && a.wg_per_cu >= 1u && a.wg_per_cu <= 5u && stage_bytes < 160u * 1024u / a.wg_per_cu) // residency cap: unused LDS
             stage_bytes = (160u * 1024u / a.wg_per_cu) & ~1023u;
-#endif
-#ifdef DCS_PROBES
-        if (nw == 8u) {
-            if (a.A == 64u)
-                hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, true, 8>), grid, block, stage_bytes, stream, a);
-            else
-                hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, false, 8>), grid, block, stage_bytes, stream, a);
-        } else if (nw == 16u) {
-            if (a.A == 64u)
-                hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, true, 16>), grid, block, stage_bytes, stream, a);
-            else
-                hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, false, 16>), grid, block, stage_bytes, stream, a);
-        } else
-#endif
-        if (a.A == 64u)
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, true>), grid, block, stage_bytes, stream, a);
+        if (nw == 8u)
+            launch_i8_form<kStaged, 8>(full, grid, block, stage_bytes, stream, a, w, q, power);
+        else if (nw == 16u)
+            launch_i8_form<kStaged, 16>(full, grid, block, stage_bytes, stream, a, w, q, power);
         else
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kStaged, false>), grid, block, stage_bytes, stream, a);
+#endif
+        launch_i8_form<kStaged>(full, grid, block, stage_bytes, stream, a, w, q, power);
 #ifdef DCS_PROBES
     } else if (a.A <= 64u) { // kDirect: the probes build's A/B form only
-        if (a.A == 64u)
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kDirect, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kDirect, false>), grid, block, 0, stream, a);
-#endif
-#ifdef DCS_PROBES
+        launch_i8_form<kDirect>(full, grid, block, 0, stream, a, w, q, power);
     } else if (split) { // 2 pairs x 4 registers x 4 chunks x 64 lanes x 16 bytes of partial sums
-        const size_t part_bytes = 2u * 4u * 4u * 64u * 16u;
-        if (a.A % 64u == 0u)
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kSplit, true>), grid, block, part_bytes, stream, a);
-        else
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kSplit, false>), grid, block, part_bytes, stream, a);
+        launch_i8_form<kSplit>(full, grid, block, 2u * 4u * 4u * 64u * 16u, stream, a, w, q, power);
 #endif
-    } else { // kChain: 4 chunks x 6 operands x 64 lanes x 16 bytes of coefficients + the chunks' NaN-row words
-        const size_t coef_bytes = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t);
-        if (a.A % 64u == 0u)
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kChain, true>), grid, block, coef_bytes, stream, a);
-        else
-            hipLaunchKernelGGL((bf_beamform_i8_kernel<kChain, false>), grid, block, coef_bytes, stream, a);
+    } else { // kChain: 4 chunks x 6 operands x 64 lanes x 16 bytes of coefficients + the chunks' NaN-row words, then the 16
+             // beams' scale factors (weighted) and behind them their 16 gains (quantised, weighted or not)
+        const size_t coef_bytes = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + (q ? 32u : (w ? 16u : 0u)) * sizeof(float);
+        launch_i8_form<kChain>(full, grid, block, coef_bytes, stream, a, w, q, power);
     }
     return hipGetLastError();
-}
-} // namespace
-
-hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream) { return launch_beamform_acc(a, nullptr, nullptr, stream); }
-
-hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream)
-{
-    return launch_beamform_acc(a, &w, nullptr, stream);
-}
-
-hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream)
-{
-    return launch_beamform_acc(a, w, &q, stream);
-}
-
-hipError_t bf_launch_beamform_acc_power(const bf_bacc_args &a, const bf_weights_args *w, hipStream_t stream)
-{
-    return launch_beamform_acc(a, w, nullptr, stream, true);
 }
 
 hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream)

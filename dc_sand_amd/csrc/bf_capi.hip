@@ -880,6 +880,8 @@ struct dt_source {
     const float *values; // nullptr: derive from the time index
     uint64_t t0;
 };
+// the calls behind bf_ctx_ext_ops take both: the caller's values where there are any, else the time index
+dt_source dt_or_index(const float *dt, uint64_t t) { return dt_source{dt, dt ? 0 : t}; }
 
 int fill_dt(const dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, float *dst)
 {
@@ -1123,6 +1125,30 @@ int ensure_weights(dcs_bf_context *c, hipStream_t stream)
 
 bool weights_ok(const float *d_weights) { return d_weights && !(reinterpret_cast<uintptr_t>(d_weights) & 3u); }
 
+// The terms pre-pass of both beamformers: draws the call's number for the class words (*epoch) and makes the terms of nt time
+// steps -- with d_weights, the normalised weights and scales as well.  dt_dev, dt0, dt_inline: as bf_launch_bform_terms takes them.
+int launch_bform_terms(dcs_bf_context *c, const float *d_weights, uint32_t nt, const float *dt_dev, float dt0, const float *dt_inline,
+                       hipStream_t s, uint32_t *epoch)
+{
+    const int st_ep = next_flag_epoch(c, s, epoch);
+    if (st_ep != DCS_OK) return st_ep;
+    bf_bform_terms_args ta;
+    std::memset(&ta, 0, sizeof(ta));
+    ta.delays = c->d_table[c->cur];
+    ta.terms = c->d_terms;
+    ta.flags = c->d_flags;
+    ta.epoch = *epoch;
+    ta.dt_dev = dt_dev;
+    ta.dt0 = dt0;
+    ta.n_pairs = c->n_pairs;
+    ta.A = (uint32_t)c->p.nr_stations;
+    ta.B = (uint32_t)c->p.nr_beams;
+    ta.nt = nt;
+    ta.k = c->k;
+    const bf_weights_args wa = {d_weights, c->d_wnorm, c->d_wscale};
+    return (int)(d_weights ? bf_launch_bform_terms_weighted(ta, wa, dt_inline, s) : bf_launch_bform_terms(ta, dt_inline, s));
+}
+
 // d_weights: nullptr (the unweighted call) or [B][A] fp32 weights in device memory (include/dcs_beam_weights.h)
 int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna,
                   size_t antenna_bytes, float *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr)
@@ -1165,26 +1191,8 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
         int st = inl ? fill_dt(c, src, done, n, dt_val) : stage_dt(c, src, done, n, s, &dt_dev);
         if (st != DCS_OK) return st;
         uint32_t epoch = 0;
-        {
-            const int st_ep = next_flag_epoch(c, s, &epoch);
-            if (st_ep != DCS_OK) return st_ep;
-        }
-        bf_bform_terms_args ta;
-        std::memset(&ta, 0, sizeof(ta));
-        ta.delays = c->d_table[c->cur];
-        ta.terms = c->d_terms;
-        ta.flags = c->d_flags;
-        ta.epoch = epoch;
-        ta.dt_dev = dt_dev;
-        ta.n_pairs = c->n_pairs;
-        ta.A = A;
-        ta.B = B;
-        ta.nt = n;
-        ta.k = c->k;
-        if (d_weights)
-            DCS_TRY(bf_launch_bform_terms_weighted(ta, wa, inl ? dt_val : nullptr, s));
-        else
-            DCS_TRY(bf_launch_bform_terms(ta, inl ? dt_val : nullptr, s));
+        st = launch_bform_terms(c, d_weights, n, dt_dev, 0.0f, inl ? dt_val : nullptr, s, &epoch);
+        if (st != DCS_OK) return st;
         bf_beamform_args a;
         std::memset(&a, 0, sizeof(a));
         a.terms = c->d_terms;
@@ -1204,10 +1212,7 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
         while (cpb > 1 && (uint64_t)((B + 15u) / 16u) * ((C + cpb - 1) / cpb) * a.nt16 < 2048u) cpb >>= 1;
         a.chan_per_block = cpb;
         a.k = c->k;
-        if (d_weights)
-            DCS_TRY(bf_launch_beamform_weighted(a, wa, s));
-        else
-            DCS_TRY(bf_launch_beamform(a, s));
+        DCS_TRY(bf_launch_beamform(a, d_weights ? &wa : nullptr, s));
         done += n;
     }
     return DCS_OK;
@@ -1229,11 +1234,22 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *c, const float *dt, uint32_t
 }
 
 namespace {
-// quant: nullptr, or the quantiser's gains and counters (include/dcs_beam_quant.h): d_beams is then the int8 tensor, a quarter the size
-// power: d_beams is the block power tensor (include/dcs_beam_power.h): one float per beam and 16-sample block, 4-byte aligned
+// What a call of the matrix-core beamformer writes to d_beams, and what it applies on the way.  kFloat: the beams, (re, im)
+// fp32 per sample; kInt8: the same quantised (include/dcs_beam_quant.h), a quarter the size; kBlockPower: one float per beam
+// and 16-sample block (include/dcs_beam_power.h), 4-byte aligned.
+struct bacc_output {
+    enum { kFloat, kInt8, kBlockPower } kind;
+    const float *d_weights; // nullptr (unweighted) or [B][A] fp32 weights in device memory (include/dcs_beam_weights.h)
+    bf_quant_args quant;    // kInt8 only: the quantiser's gains and counters
+    size_t block_bytes() const // per beam and 16-sample block
+    {
+        return kind == kBlockPower ? sizeof(float) : 32u * (kind == kInt8 ? sizeof(int8_t) : sizeof(float));
+    }
+    uintptr_t align_mask() const { return kind == kBlockPower ? 3u : 7u; }
+};
+
 int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes,
-                      void *d_beams, size_t beams_bytes, void *stream, const float *d_weights = nullptr,
-                      const bf_quant_args *quant = nullptr, bool power = false)
+                      void *d_beams, size_t beams_bytes, void *stream, const bacc_output &out = {bacc_output::kFloat, nullptr, {}})
 {
     if (!c || (nt && (!d_antenna || !d_beams))) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
@@ -1242,11 +1258,10 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     const uint32_t A = (uint32_t)c->p.nr_stations, B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     if (A > 256u) return DCS_ERR_UNSUPPORTED; // the coefficient planes of one workgroup must fit 64 KiB of LDS
     if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
-    if (beams_bytes < (power ? (size_t)B * C * (nt / 16u) * sizeof(float) : (size_t)B * C * nt * 2u * (quant ? sizeof(int8_t) : sizeof(float))))
+    if (beams_bytes < (size_t)B * C * (nt / 16u) * out.block_bytes()) return DCS_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & out.align_mask()))
         return DCS_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & (power ? 3u : 7u)))
-        return DCS_ERR_INVALID_ARGUMENT;
-    if ((d_weights || quant || power) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights, no quantiser, no detector
+    if ((out.d_weights || out.kind != bacc_output::kFloat) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights, no quantiser, no detector
     if (nt == 0) return DCS_OK;
     {
         const int st_range = check_dt_range(c, src, 1); // the one coefficient time, before anything is allocated
@@ -1255,35 +1270,15 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     hipStream_t s = as_stream(stream);
     {
         int st_alloc = ensure_terms(c, s);
-        if (st_alloc == DCS_OK && d_weights) st_alloc = ensure_weights(c, s);
+        if (st_alloc == DCS_OK && out.d_weights) st_alloc = ensure_weights(c, s);
         if (st_alloc != DCS_OK) return st_alloc;
     }
-    const bf_weights_args wa = {d_weights, c->d_wnorm, c->d_wscale};
     float dt_coeff = 0.0f; // ONE coefficient time for the whole block of samples: by value, in the kernel arguments
     int st = fill_dt(c, src, 0, 1, &dt_coeff);
     if (st != DCS_OK) return st;
     uint32_t epoch = 0;
-    {
-        const int st_ep = next_flag_epoch(c, s, &epoch);
-        if (st_ep != DCS_OK) return st_ep;
-    }
-    bf_bform_terms_args ta;
-    std::memset(&ta, 0, sizeof(ta));
-    ta.delays = c->d_table[c->cur];
-    ta.terms = c->d_terms;
-    ta.flags = c->d_flags;
-    ta.epoch = epoch;
-    ta.dt_dev = nullptr;
-    ta.dt0 = dt_coeff;
-    ta.n_pairs = c->n_pairs;
-    ta.A = A;
-    ta.B = B;
-    ta.nt = 1;
-    ta.k = c->k;
-    if (d_weights)
-        DCS_TRY(bf_launch_bform_terms_weighted(ta, wa, nullptr, s));
-    else
-        DCS_TRY(bf_launch_bform_terms(ta, nullptr, s));
+    st = launch_bform_terms(c, out.d_weights, 1, nullptr, dt_coeff, nullptr, s, &epoch);
+    if (st != DCS_OK) return st;
     bf_bacc_args a;
     std::memset(&a, 0, sizeof(a));
     a.terms = c->d_terms;
@@ -1311,9 +1306,9 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     a.nbt_force = knob(c->probe.bacc_nbt, "DCS_BACC_NBT");
     a.nw_force = knob(c->probe.bacc_waves, "DCS_BACC_WAVES");
 #endif
-    if (quant) return (int)bf_launch_beamform_acc_q8(a, d_weights ? &wa : nullptr, *quant, s);
-    if (power) return (int)bf_launch_beamform_acc_power(a, d_weights ? &wa : nullptr, s);
-    return (int)(d_weights ? bf_launch_beamform_acc_weighted(a, wa, s) : bf_launch_beamform_acc(a, s));
+    const bf_weights_args wa = {out.d_weights, c->d_wnorm, c->d_wscale};
+    return (int)bf_launch_beamform_acc(a, out.d_weights ? &wa : nullptr, out.kind == bacc_output::kInt8 ? &out.quant : nullptr,
+                                       out.kind == bacc_output::kBlockPower, s);
 }
 
 // include/dcs_beam_weights.h, reached through the table at the head of every context (bf_ctx_ext.h)
@@ -1323,7 +1318,7 @@ int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint
 {
     if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
     if (!dt && t0 % 16u) return DCS_ERR_INVALID_ARGUMENT; // whole 16-sample blocks
-    return beamform_impl(c, dt_source{dt, dt ? 0 : t0}, nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream, d_weights);
+    return beamform_impl(c, dt_or_index(dt, t0), nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream, d_weights);
 }
 
 int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
@@ -1331,8 +1326,8 @@ int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff,
                                        size_t beams_bytes, void *stream)
 {
     if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
-    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams, beams_bytes,
-                             stream, d_weights);
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams, beams_bytes,
+                             stream, {bacc_output::kFloat, d_weights, {}});
 }
 
 // include/dcs_beam_quant.h, reached the same way
@@ -1342,9 +1337,8 @@ int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint6
 {
     if (!c || !weights_ok(d_quant_gains) || (d_weights && !weights_ok(d_weights)) || (reinterpret_cast<uintptr_t>(d_clip_count) & 7u))
         return DCS_ERR_INVALID_ARGUMENT;
-    const bf_quant_args quant = {d_quant_gains, d_clip_count};
-    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes,
-                             stream, d_weights, &quant);
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes,
+                             stream, {bacc_output::kInt8, d_weights, {d_quant_gains, d_clip_count}});
 }
 
 // include/dcs_beam_power.h, reached the same way
@@ -1353,8 +1347,8 @@ int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, ui
                                     void *stream)
 {
     if (!c || !d_block_power || (d_weights && !weights_ok(d_weights))) return DCS_ERR_INVALID_ARGUMENT;
-    return beamform_acc_impl(c, dt_source{dt_coeff, dt_coeff ? 0 : t_coeff}, nt, d_antenna, antenna_bytes, d_block_power, power_bytes,
-                             stream, d_weights, nullptr, true);
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes,
+                             stream, {bacc_output::kBlockPower, d_weights, {}});
 }
 
 int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,

@@ -44,4 +44,11 @@ struct bf_ctx_ext_head {
     const bf_ctx_ext_ops *ops;
 };
 
+// a companion's way to the table, once its own checks have found c non-null: nullptr where the versions differ
+static inline const bf_ctx_ext_ops *ops_of(dcs_bf_context *c)
+{
+    const bf_ctx_ext_ops *ops = reinterpret_cast<const bf_ctx_ext_head *>(c)->ops;
+    return ops && ops->version == BF_CTX_EXT_VERSION ? ops : nullptr;
+}
+
 #endif // BF_CTX_EXT_H

@@ -140,9 +140,8 @@ struct bf_beamform_args {
     uint32_t n_bgroups, n_cblocks; // filled by the launcher
     dcs_bf_consts k;
 };
-hipError_t bf_launch_beamform(const bf_beamform_args &a, hipStream_t stream);
-// The same with weights: w.gn, w.gs as bf_launch_bform_terms_weighted wrote them (w.g unused)
-hipError_t bf_launch_beamform_weighted(const bf_beamform_args &a, const bf_weights_args &w, hipStream_t stream);
+// w: nullptr, or the weights: w->gn, w->gs as bf_launch_bform_terms_weighted wrote them (w->g unused)
+hipError_t bf_launch_beamform(const bf_beamform_args &a, const bf_weights_args *w, hipStream_t stream);
 
 // Beamformer with coefficient reuse on the matrix cores (bf_beamform_mfma.hip): the coefficients of ONE time
 // (terms table [A][B] from bf_launch_bform_terms with nt = 1) applied to nT16 blocks of 16 samples.
@@ -190,21 +189,18 @@ __host__ __device__ inline uint32_t bf_xcd_grouped(uint32_t w, uint32_t total, u
 #else
 #define BACC_KNOB(a, f) 0u
 #endif
-hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, hipStream_t stream);
-// The same with weights (int8 form only: kStaged and kChain; a.fp32_chain must be 0)
-hipError_t bf_launch_beamform_acc_weighted(const bf_bacc_args &a, const bf_weights_args &w, hipStream_t stream);
 // Quantised int8 beam output (include/dcs_beam_quant.h): a.beams is then the int8 tensor
-// [C][nT16][B][16][2], written by the quantised kernels' epilogue from the floats the calls above would have stored
+// [C][nT16][B][16][2], written by the quantised kernels' epilogue from the floats the float kernels would have stored
 struct bf_quant_args {
     const float *gains;        // [B]: the beams' quantisation gains (device)
     unsigned long long *clips; // [B]: clipped components per beam, added to; or nullptr: no counting
 };
-// w: nullptr (unweighted) or the weights, as bf_launch_beamform_acc_weighted (int8 form only: kStaged and kChain)
-hipError_t bf_launch_beamform_acc_q8(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args &q, hipStream_t stream);
-// Detected beam power (include/dcs_beam_power.h): a.beams is then the block power tensor
-// [C][nT16][B], one float per beam and 16-sample block, written by the detecting kernels' epilogue from the floats the
-// float calls would have stored.  w as above.
-hipError_t bf_launch_beamform_acc_power(const bf_bacc_args &a, const bf_weights_args *w, hipStream_t stream);
+// w: nullptr, or the weights as for bf_launch_beamform; q: nullptr, or the quantiser; power: detected beam power
+// (include/dcs_beam_power.h): a.beams is then the block power tensor [C][nT16][B], one float per beam
+// and 16-sample block, written by the detecting kernels' epilogue from the floats the float kernels would have stored.
+// All three exist for the int8 form's kStaged and kChain only (a.fp32_chain must be 0), and q excludes power.
+hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args *q, bool power,
+                                  hipStream_t stream);
 // Block powers [C][nr_blocks][B] summed n at a time, in order, into spectra [nr_blocks / n][C][B]
 struct bf_pint_args {
     const float *block_power;

@@ -592,12 +592,9 @@ __global__ void __launch_bounds__(kBlock) bf_bform_terms_w_kernel(const bf_bform
 // CH channels per pass: a lane's terms load and the LDS sample reads are shared by CH
 // independent coefficient chains (more ILP, fewer loads per product).
 constexpr uint32_t kAntChunk = 128; // antennas staged in LDS at a time (as fp32: 16 KiB per channel)
-#define BF_FUSED_WEIGHTED 0
 #include "bf_beamform_kernel.inc"
-#undef BF_FUSED_WEIGHTED
 #define BF_FUSED_WEIGHTED 1
 #include "bf_beamform_kernel.inc"
-#undef BF_FUSED_WEIGHTED
 
 // ---------------------------------------------------------------------------
 // One coefficient per lane (the launch shape of the reference's
@@ -942,8 +939,7 @@ hipError_t bf_launch_bform_terms_weighted(const bf_bform_terms_args &a, const bf
     return hipGetLastError();
 }
 
-namespace {
-hipError_t launch_beamform(const bf_beamform_args &a_in, const bf_weights_args *w, hipStream_t stream)
+hipError_t bf_launch_beamform(const bf_beamform_args &a_in, const bf_weights_args *w, hipStream_t stream)
 {
     bf_beamform_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nt16 == 0) return hipSuccess;
@@ -971,13 +967,5 @@ hipError_t launch_beamform(const bf_beamform_args &a_in, const bf_weights_args *
     else
         hipLaunchKernelGGL(bf_beamform_kernel<1>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
     return hipGetLastError();
-}
-} // namespace
-
-hipError_t bf_launch_beamform(const bf_beamform_args &a, hipStream_t stream) { return launch_beamform(a, nullptr, stream); }
-
-hipError_t bf_launch_beamform_weighted(const bf_beamform_args &a, const bf_weights_args &w, hipStream_t stream)
-{
-    return launch_beamform(a, &w, stream);
 }
 
