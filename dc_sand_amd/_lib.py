@@ -8,6 +8,7 @@ import ctypes
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
 from pathlib import Path
 
+from .companions import COMPANIONS
 from .parameters import CParams
 
 import os
@@ -138,112 +139,25 @@ def lib() -> ctypes.CDLL:
     return _lib()
 
 
-# include/dcs_stream_staging.h: the companion library of staged delay tables, built with the product library; it takes
-# the stream handles of the library above
-STAGING_LIB_PATH = LIB_PATH.parent / "libdcs_stream_staging.so"
-STAGING_SIGNATURES = [
-    ("dcs_bf_stream_stage_table", c_int, [_VP, _VP, c_int]),
-    ("dcs_bf_stream_stage_table_from_global", c_int, [_VP, _VP, c_uint32, c_uint32, _VP]),
-]
-
-_STAGING = None
+_COMPANIONS = {}
 
 
-def staging_lib() -> ctypes.CDLL:
-    global _STAGING
-    if _STAGING is None:
-        _lib()  # the product library first: its streams are what the companion works on
-        if not STAGING_LIB_PATH.exists():
-            raise ImportError(f"{STAGING_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
-        slib = ctypes.CDLL(str(STAGING_LIB_PATH))
-        for name, restype, argtypes in STAGING_SIGNATURES:
-            fn = getattr(slib, name)
+def companion(key: str) -> ctypes.CDLL:
+    """The companion library ``key`` of the table in :mod:`dc_sand_amd.companions`, built with the product library and
+    loaded from beside it; it takes the context and stream handles of the library above."""
+    if key not in _COMPANIONS:
+        _lib()  # the product library first: its contexts and streams are what the companions work on
+        entry = COMPANIONS[key]
+        path = LIB_PATH.parent / entry.lib
+        if not path.exists():
+            raise ImportError(f"{path} is missing: build it with `python -m dc_sand_amd.build`")
+        clib = ctypes.CDLL(str(path))
+        for name, restype, argtypes in entry.signatures:
+            fn = getattr(clib, name)
             fn.restype = restype
             fn.argtypes = argtypes
-        _STAGING = slib
-    return _STAGING
-
-
-# include/dcs_beam_weights.h: the companion library of per-input beam weights, built with the product library; it takes
-# the context handles of the library above
-WEIGHTS_LIB_PATH = LIB_PATH.parent / "libdcs_beam_weights.so"
-BEAM_WEIGHTS_SIGNATURES = [
-    ("dcs_bf_generate_and_beamform_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-    ("dcs_bf_generate_and_beamform_weighted_dt", c_int,
-     [_VP, POINTER(c_float), c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-    ("dcs_bf_beamform_accumulated_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-    ("dcs_bf_beamform_accumulated_weighted_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-]
-
-_WEIGHTS = None
-
-
-def beam_weights_lib() -> ctypes.CDLL:
-    global _WEIGHTS
-    if _WEIGHTS is None:
-        _lib()  # the product library first: its contexts are what the companion works on
-        if not WEIGHTS_LIB_PATH.exists():
-            raise ImportError(f"{WEIGHTS_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
-        wlib = ctypes.CDLL(str(WEIGHTS_LIB_PATH))
-        for name, restype, argtypes in BEAM_WEIGHTS_SIGNATURES:
-            fn = getattr(wlib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _WEIGHTS = wlib
-    return _WEIGHTS
-
-
-# include/dcs_beam_quant.h: the companion library of quantised int8 beam output, built with the product library; it
-# takes the context handles of the library above
-QUANT_LIB_PATH = LIB_PATH.parent / "libdcs_beam_quant.so"
-BEAM_QUANT_SIGNATURES = [
-    ("dcs_bf_beamform_accumulated_q8", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
-    ("dcs_bf_beamform_accumulated_q8_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
-]
-
-_QUANT = None
-
-
-def beam_quant_lib() -> ctypes.CDLL:
-    global _QUANT
-    if _QUANT is None:
-        _lib()  # the product library first: its contexts are what the companion works on
-        if not QUANT_LIB_PATH.exists():
-            raise ImportError(f"{QUANT_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
-        qlib = ctypes.CDLL(str(QUANT_LIB_PATH))
-        for name, restype, argtypes in BEAM_QUANT_SIGNATURES:
-            fn = getattr(qlib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _QUANT = qlib
-    return _QUANT
-
-
-# include/dcs_beam_power.h: the companion library of detected, time-integrated beam power, built with the product
-# library; it takes the context handles of the library above
-POWER_LIB_PATH = LIB_PATH.parent / "libdcs_beam_power.so"
-BEAM_POWER_SIGNATURES = [
-    ("dcs_bf_beamform_accumulated_power", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-    ("dcs_bf_beamform_accumulated_power_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
-    ("dcs_bf_integrate_block_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
-]
-
-_POWER = None
-
-
-def beam_power_lib() -> ctypes.CDLL:
-    global _POWER
-    if _POWER is None:
-        _lib()  # the product library first: its contexts are what the companion works on
-        if not POWER_LIB_PATH.exists():
-            raise ImportError(f"{POWER_LIB_PATH} is missing: build it with `python -m dc_sand_amd.build`")
-        plib = ctypes.CDLL(str(POWER_LIB_PATH))
-        for name, restype, argtypes in BEAM_POWER_SIGNATURES:
-            fn = getattr(plib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _POWER = plib
-    return _POWER
+        _COMPANIONS[key] = clib
+    return _COMPANIONS[key]
 
 
 def check(status: int, where: str) -> None:

@@ -1,10 +1,8 @@
 """Build driver: compiles the gfx950 kernels and the C-ABI into
-``dc_sand_amd/csrc/libdcs_beamformer.so`` and its companions -- staged delay tables
-(``include/dcs_stream_staging.h``) into ``libdcs_stream_staging.so``, per-input beam weights
-(``include/dcs_beam_weights.h``) into ``libdcs_beam_weights.so``, quantised int8 beam output
-(``include/dcs_beam_quant.h``) into ``libdcs_beam_quant.so``, detected beam power
-(``include/dcs_beam_power.h``) into ``libdcs_beam_power.so`` -- with hipcc (in-tree, so the libraries
-travel with the source tree).  ``python -m dc_sand_amd.build [--force]``.
+``dc_sand_amd/csrc/libdcs_beamformer.so``, and every companion library that the table of
+:mod:`dc_sand_amd.companions` lists (its source under ``csrc/``, its public header under ``include/``) into its own
+``.so`` beside it, with hipcc (in-tree, so the libraries travel with the source tree).
+``python -m dc_sand_amd.build [--force]``.
 
 Flags that are part of the numerical contract (DESIGN.md "numerics"):
   -ffp-contract=off   no fused multiply-add except where bf_math.h writes one;
@@ -20,24 +18,14 @@ import subprocess
 import sys
 from pathlib import Path
 
+from .companions import COMPANIONS
+
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libdcs_beamformer.so"
 SOURCES = ["bf_kernels.hip", "bf_beamform_mfma.hip", "bf_capi.hip"]
 HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "bf_stream_ext.h", "bf_ctx_ext.h", "bf_beamform_kernel.inc",
-           "bf_beamform_i8_kernel.inc", "../../include/dcs_beamformer.h", "../../include/dcs_stream_staging.h",
-           "../../include/dcs_beam_weights.h", "../../include/dcs_beam_quant.h", "../../include/dcs_beam_power.h"]
-# the companion library of include/dcs_stream_staging.h (staged delay tables for the streams of the product library)
-STAGING_LIB = CSRC / "libdcs_stream_staging.so"
-STAGING_SOURCES = ["bf_stream_staging.cpp"]
-# the companion library of include/dcs_beam_weights.h (per-input beam weights for the product library's beamformers)
-WEIGHTS_LIB = CSRC / "libdcs_beam_weights.so"
-WEIGHTS_SOURCES = ["bf_beam_weights.cpp"]
-# the companion library of include/dcs_beam_quant.h (quantised int8 beam output of the product library's matrix-core beamformer)
-QUANT_LIB = CSRC / "libdcs_beam_quant.so"
-QUANT_SOURCES = ["bf_beam_quant.cpp"]
-# the companion library of include/dcs_beam_power.h (detected, time-integrated beam power of the same beamformer)
-POWER_LIB = CSRC / "libdcs_beam_power.so"
-POWER_SOURCES = ["bf_beam_power.cpp"]
+           "bf_beamform_i8_kernel.inc", "../../include/dcs_beamformer.h",
+           *["../../include/" + c.header for c in COMPANIONS.values()]]
 ARCH = "gfx950"
 
 
@@ -105,17 +93,10 @@ def compile_and_link(sources, extra_flags, out: Path, verbose: bool = False) -> 
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """All five libraries; returns the product library's path."""
-    if force or needs_build():
-        compile_and_link([CSRC / s for s in SOURCES], [], LIB, verbose)
-    if force or needs_build(STAGING_LIB, STAGING_SOURCES):
-        compile_and_link([CSRC / s for s in STAGING_SOURCES], [], STAGING_LIB, verbose)
-    if force or needs_build(WEIGHTS_LIB, WEIGHTS_SOURCES):
-        compile_and_link([CSRC / s for s in WEIGHTS_SOURCES], [], WEIGHTS_LIB, verbose)
-    if force or needs_build(QUANT_LIB, QUANT_SOURCES):
-        compile_and_link([CSRC / s for s in QUANT_SOURCES], [], QUANT_LIB, verbose)
-    if force or needs_build(POWER_LIB, POWER_SOURCES):
-        compile_and_link([CSRC / s for s in POWER_SOURCES], [], POWER_LIB, verbose)
+    """The product library and every companion of the table; returns the product library's path."""
+    for lib, sources in [(LIB, SOURCES)] + [(CSRC / c.lib, [c.source]) for c in COMPANIONS.values()]:
+        if force or needs_build(lib, sources):
+            compile_and_link([CSRC / s for s in sources], [], lib, verbose)
     return LIB
 
 

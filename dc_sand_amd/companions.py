@@ -1,0 +1,45 @@
+"""The companion libraries of ``libdcs_beamformer.so``, one row each: the build (``build.py``) compiles ``source`` into
+``lib`` and watches ``header``; the binding (``_lib.companion``) loads ``lib`` from beside the product library and gives
+every function of ``signatures`` its ``(name, restype, argtypes)``.  Needs no built library to import.
+"""
+from __future__ import annotations
+
+from ctypes import POINTER, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
+from typing import NamedTuple
+
+_VP = c_void_p
+
+
+class Companion(NamedTuple):
+    header: str  # under include/
+    source: str  # under dc_sand_amd/csrc/
+    lib: str  # beside the product library
+    signatures: list
+
+
+COMPANIONS = {
+    # staged delay tables for the streams of the product library
+    "stream_staging": Companion("dcs_stream_staging.h", "bf_stream_staging.cpp", "libdcs_stream_staging.so", [
+        ("dcs_bf_stream_stage_table", c_int, [_VP, _VP, c_int]),
+        ("dcs_bf_stream_stage_table_from_global", c_int, [_VP, _VP, c_uint32, c_uint32, _VP]),
+    ]),
+    # per-input beam weights for the product library's beamformers
+    "beam_weights": Companion("dcs_beam_weights.h", "bf_beam_weights.cpp", "libdcs_beam_weights.so", [
+        ("dcs_bf_generate_and_beamform_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_generate_and_beamform_weighted_dt", c_int,
+         [_VP, POINTER(c_float), c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_weighted", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_weighted_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+    ]),
+    # quantised int8 beam output of the product library's matrix-core beamformer
+    "beam_quant": Companion("dcs_beam_quant.h", "bf_beam_quant.cpp", "libdcs_beam_quant.so", [
+        ("dcs_bf_beamform_accumulated_q8", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
+        ("dcs_bf_beamform_accumulated_q8_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, _VP, c_size_t, _VP, _VP]),
+    ]),
+    # detected, time-integrated beam power of the same beamformer
+    "beam_power": Companion("dcs_beam_power.h", "bf_beam_power.cpp", "libdcs_beam_power.so", [
+        ("dcs_bf_beamform_accumulated_power", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_power_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_integrate_block_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+    ]),
+}

@@ -43,6 +43,32 @@ def _dt_array(dt) -> np.ndarray:
     return np.ascontiguousarray(np.atleast_1d(np.asarray(dt, dtype=np.float32)))
 
 
+def _p(ptr) -> c_void_p:
+    """An address (device or host, anything ``int()`` takes) as the C-ABI's ``void *``."""
+    return c_void_p(int(ptr))
+
+
+def _p_or_null(ptr) -> c_void_p:
+    """:func:`_p` for an optional argument: ``None`` is NULL."""
+    return c_void_p(None if ptr is None else int(ptr))
+
+
+def _fp(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(c_float))
+
+
+def _coeff_time_entry(key, name: str, t_coeff, dt_coeff):
+    """The entry point that takes the coefficient time as given: ``name`` with the time index ``t_coeff``, or
+    ``name + "_dt"`` with fDeltaTime ``dt_coeff`` rounded to fp32 here; of the companion library ``key``, or with
+    ``None`` of the product library.  Returns (function, its time argument, its name for ``check``)."""
+    if (t_coeff is None) == (dt_coeff is None):
+        raise ValueError("give exactly one of t_coeff / dt_coeff")
+    lib = _lib.lib() if key is None else _lib.companion(key)
+    if dt_coeff is None:
+        return getattr(lib, name), int(t_coeff), name
+    return getattr(lib, name + "_dt"), float(np.float32(dt_coeff)), name + "_dt"
+
+
 def _timespecs(times):
     arr = (_lib.Timespec * len(times))()
     for i, (sec, nsec) in enumerate(times):
@@ -170,8 +196,7 @@ class SteeringCoefficientGenerator:
     def generate_and_beamform_dt(self, d_antenna, antenna_bytes: int, d_beams, beams_bytes: int, dt, stream=None) -> None:
         a = _dt_array(dt)
         check(
-            _lib.lib().dcs_bf_generate_and_beamform_dt(c_void_p(self._h), a.ctypes.data_as(ctypes.POINTER(c_float)), a.size,
-                                                       c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_beams)),
+            _lib.lib().dcs_bf_generate_and_beamform_dt(c_void_p(self._h), _fp(a), a.size, _p(d_antenna), int(antenna_bytes), _p(d_beams),
                                                        int(beams_bytes), _s(stream)),
             "dcs_bf_generate_and_beamform_dt",
         )
@@ -182,8 +207,8 @@ class SteeringCoefficientGenerator:
         ``BeamformerCoefficientTest.cu:259-262``); the table is indexed [beam*A + antenna]."""
         nt = self.params.NR_SAMPLES_PER_CHANNEL if nt is None else nt
         check(
-            _lib.lib().dcs_bf_generate_and_beamform(c_void_p(self._h), int(t0), int(nt), c_void_p(int(d_antenna)), int(antenna_bytes),
-                                                    c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
+            _lib.lib().dcs_bf_generate_and_beamform(c_void_p(self._h), int(t0), int(nt), _p(d_antenna), int(antenna_bytes), _p(d_beams),
+                                                    int(beams_bytes), _s(stream)),
             "dcs_bf_generate_and_beamform",
         )
 
@@ -191,20 +216,8 @@ class SteeringCoefficientGenerator:
                              dt_coeff: float | None = None, stream=None) -> None:
         """Beamformer with coefficient reuse on the matrix cores (``dcs_bf_beamform_accumulated``): the coefficients of
         ONE time (time index ``t_coeff`` or fDeltaTime ``dt_coeff``) applied to ``nt`` samples; table indexed [beam*A + antenna]."""
-        if (t_coeff is None) == (dt_coeff is None):
-            raise ValueError("give exactly one of t_coeff / dt_coeff")
-        if dt_coeff is None:
-            check(
-                _lib.lib().dcs_bf_beamform_accumulated(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)), int(antenna_bytes),
-                                                       c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
-                "dcs_bf_beamform_accumulated",
-            )
-        else:
-            check(
-                _lib.lib().dcs_bf_beamform_accumulated_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt), c_void_p(int(d_antenna)),
-                                                          int(antenna_bytes), c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
-                "dcs_bf_beamform_accumulated_dt",
-            )
+        fn, when, where = _coeff_time_entry(None, "dcs_bf_beamform_accumulated", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p(d_beams), int(beams_bytes), _s(stream)), where)
 
     # -- per-input beam weights (include/dcs_beam_weights.h, companion library libdcs_beam_weights.so): d_weights is a
     #    device [nr_beams][nr_stations] fp32 array (:class:`dc_sand_amd.beam_weights.BeamWeights.device_ptr`), read when
@@ -212,35 +225,22 @@ class SteeringCoefficientGenerator:
     def generate_and_beamform_weighted(self, d_antenna, antenna_bytes: int, d_weights, d_beams, beams_bytes: int,
                                        t0: int = 0, nt: int | None = None, dt=None, stream=None) -> None:
         """:meth:`generate_and_beamform` (or, with ``dt``, :meth:`generate_and_beamform_dt`) with per-input beam weights."""
-        wl = _lib.beam_weights_lib()
+        wl = _lib.companion("beam_weights")
+        tail = (_p(d_antenna), int(antenna_bytes), _p(d_weights), _p(d_beams), int(beams_bytes), _s(stream))
         if dt is not None:
             a = _dt_array(dt)
-            check(wl.dcs_bf_generate_and_beamform_weighted_dt(c_void_p(self._h), a.ctypes.data_as(ctypes.POINTER(c_float)), a.size,
-                                                             c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_weights)),
-                                                             c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
+            check(wl.dcs_bf_generate_and_beamform_weighted_dt(c_void_p(self._h), _fp(a), a.size, *tail),
                   "dcs_bf_generate_and_beamform_weighted_dt")
             return
         nt = self.params.NR_SAMPLES_PER_CHANNEL if nt is None else nt
-        check(wl.dcs_bf_generate_and_beamform_weighted(c_void_p(self._h), int(t0), int(nt), c_void_p(int(d_antenna)), int(antenna_bytes),
-                                                       c_void_p(int(d_weights)), c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
-              "dcs_bf_generate_and_beamform_weighted")
+        check(wl.dcs_bf_generate_and_beamform_weighted(c_void_p(self._h), int(t0), int(nt), *tail), "dcs_bf_generate_and_beamform_weighted")
 
     def beamform_accumulated_weighted(self, d_antenna, antenna_bytes: int, d_weights, d_beams, beams_bytes: int, nt: int,
                                       t_coeff: int | None = None, dt_coeff: float | None = None, stream=None) -> None:
         """:meth:`beamform_accumulated` with per-input beam weights."""
-        if (t_coeff is None) == (dt_coeff is None):
-            raise ValueError("give exactly one of t_coeff / dt_coeff")
-        wl = _lib.beam_weights_lib()
-        if dt_coeff is None:
-            check(wl.dcs_bf_beamform_accumulated_weighted(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
-                                                          int(antenna_bytes), c_void_p(int(d_weights)), c_void_p(int(d_beams)),
-                                                          int(beams_bytes), _s(stream)),
-                  "dcs_bf_beamform_accumulated_weighted")
-        else:
-            check(wl.dcs_bf_beamform_accumulated_weighted_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
-                                                             c_void_p(int(d_antenna)), int(antenna_bytes), c_void_p(int(d_weights)),
-                                                             c_void_p(int(d_beams)), int(beams_bytes), _s(stream)),
-                  "dcs_bf_beamform_accumulated_weighted_dt")
+        fn, when, where = _coeff_time_entry("beam_weights", "dcs_bf_beamform_accumulated_weighted", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p(d_weights), _p(d_beams), int(beams_bytes),
+                 _s(stream)), where)
 
     # -- quantised int8 beam output (include/dcs_beam_quant.h, companion library libdcs_beam_quant.so): d_quant_gains is a
     #    device [nr_beams] fp32 array, d_clip_count a device [nr_beams] uint64 array or None
@@ -251,21 +251,9 @@ class SteeringCoefficientGenerator:
         """:meth:`beamform_accumulated` (with ``d_weights``: :meth:`beamform_accumulated_weighted`) whose epilogue
         requantises every beam to int8 with its gain: ``q = clamp(rint(v * k_b), -127, 127)``, NaN -> -128; the int8
         tensor is ``[C][nt / 16][B][16][{re, im}]`` (:func:`quantised_beams_bytes`)."""
-        if (t_coeff is None) == (dt_coeff is None):
-            raise ValueError("give exactly one of t_coeff / dt_coeff")
-        ql = _lib.beam_quant_lib()
-        w = c_void_p(None if d_weights is None else int(d_weights))
-        clips = c_void_p(None if d_clip_count is None else int(d_clip_count))
-        if dt_coeff is None:
-            check(ql.dcs_bf_beamform_accumulated_q8(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
-                                                    int(antenna_bytes), w, c_void_p(int(d_quant_gains)), c_void_p(int(d_beams_q8)),
-                                                    int(beams_bytes), clips, _s(stream)),
-                  "dcs_bf_beamform_accumulated_q8")
-        else:
-            check(ql.dcs_bf_beamform_accumulated_q8_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
-                                                       c_void_p(int(d_antenna)), int(antenna_bytes), w, c_void_p(int(d_quant_gains)),
-                                                       c_void_p(int(d_beams_q8)), int(beams_bytes), clips, _s(stream)),
-                  "dcs_bf_beamform_accumulated_q8_dt")
+        fn, when, where = _coeff_time_entry("beam_quant", "dcs_bf_beamform_accumulated_q8", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), _p(d_quant_gains),
+                 _p(d_beams_q8), int(beams_bytes), _p_or_null(d_clip_count), _s(stream)), where)
 
     # -- detected beam power (include/dcs_beam_power.h, companion library libdcs_beam_power.so): d_block_power is a device
     #    float [C][nt / 16][B] array, d_spectra a device float [nr_blocks / blocks_per_spectrum][C][B] array
@@ -274,30 +262,19 @@ class SteeringCoefficientGenerator:
         """:meth:`beamform_accumulated` (with ``d_weights``: :meth:`beamform_accumulated_weighted`) whose epilogue
         detects: ``|v|^2`` of every sample, summed pairwise over each 16-sample block, one float per (channel, block,
         beam) (:func:`block_power_bytes`)."""
-        if (t_coeff is None) == (dt_coeff is None):
-            raise ValueError("give exactly one of t_coeff / dt_coeff")
-        pl = _lib.beam_power_lib()
-        w = c_void_p(None if d_weights is None else int(d_weights))
-        if dt_coeff is None:
-            check(pl.dcs_bf_beamform_accumulated_power(c_void_p(self._h), int(t_coeff), int(nt), c_void_p(int(d_antenna)),
-                                                       int(antenna_bytes), w, c_void_p(int(d_block_power)), int(power_bytes),
-                                                       _s(stream)),
-                  "dcs_bf_beamform_accumulated_power")
-        else:
-            check(pl.dcs_bf_beamform_accumulated_power_dt(c_void_p(self._h), float(np.float32(dt_coeff)), int(nt),
-                                                          c_void_p(int(d_antenna)), int(antenna_bytes), w,
-                                                          c_void_p(int(d_block_power)), int(power_bytes), _s(stream)),
-                  "dcs_bf_beamform_accumulated_power_dt")
+        fn, when, where = _coeff_time_entry("beam_power", "dcs_bf_beamform_accumulated_power", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), _p(d_block_power),
+                 int(power_bytes), _s(stream)), where)
 
     def integrate_block_power(self, d_block_power, power_bytes: int, nr_blocks: int, blocks_per_spectrum: int, d_spectra,
                               spectra_bytes: int, accumulate: bool = False, stream=None) -> None:
         """Sums the block powers ``[C][nr_blocks][B]`` ``blocks_per_spectrum`` at a time, in order, into the spectra
         ``[nr_blocks / blocks_per_spectrum][C][B]`` (:func:`power_spectra_bytes`); with ``accumulate`` the sums start
         from what ``d_spectra`` holds, so an integration can span calls."""
-        pl = _lib.beam_power_lib()
-        check(pl.dcs_bf_integrate_block_power(c_void_p(self._h), c_void_p(int(d_block_power)), int(power_bytes), int(nr_blocks),
-                                              int(blocks_per_spectrum), 1 if accumulate else 0, c_void_p(int(d_spectra)),
-                                              int(spectra_bytes), _s(stream)),
+        pl = _lib.companion("beam_power")
+        check(pl.dcs_bf_integrate_block_power(c_void_p(self._h), _p(d_block_power), int(power_bytes), int(nr_blocks),
+                                              int(blocks_per_spectrum), 1 if accumulate else 0, _p(d_spectra), int(spectra_bytes),
+                                              _s(stream)),
               "dcs_bf_integrate_block_power")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
@@ -426,8 +403,8 @@ class CoefficientStream:
             table = np.ascontiguousarray(table)
         if table.dtype != delay_vals_dtype or table.size != self._gen.params.n_pairs:
             raise ValueError("bad delay table")
-        check(_lib.staging_lib().dcs_bf_stream_stage_table(c_void_p(self._h), c_void_p(table.ctypes.data),
-                                                   _lib.DCS_BF_STAGE_CALLER_PINNED if pinned else 0),
+        check(_lib.companion("stream_staging").dcs_bf_stream_stage_table(c_void_p(self._h), _p(table.ctypes.data),
+                                                                         _lib.DCS_BF_STAGE_CALLER_PINNED if pinned else 0),
               "dcs_bf_stream_stage_table")
         if pinned:
             self._pinned_staged = table  # the copy reads it asynchronously: keep the allocation alive
@@ -437,8 +414,8 @@ class CoefficientStream:
         """Stage this context's beam slice of a device-resident global table; the gather waits (on the device) for
         ``ready_event`` -- a :class:`device.Event` or a raw ``hipEvent_t`` the producer recorded -- when given."""
         ev = ready_event.handle if hasattr(ready_event, "handle") else ready_event
-        check(_lib.staging_lib().dcs_bf_stream_stage_table_from_global(c_void_p(self._h), *self._global_args(d_global_table, nr_beams_total, beam_offset),
-                                                               c_void_p(None if ev is None else int(ev))),
+        check(_lib.companion("stream_staging").dcs_bf_stream_stage_table_from_global(
+                  c_void_p(self._h), *self._global_args(d_global_table, nr_beams_total, beam_offset), _p_or_null(ev)),
               "dcs_bf_stream_stage_table_from_global")
 
     def end(self) -> None:

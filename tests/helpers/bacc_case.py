@@ -1,0 +1,104 @@
+"""What the GPU tests of the beamformers share (tests/test_gpu_beam_weights.py, test_gpu_beamformer_exact.py,
+test_gpu_beam_quant.py, test_gpu_beam_power.py): the shapes, one context with its samples and output buffer, and
+seeded random weights."""
+import numpy as np
+
+from conftest import rand_table
+
+# test_beamform_accumulated_on_the_matrix_cores's shapes: staged and kChain, ragged antennas / beams, several beam groups
+# and several workgroups per channel
+ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 48), (8, 4, 5, 16), (37, 21, 9, 48),
+              (130, 3, 4, 16), (4, 40, 7, 32), (9, 5, 3, 16), (129, 33, 2, 32), (256, 17, 2, 16), (1, 1, 1, 16),
+              (66, 70, 2, 80), (128, 16, 3, 64), (192, 48, 2, 32), (200, 20, 2, 32), (64, 1024, 1, 32),
+              (64, 32, 3, 112), (64, 24, 2, 272), (64, 16, 2, 592), (48, 16, 3, 48), (64, 64, 2, 272),
+              (256, 64, 2, 272), (100, 20, 3, 112), (256, 16, 1, 1600), (65, 16, 2, 48),
+              (64, 1024, 9, 32), (130, 20, 9, 32), (256, 64, 9, 16), (192, 48, 11, 48),
+              (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
+FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
+                (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
+T_COEFF = 9
+CANARY = 64
+
+
+class Case:
+    """One context, its samples and output buffer (with a canary), and both beamformers with and without weights."""
+
+    def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None):
+        from dc_sand_amd import BeamformerParameters
+        from dc_sand_amd.generator import SteeringCoefficientGenerator
+
+        self.gpu, self.oracle = gpu, oracle
+        self.A, self.B, self.C, self.nt = A, B, C, nt
+        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        self.op = oracle.params_from(self.bp)
+        self.table = rand_table(self.bp.n_pairs, seed=A + B + seed) if table is None else table  # [b*A + a]
+        self.ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+        self.g = SteeringCoefficientGenerator(self.bp)
+        self.g.upload_delays(self.table)
+        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
+        gpu.memcpy_htod(self.d_ant, self.ant)
+        self.shape = (C, nt // 16, B, 16, 2)
+        self.nbytes = int(np.prod(self.shape)) * 4
+        self.d_beams = gpu.mem_alloc(self.nbytes + CANARY)
+        self.d_w = gpu.mem_alloc(B * A * 4)
+
+    def set_ant(self, ant):
+        self.ant = ant
+        self.gpu.memcpy_htod(self.d_ant, ant)
+
+    def set_table(self, table):
+        self.table = table
+        self.g.upload_delays(table)
+
+    def run(self, kind, w=None, stream=None):
+        """kind 'acc' / 'fused'; w: None (unweighted) or a [B][A] array (copied to the device first)."""
+        gpu = self.gpu
+        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
+        if w is not None:
+            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
+        if kind == "acc":
+            if w is None:
+                self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, t_coeff=T_COEFF)
+            else:
+                self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt,
+                                                     t_coeff=T_COEFF)
+        else:
+            if w is None:
+                self.g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, t0=0, nt=self.nt)
+            else:
+                self.g.generate_and_beamform_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, t0=0,
+                                                      nt=self.nt)
+        return self.read()
+
+    def floats(self, w=None, dt=None, t_coeff=T_COEFF):
+        """What the float call returns (index entry point, or with dt the _dt one)."""
+        gpu = self.gpu
+        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
+        kw = {"t_coeff": t_coeff} if dt is None else {"dt_coeff": dt}
+        if w is None:
+            self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, **kw)
+        else:
+            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
+            self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt, **kw)
+        return self.read()
+
+    def read(self):
+        host = np.empty(self.nbytes + CANARY, dtype=np.uint8)
+        self.gpu.memcpy_dtoh(host, self.d_beams)
+        assert np.all(host[self.nbytes:] == 0xFF), "written past the output tensor"
+        return host[:self.nbytes].view(np.float32).reshape(self.shape).copy()
+
+    def coefficients(self, dts):
+        """The oracle's fp32 coefficients [t][c][a][b][2] (the table turned to the generator's [a*B + b])."""
+        t_ab = np.ascontiguousarray(self.table.reshape(self.B, self.A).T).ravel()
+        return self.oracle.generate_dt(self.op, t_ab, dts)
+
+    def close(self):
+        self.g.close()
+
+
+def random_weights(rng, B, A, zero_beam=True):
+    w = (rng.choice([-1.0, 1.0], size=(B, A)) * 10.0 ** rng.uniform(-3, 3, size=(B, A))).astype(np.float32)
+    if zero_beam:
+        w[rng.integers(0, B)] = 0.0
+    return w

@@ -8,7 +8,6 @@ hipErrorLaunchFailure without being enqueued.  What must hold then (include/dcs_
   yields replays the launches that were made.
 Prints "OK" on success.
 """
-import ctypes
 import sys
 from pathlib import Path
 
@@ -21,6 +20,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 from conftest import rand_table  # noqa: E402
 from dc_sand_amd import BeamformerParameters, _lib, device  # noqa: E402
 from dc_sand_amd.generator import SteeringCoefficientGenerator  # noqa: E402
+from helpers import hip_graph  # noqa: E402
 from oracle import bf_oracle as oracle  # noqa: E402
 from probes import dcs_probes  # noqa: E402
 
@@ -67,33 +67,19 @@ def main():
         assert oracle.max_ulp(got, exp, 1)[1] == 0
 
         # ---- inside a capture
-        hip = ctypes.CDLL("libamdhip64.so")
-        V = ctypes.c_void_p
-        hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-        hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-        hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-        hip.hipGraphLaunch.argtypes = [V, V]
-        hip.hipGraphExecDestroy.argtypes = [V]
-        hip.hipGraphDestroy.argtypes = [V]
         dcs_probes.set_knobs(g, fail_at_step=fail_at)
-        assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-        try:
-            g.generate(buf, nbytes, t0=3, nt=nt, kernel=kernel, stream=s)
-            raise AssertionError("the injected failure was not reported (capture)")
-        except _lib.DcsError as e:
-            assert e.status == HIP_ERROR_LAUNCH_FAILURE, e.status
-        graph = V()
-        rc = hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph))
-        assert rc == 0 and graph.value, f"hipStreamEndCapture after the failed call: {rc} (an unjoined fork?)"
-        ex = V()
-        assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+        with hip_graph.capture(s) as graph:  # ending it after the failed call asserts that no fork was left unjoined
+            try:
+                g.generate(buf, nbytes, t0=3, nt=nt, kernel=kernel, stream=s)
+                raise AssertionError("the injected failure was not reported (capture)")
+            except _lib.DcsError as e:
+                assert e.status == HIP_ERROR_LAUNCH_FAILURE, e.status
         device.memset(buf, 0xFF, nbytes, stream=s)
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         device.memcpy_dtoh(got, buf, stream=s)
         assert oracle.max_ulp(got[:done], exp[:done], 1)[1] == 0
         assert np.all(np.isnan(got[done:]))
-        hip.hipGraphExecDestroy(ex)
-        hip.hipGraphDestroy(graph)
+        graph.close()
         dcs_probes.set_knobs(g)
     g.close()
     buf.free()

@@ -3,14 +3,13 @@ the expectation is finite, NaN for NaN otherwise (payloads are not compared), no
 model (helpers/beam_power_model.py, anchored on the CPU by tests/test_beam_power_model.py) applied to what the float call
 returns on the same context and inputs, which tests/test_gpu_beamformer_exact.py holds to its own arithmetic.  Every call
 writes into an exactly sized buffer with a canary behind it, which must stay untouched."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from helpers import hip_graph
+from helpers.bacc_case import CANARY, T_COEFF, Case
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beam_quant_model import SHAPES, seeded_weights
-from test_gpu_beam_weights import CANARY, T_COEFF, Case
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +27,6 @@ class PCase(Case):
         self.pbytes = C * self.nblk * B * 4
         self.d_p = gpu.mem_alloc(self.pbytes + CANARY)
         self.d_s = gpu.mem_alloc(self.pbytes + CANARY)  # spectra: at most one per block
-
-    def floats(self, w=None, dt=None, t_coeff=T_COEFF):
-        """What the float call returns (index entry point, or with dt the _dt one)."""
-        gpu = self.gpu
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
-        kw = {"t_coeff": t_coeff} if dt is None else {"dt_coeff": dt}
-        if w is None:
-            self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, **kw)
-        else:
-            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
-            self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt, **kw)
-        return self.read()
 
     def call_power(self, weighted=False, dt=None, t_coeff=T_COEFF, stream=None):
         kw = {"t_coeff": t_coeff} if dt is None else {"dt_coeff": dt}
@@ -293,30 +280,17 @@ def test_captured_calls_pick_up_new_samples_on_replay(gpu, oracle, A, B, C, nt):
         refs.append((P, integrate(P, n)))
     assert same_bits(refs[0][0], refs[1][0]) is not None
     s = gpu.Stream()
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-    c.call_power(weighted=True, stream=s.handle)
-    c.call_integrate(n, stream=s.handle)
-    graph = V()
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:
+        c.call_power(weighted=True, stream=s.handle)
+        c.call_integrate(n, stream=s.handle)
     for i in (1, 2, 0, 1):
         gpu.memcpy_htod(c.d_ant, ants[i], stream=s.handle, sync=False)
         gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY, stream=s.handle)
         gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY, stream=s.handle)
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         s.synchronize()
         assert same_bits(c.read_power(), refs[i][0]) is None and same_bits(c.read_spectra(n), refs[i][1]) is None, i
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     c.close()
 
 

@@ -3,14 +3,13 @@ byte, no tolerance: the expectation is the numpy quantiser (helpers/beam_quant_m
 tests/test_beam_quant_model.py) applied to what the float call returns on the same context and inputs, which
 tests/test_gpu_beamformer_exact.py holds to its own arithmetic.  Every quantised call writes into an exactly sized buffer
 with a canary behind it, which must stay untouched."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from helpers import hip_graph
+from helpers.bacc_case import CANARY, T_COEFF, Case
 from helpers.beam_quant_model import (SHAPES, expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
-from test_gpu_beam_weights import CANARY, T_COEFF, Case
 
 pytestmark = pytest.mark.gpu
 
@@ -26,18 +25,6 @@ class QCase(Case):
         self.d_q = gpu.mem_alloc(self.qbytes + CANARY)
         self.d_k = gpu.mem_alloc(B * 4)
         self.d_clip = gpu.mem_alloc(B * 8)
-
-    def floats(self, w=None, dt=None):
-        """What the float call returns (index entry point, or with dt the _dt one)."""
-        gpu = self.gpu
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
-        kw = {"t_coeff": T_COEFF} if dt is None else {"dt_coeff": dt}
-        if w is None:
-            self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, **kw)
-        else:
-            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
-            self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt, **kw)
-        return self.read()
 
     def call_q8(self, weighted=False, count=True, dt=None, stream=None):
         kw = {"t_coeff": T_COEFF} if dt is None else {"dt_coeff": dt}
@@ -231,29 +218,16 @@ def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, A, B, C, nt):
     ref2, n2 = c.q8(k2, w)
     assert n1.sum() > 0 and n2.sum() == 0
     s = gpu.Stream()
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-    c.call_q8(weighted=True, stream=s.handle)
-    graph = V()
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:
+        c.call_q8(weighted=True, stream=s.handle)
     for k, ref, n_ref in ((k1, ref1, n1), (k2, ref2, n2), (k1, ref1, n1)):
         gpu.memcpy_htod(c.d_k, k, stream=s.handle, sync=False)
         gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY, stream=s.handle)
         gpu.memset(c.d_clip, 0, B * 8, stream=s.handle)
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     c.close()
 
 

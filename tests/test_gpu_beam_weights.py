@@ -4,94 +4,14 @@ numerical contract -- unit weights bit-identical to the unweighted calls, 2^k we
 own beam only, random weights within the derived bounds -- and the calls' plumbing: the fp32-chain refusal, capture
 with weights changed between replays, beam shards.  Every weighted call writes into a buffer with a canary behind the
 output tensor, which must stay untouched."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from conftest import rand_table
+from helpers import hip_graph
+from helpers.bacc_case import ACC_SHAPES, CANARY, FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import fused_model, normalise
 
 pytestmark = pytest.mark.gpu
-
-# test_beamform_accumulated_on_the_matrix_cores's shapes: staged and kChain, ragged antennas / beams, several beam groups
-# and several workgroups per channel
-ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 48), (8, 4, 5, 16), (37, 21, 9, 48),
-              (130, 3, 4, 16), (4, 40, 7, 32), (9, 5, 3, 16), (129, 33, 2, 32), (256, 17, 2, 16), (1, 1, 1, 16),
-              (66, 70, 2, 80), (128, 16, 3, 64), (192, 48, 2, 32), (200, 20, 2, 32), (64, 1024, 1, 32),
-              (64, 32, 3, 112), (64, 24, 2, 272), (64, 16, 2, 592), (48, 16, 3, 48), (64, 64, 2, 272),
-              (256, 64, 2, 272), (100, 20, 3, 112), (256, 16, 1, 1600), (65, 16, 2, 48),
-              (64, 1024, 9, 32), (130, 20, 9, 32), (256, 64, 9, 16), (192, 48, 11, 48),
-              (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
-FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
-                (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
-T_COEFF = 9
-CANARY = 64
-
-
-class Case:
-    """One context, its samples and output buffer (with a canary), and both beamformers with and without weights."""
-
-    def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu, self.oracle = gpu, oracle
-        self.A, self.B, self.C, self.nt = A, B, C, nt
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
-        self.op = oracle.params_from(self.bp)
-        self.table = rand_table(self.bp.n_pairs, seed=A + B + seed) if table is None else table  # [b*A + a]
-        self.ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
-        self.g = SteeringCoefficientGenerator(self.bp)
-        self.g.upload_delays(self.table)
-        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
-        gpu.memcpy_htod(self.d_ant, self.ant)
-        self.shape = (C, nt // 16, B, 16, 2)
-        self.nbytes = int(np.prod(self.shape)) * 4
-        self.d_beams = gpu.mem_alloc(self.nbytes + CANARY)
-        self.d_w = gpu.mem_alloc(B * A * 4)
-
-    def set_ant(self, ant):
-        self.ant = ant
-        self.gpu.memcpy_htod(self.d_ant, ant)
-
-    def set_table(self, table):
-        self.table = table
-        self.g.upload_delays(table)
-
-    def run(self, kind, w=None, stream=None):
-        """kind 'acc' / 'fused'; w: None (unweighted) or a [B][A] array (copied to the device first)."""
-        gpu = self.gpu
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
-        if w is not None:
-            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
-        if kind == "acc":
-            if w is None:
-                self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, t_coeff=T_COEFF)
-            else:
-                self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt,
-                                                     t_coeff=T_COEFF)
-        else:
-            if w is None:
-                self.g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, t0=0, nt=self.nt)
-            else:
-                self.g.generate_and_beamform_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, t0=0,
-                                                      nt=self.nt)
-        return self.read()
-
-    def read(self):
-        host = np.empty(self.nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_beams)
-        assert np.all(host[self.nbytes:] == 0xFF), "written past the output tensor"
-        return host[:self.nbytes].view(np.float32).reshape(self.shape).copy()
-
-    def coefficients(self, dts):
-        """The oracle's fp32 coefficients [t][c][a][b][2] (the table turned to the generator's [a*B + b])."""
-        t_ab = np.ascontiguousarray(self.table.reshape(self.B, self.A).T).ravel()
-        return self.oracle.generate_dt(self.op, t_ab, dts)
-
-    def close(self):
-        self.g.close()
 
 
 def bits(x):
@@ -120,13 +40,6 @@ def fused_expected(case, w):
 
     s, gh = normalise(w)
     return fused_model(case.coefficients(delta_times(case.bp, 0, case.nt)), case.ant, ghat=gh, scale=s)
-
-
-def random_weights(rng, B, A, zero_beam=True):
-    w = (rng.choice([-1.0, 1.0], size=(B, A)) * 10.0 ** rng.uniform(-3, 3, size=(B, A))).astype(np.float32)
-    if zero_beam:
-        w[rng.integers(0, B)] = 0.0
-    return w
 
 
 @pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
@@ -283,31 +196,18 @@ def test_captured_call_picks_up_new_weights_on_replay(gpu, oracle, kind):
     ref2 = c.run(kind, w2)  # (also the plain call the capture rule asks for first)
     ref1 = c.run(kind, w1)
     s = gpu.Stream()
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-    if kind == "acc":
-        c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
-    else:
-        c.g.generate_and_beamform_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, t0=0, nt=nt, stream=s.handle)
-    graph = V()
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:
+        if kind == "acc":
+            c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
+        else:
+            c.g.generate_and_beamform_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, t0=0, nt=nt, stream=s.handle)
     for w, ref in ((w1, ref1), (w2, ref2)):
         gpu.memcpy_htod(c.d_w, w, stream=s.handle, sync=False)
         gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY, stream=s.handle)
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         s.synchronize()
         assert np.array_equal(bits(c.read()), bits(ref))
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     c.close()
 
 

@@ -18,12 +18,11 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
+from helpers.bacc_case import ACC_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import (acc_model, all_pairs_fast, first_difference, fused_model, normalise, weighted_coefficients)
-from test_gpu_beam_weights import ACC_SHAPES, FUSED_SHAPES, Case, random_weights
 
 pytestmark = pytest.mark.gpu
 
-T_COEFF = 9
 DT_COEFF = np.float32(0.3710937)  # an fDeltaTime off the time-index grid, for the calls by value
 PAIRS_PER_SLICE = 24 << 20  # coefficient pairs generated, checked and modelled at a time (192 MiB of fp32 pairs)
 

@@ -1,7 +1,6 @@
 """Error paths of the C-ABI on the GPU: a call that cannot be part of a stream capture says so
 with a status BEFORE it enqueues anything -- the capture stays valid --, and a failure in the middle of a per-time-step
 launch loop leaves the side streams joined and the caller's stream usable."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -11,21 +10,10 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
+from helpers import hip_graph
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-
-
-def _hip():
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
-    return hip, V
 
 
 def test_non_capturable_calls_are_refused_up_front_and_the_capture_survives(gpu, oracle):
@@ -37,7 +25,6 @@ def test_non_capturable_calls_are_refused_up_front_and_the_capture_survives(gpu,
     from dc_sand_amd import BeamformerParameters, _lib
     from dc_sand_amd.generator import SteeringCoefficientGenerator
 
-    hip, V = _hip()
     bp = BeamformerParameters(NR_CHANNELS=24, NR_STATIONS=5, NR_BEAMS=13)
     op = oracle.params_from(bp)
     table = rand_table(bp.n_pairs, seed=31)
@@ -54,36 +41,30 @@ def test_non_capturable_calls_are_refused_up_front_and_the_capture_survives(gpu,
     gpu.memset(ant, 1, ant.nbytes)
     s = gpu.Stream()
     dts = np.linspace(0.0, 0.3, 300).astype(np.float32)
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-    refused = [
-        lambda: g.generate_dt(buf, nbytes, dts, stream=s),
-        lambda: g.generate(buf, nbytes, t0=0, nt=300, stream=s),
-        lambda: g_rows.generate(buf, nbytes, t0=0, nt=2, stream=s),
-        lambda: g.beamform_accumulated(ant, ant.nbytes, beams, beams.nbytes, 16, t_coeff=1, stream=s),
-        lambda: g.generate_and_beamform(ant, ant.nbytes, beams, beams.nbytes, 0, 16, stream=s),
-        lambda: g.autotune(buf, nbytes, stream=s),
-        lambda: g.stream_begin(buf, nbytes, 0, bp.NR_CHANNELS, s),
-    ]
-    for i, call in enumerate(refused):
-        with pytest.raises(_lib.DcsError) as e:
-            call()
-        assert e.value.status == _lib.DCS_ERR_UNSUPPORTED, (i, e.value.status)
-    # the capture is still alive: these ARE capturable (up to 256 time steps ride in the kernel arguments)
-    g.generate(buf, nbytes, t0=7, nt=256, stream=s)
-    graph = V()
-    rc = hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph))
-    assert rc == 0 and graph.value, rc
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:
+        refused = [
+            lambda: g.generate_dt(buf, nbytes, dts, stream=s),
+            lambda: g.generate(buf, nbytes, t0=0, nt=300, stream=s),
+            lambda: g_rows.generate(buf, nbytes, t0=0, nt=2, stream=s),
+            lambda: g.beamform_accumulated(ant, ant.nbytes, beams, beams.nbytes, 16, t_coeff=1, stream=s),
+            lambda: g.generate_and_beamform(ant, ant.nbytes, beams, beams.nbytes, 0, 16, stream=s),
+            lambda: g.autotune(buf, nbytes, stream=s),
+            lambda: g.stream_begin(buf, nbytes, 0, bp.NR_CHANNELS, s),
+        ]
+        for i, call in enumerate(refused):
+            with pytest.raises(_lib.DcsError) as e:
+                call()
+            assert e.value.status == _lib.DCS_ERR_UNSUPPORTED, (i, e.value.status)
+        # the capture is still alive: these ARE capturable (up to 256 time steps ride in the kernel arguments)
+        g.generate(buf, nbytes, t0=7, nt=256, stream=s)
     gpu.memset(buf, 0xFF, nbytes, stream=s)
-    assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+    graph.launch(s)
     s.synchronize()
     exp = oracle.generate(op, table, 7, 256)
     got = np.empty(exp.shape, dtype=np.float32)
     gpu.memcpy_dtoh(got, buf)
     assert oracle.max_ulp(got, exp, 1)[1] == 0
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     # outside a capture every one of the refused calls works (and the beamformers become capturable after their first call)
     g.generate_dt(buf, nbytes, dts, stream=s)
     s.synchronize()
@@ -91,10 +72,9 @@ def test_non_capturable_calls_are_refused_up_front_and_the_capture_survives(gpu,
     assert oracle.max_ulp(got, oracle.generate_dt(op, table, dts[:256]), 1)[1] == 0
     g.beamform_accumulated(ant, ant.nbytes, beams, beams.nbytes, 16, t_coeff=1, stream=s)
     s.synchronize()
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
+    hip_graph.begin(s)
     g.beamform_accumulated(ant, ant.nbytes, beams, beams.nbytes, 16, t_coeff=1, stream=s)
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    hip.hipGraphDestroy(graph)
+    hip_graph.destroy(hip_graph.end(s))
     g.close()
     g_rows.close()
     for b in (buf, ant, beams):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
+from helpers import hip_graph
+from helpers.every_element import compare_every_element
 
 pytestmark = pytest.mark.gpu
 
@@ -64,40 +66,6 @@ def _check_float_reading(oracle, got, op, table, t0, nt, limit=1):
     assert n_over == 0, f"float-libm reading: max ULP {mx}, {n_over} elements over {limit} ULP, first flat index {first}"
     assert oracle.compare(got, exp, 1e-4) == -1
     return mx
-
-
-def _compare_every_element(gpu, oracle, d_buf, op, table, dt, nc_total, n_pairs, readings=(0, 1), slab_bytes=1 << 30, half=False):
-    """verify_output at full size (BeamformerCoefficientTest.cu:348-357 compares EVERY element): the device tensor
-    [nc_total][n_pairs][2] fp32 of ONE time step comes back in <= 1 GiB slabs through a pinned buffer and each slab
-    is compared with the verifier generated on the fly over all host cores (oracle.compare_generated).  Returns
-    {reading: dict(hist, max_ulp, first_over_1ulp, seconds)} accumulated over the slabs.  ``half``: the packed binary16
-    output, compared as bit patterns with RN-even(verifier's fp32), distances in binary16 ulps."""
-    import os
-    import time
-
-    row = n_pairs * (4 if half else 8)
-    per = max(1, slab_bytes // row)
-    nthreads = max(1, min(64, len(os.sched_getaffinity(0))))
-    pinned = gpu.pagelocked_empty(per * n_pairs * 2, np.uint16 if half else np.float32)
-    tot = {r: dict(hist=[0, 0, 0, 0], max_ulp=0, first_over_1ulp=-1, seconds=0.0) for r in readings}
-    t_copy = 0.0
-    for c0 in range(0, nc_total, per):
-        nc = min(per, nc_total - c0)
-        view = pinned[: nc * n_pairs * 2]
-        t0 = time.perf_counter()
-        gpu.memcpy_dtoh(view, int(d_buf) + c0 * row)
-        t_copy += time.perf_counter() - t0
-        for r in readings:
-            res = oracle.compare_generated(op, table, [dt], c0, nc, view, nthreads=nthreads, reading=r)
-            acc = tot[r]
-            acc["hist"] = [a + b for a, b in zip(acc["hist"], res["hist"])]
-            acc["max_ulp"] = max(acc["max_ulp"], res["max_ulp"])
-            if acc["first_over_1ulp"] < 0 and res["first_over_1ulp"] >= 0:
-                acc["first_over_1ulp"] = c0 * n_pairs * 2 + res["first_over_1ulp"]
-            acc["seconds"] += res["seconds"]
-    tot["copy_seconds"] = t_copy
-    tot["threads"] = nthreads
-    return tot
 
 
 @pytest.mark.parametrize("kernel", [0, 1, 2])
@@ -417,7 +385,7 @@ def test_config3_full_size_every_element(gpu, oracle, probes, record_property):
     g.generate(buf, nbytes, t0=t, nt=1)
     gpu.synchronize()
     t0 = time.perf_counter()
-    res = _compare_every_element(gpu, oracle, buf, op, table, delta_times(bp, t, 1)[0], bp.NR_CHANNELS, bp.n_pairs)
+    res = compare_every_element(gpu, oracle, buf, op, table, delta_times(bp, t, 1)[0], bp.NR_CHANNELS, bp.n_pairs)
     wall = time.perf_counter() - t0
     n = bp.NR_CHANNELS * bp.n_pairs * 2
     for r in (0, 1):
@@ -475,7 +443,7 @@ def test_config3_full_size_fp16_every_element(gpu, oracle, record_property, math
     g.generate(buf, nbytes, t0=t, nt=1, bitwidth=B16)
     gpu.synchronize()
     t0 = time.perf_counter()
-    res = _compare_every_element(gpu, oracle, buf, op, table, delta_times(bp, t, 1)[0], bp.NR_CHANNELS, bp.n_pairs, readings=(0,), half=True)
+    res = compare_every_element(gpu, oracle, buf, op, table, delta_times(bp, t, 1)[0], bp.NR_CHANNELS, bp.n_pairs, readings=(0,), half=True)
     wall = time.perf_counter() - t0
     n = bp.NR_CHANNELS * bp.n_pairs * 2
     h = res[0]["hist"]
@@ -618,8 +586,6 @@ def test_fused_seeded_fuzz(gpu, oracle):
 def test_fused_more_steps_than_ride_in_the_kernel_arguments_and_under_capture(gpu, oracle):
     """The per-sample fused kernel with 288 > 256 time steps (their fDeltaTime table is staged through pinned memory, two
     terms launches) and, with 256, captured into a hipGraph after a first plain call and replayed on new samples."""
-    import ctypes
-
     from dc_sand_amd import BeamformerParameters
     from dc_sand_amd.generator import SteeringCoefficientGenerator
 
@@ -643,30 +609,17 @@ def test_fused_more_steps_than_ride_in_the_kernel_arguments_and_under_capture(gp
         gpu.memcpy_dtoh(got, d_beams)
         assert np.abs(got - exp).max() <= 2e-5 * A + 1e-6
         if nt == 256:
-            hip = ctypes.CDLL("libamdhip64.so")
-            V = ctypes.c_void_p
-            hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-            hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-            hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-            hip.hipGraphLaunch.argtypes = [V, V]
-            hip.hipGraphExecDestroy.argtypes = [V]
-            hip.hipGraphDestroy.argtypes = [V]
-            assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-            g.generate_and_beamform(d_ant, ant.nbytes, d_beams, exp.nbytes, t0=0, nt=nt, stream=s.handle)
-            graph = V()
-            assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-            ex = V()
-            assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+            with hip_graph.capture(s) as graph:
+                g.generate_and_beamform(d_ant, ant.nbytes, d_beams, exp.nbytes, t0=0, nt=nt, stream=s.handle)
             for rep in range(2):
                 ant2 = rng.integers(-128, 128, size=ant.shape, dtype=np.int8)
                 gpu.memcpy_htod(d_ant, ant2, stream=s.handle)
                 gpu.memset(d_beams, 0xFF, exp.nbytes, stream=s.handle)
-                assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+                graph.launch(s)
                 s.synchronize()
                 gpu.memcpy_dtoh(got, d_beams)
                 assert np.abs(got - oracle.beamform(op, table, nt, ant2)).max() <= 2e-5 * A + 1e-6
-            hip.hipGraphExecDestroy(ex)
-            hip.hipGraphDestroy(graph)
+            graph.close()
         g.close()
 
 
@@ -763,7 +716,7 @@ def test_config4_one_rank_shard_at_full_size_every_element(gpu, oracle, probes, 
     local = slice_table(glob, gp, sh)
     op = oracle.params_from(lp)
     t0 = time.perf_counter()
-    res = _compare_every_element(gpu, oracle, buf, op, local, delta_times(lp, t, 1)[0], lp.NR_CHANNELS, lp.n_pairs, readings=(0,))
+    res = compare_every_element(gpu, oracle, buf, op, local, delta_times(lp, t, 1)[0], lp.NR_CHANNELS, lp.n_pairs, readings=(0,))
     wall = time.perf_counter() - t0
     h = res[0]["hist"]
     assert sum(h) == 2 ** 33 and h[2] == 0 and h[3] == 0 and res[0]["max_ulp"] <= 1, res[0]
@@ -1082,22 +1035,11 @@ def test_seeded_fuzz_of_shapes_slabs_time_ranges_and_geometries(gpu, oracle):
 @pytest.mark.parametrize("nt,kernel", [(1, 2), (256, 2), (16, 1), (3, 1), (16, 0)])
 def test_generate_under_stream_capture(gpu, oracle, nt, kernel):
     """include/dcs_beamformer.h: "all device work is enqueued on the caller's stream so the calls can be
-    captured in a hipGraph".  dcs_bf_generate under hipStreamBeginCapture / EndCapture (up to 256 time steps:
+    captured in a hipGraph".  dcs_bf_generate under a stream capture (helpers/hip_graph.py; up to 256 time steps:
     their fDeltaTime values are kernel arguments; longer launches stage a table through pinned memory and
     are not capturable), instantiated and replayed twice: the replays write what a direct launch writes."""
-    import ctypes
-
     from dc_sand_amd import BeamformerParameters
     from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
 
     bp = BeamformerParameters(NR_CHANNELS=24, NR_STATIONS=5, NR_BEAMS=13)
     table = rand_table(bp.n_pairs, seed=31)
@@ -1107,22 +1049,17 @@ def test_generate_under_stream_capture(gpu, oracle, nt, kernel):
     nbytes = g.output_bytes(1, nt)
     buf = gpu.mem_alloc(nbytes)
     s = gpu.Stream()
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0  # hipStreamCaptureModeGlobal
-    g.generate(buf, nbytes, t0=7, nt=nt, stream=s.handle, kernel=kernel)  # (kernel 1 from 8 time steps on: a fork and a join over side streams)
-    graph = V()
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:  # hipStreamCaptureModeGlobal
+        g.generate(buf, nbytes, t0=7, nt=nt, stream=s.handle, kernel=kernel)  # (kernel 1 from 8 time steps on: a fork and a join over side streams)
     exp = oracle.generate(oracle.params_from(bp), table, 7, nt)
     for _ in range(2):
         gpu.memset(buf, 0xFF, nbytes, stream=s.handle)  # nothing was generated yet by the capture itself
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         s.synchronize()
         got = np.empty(exp.shape, dtype=np.float32)
         gpu.memcpy_dtoh(got, buf)
         _check(oracle, got, exp)
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     g.close()
     buf.free()
 
@@ -1781,19 +1718,8 @@ def test_beamform_accumulated_under_stream_capture(gpu, oracle, A, B):
     """dcs_bf_beamform_accumulated is two kernel launches and nothing else once the context's terms table exists (its one
     fDeltaTime travels in the kernel arguments): captured into a hipGraph after a first, plain, call and replayed -- a
     real-time beamformer re-launching one graph per block of samples."""
-    import ctypes
-
     from dc_sand_amd import BeamformerParameters
     from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-    hip = ctypes.CDLL("libamdhip64.so")
-    V = ctypes.c_void_p
-    hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-    hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-    hip.hipGraphLaunch.argtypes = [V, V]
-    hip.hipGraphExecDestroy.argtypes = [V]
-    hip.hipGraphDestroy.argtypes = [V]
 
     C, nt = 5, 48
     bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
@@ -1811,23 +1737,18 @@ def test_beamform_accumulated_under_stream_capture(gpu, oracle, A, B):
     s = gpu.Stream()
     g.beamform_accumulated(d_ant, ant.nbytes, d_beams, exp.nbytes, nt, dt_coeff=float(dt), stream=s.handle)  # allocates the terms table
     s.synchronize()
-    assert hip.hipStreamBeginCapture(V(s.handle), 0) == 0
-    g.beamform_accumulated(d_ant, ant.nbytes, d_beams, exp.nbytes, nt, dt_coeff=float(dt), stream=s.handle)
-    graph = V()
-    assert hip.hipStreamEndCapture(V(s.handle), ctypes.byref(graph)) == 0 and graph.value
-    ex = V()
-    assert hip.hipGraphInstantiate(ctypes.byref(ex), graph, None, None, 0) == 0
+    with hip_graph.capture(s) as graph:
+        g.beamform_accumulated(d_ant, ant.nbytes, d_beams, exp.nbytes, nt, dt_coeff=float(dt), stream=s.handle)
     for rep in range(3):
         ant2 = rng.integers(-128, 128, size=ant.shape, dtype=np.int8)  # new samples, same coefficients: what a replay is for
         gpu.memcpy_htod(d_ant, ant2, stream=s.handle)
         gpu.memset(d_beams, 0xFF, exp.nbytes, stream=s.handle)
-        assert hip.hipGraphLaunch(ex, V(s.handle)) == 0
+        graph.launch(s)
         s.synchronize()
         got = np.empty_like(exp)
         gpu.memcpy_dtoh(got, d_beams)
         assert np.abs(got - oracle.beamform_accumulated(op, table, dt, nt, ant2)).max() <= 4e-5 * A + 1e-6
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
+    graph.close()
     g.close()
 
 

@@ -208,7 +208,7 @@ def test_config5_full_tensor_two_node_graph_every_element(gpu, oracle, record_pr
 
     from dc_sand_amd import BeamformerParameters
     from dc_sand_amd.generator import SteeringCoefficientGenerator
-    from test_gpu_parity import _compare_every_element
+    from helpers.every_element import compare_every_element
 
     bp = BeamformerParameters(NR_CHANNELS=32768, NR_STATIONS=64, NR_BEAMS=1024)
     op = oracle.params_from(bp)
@@ -238,7 +238,7 @@ def test_config5_full_tensor_two_node_graph_every_element(gpu, oracle, record_pr
     st.tick_dt_from_global(float(dts[2]), d_tab)
     stream.synchronize()
     t0 = time.perf_counter()
-    res = _compare_every_element(gpu, oracle, buf, op, tables[2], dts[2], bp.NR_CHANNELS, bp.n_pairs)
+    res = compare_every_element(gpu, oracle, buf, op, tables[2], dts[2], bp.NR_CHANNELS, bp.n_pairs)
     wall = time.perf_counter() - t0
     n = bp.NR_CHANNELS * bp.n_pairs * 2
     for r in (0, 1):

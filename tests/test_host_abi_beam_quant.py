@@ -3,15 +3,13 @@ what its header declares, the product library none of it (its ABI 3 inventory of
 binding has the header's argument types, the argument checks that need no device, the header from C, and the range check
 of BeamQuantGains.  No GPU needed."""
 import ctypes
-import re
-import subprocess
-from ctypes import c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
-from pathlib import Path
+from ctypes import c_float, c_size_t, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
+from helpers.companion_abi import (check_exports_and_binding, check_header_parameter_kinds, check_product_inventory,
+                                   compile_against, fake_handle)
 
 QUANT = {
     "dcs_bf_beamform_accumulated_q8":
@@ -21,54 +19,13 @@ QUANT = {
 }
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / header).read_text(), flags=re.S)
-    return set(re.findall(r"\b(dcs_[a-z0-9_]+)\s*\(", text))
-
-
-def _exported(path):
-    syms = subprocess.run(["nm", "-D", "--defined-only", str(path)], check=True, capture_output=True, text=True).stdout
-    return {l.split()[-1] for l in syms.splitlines() if " T " in l}
-
-
 def test_companion_exports_what_its_header_declares_and_is_bound(dcs_lib):
-    from dc_sand_amd import _lib
-
-    qlib = _lib.beam_quant_lib()
-    assert _declared("dcs_beam_quant.h") == set(QUANT)
-    assert _exported(_lib.QUANT_LIB_PATH) == set(QUANT)
-    sigs = {name: (res, args) for name, res, args in _lib.BEAM_QUANT_SIGNATURES}
-    assert set(sigs) == set(QUANT)
-    for name, argtypes in QUANT.items():
-        res, args = sigs[name]
-        assert res is c_int and list(args) == argtypes, (name, args)
-        assert getattr(qlib, name).argtypes == argtypes
-    # the header's own parameter lists: pointer / integer / float kinds in the bound order
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "dcs_beam_quant.h").read_text(), flags=re.S)
-    for name, argtypes in QUANT.items():
-        params = re.search(name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == len(argtypes), name
-        for prm, ct in zip(params, argtypes):
-            if "*" in prm:
-                assert ct is c_void_p, (name, prm)
-            elif "float" in prm:
-                assert ct is c_float, (name, prm)
-            elif "uint64_t" in prm:
-                assert ct is c_uint64, (name, prm)
-            elif "uint32_t" in prm:
-                assert ct is c_uint32, (name, prm)
-            else:
-                assert "size_t" in prm and ct is c_size_t, (name, prm)
+    check_exports_and_binding("beam_quant", QUANT)
+    check_header_parameter_kinds("beam_quant", QUANT)
 
 
 def test_product_library_keeps_its_52_functions(dcs_lib):
-    from dc_sand_amd import _lib
-
-    product = _exported(_lib.LIB_PATH)
-    assert product == _declared("dcs_beamformer.h")
-    assert len(product) == 52
-    assert not {s for s in product if "q8" in s}
-    assert not set(QUANT) & _declared("dcs_beamformer.h")
+    check_product_inventory(QUANT, "q8")
     assert dcs_lib.dcs_abi_version() == 3
 
 
@@ -80,12 +37,12 @@ def _call(qlib, name, ctx, nt, gains, weights=None, clips=None):
 def test_quantised_calls_refuse_bad_arguments_without_a_device(dcs_lib):
     from dc_sand_amd import _lib
 
-    qlib = _lib.beam_quant_lib()
+    qlib = _lib.companion("beam_quant")
     buf = (ctypes.c_uint64 * 64)()
     p = ctypes.cast(buf, c_void_p)
     odd2, odd4 = c_void_p(p.value + 2), c_void_p(p.value + 4)
-    fake = (ctypes.c_uint64 * 64)()  # no context of this build: no table at its head
-    fp = ctypes.cast(fake, c_void_p)
+    fake = fake_handle()  # no context of this build: no table at its head
+    fp = fake.ptr
     for name in QUANT:
         assert _call(qlib, name, None, 16, p) == _lib.DCS_ERR_INVALID_ARGUMENT, name
         assert _call(qlib, name, fp, 16, None) == _lib.DCS_ERR_INVALID_ARGUMENT, name
@@ -100,19 +57,14 @@ def test_quantised_calls_refuse_bad_arguments_without_a_device(dcs_lib):
         assert _call(qlib, name, fp, 16, odd4, weights=odd4, clips=p) == _lib.DCS_ERR_UNSUPPORTED, name
         assert _call(qlib, name, fp, 0, p) == _lib.DCS_ERR_UNSUPPORTED, name
     # a context whose table is of another version is refused too
-    ops = (ctypes.c_uint64 * 8)()
-    ctypes.cast(ops, ctypes.POINTER(ctypes.c_uint32))[0] = 1  # the version before the quantiser
-    fake[0] = ctypes.addressof(ops)
+    fake.set_version(1)  # the version before the quantiser
     for name in QUANT:
         assert _call(qlib, name, fp, 16, p) == _lib.DCS_ERR_UNSUPPORTED, name
 
 
 def test_header_compiles_from_c(dcs_lib, tmp_path):
-    from dc_sand_amd import _lib
-
-    _lib.beam_quant_lib()
-    src = tmp_path / "q.c"
-    src.write_text(
+    out = compile_against(
+        "beam_quant",
         '#include <stdio.h>\n#include "dcs_beam_quant.h"\n'
         "int main(void) {\n"
         "  int (*f)(dcs_bf_context *, uint64_t, uint32_t, const int8_t *, size_t, const float *, const float *, int8_t *, size_t,\n"
@@ -120,13 +72,8 @@ def test_header_compiles_from_c(dcs_lib, tmp_path):
         "  int (*g)(dcs_bf_context *, float, uint32_t, const int8_t *, size_t, const float *, const float *, int8_t *, size_t,\n"
         "           unsigned long long *, void *) = dcs_bf_beamform_accumulated_q8_dt;\n"
         '  printf("%d %d %d\\n", f != 0, g != 0, DCS_BF_ABI_VERSION);\n'
-        "  return 0;\n}\n"
-    )
-    exe = tmp_path / "q"
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    "-L", str(_lib.QUANT_LIB_PATH.parent), "-l:libdcs_beam_quant.so", "-l:libdcs_beamformer.so",
-                    f"-Wl,-rpath,{_lib.QUANT_LIB_PATH.parent}"], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+        "  return 0;\n}\n",
+        tmp_path)
     assert out == ["1", "1", "3"]
 
 

@@ -3,15 +3,12 @@ exactly what its header declares, the product library none of it (its ABI 3 inve
 Python binding has the header's argument types, the argument checks that need no device, the servlet's count check in
 BeamWeights.set, and slice_weights against slice_table.  No GPU needed."""
 import ctypes
-import re
-import subprocess
-from ctypes import POINTER, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
-from pathlib import Path
+from ctypes import POINTER, c_float, c_size_t, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
+from helpers.companion_abi import check_exports_and_binding, check_product_inventory, compile_against, fake_handle
 
 WEIGHTS = {
     "dcs_bf_generate_and_beamform_weighted":
@@ -25,38 +22,12 @@ WEIGHTS = {
 }
 
 
-def _declared(header):
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / header).read_text(), flags=re.S)
-    return set(re.findall(r"\b(dcs_[a-z0-9_]+)\s*\(", text))
-
-
-def _exported(path):
-    syms = subprocess.run(["nm", "-D", "--defined-only", str(path)], check=True, capture_output=True, text=True).stdout
-    return {l.split()[-1] for l in syms.splitlines() if " T " in l}
-
-
 def test_companion_exports_what_its_header_declares_and_is_bound(dcs_lib):
-    from dc_sand_amd import _lib
-
-    wlib = _lib.beam_weights_lib()
-    assert _declared("dcs_beam_weights.h") == set(WEIGHTS)
-    assert _exported(_lib.WEIGHTS_LIB_PATH) == set(WEIGHTS)
-    sigs = {name: (res, args) for name, res, args in _lib.BEAM_WEIGHTS_SIGNATURES}
-    assert set(sigs) == set(WEIGHTS)
-    for name, argtypes in WEIGHTS.items():
-        res, args = sigs[name]
-        assert res is c_int and list(args) == argtypes, (name, args)
-        assert getattr(wlib, name).argtypes == argtypes
+    check_exports_and_binding("beam_weights", WEIGHTS)
 
 
 def test_product_library_keeps_its_52_functions(dcs_lib):
-    from dc_sand_amd import _lib
-
-    product = _exported(_lib.LIB_PATH)
-    assert product == _declared("dcs_beamformer.h")
-    assert len(product) == 52
-    assert not {s for s in product if "weighted" in s}
-    assert not set(WEIGHTS) & _declared("dcs_beamformer.h")
+    check_product_inventory(WEIGHTS, "weighted")
 
 
 def _call(wlib, name, ctx, nt, w, t=0):
@@ -71,12 +42,11 @@ def _call(wlib, name, ctx, nt, w, t=0):
 def test_weighted_calls_refuse_bad_arguments_without_a_device(dcs_lib):
     from dc_sand_amd import _lib
 
-    wlib = _lib.beam_weights_lib()
+    wlib = _lib.companion("beam_weights")
     buf = (ctypes.c_float * 64)()
     w = ctypes.cast(buf, c_void_p)
     w_odd = c_void_p(w.value + 2)
-    fake = (ctypes.c_uint64 * 64)()  # no context of this build: no weights table at its head
-    fp = ctypes.cast(fake, c_void_p)
+    fp = fake_handle().ptr  # no context of this build: no weights table at its head
     for name in WEIGHTS:
         assert _call(wlib, name, None, 16, w) == _lib.DCS_ERR_INVALID_ARGUMENT, name
         assert _call(wlib, name, fp, 16, None) == _lib.DCS_ERR_INVALID_ARGUMENT, name
@@ -94,23 +64,15 @@ def test_weighted_calls_refuse_bad_arguments_without_a_device(dcs_lib):
 
 
 def test_header_compiles_from_c(dcs_lib, tmp_path):
-    from dc_sand_amd import _lib
-
-    _lib.beam_weights_lib()
-    src = tmp_path / "w.c"
-    src.write_text(
+    out = compile_against(
+        "beam_weights",
         '#include <stdio.h>\n#include "dcs_beam_weights.h"\n'
         "int main(void) {\n"
         "  int (*f)(dcs_bf_context *, uint64_t, uint32_t, const int8_t *, size_t, const float *, float *, size_t, void *) =\n"
         "      dcs_bf_beamform_accumulated_weighted;\n"
         '  printf("%d %d\\n", f != 0, DCS_BF_ABI_VERSION);\n'
-        "  return 0;\n}\n"
-    )
-    exe = tmp_path / "w"
-    subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", "-I", str(ROOT / "include"), str(src), "-o", str(exe),
-                    "-L", str(_lib.WEIGHTS_LIB_PATH.parent), "-l:libdcs_beam_weights.so", "-l:libdcs_beamformer.so",
-                    f"-Wl,-rpath,{_lib.WEIGHTS_LIB_PATH.parent}"], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+        "  return 0;\n}\n",
+        tmp_path)
     assert out == ["1", "3"]
 
 
