@@ -42,4 +42,9 @@ COMPANIONS = {
         ("dcs_bf_beamform_accumulated_power_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
         ("dcs_bf_integrate_block_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
     ]),
+    # the incoherent beam: the antennas' own power, summed exactly and integrated like the detected beams
+    "incoherent_beam": Companion("dcs_incoherent_beam.h", "bf_incoherent_beam.cpp", "libdcs_incoherent_beam.so", [
+        ("dcs_bf_incoherent_block_power", c_int, [_VP, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
+        ("dcs_bf_integrate_incoherent_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+    ]),
 }

@@ -398,8 +398,14 @@ int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, ui
                                     void *stream);
 int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
                                uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream);
+int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                uint32_t *d_block_power, size_t power_bytes, void *stream);
+int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                                    uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
+                                    void *stream);
 const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl,
-                                    beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl};
+                                    beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl,
+                                    incoherent_block_power_impl, integrate_incoherent_power_impl};
 }
 
 int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
@@ -432,6 +438,7 @@ int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
         if ((st = (int)hipGetDevice(&c->device)) != 0) break;
         if ((st = (int)bf_warm_module()) != 0) break; // load the kernels now, not in the first timed launch
         if ((st = (int)bf_warm_module_mfma()) != 0) break;
+        if ((st = (int)bf_warm_module_incoherent()) != 0) break;
         const size_t tb = (size_t)c->n_pairs * sizeof(dcs_delay_vals);
         if ((st = (int)hipMalloc((void **)&c->d_table[0], tb)) != 0) break;
         if ((st = (int)hipMalloc((void **)&c->d_table[1], tb)) != 0) break;
@@ -1372,6 +1379,54 @@ int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, si
     a.n = blocks_per_spectrum;
     a.accumulate = accumulate ? 1u : 0u;
     return (int)bf_launch_power_integrate(a, as_stream(stream));
+}
+
+// include/dcs_incoherent_beam.h, reached the same way.  No coefficients: no delay table, no terms, nothing allocated, and
+// math_mode plays no part.
+int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                uint32_t *d_block_power, size_t power_bytes, void *stream)
+{
+    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights)) || (nt && !d_antenna)) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    if (nt % 16u) return DCS_ERR_INVALID_ARGUMENT;
+    const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
+    if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
+    if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
+    if (power_bytes < (size_t)C * (nt / 16u) * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_block_power) & 3u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    bf_incoh_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ant = d_antenna;
+    a.weights = d_weights;
+    a.block_power = d_block_power;
+    a.rows = (uint64_t)C * (nt / 16u);
+    a.A = A;
+    return (int)bf_launch_incoherent_power(a, as_stream(stream));
+}
+
+int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                                    uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
+                                    void *stream)
+{
+    if (!c || !d_block_power || !d_spectra || ((reinterpret_cast<uintptr_t>(d_block_power) | reinterpret_cast<uintptr_t>(d_spectra)) & 3u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
+    if (power_bytes < (size_t)C * nr_blocks * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
+    if (spectra_bytes < (size_t)n_spectra * C * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_incoh_int_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_power = d_block_power;
+    a.spectra = d_spectra;
+    a.total = n_spectra * C;
+    a.C = C;
+    a.nr_blocks = nr_blocks;
+    a.n = blocks_per_spectrum;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_incoherent_integrate(a, as_stream(stream));
 }
 } // namespace
 

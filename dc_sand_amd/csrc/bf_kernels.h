@@ -214,6 +214,30 @@ struct bf_pint_args {
 hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
+// The incoherent beam (bf_incoherent.hip; include/dcs_incoherent_beam.h): the sample tensor as
+// rows = C * nT16 rows of A * 32 bytes, each summed to one exact dword of block_power [C][nT16]
+struct bf_incoh_args {
+    const int8_t *ant;     // [rows][A][16][2], 16-byte aligned
+    const float *weights;  // nullptr (every antenna), or [A] flags: antenna a takes part iff weights[a] != 0
+    uint32_t *block_power; // [rows]
+    uint64_t rows;
+    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
+    uint32_t A;            // 1 .. 256
+};
+hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream);
+// Block powers [C][nr_blocks] summed n at a time, exactly, into spectra [nr_blocks / n][C]
+struct bf_incoh_int_args {
+    const uint32_t *block_power;
+    float *spectra;
+    uint64_t total;      // (nr_blocks / n) * C
+    uint32_t C;
+    uint32_t nr_blocks;  // a multiple of n
+    uint32_t n;          // blocks per spectrum, >= 1
+    uint32_t accumulate; // non-zero: the rounded sums are added to what spectra holds
+};
+hipError_t bf_launch_incoherent_integrate(const bf_incoh_int_args &a, hipStream_t stream);
+hipError_t bf_warm_module_incoherent();
+
 // One coefficient per lane, one time step (reference kernel a1's shape).
 struct bf_naive_args {
     const dcs_delay_vals *delays;

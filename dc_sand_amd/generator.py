@@ -109,6 +109,19 @@ def power_spectra_bytes(params: BeamformerParameters, nr_blocks: int, blocks_per
     return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * int(params.NR_BEAMS) * 4
 
 
+def incoherent_block_power_bytes(params: BeamformerParameters, nt: int) -> int:
+    """Size of the block power tensor ``uint32 [C][nt / 16]`` of :meth:`SteeringCoefficientGenerator.incoherent_block_power`."""
+    return int(params.NR_CHANNELS) * (int(nt) // 16) * 4
+
+
+def incoherent_spectra_bytes(params: BeamformerParameters, nr_blocks: int, blocks_per_spectrum: int) -> int:
+    """Size of the spectra ``float [nr_blocks / blocks_per_spectrum][C]`` of
+    :meth:`SteeringCoefficientGenerator.integrate_incoherent_power`."""
+    if blocks_per_spectrum <= 0 or nr_blocks % blocks_per_spectrum:
+        raise ValueError("nr_blocks must be a multiple of blocks_per_spectrum >= 1")
+    return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * 4
+
+
 def gpu_utilisation(params: BeamformerParameters, kernel_ms: float) -> tuple[float, float]:
     """``BeamformerCoeffTest::get_time`` model (``BeamformerCoefficientTest.cu:426-448``)."""
     out = (c_float * 2)()
@@ -276,6 +289,29 @@ class SteeringCoefficientGenerator:
                                               int(blocks_per_spectrum), 1 if accumulate else 0, _p(d_spectra), int(spectra_bytes),
                                               _s(stream)),
               "dcs_bf_integrate_block_power")
+
+    # -- the incoherent beam (include/dcs_incoherent_beam.h, companion library libdcs_incoherent_beam.so): d_block_power is a
+    #    device uint32 [C][nt / 16] array, d_spectra a device float [nr_blocks / blocks_per_spectrum][C] array
+    def incoherent_block_power(self, d_antenna, antenna_bytes: int, d_block_power, power_bytes: int, nt: int, d_weights=None,
+                               stream=None) -> None:
+        """The antennas' own power, ``re^2 + im^2`` summed over every 16-sample block and over the antennas taking part, as
+        exact integers, one per (channel, block) (:func:`incoherent_block_power_bytes`).  ``d_weights``: ``None``, or a
+        device ``float [A]`` array of FLAGS -- antenna ``a`` takes part iff its value is not 0; other values do not scale."""
+        il = _lib.companion("incoherent_beam")
+        check(il.dcs_bf_incoherent_block_power(c_void_p(self._h), int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights),
+                                               _p(d_block_power), int(power_bytes), _s(stream)),
+              "dcs_bf_incoherent_block_power")
+
+    def integrate_incoherent_power(self, d_block_power, power_bytes: int, nr_blocks: int, blocks_per_spectrum: int, d_spectra,
+                                   spectra_bytes: int, accumulate: bool = False, stream=None) -> None:
+        """Sums the block powers ``[C][nr_blocks]`` ``blocks_per_spectrum`` at a time, exactly, into the spectra
+        ``[nr_blocks / blocks_per_spectrum][C]`` (:func:`incoherent_spectra_bytes`), each sum rounded to float once; with
+        ``accumulate`` it is added to what ``d_spectra`` holds, so an integration can span calls."""
+        il = _lib.companion("incoherent_beam")
+        check(il.dcs_bf_integrate_incoherent_power(c_void_p(self._h), _p(d_block_power), int(power_bytes), int(nr_blocks),
+                                                   int(blocks_per_spectrum), 1 if accumulate else 0, _p(d_spectra),
+                                                   int(spectra_bytes), _s(stream)),
+              "dcs_bf_integrate_incoherent_power")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -1,0 +1,290 @@
+"""The incoherent beam on the GPU (include/dcs_incoherent_beam.h).  No tolerance anywhere: the block
+powers are compared as integers and the spectra as float bits with the numpy model (helpers/incoherent_model.py, anchored
+on the CPU by tests/test_incoherent_model.py).  The sample buffer is exactly sized, so its last row ends where the
+allocation ends, and every output is exactly sized with a canary behind it, which must stay untouched."""
+import numpy as np
+import pytest
+
+from helpers import hip_graph
+from helpers.incoherent_model import block_power, integrate, same_bits
+
+pytestmark = pytest.mark.gpu
+
+CANARY = 64
+SPECIALS = np.array([0.0, -0.0, np.nan, np.inf, -np.inf, 0.5, 1.0, -3.0, 1e-45], dtype=np.float32)
+
+
+def seeded_samples(A, C, nt, seed=0):
+    ant = np.random.default_rng(1000 * A + C + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+    ant.reshape(-1)[0], ant.reshape(-1)[-1] = -128, 127
+    return ant
+
+
+def seeded_flags(A, seed=0):
+    """Some antennas off (+0 or -0), the others on with every kind of value that is not 0."""
+    rng = np.random.default_rng(A + seed)
+    return SPECIALS[rng.integers(0, SPECIALS.size, size=A)] if A > 1 else np.array([0.5], np.float32)
+
+
+class ICase:
+    """One context of A antennas and C channels (no delay table: the incoherent beam has no coefficients), its samples
+    and its two outputs."""
+
+    def __init__(self, gpu, A, C, nt, seed=0):
+        from dc_sand_amd import BeamformerParameters
+        from dc_sand_amd.generator import (SteeringCoefficientGenerator, incoherent_block_power_bytes,
+                                           incoherent_spectra_bytes)
+
+        self.gpu, self.A, self.C, self.nt, self.nblk = gpu, A, C, nt, nt // 16
+        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=nt)
+        self.spectra_bytes = lambda n: incoherent_spectra_bytes(self.bp, self.nblk, n)
+        self.g = SteeringCoefficientGenerator(self.bp)
+        self.ant = seeded_samples(A, C, nt, seed)
+        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
+        self.pbytes = incoherent_block_power_bytes(self.bp, nt)
+        assert self.pbytes == C * self.nblk * 4
+        self.d_p = gpu.mem_alloc(self.pbytes + CANARY)
+        self.d_s = gpu.mem_alloc(self.pbytes + CANARY)  # spectra: at most one per block
+        self.d_w = gpu.mem_alloc(A * 4)
+
+    def set_ant(self, ant):
+        self.ant = ant
+        self.gpu.memcpy_htod(self.d_ant, ant)
+
+    def call_power(self, weighted=False, stream=None):
+        self.g.incoherent_block_power(self.d_ant, self.ant.nbytes, self.d_p, self.pbytes, self.nt,
+                                      d_weights=self.d_w if weighted else None, stream=stream)
+
+    def read_power(self):
+        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
+        self.gpu.memcpy_dtoh(host, self.d_p)
+        assert np.all(host[self.pbytes:] == 0xA5), "written past the block power tensor"
+        return host[:self.pbytes].view(np.uint32).reshape(self.C, self.nblk).copy()
+
+    def power(self, w=None):
+        """One call from a clean output buffer."""
+        gpu = self.gpu
+        gpu.memcpy_htod(self.d_ant, self.ant)
+        gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        if w is not None:
+            gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
+        self.call_power(weighted=w is not None)
+        gpu.synchronize()
+        return self.read_power()
+
+    def call_integrate(self, n, accumulate=False, stream=None):
+        self.g.integrate_incoherent_power(self.d_p, self.pbytes, self.nblk, n, self.d_s, self.spectra_bytes(n),
+                                          accumulate=accumulate, stream=stream)
+
+    def read_spectra(self, n):
+        nb = self.spectra_bytes(n)
+        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
+        self.gpu.memcpy_dtoh(host, self.d_s)
+        assert np.all(host[nb:] == 0xA5), "written past the spectra"
+        return host[:nb].view(np.float32).reshape(self.nblk // n, self.C).copy()
+
+    def spectra(self, n, accumulate=False, prior=None):
+        """One integration of what d_p holds; without ``accumulate`` from a clean buffer, with ``prior`` from that."""
+        gpu = self.gpu
+        if not accumulate or prior is not None:
+            gpu.memset(self.d_s, 0xA5, self.pbytes + CANARY)
+        if prior is not None:
+            gpu.memcpy_htod(self.d_s, np.ascontiguousarray(prior, dtype=np.float32))
+        self.call_integrate(n, accumulate)
+        gpu.synchronize()
+        return self.read_spectra(n)
+
+    def close(self):
+        self.g.close()
+
+
+# a single row; rows that could share a wave's load; both sides of a wave-load boundary (32 antennas); a last partial
+# load; every loads-per-row count's neighbourhood; row counts odd and no multiple of any rows-per-wave choice
+SHAPES = [(1, 1, 16), (3, 5, 48), (8, 4, 32), (31, 3, 48), (32, 3, 48), (33, 3, 48), (64, 7, 64), (65, 2, 48), (130, 4, 16),
+          (255, 2, 32), (256, 3, 80), (64, 1, 1600)]
+
+
+@pytest.mark.parametrize("A,C,nt", SHAPES)
+def test_block_power_is_the_model(gpu, A, C, nt):
+    c = ICase(gpu, A, C, nt)
+    exp = block_power(c.ant)
+    assert np.unique(exp).size >= min(100, exp.size), (np.unique(exp).size, exp.size)  # no trivial expectation
+    got = c.power()
+    assert got.dtype == exp.dtype and np.array_equal(got, exp), np.argwhere(got != exp)[:4]
+    w = seeded_flags(A)
+    got = c.power(w)
+    assert np.array_equal(got, block_power(c.ant, w)), np.argwhere(got != block_power(c.ant, w))[:4]
+    c.close()
+
+
+@pytest.mark.parametrize("A,C,nt", [(37, 2, 32), (130, 2, 32)])
+def test_weights_are_flags(gpu, A, C, nt):
+    c = ICase(gpu, A, C, nt)
+    ref = block_power(c.ant)
+    assert np.array_equal(c.power(), ref) and np.array_equal(c.power(np.ones(A, np.float32)), ref)  # NULL = all ones
+    assert not c.power(np.zeros(A, np.float32)).any()
+    assert not c.power(np.full(A, -0.0, np.float32)).any()
+    # one antenna at a time, every antenna: that antenna's own sum (an index error cannot hide)
+    x = c.ant.astype(np.int64)
+    own = (x * x).sum(axis=(3, 4))  # [C][K][A]
+    assert np.unique(own).size >= 100
+    total = np.zeros_like(ref, dtype=np.int64)
+    for a in range(A):
+        w = np.zeros(A, np.float32)
+        w[a] = SPECIALS[2 + a % (SPECIALS.size - 2)]  # some value that is not 0
+        got = c.power(w)
+        assert np.array_equal(got, own[:, :, a]), a
+        total += got
+    assert np.array_equal(total, ref)
+    # seeded flags with -0.0, NaN, the infinities and 0.5 among them
+    for seed in range(3):
+        w = seeded_flags(A, seed)
+        on = w != 0
+        assert 0 < on.sum() < A and np.isnan(w).any() and np.isinf(w).any() and (w == 0.5).any() and np.signbit(w[w == 0]).any()
+        assert np.array_equal(c.power(w), block_power(c.ant, w)), seed
+    c.close()
+
+
+def test_full_scale_needs_all_32_and_64_bits(gpu):
+    A, C, nt, n = 256, 1, 640, 40
+    c = ICase(gpu, A, C, nt)
+    c.ant = np.full_like(c.ant, -128)
+    got = c.power()
+    assert np.all(got == 1 << 27)
+    s = c.spectra(n)
+    assert s.shape == (1, 1) and float(s[0, 0]) == float(5 << 30) and 5 << 30 > 1 << 32
+    assert same_bits(s, integrate(got, n)) is None
+    c.close()
+
+
+@pytest.mark.parametrize("A,C,nt", [(64, 5, 256), (256, 2, 96)])
+def test_integration_is_the_exact_sum_rounded_once(gpu, A, C, nt):
+    from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
+
+    c = ICase(gpu, A, C, nt)
+    P = c.power()
+    assert np.array_equal(P, block_power(c.ant))
+    for n in (1, 2, c.nblk):
+        got = c.spectra(n)
+        exp = integrate(P, n)
+        assert np.unique(exp).size >= min(100, exp.size)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        if n > 1:  # sums that are no floats: the one rounding is exercised
+            S = P.astype(np.int64).reshape(C, c.nblk // n, n).sum(axis=2).T
+            assert np.any(exp.astype(np.float64) != S)
+        # accumulate from a seeded prior
+        prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
+        got = c.spectra(n, accumulate=True, prior=prior)
+        assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate")
+    # one integration across two calls with different samples
+    n = c.nblk
+    first = c.spectra(n)
+    c.ant = seeded_samples(A, C, nt, seed=5)
+    P2 = c.power()
+    assert np.array_equal(P2, block_power(c.ant)) and not np.array_equal(P2, P)
+    both = c.spectra(n, accumulate=True)
+    assert same_bits(first, integrate(P, n)) is None
+    assert same_bits(both, integrate(P2, n, prior=integrate(P, n))) is None
+    # a bad blocks_per_spectrum and buffers one byte short are refused, nothing is enqueued, the stream stays usable
+    s = gpu.Stream()
+    gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY)
+    gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY)
+    gpu.synchronize()
+    for bad in (0, c.nblk + 1, 3 if c.nblk % 3 else 5):
+        with pytest.raises(DcsError) as e:
+            c.g.integrate_incoherent_power(c.d_p, c.pbytes, c.nblk, bad, c.d_s, c.pbytes, stream=s.handle)
+        assert e.value.status == DCS_ERR_INVALID_ARGUMENT, bad
+    with pytest.raises(DcsError) as e:  # block powers one byte short
+        c.g.integrate_incoherent_power(c.d_p, c.pbytes - 1, c.nblk, 2, c.d_s, c.spectra_bytes(2), stream=s.handle)
+    assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    with pytest.raises(DcsError) as e:  # spectra one byte short
+        c.g.integrate_incoherent_power(c.d_p, c.pbytes, c.nblk, 2, c.d_s, c.spectra_bytes(2) - 1, stream=s.handle)
+    assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    with pytest.raises(DcsError) as e:  # samples one byte short
+        c.g.incoherent_block_power(c.d_ant, c.ant.nbytes - 1, c.d_p, c.pbytes, nt, stream=s.handle)
+    assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    with pytest.raises(DcsError) as e:  # block powers one byte short
+        c.g.incoherent_block_power(c.d_ant, c.ant.nbytes, c.d_p, c.pbytes - 1, nt, stream=s.handle)
+    assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    with pytest.raises(DcsError) as e:  # samples not 16-byte aligned
+        c.g.incoherent_block_power(int(c.d_ant) + 8, c.ant.nbytes, c.d_p, c.pbytes, nt, stream=s.handle)
+    assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    s.synchronize()
+    host = np.empty(c.pbytes + CANARY, dtype=np.uint8)
+    for d in (c.d_s, c.d_p):
+        gpu.memcpy_dtoh(host, d)
+        assert np.all(host == 0xA5)
+    c.call_power(stream=s.handle)
+    c.call_integrate(2, stream=s.handle)
+    s.synchronize()
+    assert np.array_equal(c.read_power(), P2) and same_bits(c.read_spectra(2), integrate(P2, 2)) is None
+    c.close()
+
+
+@pytest.mark.parametrize("A,C,nt", [(64, 3, 48), (130, 2, 32)])
+def test_outputs_at_an_address_that_is_4_byte_aligned_only(gpu, A, C, nt):
+    from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
+
+    c = ICase(gpu, A, C, nt)
+    w = seeded_flags(A)
+    gpu.memcpy_htod(c.d_ant, c.ant)
+    ref = block_power(c.ant, w)
+    d_w = gpu.mem_alloc(A * 4 + 16)
+    gpu.memcpy_htod(int(d_w) + 4, w)
+    d_big = gpu.mem_alloc(c.pbytes + CANARY + 16)
+    gpu.memset(d_big, 0xA5, c.pbytes + CANARY + 16)
+    c.g.incoherent_block_power(c.d_ant, c.ant.nbytes, int(d_big) + 4, c.pbytes, nt, d_weights=int(d_w) + 4)
+    gpu.synchronize()
+    host = np.empty(c.pbytes + CANARY + 16, dtype=np.uint8)
+    gpu.memcpy_dtoh(host, d_big)
+    assert np.all(host[:4] == 0xA5) and np.all(host[4 + c.pbytes:] == 0xA5)
+    assert np.array_equal(host[4:4 + c.pbytes].view(np.uint32).reshape(C, c.nblk), ref)
+    # ... and integrated from there, into spectra that are 4-byte aligned only
+    d_sp = gpu.mem_alloc(c.pbytes + CANARY + 16)
+    gpu.memset(d_sp, 0xA5, c.pbytes + CANARY + 16)
+    nb = c.spectra_bytes(c.nblk)
+    c.g.integrate_incoherent_power(int(d_big) + 4, c.pbytes, c.nblk, c.nblk, int(d_sp) + 4, nb)
+    gpu.synchronize()
+    gpu.memcpy_dtoh(host, d_sp)
+    assert np.all(host[:4] == 0xA5) and np.all(host[4 + nb:] == 0xA5)
+    assert same_bits(host[4:4 + nb].view(np.float32).reshape(1, C), integrate(ref, c.nblk)) is None
+    for args in ((int(d_big) + 2, None), (int(d_big), int(d_w) + 2)):  # 2-byte alignment is refused
+        with pytest.raises(DcsError) as e:
+            c.g.incoherent_block_power(c.d_ant, c.ant.nbytes, args[0], c.pbytes, nt, d_weights=args[1])
+        assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    for p_in, p_out in ((int(d_big) + 2, int(d_sp)), (int(d_big), int(d_sp) + 2)):
+        with pytest.raises(DcsError) as e:
+            c.g.integrate_incoherent_power(p_in, c.pbytes, c.nblk, c.nblk, p_out, nb)
+        assert e.value.status == DCS_ERR_INVALID_ARGUMENT
+    d_big.free()
+    d_sp.free()
+    d_w.free()
+    c.close()
+
+
+@pytest.mark.parametrize("A,C,nt", [(64, 3, 64), (130, 3, 64)])
+def test_captured_first_calls_pick_up_new_samples_on_replay(gpu, A, C, nt):
+    """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates, so nothing has to be run
+    outside the capture first -- replayed with new samples in the same buffer (the process's default queue count is
+    left as it is)."""
+    c = ICase(gpu, A, C, nt)
+    n = 2
+    w = seeded_flags(A)
+    gpu.memcpy_htod(c.d_w, w)
+    s = gpu.Stream()
+    with hip_graph.capture(s) as graph:
+        c.call_power(weighted=True, stream=s.handle)
+        c.call_integrate(n, stream=s.handle)
+    ants = [c.ant] + [seeded_samples(A, C, nt, seed=100 + i) for i in range(2)]
+    refs = [block_power(ant, w) for ant in ants]
+    assert not np.array_equal(refs[0], refs[1])
+    for i in (1, 2, 0, 1):
+        gpu.memcpy_htod(c.d_ant, ants[i], stream=s.handle, sync=False)
+        gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY, stream=s.handle)
+        gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY, stream=s.handle)
+        graph.launch(s)
+        s.synchronize()
+        assert np.array_equal(c.read_power(), refs[i]), i
+        assert same_bits(c.read_spectra(n), integrate(refs[i], n)) is None, i
+    graph.close()
+    c.close()

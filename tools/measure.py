@@ -23,6 +23,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py bfpower [--rounds 5] [--shape AxBxCxNT --variant float|power|power+int]
         detected beam power: the float call (twice: its own spread) against the detecting call and the detecting call plus
         the integration, alternating, in one process                              -> profiles/r06_beam_power.md
+    python tools/measure.py incoh [--rounds 5] [--trace]
+        the incoherent beam against the read probe (dcs_probe_reduce) over the same bytes and against the detecting call
+        at 16 and 256 beams, alternating, in one process; --trace: a few launches of each kernel for
+        `rocprofv3 --kernel-trace --stats -- python3 tools/measure.py incoh --trace`  -> profiles/r07_incoherent_beam.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -455,6 +459,94 @@ def cmd_bfpower(args):
     print(json.dumps({"bfpower": rows}), flush=True)
 
 
+def cmd_incoh(args):
+    """The incoherent beam (include/dcs_incoherent_beam.h), read-bound: 2 A bytes per sample and channel.  Per shape, in
+    turn ``--rounds`` times in one process on the same noise-like samples: the new call (events around a run of launches),
+    the read probe ``dcs_probe_reduce`` over the same bytes twice (its own spread; ONE event pair per call, because the
+    probe call synchronises -- it also allocates and copies 128 KiB of partial sums back, which the events include, so
+    the kernel-to-kernel comparison is the one of ``--trace``), the integration, and the detecting call at 16 and 256 beams.
+    Inputs above the 256 MiB Infinity Cache are read from one buffer; the 128 MiB shape rotates over five buffers so that
+    no call finds its lines cached.  ``--trace``: five launches of the new kernel and of the probe per shape, for a kernel
+    trace's own durations."""
+    from dc_sand_amd.generator import block_power_bytes, incoherent_block_power_bytes, incoherent_spectra_bytes
+    from probes import dcs_probes as pr
+
+    rows = []
+    for A, C, nt, nbuf in [(64, 32768, 256, 1), (256, 4096, 256, 1), (64, 4096, 256, 5)]:
+        nblk = nt // 16
+        ab = A * C * nt * 2
+        d_ants = [device.mem_alloc(ab) for _ in range(nbuf)]
+        for d in d_ants:
+            _noise(d, ab)
+        turn = [0]
+
+        def d_ant():
+            turn[0] = (turn[0] + 1) % nbuf
+            return d_ants[turn[0]]
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=16, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        pb, sb = incoherent_block_power_bytes(bp, nt), incoherent_spectra_bytes(bp, nblk, nblk)
+        d_p, d_s = device.mem_alloc(pb), device.mem_alloc(sb)
+        incoh = lambda: g.incoherent_block_power(d_ant(), ab, d_p, pb, nt)  # noqa: E731
+        integ = lambda: g.integrate_incoherent_power(d_p, pb, nblk, nblk, d_s, sb)  # noqa: E731
+
+        def probe_us():
+            e0, e1 = device.Event(), device.Event()
+            d = d_ant()
+            e0.record()
+            pr.tensor_properties(d, ab)
+            e1.record()
+            e1.synchronize()
+            return e1.elapsed_ms_since(e0)
+        incoh()
+        integ()
+        probe_us()
+        if args.trace:
+            for _ in range(5):
+                incoh()
+                device.synchronize()
+                pr.tensor_properties(d_ant(), ab)
+            print(f"trace {A}x{C}x{nt}: {ab} bytes read per launch of either kernel", flush=True)
+        else:
+            t = {name: [] for name in ("incoh", "probe", "probe_again", "int")}
+            for _ in range(args.rounds):
+                t["incoh"].append(per_launch_ms(incoh))
+                t["probe"].append(float(np.median([probe_us() for _ in range(20)])))
+                t["probe_again"].append(float(np.median([probe_us() for _ in range(20)])))
+                t["int"].append(per_launch_ms(integ))
+            med = {name: float(np.median(x)) for name, x in t.items()}
+            both = t["probe"] + t["probe_again"]
+            spread = max(max(both) / min(both) - 1.0, abs(med["probe_again"] / med["probe"] - 1.0))
+            row = {"shape": f"{A}x{C}x{nt}", "input_MiB": ab >> 20, "buffers": nbuf,
+                   "cache": "rotated" if nbuf > 1 else ("above the Infinity Cache" if ab > 256 << 20 else "cache-resident"),
+                   "incoh_us": round(med["incoh"] * 1e3, 1), "incoh_TBps": round(ab / (med["incoh"] * 1e-3) / 1e12, 2),
+                   "incoh_frac_8TBps": round(ab / (med["incoh"] * 1e-3) / 8e12, 3),
+                   "probe_call_us": round(med["probe"] * 1e3, 1), "probe_call_again_us": round(med["probe_again"] * 1e3, 1),
+                   "probe_call_TBps": round(ab / (med["probe"] * 1e-3) / 1e12, 2), "probe_spread": round(spread, 4),
+                   "incoh_over_probe_call": round(med["incoh"] / med["probe"], 4), "int_us": round(med["int"] * 1e3, 1)}
+        g.close()
+        if not args.trace:  # what the incoherent beam adds to a detected-beam pipeline on the same samples
+            for B in (16, 256):
+                bpb = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+                gb = SteeringCoefficientGenerator(bpb)
+                gb.upload_delays(simulate_input(bpb))
+                dpb = block_power_bytes(bpb, nt)
+                d_bp = device.mem_alloc(dpb)
+                detect = lambda: gb.beamform_accumulated_power(d_ant(), ab, d_bp, dpb, nt, t_coeff=1)  # noqa: E731
+                detect()
+                ms = float(np.median([per_launch_ms(detect) for _ in range(args.rounds)]))
+                row[f"bfpower_B{B}_us"] = round(ms * 1e3, 1)
+                row[f"incoh_adds_to_B{B}"] = round(med["incoh"] / ms, 4)
+                gb.close()
+                d_bp.free()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        for d in d_ants + [d_p, d_s]:
+            d.free()
+    if not args.trace:
+        print(json.dumps({"incoh": rows}), flush=True)
+
+
 def cmd_copy(args):
     """Mixed read + write ceiling: device-to-device copies (lean kernel in address order; hipMemcpyDtoD)."""
     from probes import dcs_probes as pr
@@ -747,6 +839,9 @@ def main():
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
     p.add_argument("--variant", default="power", choices=["float", "power", "power+int"],
                    help="with --shape: float call, detecting call, detecting call + integration")
+    p = sub.add_parser("incoh")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the new call and the read probe per shape")
+    p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
     p = sub.add_parser("bfq8")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the float and the int8 timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
@@ -785,7 +880,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
