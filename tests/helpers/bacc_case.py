@@ -16,8 +16,35 @@ ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 4
               (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
 FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
                 (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
+# The shapes above launch fewer workgroups than the chip holds (1280 four-wave ones of the matrix-core beamformer), and the
+# launcher then halves a workgroup's share of the sample blocks until every wave has ONE: the second block of a pair, the
+# later pairs and every later trip of the kernels' loops never run at them.  These launch 1280 to 1296 workgroups, so the
+# launcher leaves a wave several blocks: (A, B, C, nt, the number of blocks that blocks_on_some_wave must prove).
+# staged: 1 tile per workgroup and waves of 3 / 2, 1, 1, 1 blocks (whole and ragged antennas and beams); 2 tiles (shared
+# coefficient making); 4 tiles with one beam group (the 8-block cap: 5 / 4 blocks) and with two, ragged; the XCD-grouped
+# numbering.  kChain: 2 chunks with a partial one, 2 whole chunks, 3 chunks (a wave without one), 4 whole chunks with a
+# ragged last beam group.  Last, the deep ones: 4 blocks per wave (two whole pairs), 16 (eight pairs), and kChain's 4.
+MIN_DEPTH = 3  # a third block is a live second pair
+DEEP_SHAPES = [(64, 16, 640, 272, MIN_DEPTH), (37, 9, 640, 272, MIN_DEPTH), (64, 24, 640, 144, MIN_DEPTH),
+               (64, 40, 640, 144, MIN_DEPTH), (48, 72, 320, 144, MIN_DEPTH), (64, 1024, 40, 80, MIN_DEPTH),
+               (100, 20, 320, 272, MIN_DEPTH), (128, 16, 640, 272, MIN_DEPTH), (130, 20, 320, 272, MIN_DEPTH),
+               (256, 33, 216, 272, MIN_DEPTH),
+               (64, 16, 1280, 256, 4), (48, 72, 640, 256, 10), (130, 20, 640, 256, 4)]
+DEEPEST_SHAPES = DEEP_SHAPES[-3:]
 T_COEFF = 9
 CANARY = 64
+
+
+def blocks_on_some_wave(B, C, nt, grid, block):
+    """A lower bound, from the launch geometry alone, on the sample blocks the busiest wave of a matrix-core beamformer
+    launch works on.  A wave (64 lanes) works on one 16-beam tile and whole 16-sample blocks, so the launch's
+    C * ceil(B / 16) * (nt / 16) (tile, block) units are spread over gridDim.x * blockDim.x / 64 waves: some wave has at
+    least the quotient, rounded up.  Nothing of the launcher's arithmetic is restated: if it comes to give these shapes one
+    block per wave again, the tests that assert this number fail instead of testing nothing."""
+    assert grid[1] == grid[2] == 1 and block[1] == block[2] == 1 and block[0] % 64 == 0, (grid, block)
+    waves = grid[0] * (block[0] // 64)
+    units = C * -(-B // 16) * (nt // 16)
+    return -(-units // waves)
 
 
 class Case:
@@ -81,6 +108,28 @@ class Case:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
             self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt, **kw)
         return self.read()
+
+    def enqueue_floats(self, weighted, stream):
+        """The float call (by index) on ``stream`` and nothing else: what prove_depth captures."""
+        if weighted:
+            self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt,
+                                                 t_coeff=T_COEFF, stream=stream)
+        else:
+            self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, t_coeff=T_COEFF, stream=stream)
+
+    def prove_depth(self, depth, call):
+        """Asserts that the beamformer launch of ``call(stream)`` gives some wave at least ``depth`` sample blocks
+        (blocks_on_some_wave); ``call`` must have been made once already, since a first call allocates.  Nothing runs.
+        Returns (gridDim.x, blockDim.x, proven blocks)."""
+        from helpers import hip_graph
+
+        s = self.gpu.Stream()
+        grid, block = hip_graph.largest_launch(hip_graph.launches(s, lambda: call(s.handle)))
+        s.synchronize()
+        proven = blocks_on_some_wave(self.B, self.C, self.nt, grid, block)
+        assert proven >= depth, (f"(A, B, C, nt) = {(self.A, self.B, self.C, self.nt)} launches {grid[0]} workgroups of {block[0]} lanes: "
+                                 f"only {proven} block(s) proven on some wave, {depth} wanted -- raise the shape's channel count")
+        return grid[0], block[0], proven
 
     def read(self):
         host = np.empty(self.nbytes + CANARY, dtype=np.uint8)

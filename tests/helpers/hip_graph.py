@@ -5,11 +5,26 @@ makes it.
 ``with capture(s) as g:`` begins a capture on ``s`` and always ends it, also when the body raises -- the graph is then
 destroyed and the exception goes on, so the stream is not left capturing for the next test.  After the block ``g`` is
 the instantiated graph: ``g.launch(s)`` as often as wanted, then ``g.close()``.  ``begin`` / ``end`` / ``destroy`` are
-for the sites that do not instantiate what they capture."""
+for the sites that do not instantiate what they capture.
+
+``launches(s, fn)`` captures what ``fn()`` enqueues on ``s`` and returns the (gridDim, blockDim) of every kernel node without
+running anything: how a test proves the geometry a launcher chose instead of restating the launcher's arithmetic."""
 import ctypes
 
 V = ctypes.c_void_p
 _HIP = None
+
+
+class _Dim3(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint), ("y", ctypes.c_uint), ("z", ctypes.c_uint)]
+
+
+class _KernelNodeParams(ctypes.Structure):  # hipKernelNodeParams (hip_runtime_api.h)
+    _fields_ = [("blockDim", _Dim3), ("extra", V), ("func", V), ("gridDim", _Dim3), ("kernelParams", V),
+                ("sharedMemBytes", ctypes.c_uint)]
+
+
+_NODE_TYPE_KERNEL = 0  # hipGraphNodeTypeKernel
 
 
 def _hip():
@@ -22,6 +37,9 @@ def _hip():
         hip.hipGraphLaunch.argtypes = [V, V]
         hip.hipGraphExecDestroy.argtypes = [V]
         hip.hipGraphDestroy.argtypes = [V]
+        hip.hipGraphGetNodes.argtypes = [V, ctypes.POINTER(V), ctypes.POINTER(ctypes.c_size_t)]
+        hip.hipGraphNodeGetType.argtypes = [V, ctypes.POINTER(ctypes.c_int)]
+        hip.hipGraphKernelNodeGetParams.argtypes = [V, ctypes.POINTER(_KernelNodeParams)]
         _HIP = hip
     return _HIP
 
@@ -76,3 +94,54 @@ class capture:
     def close(self):
         _hip().hipGraphExecDestroy(self._exec)
         destroy(self._graph)
+
+
+def kernel_nodes(graph):
+    """[((grid x, y, z), (block x, y, z))] of every kernel node of a captured (not instantiated) graph; read-only."""
+    hip = _hip()
+    n = ctypes.c_size_t(0)
+    assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
+    nodes = (V * max(n.value, 1))()
+    assert hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) == 0
+    out = []
+    for node in nodes[:n.value]:
+        kind = ctypes.c_int(-1)
+        assert hip.hipGraphNodeGetType(V(node), ctypes.byref(kind)) == 0
+        if kind.value != _NODE_TYPE_KERNEL:
+            continue
+        p = _KernelNodeParams()
+        rc = hip.hipGraphKernelNodeGetParams(V(node), ctypes.byref(p))
+        assert rc == 0, f"hipGraphKernelNodeGetParams: {rc}"
+        g, b = p.gridDim, p.blockDim
+        assert g.x >= 1 and g.y >= 1 and g.z >= 1 and 1 <= b.x * b.y * b.z <= 1024, ((g.x, g.y, g.z), (b.x, b.y, b.z))
+        out.append(((g.x, g.y, g.z), (b.x, b.y, b.z)))
+    return out
+
+
+def launches(stream, fn):
+    """The kernel launches ``fn()`` enqueues on ``stream``, captured and thrown away: nothing runs.  ``fn`` must only
+    launch (a call that allocates on first use is made once, plainly, beforehand)."""
+    begin(stream)
+    try:
+        fn()
+    except BaseException:
+        _, graph = _end(stream)
+        if graph.value:
+            destroy(graph)
+        raise
+    graph = end(stream)
+    try:
+        return kernel_nodes(graph)
+    finally:
+        destroy(graph)
+
+
+def largest_launch(nodes):
+    """The rule that names a call's main kernel among its launches: the node with the most workgroups.  (A beamformer
+    call is the small kernel that makes the table's terms, one lane per pair, and the beamformer itself, whose every
+    workgroup takes a few sample blocks of one channel: at the shapes that use this rule it has at least five times the
+    terms kernel's workgroups, and the caller asserts that the maximum is unique.)"""
+    assert nodes, "no kernel node was captured"
+    sizes = sorted((g[0] * g[1] * g[2] for g, _ in nodes), reverse=True)
+    assert len(sizes) == 1 or sizes[0] > sizes[1], nodes
+    return max(nodes, key=lambda n: n[0][0] * n[0][1] * n[0][2])

@@ -248,3 +248,21 @@ def test_fast_class_precondition_notices_a_slow_pair():
     assert not all_pairs_fast(nan, dts, 64, 1e-7)
     zero = np.zeros(6, dtype=table.dtype)  # a zero table is fast: rate term 0
     assert all_pairs_fast(zero, dts, 64, 1e-7)
+
+
+def test_depth_bound_of_the_gpu_tests_is_the_pigeonhole_quotient():
+    """helpers/bacc_case.py: blocks_on_some_wave, the guard of the GPU tests' DEEP_SHAPES, on geometries worked by hand."""
+    from helpers.bacc_case import DEEP_SHAPES, MIN_DEPTH, blocks_on_some_wave
+
+    one, four = (1, 1), (256, 1, 1)
+    # 640 channels x 1 tile x 17 blocks = 10880 units: on 1280 four-wave workgroups 2.125 per wave, so some wave has 3; on
+    # 2720 (a wave per block and more) nothing is proven beyond 1
+    assert blocks_on_some_wave(16, 640, 272, (1280,) + one, four) == 3
+    assert blocks_on_some_wave(16, 640, 272, (2720,) + one, four) == 1
+    assert blocks_on_some_wave(16, 640, 272, (2719,) + one, four) == 2
+    assert blocks_on_some_wave(17, 640, 272, (1280,) + one, four) == 5  # a ragged second tile counts as a tile
+    assert blocks_on_some_wave(72, 640, 256, (1280,) + one, four) == 10
+    assert blocks_on_some_wave(72, 640, 256, (1280,) + one, (512, 1, 1)) == 5  # eight waves per workgroup
+    with pytest.raises(AssertionError):
+        blocks_on_some_wave(16, 640, 272, (640, 2, 1), four)  # a grid that is not one-dimensional is not this kernel's
+    assert all(depth >= MIN_DEPTH == 3 and nt % 16 == 0 for _, _, _, nt, depth in DEEP_SHAPES)

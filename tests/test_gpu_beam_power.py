@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, T_COEFF, Case
+from helpers.bacc_case import CANARY, DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beam_quant_model import SHAPES, seeded_weights
 
@@ -91,6 +91,41 @@ def test_block_power_is_the_model_of_the_float_output(gpu, oracle, A, B, C, nt, 
         assert np.unique(exp).size >= min(100, exp.size), (np.unique(exp).size, exp.size)
         got = c.power(w, dt)
         assert same_bits(got, exp) is None, (dt, same_bits(got, exp))
+    c.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+def test_block_power_with_several_blocks_per_wave(gpu, oracle, record_property, A, B, C, nt, depth, weighted):
+    """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
+    in its pairs and several pairs.  One time form per shape, in turn; then the integrator over many workgroups, every block
+    its own spectrum and all blocks in one.  The launch itself, read from a captured graph, must prove `depth` blocks on
+    some wave."""
+    c = PCase(gpu, oracle, A, B, C, nt)
+    w = seeded_weights(B, A) if weighted else None
+    dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
+    v = c.floats(w, dt)
+    exp = block_power(v)
+    assert np.all(np.isfinite(v)) and np.all(np.isfinite(exp)) and np.all(exp > 0)
+    assert np.unique(exp[::7]).size >= 100
+    got = c.power(w, dt)
+    assert same_bits(got, exp) is None, (dt, same_bits(got, exp))
+    for n in (1, c.nblk):
+        sp = c.spectra(n)
+        assert same_bits(sp, integrate(got, n)) is None, (n, same_bits(sp, integrate(got, n)))
+    record_property("gridDim.x, blockDim.x, blocks proven on some wave",
+                    c.prove_depth(depth, lambda s: c.call_power(weighted=weighted, dt=dt, stream=s)))
+    if (A, B, C, nt, depth) in DEEPEST_SHAPES and not weighted:
+        # a NaN pair (the whole table in the slow class): its beam NaN in every pair of blocks, the others the model's
+        nb = B // 2
+        t = c.table.copy().reshape(B, A)
+        t["fDelay_s"][nb, A // 3] = np.nan
+        c.set_table(t.ravel())
+        v2 = c.floats(dt=dt)
+        assert np.all(np.isnan(v2[:, :, nb])) and np.all(np.isfinite(np.delete(v2, nb, axis=2)))
+        got = c.power(dt=dt)
+        assert same_bits(got, block_power(v2)) is None, ("NaN pair", same_bits(got, block_power(v2)))
+        assert np.all(np.isnan(got[:, :, nb]))
     c.close()
 
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, T_COEFF, Case
+from helpers.bacc_case import CANARY, DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_quant_model import (SHAPES, expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
 
@@ -81,6 +81,49 @@ def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, A, B, C,
             assert np.array_equal(n, n_exp), (expected.__name__, dt, n, n_exp)
             got0, _ = c.q8(k, w, count=False, dt=dt)  # no counters: the same bytes
             assert same(got0, exp) is None, (expected.__name__, dt, "no counters", same(got0, exp))
+    c.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, record_property, A, B, C, nt, depth, weighted):
+    """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
+    in its pairs and several pairs, and its byte counters run across them.  One time form per shape, in turn.  The launch
+    itself, read from a captured graph, must prove `depth` blocks on some wave."""
+    c = QCase(gpu, oracle, A, B, C, nt)
+    w = seeded_weights(B, A) if weighted else None
+    dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
+    v = c.floats(w, dt)
+    assert np.all(np.isfinite(v))
+    for expected in (expected_without_clipping, expected_with_clipping):
+        k, exp, n_exp = expected(v)
+        got, n = c.q8(k, w, dt=dt)
+        assert same(got, exp) is None, (expected.__name__, dt, same(got, exp))
+        assert np.array_equal(n, n_exp), (expected.__name__, dt, n, n_exp)
+    got0, _ = c.q8(k, w, count=False, dt=dt)  # no counters: the same bytes
+    assert same(got0, exp) is None, ("no counters", dt, same(got0, exp))
+    record_property("gridDim.x, blockDim.x, blocks proven on some wave",
+                    c.prove_depth(depth, lambda s: c.call_q8(weighted=weighted, dt=dt, stream=s)))
+    if (A, B, C, nt, depth) in DEEPEST_SHAPES and not weighted:
+        # a gain that clips every component: a lane's byte counters go as high as the geometry lets them (4 per pair of
+        # blocks and register).  No component is 0 (asserted: the inputs are seeded), so every product is beyond 127
+        assert np.all(v != 0) and np.abs(v).min() * 1e30 > 127 and np.abs(v).max() * 1e30 < np.finfo(np.float32).max
+        got, n = c.q8(np.full(B, 1e30, np.float32), dt=dt)
+        assert np.all(n == C * nt * 2), n
+        assert np.all(np.abs(got.astype(np.int16)) == 127) and np.array_equal(got > 0, v > 0)
+        # a NaN pair (the whole table in the slow class): its beam -128 and counted in every pair of blocks
+        nb = B // 2
+        t = c.table.copy().reshape(B, A)
+        t["fDelay_s"][nb, A // 3] = np.nan
+        c.set_table(t.ravel())
+        v2 = c.floats(dt=dt)
+        assert np.all(np.isnan(v2[:, :, nb])) and np.all(np.isfinite(np.delete(v2, nb, axis=2)))
+        k = gains_with_clipping(np.delete(v2, nb, axis=2))
+        k = np.insert(k, nb, np.float32(1.0))
+        exp, n_exp = quantise(v2, k)
+        got, n = c.q8(k, dt=dt)
+        assert same(got, exp) is None, ("NaN pair", same(got, exp))
+        assert np.array_equal(n, n_exp) and n[nb] == C * nt * 2 and np.all(got[:, :, nb] == -128), (n, n_exp)
     c.close()
 
 

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
-from helpers.bacc_case import ACC_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
+from helpers.bacc_case import ACC_SHAPES, DEEP_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import (acc_model, all_pairs_fast, first_difference, fused_model, normalise, weighted_coefficients)
 
 pytestmark = pytest.mark.gpu
@@ -146,7 +146,9 @@ def weights_for(A, B, seed):
 
 # ---- a. the int8 matrix-core form.  All 35 shapes of ACC_SHAPES: 1 / 2 / 4 beam tiles per workgroup and partial tiles, the
 # staged form at 1 .. 64 antennas, kChain at 65 .. 256 (whole and partial chunks, waves without a chunk), odd block counts,
-# more than 16 blocks per workgroup, the shapes that leave the XCD-grouped numbering's identity tail, (64, 1024, 1, 32).
+# several workgroups per (channel, beam group), the shapes that leave the XCD-grouped numbering's identity tail,
+# (64, 1024, 1, 32).  At these channel counts (64 at the most) the launcher splits the sample blocks until every wave has
+# ONE: no wave sees a second block, a second pair or a second round.  DEEP_SHAPES, below, are the shapes that do.
 @pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
 def test_matrix_core_form_is_the_fixed_point_model_bit_for_bit(gpu, oracle, A, B, C, nt):
     """By time index (unweighted and weighted) and by fDeltaTime value (unweighted and weighted)."""
@@ -154,6 +156,25 @@ def test_matrix_core_form_is_the_fixed_point_model_bit_for_bit(gpu, oracle, A, B
     w = weights_for(A, B, A + 7 * B)
     c.check_acc(weights=(None, w), t_coeff=T_COEFF)
     c.check_acc(weights=(None, w), dt_coeff=DT_COEFF)
+    c.close()
+
+
+# ---- a'. the same form where a wave takes several sample blocks (helpers/bacc_case.py: DEEP_SHAPES): the live second block
+# of a pair, the later pairs (kStaged's LDS offsets of later blocks, kChain's stepping of its two sample buffers and the
+# re-zeroed accumulators), waves of one workgroup with different block counts, the equal-shares split with several rounds
+@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+def test_matrix_core_form_with_several_blocks_per_wave_bit_for_bit(gpu, oracle, record_property, A, B, C, nt, depth):
+    """Unweighted and weighted at one time form per shape (by index and by value in turn).  The launch itself, read from
+    a captured graph, must prove `depth` blocks on some wave: 3 is a live second pair."""
+    c = Exact(gpu, oracle, A, B, C, nt)
+    w = weights_for(A, B, A + 7 * B)
+    if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 == 0:
+        c.check_acc(weights=(None, w), t_coeff=T_COEFF)
+    else:
+        c.check_acc(weights=(None, w), dt_coeff=DT_COEFF)
+    for weighted in (False, True):
+        record_property(f"{'weighted' if weighted else 'unweighted'}: gridDim.x, blockDim.x, blocks proven on some wave",
+                        c.prove_depth(depth, lambda s: c.enqueue_floats(weighted, s)))
     c.close()
 
 

@@ -117,6 +117,58 @@ def test_block_power_is_the_model(gpu, A, C, nt):
     c.close()
 
 
+# SHAPES have 25 groups of rows at the most, and the kernel's grid holds 2048 workgroups x 4 waves: no wave takes a second
+# trip of its loop over the row groups.  These have 1.25 to 1.35 times 8192 groups, and an odd row count that is no multiple of the rows a
+# wave carries per trip (A, C, nt, those rows: 8 / loads per row, a load being 32 antennas): (1 load, 8 rows), (3 loads, 2
+# rows, ragged), (8 loads, 1 row, ragged)
+LOOPING_SHAPES = [(32, 1283, 1040, 8), (65, 1283, 272, 2), (255, 643, 256, 1)]
+
+
+@pytest.mark.parametrize("A,C,nt,rows_per_trip", LOOPING_SHAPES)
+def test_block_power_when_a_wave_takes_a_second_trip(gpu, record_property, A, C, nt, rows_per_trip):
+    """The launch geometry, read from a captured graph (nothing allocates, so the capture may come first), must prove the
+    second trip: its waves, each carrying `rows_per_trip` rows per trip, cannot hold the rows in one."""
+    c = ICase(gpu, A, C, nt)
+    rows = C * c.nblk
+    assert rows % rows_per_trip != 0 or rows_per_trip == 1
+    s = gpu.Stream()
+    nodes = hip_graph.launches(s, lambda: c.call_power(stream=s.handle))
+    s.synchronize()
+    assert len(nodes) == 1, nodes
+    grid, block = nodes[0]
+    assert grid[1] == grid[2] == 1 and block[1] == block[2] == 1 and block[0] % 64 == 0, nodes
+    waves = grid[0] * (block[0] // 64)
+    record_property("gridDim.x, blockDim.x, rows", (grid[0], block[0], rows))
+    assert waves * rows_per_trip < rows, f"{grid[0]} workgroups of {block[0]} lanes take {rows} rows in one trip: raise the channel count"
+    exp = block_power(c.ant)
+    assert np.unique(exp).size >= 100
+    got = c.power()
+    assert got.dtype == exp.dtype and np.array_equal(got, exp), np.argwhere(got != exp)[:4]
+    w = seeded_flags(A)
+    exp = block_power(c.ant, w)
+    got = c.power(w)
+    assert np.array_equal(got, exp), np.argwhere(got != exp)[:4]
+    c.close()
+
+
+def test_integration_over_several_workgroups(gpu):
+    """(33, 70, 128): 560 spectra values with one block per spectrum -- three workgroups of 256 lanes, the last one partial --
+    and 280 with two, plain and accumulating from a seeded prior."""
+    A, C, nt = 33, 70, 128
+    c = ICase(gpu, A, C, nt)
+    P = c.power()
+    assert np.array_equal(P, block_power(c.ant))
+    for n, total in ((1, 560), (2, 280)):
+        exp = integrate(P, n)
+        assert exp.size == total and np.unique(exp).size >= 100
+        got = c.spectra(n)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
+        got = c.spectra(n, accumulate=True, prior=prior)
+        assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate", same_bits(got, integrate(P, n, prior=prior)))
+    c.close()
+
+
 @pytest.mark.parametrize("A,C,nt", [(37, 2, 32), (130, 2, 32)])
 def test_weights_are_flags(gpu, A, C, nt):
     c = ICase(gpu, A, C, nt)

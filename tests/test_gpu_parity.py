@@ -1573,7 +1573,9 @@ def test_beamform_accumulated_on_the_matrix_cores(gpu, oracle, A, B, C, nt, math
     1e-1 (runBeamformerTests.cpp:15).  The fixed-point form is also held to its own, much tighter, bound against the
     sum in exact (fp64) arithmetic of the oracle's fp32 coefficients: 2.5e-7 * sum_a |sample_a| + 2e-7 * |sum|.
     Shapes cover every beam-tile count (1, 2, 4 per workgroup: coefficients shared by 4, 2, 1 waves), ragged antennas /
-    beams / sample blocks, odd block counts and more than 16 blocks per (channel, beam group) (several workgroups), 1-4
+    beams / sample blocks, odd block counts and several workgroups per (channel, beam group) -- at these channel counts the
+    launcher splits the blocks until every wave has ONE, whatever their number: what a wave does with several is held, bit
+    for bit, at the DEEP_SHAPES of helpers/bacc_case.py (tests/test_gpu_beamformer_exact.py, _beam_quant.py, _beam_power.py) --, 1-4
     64-antenna chunks (whole and partial) and the 256-antenna limit -- above 64 antennas the kChain form (round 3: the
     coefficients in LDS, the integer sums chained through the chunks by the matrix instruction's accumulator), with fewer
     sample blocks than waves (waves that only make their chunk's coefficients), odd pair counts and several workgroups
@@ -1711,6 +1713,28 @@ def test_beamform_accumulated_non_finite_coefficients(gpu, oracle, A, B, C, nt, 
     fin = ~np.isnan(exp)
     assert np.abs(np.where(fin, got - exp, 0)).max() <= 4e-5 * A + 1e-6
     g.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt,depth", [(64, 16, 1280, 256, 4), (130, 20, 640, 256, 4)])
+def test_beamform_accumulated_non_finite_coefficients_in_every_pair_of_blocks(gpu, oracle, record_property, A, B, C, nt, depth):
+    """The shapes above give every wave one sample block.  Here the launch fills the chip, so a wave has four blocks (the
+    launch geometry, read from a captured graph, must prove it): the NaN rows are marked in the first pair of blocks and
+    in the later ones, kStaged (64 antennas) and kChain (130), exactly where the verifier's NaNs are."""
+    from helpers.bacc_case import Case
+
+    table = rand_table(A * B, seed=5)  # [b*A + a]
+    table["fDelayRate_sps"][2 * A + 3] = np.inf        # beam 2
+    table["fPhase_rad"][(B - 1) * A + A - 1] = np.nan  # the last beam, the last antenna
+    c = Case(gpu, oracle, A, B, C, nt, seed=1, table=table)
+    dt = np.float32(0.25)
+    exp = oracle.beamform_accumulated(c.op, table, dt, nt, c.ant)
+    nan = np.isnan(exp)
+    assert nan[:, :, 2].all() and nan[:, :, B - 1].any() and not nan[:, :, [b for b in range(B) if b not in (2, B - 1)]].any()
+    got = c.floats(dt=float(dt))
+    assert np.array_equal(nan, np.isnan(got)), np.argwhere(nan != np.isnan(got))[:4]
+    assert np.abs(np.where(nan, 0, got - exp)).max() <= 4e-5 * A + 1e-6
+    record_property("gridDim.x, blockDim.x, blocks proven on some wave", c.prove_depth(depth, lambda s: c.enqueue_floats(False, s)))
+    c.close()
 
 
 @pytest.mark.parametrize("A,B", [(64, 16), (130, 20)])
