@@ -13,17 +13,18 @@ WEIGHTS := dc_sand_amd/csrc/libdcs_beam_weights.so
 QUANT   := dc_sand_amd/csrc/libdcs_beam_quant.so
 POWER   := dc_sand_amd/csrc/libdcs_beam_power.so
 INCOH   := dc_sand_amd/csrc/libdcs_incoherent_beam.so
+FBANK   := dc_sand_amd/csrc/libdcs_filterbank.so
 SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_incoherent.hip \
-           dc_sand_amd/csrc/bf_capi.hip
+           dc_sand_amd/csrc/bf_filterbank.hip dc_sand_amd/csrc/bf_capi.hip
 HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h dc_sand_amd/csrc/bf_stream_ext.h \
            dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_beamform_kernel.inc dc_sand_amd/csrc/bf_beamform_i8_kernel.inc \
            include/dcs_beamformer.h include/dcs_stream_staging.h include/dcs_beam_weights.h include/dcs_beam_quant.h \
-           include/dcs_beam_power.h include/dcs_incoherent_beam.h
+           include/dcs_beam_power.h include/dcs_incoherent_beam.h include/dcs_filterbank.h
 # -ffp-contract=off is part of the numerical contract; keep in step with dc_sand_amd/build.py
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -fvisibility=hidden \
             -Wall -Wextra -Wno-unused-parameter
 
-all: $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) probes oracle hosts
+all: $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) $(FBANK) probes oracle hosts
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS)
@@ -48,6 +49,10 @@ $(POWER): dc_sand_amd/csrc/bf_beam_power.cpp $(HDRS)
 $(INCOH): dc_sand_amd/csrc/bf_incoherent_beam.cpp $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_incoherent_beam.cpp
 
+# 8-bit search filterbanks (include/dcs_filterbank.h): forwards to the product library's kernels of bf_filterbank.hip
+$(FBANK): dc_sand_amd/csrc/bf_filterbank.cpp $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_filterbank.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -70,7 +75,7 @@ bench: $(LIB)
 	$(PYTHON) bench.py
 
 clean:
-	rm -f $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) probes/libdcs_probes.so
+	rm -f $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) $(FBANK) probes/libdcs_probes.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tests/cpp clean
 	rm -f tests/numerics/libnumerics_lab.so

@@ -47,4 +47,11 @@ COMPANIONS = {
         ("dcs_bf_incoherent_block_power", c_int, [_VP, c_uint32, _VP, c_size_t, _VP, _VP, c_size_t, _VP]),
         ("dcs_bf_integrate_incoherent_power", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
     ]),
+    # 8-bit search filterbanks from float spectra: running sums, scales, and the quantiser that transposes to beam-major bytes
+    "filterbank": Companion("dcs_filterbank.h", "bf_filterbank.cpp", "libdcs_filterbank.so", [
+        ("dcs_bf_spectra_sums", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_filterbank_scales", c_int, [_VP, _VP, c_size_t, c_uint64, c_uint32, c_float, _VP, c_size_t, _VP]),
+        ("dcs_bf_filterbank_q8", c_int,
+         [_VP, _VP, c_size_t, c_uint32, c_uint32, _VP, c_float, c_uint32, _VP, c_size_t, c_uint64, c_uint64, _VP, _VP]),
+    ]),
 }

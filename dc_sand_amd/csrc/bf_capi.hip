@@ -403,9 +403,17 @@ int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_
 int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
                                     uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
                                     void *stream);
+int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                      uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream);
+int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
+                           float target_std, float *d_scales, size_t scales_bytes, void *stream);
+int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                       const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
+                       uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream);
 const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl,
                                     beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl,
-                                    incoherent_block_power_impl, integrate_incoherent_power_impl};
+                                    incoherent_block_power_impl, integrate_incoherent_power_impl,
+                                    spectra_sums_impl, filterbank_scales_impl, filterbank_q8_impl};
 }
 
 int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
@@ -439,6 +447,7 @@ int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
         if ((st = (int)bf_warm_module()) != 0) break; // load the kernels now, not in the first timed launch
         if ((st = (int)bf_warm_module_mfma()) != 0) break;
         if ((st = (int)bf_warm_module_incoherent()) != 0) break;
+        if ((st = (int)bf_warm_module_filterbank()) != 0) break;
         const size_t tb = (size_t)c->n_pairs * sizeof(dcs_delay_vals);
         if ((st = (int)hipMalloc((void **)&c->d_table[0], tb)) != 0) break;
         if ((st = (int)hipMalloc((void **)&c->d_table[1], tb)) != 0) break;
@@ -1427,6 +1436,86 @@ int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_p
     a.n = blocks_per_spectrum;
     a.accumulate = accumulate ? 1u : 0u;
     return (int)bf_launch_incoherent_integrate(a, as_stream(stream));
+}
+
+// include/dcs_filterbank.h, reached the same way.  No coefficients and nothing allocated; nr_beams is the caller's, so the
+// one set of calls serves detected (the context's beams) and incoherent (1) spectra.
+// have >= x * y * z * w, the product taken without overflow
+bool holds(size_t have, uint64_t x, uint64_t y, uint64_t z, uint64_t w)
+{
+    const unsigned __int128 xy = (unsigned __int128)x * y, zw = (unsigned __int128)z * w;
+    if ((xy >> 64) || (zw >> 64)) return xy == 0 || zw == 0;
+    const unsigned __int128 need = xy * zw;
+    return !(need >> 64) && (uint64_t)need <= (uint64_t)have;
+}
+
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                      uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream)
+{
+    if (!c || !d_spectra || !d_sums || misaligned(d_spectra, 3u) || misaligned(d_sums, 7u) || nr_beams == 0u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbsums_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.sums = d_sums;
+    a.cb = (uint64_t)C * nr_beams;
+    a.T = nr_spectra;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_spectra_sums(a, as_stream(stream));
+}
+
+int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
+                           float target_std, float *d_scales, size_t scales_bytes, void *stream)
+{
+    if (!c || !d_sums || !d_scales || misaligned(d_sums, 7u) || misaligned(d_scales, 7u) || nr_beams == 0u || count == 0u ||
+        count >= (1ull << 53))
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(scales_bytes, C, nr_beams, 2u, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbscales_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.sums = d_sums;
+    a.scales = d_scales;
+    a.cb = (uint64_t)C * nr_beams;
+    a.count = count;
+    a.target_std = target_std;
+    return (int)bf_launch_filterbank_scales(a, as_stream(stream));
+}
+
+int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                       const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
+                       uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream)
+{
+    if (!c || !d_spectra || !d_scales || !d_filterbank || misaligned(d_spectra, 3u) || misaligned(d_scales, 7u) ||
+        misaligned(d_filterbank, 15u) || misaligned(d_clip_count, 7u) || nr_beams == 0u || (flags & ~1u) ||
+        first_spectrum > out_spectra || nr_spectra > out_spectra - first_spectrum)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(filterbank_bytes, nr_beams, out_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbq8_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.scales = d_scales;
+    a.out = d_filterbank;
+    a.clip_count = d_clip_count;
+    a.out_spectra = out_spectra;
+    a.first = first_spectrum;
+    a.C = C;
+    a.B = nr_beams;
+    a.T = nr_spectra;
+    a.descending = flags & 1u;
+    a.level = level;
+    return (int)bf_launch_filterbank_q8(a, as_stream(stream));
 }
 } // namespace
 

@@ -1,8 +1,10 @@
 // bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
-// (include/dcs_beam_power.h) and libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h).  All are built from this tree
+// (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h) and libdcs_filterbank.so
+// (include/dcs_filterbank.h).  All are built from this tree
 // together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
-// implementation of the weighted, the quantised and the detecting beamformer calls and of the incoherent beam; a companion checks the arguments it can check
+// implementation of the weighted, the quantised and the detecting beamformer calls, of the incoherent beam and of the
+// filterbank calls; a companion checks the arguments it can check
 // without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
@@ -15,7 +17,8 @@
 // 2: beamform_accumulated_q8 appended; 3: beamform_accumulated_power, integrate_block_power appended; 5: incoherent_block_power,
 // integrate_incoherent_power appended.  4 is skipped for good: tests/test_host_abi_beam_power.py hands the power companion a
 // zeroed table whose version word is 4 and expects DCS_ERR_UNSUPPORTED -- at version 4 it would call a null pointer.
-#define BF_CTX_EXT_VERSION 5u
+// 6: spectra_sums, filterbank_scales, filterbank_q8 appended (the tests hand foreign versions 1 to 5 only).
+#define BF_CTX_EXT_VERSION 6u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -48,6 +51,15 @@ struct bf_ctx_ext_ops {
     int (*integrate_incoherent_power)(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
                                       uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
                                       void *stream);
+    // 8-bit search filterbanks (include/dcs_filterbank.h): spectra float [nr_spectra][C][nr_beams] -> running sums double
+    // [C][nr_beams][2]; sums -> scales float [C][nr_beams][2]; spectra and scales -> uint8 [nr_beams][out_spectra][C]
+    int (*spectra_sums)(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                        uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream);
+    int (*filterbank_scales)(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
+                             float target_std, float *d_scales, size_t scales_bytes, void *stream);
+    int (*filterbank_q8)(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                         const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
+                         uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream);
 };
 
 // the first member of struct dcs_bf_context

@@ -238,6 +238,41 @@ struct bf_incoh_int_args {
 hipError_t bf_launch_incoherent_integrate(const bf_incoh_int_args &a, hipStream_t stream);
 hipError_t bf_warm_module_incoherent();
 
+// 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
+// [T][C][B], beam fastest; cb = C * B.
+// Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64
+struct bf_fbsums_args {
+    const float *spectra;
+    double *sums;        // [C][B][2]
+    uint64_t cb;
+    uint32_t T;
+    uint32_t accumulate; // non-zero: the sums start from what sums holds
+};
+hipError_t bf_launch_spectra_sums(const bf_fbsums_args &a, hipStream_t stream);
+// Sums -> scales {mu, k} float [C][B][2], in fp64 rounded once per operation
+struct bf_fbscales_args {
+    const double *sums;
+    float *scales;
+    uint64_t cb;
+    uint64_t count; // spectra behind the sums: 1 .. 2^53 - 1
+    float target_std;
+};
+hipError_t bf_launch_filterbank_scales(const bf_fbscales_args &a, hipStream_t stream);
+// Spectra normalised with the scales, quantised and transposed into out uint8 [B][out_spectra][C], rows first .. first + T - 1
+struct bf_fbq8_args {
+    const float *spectra;
+    const float *scales;               // [C][B][2], 8-byte aligned; read when the work runs
+    uint8_t *out;                      // 16-byte aligned
+    unsigned long long *clip_count;    // [B], added to; or nullptr: no counting
+    uint64_t out_spectra, first;
+    uint32_t C, B, T;
+    uint32_t slices;                   // filled by the launcher: time slices a workgroup walks (gridDim.y runs of them)
+    uint32_t descending;               // non-zero: channel c lands in column C - 1 - c
+    float level;
+};
+hipError_t bf_launch_filterbank_q8(const bf_fbq8_args &a, hipStream_t stream);
+hipError_t bf_warm_module_filterbank();
+
 // One coefficient per lane, one time step (reference kernel a1's shape).
 struct bf_naive_args {
     const dcs_delay_vals *delays;

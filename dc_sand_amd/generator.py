@@ -122,6 +122,21 @@ def incoherent_spectra_bytes(params: BeamformerParameters, nr_blocks: int, block
     return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * 4
 
 
+def spectra_sums_bytes(params: BeamformerParameters, nr_beams: int) -> int:
+    """Size of the running sums ``double [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.spectra_sums`."""
+    return int(params.NR_CHANNELS) * int(nr_beams) * 16
+
+
+def filterbank_scales_bytes(params: BeamformerParameters, nr_beams: int) -> int:
+    """Size of the scales ``float [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.filterbank_scales`."""
+    return int(params.NR_CHANNELS) * int(nr_beams) * 8
+
+
+def filterbank_bytes(params: BeamformerParameters, nr_beams: int, out_spectra: int) -> int:
+    """Size of the filterbanks ``uint8 [nr_beams][out_spectra][C]`` of :meth:`SteeringCoefficientGenerator.filterbank_q8`."""
+    return int(nr_beams) * int(out_spectra) * int(params.NR_CHANNELS)
+
+
 def gpu_utilisation(params: BeamformerParameters, kernel_ms: float) -> tuple[float, float]:
     """``BeamformerCoeffTest::get_time`` model (``BeamformerCoefficientTest.cu:426-448``)."""
     out = (c_float * 2)()
@@ -312,6 +327,39 @@ class SteeringCoefficientGenerator:
                                                    int(blocks_per_spectrum), 1 if accumulate else 0, _p(d_spectra),
                                                    int(spectra_bytes), _s(stream)),
               "dcs_bf_integrate_incoherent_power")
+
+    # -- 8-bit search filterbanks (include/dcs_filterbank.h, companion library libdcs_filterbank.so): d_spectra is a device
+    #    float [nr_spectra][C][nr_beams] array -- nr_beams the context's for detected spectra, 1 for incoherent ones
+    def spectra_sums(self, d_spectra, spectra_bytes: int, nr_spectra: int, nr_beams: int, d_sums, sums_bytes: int,
+                     accumulate: bool = False, stream=None) -> None:
+        """Running fp64 sums ``{sum x, sum x^2}`` per (channel, beam) over the spectra, in time order, into ``d_sums``
+        (:func:`spectra_sums_bytes`); with ``accumulate`` they start from what ``d_sums`` holds."""
+        fl = _lib.companion("filterbank")
+        check(fl.dcs_bf_spectra_sums(c_void_p(self._h), _p(d_spectra), int(spectra_bytes), int(nr_spectra), int(nr_beams),
+                                     1 if accumulate else 0, _p(d_sums), int(sums_bytes), _s(stream)),
+              "dcs_bf_spectra_sums")
+
+    def filterbank_scales(self, d_sums, sums_bytes: int, count: int, nr_beams: int, target_std: float, d_scales,
+                          scales_bytes: int, stream=None) -> None:
+        """The sums of ``count`` spectra to the scales ``{mean, target_std / standard deviation}`` per (channel, beam)
+        (:func:`filterbank_scales_bytes`); a channel without variance gets gain 0."""
+        fl = _lib.companion("filterbank")
+        check(fl.dcs_bf_filterbank_scales(c_void_p(self._h), _p(d_sums), int(sums_bytes), int(count), int(nr_beams),
+                                          float(np.float32(target_std)), _p(d_scales), int(scales_bytes), _s(stream)),
+              "dcs_bf_filterbank_scales")
+
+    def filterbank_q8(self, d_spectra, spectra_bytes: int, nr_spectra: int, nr_beams: int, d_scales, level: float, d_filterbank,
+                      filterbank_bytes: int, out_spectra: int, first_spectrum: int = 0, descending: bool = False,
+                      d_clip_count=None, stream=None) -> None:
+        """``clamp(rint((x - mean) * gain + level), 0, 255)`` of every spectrum into rows ``first_spectrum ..`` of the
+        per-beam filterbanks ``uint8 [nr_beams][out_spectra][C]`` (:func:`filterbank_bytes`); ``descending`` reverses the
+        channel order; ``d_clip_count``: ``None``, or a zeroed device ``uint64 [nr_beams]`` array of clipped elements."""
+        fl = _lib.companion("filterbank")
+        check(fl.dcs_bf_filterbank_q8(c_void_p(self._h), _p(d_spectra), int(spectra_bytes), int(nr_spectra), int(nr_beams),
+                                      _p(d_scales), float(np.float32(level)), 1 if descending else 0, _p(d_filterbank),
+                                      int(filterbank_bytes), int(out_spectra), int(first_spectrum), _p_or_null(d_clip_count),
+                                      _s(stream)),
+              "dcs_bf_filterbank_q8")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -27,6 +27,9 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the incoherent beam against the read probe (dcs_probe_reduce) over the same bytes and against the detecting call
         at 16 and 256 beams, alternating, in one process; --trace: a few launches of each kernel for
         `rocprofv3 --kernel-trace --stats -- python3 tools/measure.py incoh --trace`  -> profiles/r07_incoherent_beam.md
+    python tools/measure.py fbank [--rounds 5] [--trace]
+        8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
+        process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -547,6 +550,125 @@ def cmd_incoh(args):
         print(json.dumps({"incoh": rows}), flush=True)
 
 
+def _spectra(d_x, C, B, T):
+    """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
+    rng = np.random.default_rng(0xFB)
+    m = np.exp2(rng.uniform(-20.0, 20.0, size=(C, B))).astype(np.float32)
+    n = min(T, 8)
+    device.memcpy_htod(d_x, (m[None] * (1.0 + 0.25 * rng.standard_normal((n, C, B), dtype=np.float32))).astype(np.float32))
+    off, nbytes = n * C * B * 4, T * C * B * 4
+    while off < nbytes:
+        k = min(off, nbytes - off)
+        device.memcpy_dtod(int(d_x) + off, d_x, k)
+        off += k
+    device.synchronize()
+
+
+def cmd_fbank(args):
+    """8-bit search filterbanks (include/dcs_filterbank.h).  The quantiser reads 4 bytes and writes 1 per element: 1.25 x
+    the bytes of the read probe ``dcs_probe_reduce`` over the same input.  Per shape (T x C x B), in turn ``--rounds`` times
+    in one process: the quantiser, the probe twice (its own spread; the probe call synchronises, allocates and copies 128 KiB
+    back, so the kernel-to-kernel comparison is the one of ``--trace``), the sums call.  512 MiB of spectra exceed the
+    Infinity Cache; the 256 MiB shape rotates over five buffers.  Then what sums + scales + quantiser add to the detecting
+    call plus its integration at 64 antennas x 256 beams.  ``--trace``: five launches of each kernel and of the probe."""
+    from dc_sand_amd.generator import (block_power_bytes, filterbank_bytes, filterbank_scales_bytes, power_spectra_bytes,
+                                       spectra_sums_bytes)
+    from probes import dcs_probes as pr
+
+    rows = []
+    for T, C, B, nbuf in [(128, 4096, 256, 1), (64, 4096, 256, 5)]:
+        xb = T * C * B * 4
+        d_xs = [device.mem_alloc(xb) for _ in range(nbuf)]
+        for d in d_xs:
+            _spectra(d, C, B, T)
+        turn = [0]
+
+        def d_x():
+            turn[0] = (turn[0] + 1) % nbuf
+            return d_xs[turn[0]]
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+        g = SteeringCoefficientGenerator(bp)
+        nsums, nsc, nfb = spectra_sums_bytes(bp, B), filterbank_scales_bytes(bp, B), filterbank_bytes(bp, B, T)
+        d_sums, d_sc, d_fb, d_clips = device.mem_alloc(nsums), device.mem_alloc(nsc), device.mem_alloc(nfb), device.mem_alloc(B * 8)
+        device.memset(d_clips, 0, B * 8)
+        sums = lambda: g.spectra_sums(d_x(), xb, T, B, d_sums, nsums)  # noqa: E731
+        q8 = lambda: g.filterbank_q8(d_x(), xb, T, B, d_sc, 128.0, d_fb, nfb, T, descending=True, d_clip_count=d_clips)  # noqa: E731
+
+        def probe_us():
+            e0, e1 = device.Event(), device.Event()
+            d = d_x()
+            e0.record()
+            pr.tensor_properties(d, xb)
+            e1.record()
+            e1.synchronize()
+            return e1.elapsed_ms_since(e0)
+        sums()
+        g.filterbank_scales(d_sums, nsums, T, B, 24.0, d_sc, nsc)
+        q8()
+        probe_us()
+        if args.trace:
+            for _ in range(5):
+                q8()
+                sums()
+                device.synchronize()
+                pr.tensor_properties(d_x(), xb)
+            print(f"trace {T}x{C}x{B}: {xb} bytes read per launch of each kernel, {nfb} written by the quantiser", flush=True)
+        else:
+            t = {name: [] for name in ("q8", "probe", "probe_again", "sums")}
+            for _ in range(args.rounds):
+                t["q8"].append(per_launch_ms(q8))
+                t["probe"].append(float(np.median([probe_us() for _ in range(20)])))
+                t["probe_again"].append(float(np.median([probe_us() for _ in range(20)])))
+                t["sums"].append(per_launch_ms(sums))
+            med = {name: float(np.median(x)) for name, x in t.items()}
+            both = t["probe"] + t["probe_again"]
+            spread = max(max(both) / min(both) - 1.0, abs(med["probe_again"] / med["probe"] - 1.0))
+            row = {"shape": f"{T}x{C}x{B}", "input_MiB": xb >> 20, "buffers": nbuf,
+                   "q8_us": round(med["q8"] * 1e3, 1), "q8_TBps": round((xb + nfb) / (med["q8"] * 1e-3) / 1e12, 2),
+                   "probe_call_us": round(med["probe"] * 1e3, 1), "probe_call_again_us": round(med["probe_again"] * 1e3, 1),
+                   "probe_call_TBps": round(xb / (med["probe"] * 1e-3) / 1e12, 2), "probe_spread": round(spread, 4),
+                   "q8_over_probe_call": round(med["q8"] / med["probe"], 4),
+                   "q8_within_condition": bool(med["q8"] <= med["probe"] * (1.25 + spread)),
+                   "sums_us": round(med["sums"] * 1e3, 1), "sums_over_probe_call": round(med["sums"] / med["probe"], 4)}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        g.close()
+        for d in d_xs + [d_sums, d_sc, d_fb, d_clips]:
+            d.free()
+    if not args.trace:  # the pipeline: 64 antennas x 256 beams x 4096 channels, 1024 samples into 16 spectra of 4 blocks
+        A, B, C, nt, n = 64, 256, 4096, 1024, 4
+        nblk, T = nt // 16, nt // 16 // n
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        ab, pb, sb = A * C * nt * 2, block_power_bytes(bp, nt), power_spectra_bytes(bp, nblk, n)
+        nsums, nsc, nfb = spectra_sums_bytes(bp, B), filterbank_scales_bytes(bp, B), filterbank_bytes(bp, B, T)
+        bufs = [device.mem_alloc(x) for x in (ab, pb, sb, nsums, nsc, nfb)]
+        d_ant, d_p, d_s, d_sums, d_sc, d_fb = bufs
+        _noise(d_ant, ab)
+
+        def detect():
+            g.beamform_accumulated_power(d_ant, ab, d_p, pb, nt, t_coeff=1)
+            g.integrate_block_power(d_p, pb, nblk, n, d_s, sb)
+
+        def search():
+            g.spectra_sums(d_s, sb, T, B, d_sums, nsums)
+            g.filterbank_scales(d_sums, nsums, T, B, 24.0, d_sc, nsc)
+            g.filterbank_q8(d_s, sb, T, B, d_sc, 128.0, d_fb, nfb, T, descending=True)
+        detect()
+        search()
+        td = float(np.median([per_launch_ms(detect) for _ in range(args.rounds)]))
+        ts = float(np.median([per_launch_ms(search) for _ in range(args.rounds)]))
+        row = {"pipeline": f"{A}x{B}x{C}x{nt}, {T} spectra", "detect_and_integrate_us": round(td * 1e3, 1),
+               "sums_scales_q8_us": round(ts * 1e3, 1), "added": round(ts / td, 4)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        for d in bufs:
+            d.free()
+        print(json.dumps({"fbank": rows}), flush=True)
+
+
 def cmd_copy(args):
     """Mixed read + write ceiling: device-to-device copies (lean kernel in address order; hipMemcpyDtoD)."""
     from probes import dcs_probes as pr
@@ -842,6 +964,9 @@ def main():
     p = sub.add_parser("incoh")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the new call and the read probe per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
+    p = sub.add_parser("fbank")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
+    p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
     p = sub.add_parser("bfq8")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the float and the int8 timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
@@ -880,7 +1005,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
