@@ -123,7 +123,8 @@ struct dcs_bf_context {
     uint32_t terms_steps;   // time steps the table holds
     float *d_terms;         // [terms_steps][pairs_pad][2]; allocated on first use (ensure_terms)
     uint32_t *d_flags;      // [terms_steps][pairs_pad/64]
-    uint32_t flag_epoch;    // the beamformers' class words are tagged with the call's number instead of being zeroed per call
+    uint32_t flag_epoch;    // the beamformers' class words are tagged with the call's number instead of being zeroed per call ...
+    bool flags_cleared;     // ... until a beamformer call of this context is captured: from then on every call zeroes its words (clear_class_words)
     // per-input beam weights (include/dcs_beam_weights.h): what the weighted terms pre-pass makes from the caller's weights
     // for the beamformers; allocated on the first weighted call (ensure_weights)
     float *d_wnorm;         // [A][B]: ghat = g / s_b
@@ -803,10 +804,28 @@ int refuse_if_capturing(hipStream_t stream)
 int next_flag_epoch(dcs_bf_context *c, hipStream_t s, uint32_t *epoch)
 {
     if (c->flag_epoch >= (1u << 30) - 2u) {
-        DCS_TRY(hipMemsetAsync(c->d_flags, 0, (size_t)c->terms_steps * (c->pairs_pad / 64u) * 4u, s));
+        DCS_TRY(bf_launch_clear_words(c->d_flags, c->terms_steps * (c->pairs_pad / 64u), s));
         c->flag_epoch = 0;
     }
     *epoch = ++c->flag_epoch;
+    return DCS_OK;
+}
+
+// The tag alone makes a call's class words its own only while the calls reach the device in the order they were numbered
+// in.  A captured call keeps its number, so its replays run after calls with higher ones, whose words it could neither
+// overwrite (atomicMax) nor recognise; a call after the counter has started again meets the same from a graph captured
+// before.  So the first beamformer call made on a capturing stream, and every beamformer call of that context after it,
+// zeroes its nt words on the caller's stream in front of the pre-pass (one small launch more, a kernel node in the graph):
+// whatever ran before, the words then hold this call's classes.  A context that never captures keeps its launches as they are.
+int clear_class_words(dcs_bf_context *c, uint32_t nt, hipStream_t s)
+{
+    if (!c->flags_cleared) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        DCS_TRY(hipStreamIsCapturing(s, &cs));
+        if (cs == hipStreamCaptureStatusNone) return DCS_OK;
+        c->flags_cleared = true;
+    }
+    DCS_TRY(bf_launch_clear_words(c->d_flags, nt, s));
     return DCS_OK;
 }
 
@@ -824,7 +843,10 @@ int ensure_terms(dcs_bf_context *c, hipStream_t stream)
     if (!c->d_flags) {
         const size_t nb = (size_t)c->terms_steps * (c->pairs_pad / 64u) * 4u;
         DCS_TRY(hipMalloc((void **)&c->d_flags, nb));
-        DCS_TRY(hipMemset(c->d_flags, 0, nb)); // epoch 0: no call has that number
+        // epoch 0: no call has that number.  On the caller's stream (not capturing: asked above), in front of the launches of
+        // the call that allocates: a hipMemset on the null stream is not ordered against a non-blocking stream, and the words
+        // of a first call's pre-pass could be zeroed under it
+        DCS_TRY(bf_launch_clear_words(c->d_flags, (uint32_t)(nb / 4u), stream));
         c->flag_epoch = 0;
     }
     return DCS_OK;
@@ -1148,6 +1170,8 @@ int launch_bform_terms(dcs_bf_context *c, const float *d_weights, uint32_t nt, c
 {
     const int st_ep = next_flag_epoch(c, s, epoch);
     if (st_ep != DCS_OK) return st_ep;
+    const int st_clr = clear_class_words(c, nt, s);
+    if (st_clr != DCS_OK) return st_clr;
     bf_bform_terms_args ta;
     std::memset(&ta, 0, sizeof(ta));
     ta.delays = c->d_table[c->cur];

@@ -122,6 +122,8 @@ struct bf_weights_args {
     float *gn;      // [A][B]: ghat
     float *gs;      // [B]: s_b
 };
+// words[0 .. n) = 0: the class words of a call's time steps (clear_class_words, bf_capi.hip)
+hipError_t bf_launch_clear_words(uint32_t *words, uint32_t n, hipStream_t stream);
 // The weighted form of bf_launch_bform_terms: one more row of workgroups makes gn and gs
 hipError_t bf_launch_bform_terms_weighted(const bf_bform_terms_args &a, const bf_weights_args &w, const float *dt_inline,
                                           hipStream_t stream);

@@ -573,7 +573,8 @@ __device__ __forceinline__ void bform_terms_body(const bf_bform_terms_param<INL>
             floatx2{fRate, fPhase0};
     }
     // flags[t] = (epoch << 2) | highest class at time t: the caller numbers its calls, so a word left by an earlier call
-    // (a lower epoch) reads as "nothing above the lowest class yet" and nobody has to zero the words in between
+    // (a lower epoch) reads as "nothing above the lowest class yet" and nobody has to zero the words in between -- while calls
+    // run in the order of their numbers: a context whose calls are captured zeroes them per call (clear_class_words, bf_capi.hip)
     if (cls != DCS_CLASS_FAST_LOW) atomicMax(&a.flags[t], (a.epoch << 2) | cls);
 }
 
@@ -885,6 +886,22 @@ hipError_t bf_warm_module()
 {
     hipFuncAttributes attr;
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_gather_beams_kernel));
+}
+
+// Zeroes n class words (bf_bform_terms_args::flags): a kernel, so that in a stream and in a captured graph the clearing is
+// ordered against the pre-pass as any launch is.
+__global__ void __launch_bounds__(kBlock) bf_clear_words_kernel(uint32_t *words, const uint32_t n)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) words[i] = 0u;
+}
+
+hipError_t bf_launch_clear_words(uint32_t *words, uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    if (words == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bf_clear_words_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, words, n);
+    return hipGetLastError();
 }
 
 hipError_t bf_launch_bform_terms(const bf_bform_terms_args &a, const float *dt_inline, hipStream_t stream)

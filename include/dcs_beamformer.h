@@ -216,7 +216,9 @@ int dcs_bf_generate_at(dcs_bf_context *ctx, int kernel, int bitwidth, const stru
  * -- the reference's element-wise product (BeamformerKernels.cu:315-316), not a
  * complex one.  For this entry point the delay table is indexed
  * [beam * nr_stations + antenna] (BCT.cu:311; BeamformerKernels.cu:252).
- * No coefficient tensor is materialised.  Two launches (terms pre-pass, beamformer) per 256 time steps. */
+ * No coefficient tensor is materialised.  Two launches (terms pre-pass, beamformer) per 256 time steps (per chunk of as
+ * many time steps as the terms table holds: fewer than 256 with more than 32768 pairs); captured, each chunk has one small
+ * clearing launch in front as dcs_bf_beamform_accumulated has, and the same rule for replays holds. */
 int dcs_bf_generate_and_beamform(dcs_bf_context *ctx, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                  size_t antenna_bytes, float *d_beams, size_t beams_bytes, void *stream);
 
@@ -249,7 +251,11 @@ int dcs_bf_generate_and_beamform_dt(dcs_bf_context *ctx, const float *dt, uint32
  * accumulated as an fma chain in antenna order (differs from the verifier's loop by the chain's single
  * roundings only; same bound; 1/32 of the int8 pipe's rate).  nr_stations <= 256; d_antenna 16-byte aligned.
  * Two launches (terms pre-pass, contraction); capturable once the context's terms table exists (allocated by the
- * first call of this or of dcs_bf_generate_and_beamform: make one call outside the capture). */
+ * first call of this or of dcs_bf_generate_and_beamform: make one call outside the capture).  From the first beamformer call
+ * that a context sees on a capturing stream, every beamformer call of that context also clears the class words of its time
+ * steps in front of the pre-pass (one launch of one workgroup on the caller's stream: a third kernel node in the graph); a
+ * context that never captures launches its two kernels and nothing else.  Captured calls of one context may be replayed in
+ * any order among each other and among plain calls on the same stream. */
 int dcs_bf_beamform_accumulated(dcs_bf_context *ctx, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
                                 size_t antenna_bytes, float *d_beams, size_t beams_bytes, void *stream);
 int dcs_bf_beamform_accumulated_dt(dcs_bf_context *ctx, float dt_coeff, uint32_t nt, const int8_t *d_antenna,

@@ -8,7 +8,8 @@ the instantiated graph: ``g.launch(s)`` as often as wanted, then ``g.close()``. 
 for the sites that do not instantiate what they capture.
 
 ``launches(s, fn)`` captures what ``fn()`` enqueues on ``s`` and returns the (gridDim, blockDim) of every kernel node without
-running anything: how a test proves the geometry a launcher chose instead of restating the launcher's arithmetic."""
+running anything: how a test proves the geometry a launcher chose instead of restating the launcher's arithmetic.  With a
+list ``others`` it also names the types of the nodes that are no kernels (a memset node, say)."""
 import ctypes
 
 V = ctypes.c_void_p
@@ -25,6 +26,7 @@ class _KernelNodeParams(ctypes.Structure):  # hipKernelNodeParams (hip_runtime_a
 
 
 _NODE_TYPE_KERNEL = 0  # hipGraphNodeTypeKernel
+NODE_TYPE_MEMSET = 2   # hipGraphNodeTypeMemset
 
 
 def _hip():
@@ -96,8 +98,9 @@ class capture:
         destroy(self._graph)
 
 
-def kernel_nodes(graph):
-    """[((grid x, y, z), (block x, y, z))] of every kernel node of a captured (not instantiated) graph; read-only."""
+def kernel_nodes(graph, others=None):
+    """[((grid x, y, z), (block x, y, z))] of every kernel node of a captured (not instantiated) graph; read-only.  The
+    hipGraphNodeType of every other node is appended to ``others`` where a list is given."""
     hip = _hip()
     n = ctypes.c_size_t(0)
     assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
@@ -108,6 +111,8 @@ def kernel_nodes(graph):
         kind = ctypes.c_int(-1)
         assert hip.hipGraphNodeGetType(V(node), ctypes.byref(kind)) == 0
         if kind.value != _NODE_TYPE_KERNEL:
+            if others is not None:
+                others.append(kind.value)
             continue
         p = _KernelNodeParams()
         rc = hip.hipGraphKernelNodeGetParams(V(node), ctypes.byref(p))
@@ -118,9 +123,9 @@ def kernel_nodes(graph):
     return out
 
 
-def launches(stream, fn):
+def launches(stream, fn, others=None):
     """The kernel launches ``fn()`` enqueues on ``stream``, captured and thrown away: nothing runs.  ``fn`` must only
-    launch (a call that allocates on first use is made once, plainly, beforehand)."""
+    launch (a call that allocates on first use is made once, plainly, beforehand).  ``others``: as kernel_nodes takes it."""
     begin(stream)
     try:
         fn()
@@ -131,7 +136,7 @@ def launches(stream, fn):
         raise
     graph = end(stream)
     try:
-        return kernel_nodes(graph)
+        return kernel_nodes(graph, others)
     finally:
         destroy(graph)
 

@@ -30,6 +30,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
+    python tools/measure.py bfreplay [--rounds 5] [--shape AxBxCxNT]
+        the float matrix-core call made plainly (on a context that never captured), then replayed from a hipGraph and made
+        plainly again, alternating, in one process: what a replay and the clearing of the class words cost; run once per
+        build (DCS_LIB_PATH) to compare two                                        -> profiles/r09_class_words.md
     python tools/measure.py stream
         BASELINE configs[4]: full-tensor period and the largest slab at <= 200 us    -> profiles/r0N_streaming_config5.md
     python tools/measure.py stream --table-mode unchanged|host|device|staged-host|staged-host-pinned|staged-device ...
@@ -265,6 +269,48 @@ def cmd_bfacc(args):
         g.close()
         d_ant.free()
         d_beams.free()
+
+
+def cmd_bfreplay(args):
+    """One float call of the matrix-core beamformer per period, three ways: plain launches on a context that has never
+    captured; the captured call replayed; plain launches after the capture (from then on every call of the context clears
+    its class words: clear_class_words in bf_capi.hip)."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    from helpers import hip_graph
+
+    A, B, C, nt = (int(v) for v in args.shape.split("x"))
+    bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+    g = SteeringCoefficientGenerator(bp)
+    g.upload_delays(simulate_input(bp))
+    ab, bb = A * C * nt * 2, B * C * nt * 8
+    d_ant, d_beams = device.mem_alloc(ab), device.mem_alloc(bb)
+    _noise(d_ant, ab)
+    s = device.Stream()
+
+    def call():
+        g.beamform_accumulated(d_ant, ab, d_beams, bb, nt, t_coeff=1, stream=s.handle)
+
+    call()  # allocates
+    s.synchronize()
+    never = [per_launch_ms(call, stream=s.handle) * 1e3 for _ in range(args.rounds)]
+    others = []
+    nodes = hip_graph.launches(s, call, others)
+    with hip_graph.capture(s) as graph:
+        call()
+    replay, after = [], []
+    for _ in range(args.rounds):
+        replay.append(per_launch_ms(lambda: graph.launch(s), stream=s.handle) * 1e3)
+        after.append(per_launch_ms(call, stream=s.handle) * 1e3)
+    graph.close()
+
+    def line(name, v):
+        print(f"{name}: median {sorted(v)[len(v) // 2]:.2f} us, min {min(v):.2f}, max {max(v):.2f}  ({', '.join(f'{x:.2f}' for x in v)})", flush=True)
+
+    print(f"{A}ant x {B}beam x {C}chan x {nt}samples, float call; captured: {len(nodes)} kernel node(s), {len(others)} other node(s)", flush=True)
+    line("plain, context never captured", never)
+    line("replayed from the graph      ", replay)
+    line("plain, after the capture     ", after)
+    g.close()
 
 
 def _noise(d_ant, nbytes):
@@ -977,6 +1023,9 @@ def main():
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape only (PMC passes)")
     p.add_argument("--modes", default="0,8", help="math_mode values: 0 = int8 fixed point, 8 = fp32 chain")
     p.add_argument("--random", action="store_true", help="noise-like int8 samples instead of a constant byte (the matrix pipe's power depends on the data)")
+    p = sub.add_parser("bfreplay")
+    p.add_argument("--rounds", type=int, default=5, help="timings of each of the three ways; the last two alternate")
+    p.add_argument("--shape", default="64x16x640x272", help="AxBxCxNT")
     p = sub.add_parser("stream")
     p.add_argument("--model-step-us", type=float, default=200.0)
     p.add_argument("--table-mode", action="append", choices=TABLE_MODES,
@@ -1005,7 +1054,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
