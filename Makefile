@@ -8,50 +8,29 @@
 HIPCC   ?= /opt/rocm/bin/hipcc
 PYTHON  ?= python
 LIB     := dc_sand_amd/csrc/libdcs_beamformer.so
-STAGING := dc_sand_amd/csrc/libdcs_stream_staging.so
-WEIGHTS := dc_sand_amd/csrc/libdcs_beam_weights.so
-QUANT   := dc_sand_amd/csrc/libdcs_beam_quant.so
-POWER   := dc_sand_amd/csrc/libdcs_beam_power.so
-INCOH   := dc_sand_amd/csrc/libdcs_incoherent_beam.so
-FBANK   := dc_sand_amd/csrc/libdcs_filterbank.so
+# the companion libraries (dc_sand_amd/companions.py): each forwards to the product library through the table at the head of
+# a context or a stream (bf_ctx_ext.h, bf_stream_ext.h); libdcs_NAME.so is built from bf_NAME.cpp
+COMPANIONS := $(addprefix dc_sand_amd/csrc/libdcs_,$(addsuffix .so,stream_staging beam_weights beam_quant beam_power incoherent_beam \
+              filterbank))
 SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_incoherent.hip \
-           dc_sand_amd/csrc/bf_filterbank.hip dc_sand_amd/csrc/bf_capi.hip
+           dc_sand_amd/csrc/bf_filterbank.hip dc_sand_amd/csrc/bf_capi.hip dc_sand_amd/csrc/bf_capi_generate.hip \
+           dc_sand_amd/csrc/bf_capi_beamform.hip dc_sand_amd/csrc/bf_capi_detect.hip dc_sand_amd/csrc/bf_capi_stream.hip
 HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h dc_sand_amd/csrc/bf_stream_ext.h \
-           dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_beamform_kernel.inc dc_sand_amd/csrc/bf_beamform_i8_kernel.inc \
+           dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_host.h dc_sand_amd/csrc/bf_beamform_kernel.inc \
+           dc_sand_amd/csrc/bf_beamform_i8_kernel.inc \
            include/dcs_beamformer.h include/dcs_stream_staging.h include/dcs_beam_weights.h include/dcs_beam_quant.h \
            include/dcs_beam_power.h include/dcs_incoherent_beam.h include/dcs_filterbank.h
 # -ffp-contract=off is part of the numerical contract; keep in step with dc_sand_amd/build.py
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -fvisibility=hidden \
             -Wall -Wextra -Wno-unused-parameter
 
-all: $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) $(FBANK) probes oracle hosts
+all: $(LIB) $(COMPANIONS) probes oracle hosts
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS)
 
-# staged delay tables (include/dcs_stream_staging.h): forwards to the product library's streams
-$(STAGING): dc_sand_amd/csrc/bf_stream_staging.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_stream_staging.cpp
-
-# per-input beam weights (include/dcs_beam_weights.h): forwards to the product library's beamformers
-$(WEIGHTS): dc_sand_amd/csrc/bf_beam_weights.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_beam_weights.cpp
-
-# quantised int8 beam output (include/dcs_beam_quant.h): forwards to the product library's matrix-core beamformer
-$(QUANT): dc_sand_amd/csrc/bf_beam_quant.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_beam_quant.cpp
-
-# detected, time-integrated beam power (include/dcs_beam_power.h): forwards to the product library's matrix-core beamformer
-$(POWER): dc_sand_amd/csrc/bf_beam_power.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_beam_power.cpp
-
-# the incoherent beam (include/dcs_incoherent_beam.h): forwards to the product library's kernels of bf_incoherent.hip
-$(INCOH): dc_sand_amd/csrc/bf_incoherent_beam.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_incoherent_beam.cpp
-
-# 8-bit search filterbanks (include/dcs_filterbank.h): forwards to the product library's kernels of bf_filterbank.hip
-$(FBANK): dc_sand_amd/csrc/bf_filterbank.cpp $(HDRS)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ dc_sand_amd/csrc/bf_filterbank.cpp
+dc_sand_amd/csrc/libdcs_%.so: dc_sand_amd/csrc/bf_%.cpp $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 
 oracle:
 	$(MAKE) -C oracle
@@ -75,7 +54,7 @@ bench: $(LIB)
 	$(PYTHON) bench.py
 
 clean:
-	rm -f $(LIB) $(STAGING) $(WEIGHTS) $(QUANT) $(POWER) $(INCOH) $(FBANK) probes/libdcs_probes.so
+	rm -f $(LIB) $(COMPANIONS) probes/libdcs_probes.so
 	$(MAKE) -C oracle clean
 	$(MAKE) -C tests/cpp clean
 	rm -f tests/numerics/libnumerics_lab.so

@@ -1,0 +1,172 @@
+// bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
+// incoherent beam (include/dcs_incoherent_beam.h) and the search filterbanks (include/dcs_filterbank.h), each reached
+// through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its
+// device, nothing else.  Host code only; the kernels are in bf_beamform_mfma.hip, bf_incoherent.hip and bf_filterbank.hip.
+
+#include <cstring>
+
+#include "bf_host.h"
+
+using namespace bf_host;
+
+namespace bf_host {
+
+int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                               uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream)
+{
+    if (!c || !weights_ok(d_block_power) || !weights_ok(d_spectra)) return DCS_ERR_INVALID_ARGUMENT;
+    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
+    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
+    if (power_bytes < (size_t)C * nr_blocks * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    if (spectra_bytes < (size_t)n_spectra * C * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_pint_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_power = d_block_power;
+    a.spectra = d_spectra;
+    a.total = n_spectra * C * B;
+    a.B = B;
+    a.C = C;
+    a.nr_blocks = nr_blocks;
+    a.n = blocks_per_spectrum;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_power_integrate(a, as_stream(stream));
+}
+
+// include/dcs_incoherent_beam.h, reached the same way.  No coefficients: no delay table, no terms, nothing allocated, and
+// math_mode plays no part.
+int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                uint32_t *d_block_power, size_t power_bytes, void *stream)
+{
+    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights)) || (nt && !d_antenna)) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    if (nt % 16u) return DCS_ERR_INVALID_ARGUMENT;
+    const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
+    if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
+    if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
+    if (power_bytes < (size_t)C * (nt / 16u) * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_block_power) & 3u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    bf_incoh_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ant = d_antenna;
+    a.weights = d_weights;
+    a.block_power = d_block_power;
+    a.rows = (uint64_t)C * (nt / 16u);
+    a.A = A;
+    return (int)bf_launch_incoherent_power(a, as_stream(stream));
+}
+
+int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                                    uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
+                                    void *stream)
+{
+    if (!c || !d_block_power || !d_spectra || ((reinterpret_cast<uintptr_t>(d_block_power) | reinterpret_cast<uintptr_t>(d_spectra)) & 3u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
+    if (power_bytes < (size_t)C * nr_blocks * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
+    if (spectra_bytes < (size_t)n_spectra * C * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_incoh_int_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_power = d_block_power;
+    a.spectra = d_spectra;
+    a.total = n_spectra * C;
+    a.C = C;
+    a.nr_blocks = nr_blocks;
+    a.n = blocks_per_spectrum;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_incoherent_integrate(a, as_stream(stream));
+}
+
+} // namespace bf_host
+
+// include/dcs_filterbank.h, reached the same way.  No coefficients and nothing allocated; nr_beams is the caller's, so the
+// one set of calls serves detected (the context's beams) and incoherent (1) spectra.
+namespace {
+// have >= x * y * z * w, the product taken without overflow
+bool holds(size_t have, uint64_t x, uint64_t y, uint64_t z, uint64_t w)
+{
+    const unsigned __int128 xy = (unsigned __int128)x * y, zw = (unsigned __int128)z * w;
+    if ((xy >> 64) || (zw >> 64)) return xy == 0 || zw == 0;
+    const unsigned __int128 need = xy * zw;
+    return !(need >> 64) && (uint64_t)need <= (uint64_t)have;
+}
+
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+} // namespace
+
+namespace bf_host {
+
+int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                      uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream)
+{
+    if (!c || !d_spectra || !d_sums || misaligned(d_spectra, 3u) || misaligned(d_sums, 7u) || nr_beams == 0u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbsums_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.sums = d_sums;
+    a.cb = (uint64_t)C * nr_beams;
+    a.T = nr_spectra;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_spectra_sums(a, as_stream(stream));
+}
+
+int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
+                           float target_std, float *d_scales, size_t scales_bytes, void *stream)
+{
+    if (!c || !d_sums || !d_scales || misaligned(d_sums, 7u) || misaligned(d_scales, 7u) || nr_beams == 0u || count == 0u ||
+        count >= (1ull << 53))
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(scales_bytes, C, nr_beams, 2u, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbscales_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.sums = d_sums;
+    a.scales = d_scales;
+    a.cb = (uint64_t)C * nr_beams;
+    a.count = count;
+    a.target_std = target_std;
+    return (int)bf_launch_filterbank_scales(a, as_stream(stream));
+}
+
+int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                       const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
+                       uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream)
+{
+    if (!c || !d_spectra || !d_scales || !d_filterbank || misaligned(d_spectra, 3u) || misaligned(d_scales, 7u) ||
+        misaligned(d_filterbank, 15u) || misaligned(d_clip_count, 7u) || nr_beams == 0u || (flags & ~1u) ||
+        first_spectrum > out_spectra || nr_spectra > out_spectra - first_spectrum)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(filterbank_bytes, nr_beams, out_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbq8_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.scales = d_scales;
+    a.out = d_filterbank;
+    a.clip_count = d_clip_count;
+    a.out_spectra = out_spectra;
+    a.first = first_spectrum;
+    a.C = C;
+    a.B = nr_beams;
+    a.T = nr_spectra;
+    a.descending = flags & 1u;
+    a.level = level;
+    return (int)bf_launch_filterbank_q8(a, as_stream(stream));
+}
+
+} // namespace bf_host

@@ -1,4 +1,4 @@
-"""The beamformers' class words under graph replay (clear_class_words in dc_sand_amd/csrc/bf_capi.hip).
+"""The beamformers' class words under graph replay (clear_class_words in dc_sand_amd/csrc/bf_capi_beamform.hip).
 
 Both beamformers choose how they make their coefficients from a per-time-step class word that the terms pre-pass leaves
 in the context: the highest pair class of the table (low- or full-degree fast path, or the slow path, which also marks

@@ -274,7 +274,7 @@ def cmd_bfacc(args):
 def cmd_bfreplay(args):
     """One float call of the matrix-core beamformer per period, three ways: plain launches on a context that has never
     captured; the captured call replayed; plain launches after the capture (from then on every call of the context clears
-    its class words: clear_class_words in bf_capi.hip)."""
+    its class words: clear_class_words in bf_capi_beamform.hip)."""
     sys.path.insert(0, str(ROOT / "tests"))
     from helpers import hip_graph
 
