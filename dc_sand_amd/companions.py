@@ -54,4 +54,13 @@ COMPANIONS = {
         ("dcs_bf_filterbank_q8", c_int,
          [_VP, _VP, c_size_t, c_uint32, c_uint32, _VP, c_float, c_uint32, _VP, c_size_t, c_uint64, c_uint64, _VP, _VP]),
     ]),
+    # the true complex product (tied-array beams) of the matrix-core beamformer: float beams and detected block power
+    "beam_complex": Companion("dcs_beam_complex.h", "bf_beam_complex.cpp", "libdcs_beam_complex.so", [
+        ("dcs_bf_beamform_accumulated_complex", c_int, [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_complex_dt", c_int, [_VP, c_float, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_complex_power", c_int,
+         [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_beamform_accumulated_complex_power_dt", c_int,
+         [_VP, c_float, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, c_size_t, _VP]),
+    ]),
 }

@@ -1,4 +1,4 @@
-// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included six times by bf_beamform_mfma.hip:
+// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included ten times by bf_beamform_mfma.hip:
 // BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights); with
 // BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output), with BF_I8_POWER 1
 // bf_beamform_i8_p_kernel and bf_beamform_i8_wp_kernel (detected block power).  One text, six
@@ -23,7 +23,17 @@
 // Lane m < 4 of a group keeps register m's sum and writes that one dword: beam bw + (lane >> 4) + 4 m of its block of the
 // tensor [c][t/16][b] -- 2 x 64 contiguous bytes per wave and pair of blocks.  The weighted form's factors as in the
 // float kernels.
-// An inclusion defines the switches it wants as 1; the others read as 0, and all three are gone again at the end.
+// COMPLEX (kStaged and kChain; include/dcs_beam_complex.h, DESIGN.md section 5.13): the true complex product sum_a w_a x_a
+// instead of the element-wise one -- bf_beamform_i8_c_kernel, _wc_ (weighted), _cp_ and _wcp_ (detected block power).  A
+// coefficient gives NINE operands per 64 antennas instead of six: the digits of re, of sigma im and of -sigma im (sigma = -1
+// with bf_complex_args.conj: the sign of im is flipped before fixed_word, so the conjugate costs nothing in the loop; the
+// third operand is fixed_word(-sigma im), NOT the negated digits of the second -- a digit can be -128).  Per pair of blocks
+// and 64 antennas 24 MFMAs into the same twelve sums: re_d with all four planes' own samples, +im_d into the im planes with
+// the re samples, -im_d into the re planes with the im samples.  |sum| <= 2 * 256 * 128 * 128 = 2^23, so s2 * 256 + s3 does
+// not fit an int32: the low part is fmaf((float)s2, 256.0f, (float)s3) here -- both conversions exact, one rounding of the
+// same exact integer, the integer form's bits wherever that does not wrap.  A row with a non-finite coefficient in either
+// component is NaN in both planes.  Weights, factors and the detecting epilogue as in the other kernels.
+// An inclusion defines the switches it wants as 1; the others read as 0, and all four are gone again at the end.
 #ifndef BF_I8_WEIGHTED
 #define BF_I8_WEIGHTED 0
 #endif
@@ -33,9 +43,20 @@
 #ifndef BF_I8_POWER
 #define BF_I8_POWER 0
 #endif
+#ifndef BF_I8_COMPLEX
+#define BF_I8_COMPLEX 0
+#endif
 template <int FORM, bool FULL, int NW = 4>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT))))
-#if BF_I8_WEIGHTED && BF_I8_POWER
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT, BF_I8_COMPLEX && BF_I8_WEIGHTED && !FULL))))
+#if BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_POWER
+bf_beamform_i8_wcp_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_complex_args ca)
+#elif BF_I8_COMPLEX && BF_I8_POWER
+bf_beamform_i8_cp_kernel(const bf_bacc_args a, const bf_complex_args ca)
+#elif BF_I8_COMPLEX && BF_I8_WEIGHTED
+bf_beamform_i8_wc_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_complex_args ca)
+#elif BF_I8_COMPLEX
+bf_beamform_i8_c_kernel(const bf_bacc_args a, const bf_complex_args ca)
+#elif BF_I8_WEIGHTED && BF_I8_POWER
 bf_beamform_i8_wp_kernel(const bf_bacc_args a, const bf_weights_args w)
 #elif BF_I8_POWER
 bf_beamform_i8_p_kernel(const bf_bacc_args a)
@@ -49,17 +70,22 @@ bf_beamform_i8_w_kernel(const bf_bacc_args a, const bf_weights_args w)
 bf_beamform_i8_kernel(const bf_bacc_args a)
 #endif
 {
-    constexpr bool WEIGHTED = BF_I8_WEIGHTED, QUANT = BF_I8_QUANT;
+    constexpr bool WEIGHTED = BF_I8_WEIGHTED, QUANT = BF_I8_QUANT, COMPLEX = BF_I8_COMPLEX;
+    constexpr uint32_t NOP = COMPLEX ? 9u : 6u; // coefficient operands per 64 antennas
 #if !BF_I8_WEIGHTED
     const bf_weights_args w{}; // named by the (discarded) weighted branches only
 #endif
 #if !BF_I8_QUANT
     const bf_quant_args qa{};  // named by the (discarded) quantised branches only
 #endif
+#if !BF_I8_COMPLEX
+    const bf_complex_args ca{}; // named by the (discarded) complex branches only
+#endif
     static_assert(NW == 4 || ((NW == 8 || NW == 16) && FORM == kStaged), "8- and 16-wave workgroups exist for the staged form only");
     static_assert(!WEIGHTED || FORM == kStaged || FORM == kChain, "weights exist for the product's forms only");
     static_assert(!QUANT || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the quantiser exists for the product's forms only");
     static_assert(!BF_I8_POWER || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the detector exists for the product's forms only");
+    static_assert(!BF_I8_COMPLEX || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the complex product exists for the product's forms only");
     constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
     extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
     uint32_t bid = BACC_LOGICAL_ID(a);
@@ -122,9 +148,10 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     // of its coefficient registers each and exchange them through LDS behind the staging barrier (the slow class makes
     // everything everywhere: its rolled loop does not split)
     const bool shared_w = STAGED && a.share_off != 0u && tpr > 1u && cls != DCS_CLASS_SLOW;
-    intx4 wre[3], wim[3];
+    intx4 wre[3], wim[3], wng[3]; // (wng: the complex product's -sigma im)
 #pragma unroll
-    for (int d = 0; d < 3; d++) wre[d] = wim[d] = intx4{0, 0, 0, 0};
+    for (int d = 0; d < 3; d++) wre[d] = wim[d] = wng[d] = intx4{0, 0, 0, 0};
+    const uint32_t conj_bit = COMPLEX && ca.conj ? 0x80000000u : 0u; // complex: the sign of im before its digits are taken
     // A coefficient that is not finite (an infinite or NaN delay value: the slow class) has no fixed-point digits; the
     // verifier's sum for that beam and plane is NaN whatever the samples are (NaN * 0 = NaN), and so it is here: the lanes
     // note it, the wave folds the notes into one bit per result row and plane, and the rows are stored as NaN.
@@ -146,8 +173,8 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         };
         // antennas 64 kc + 4 (4 q + z) + lg, z = 0..3, from their terms: one register of each of the six operands
         auto four = [&](auto gen, auto track, uint32_t q, const floatx2 (&k4)[4], const float (&g4)[4], uint32_t (&nr)[3],
-                        uint32_t (&ni)[3]) {
-            uint32_t gr[4], gi[4];
+                        uint32_t (&ni)[3], uint32_t (&nn)[3]) {
+            uint32_t gr[4], gi[4], gn[4];
 #pragma unroll
             for (uint32_t z = 0; z < 4; z++) {
                 float re, im;
@@ -157,15 +184,22 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                     bad_re |= !(fabsf(re) <= 2.0f);
                     bad_im |= !(fabsf(im) <= 2.0f);
                 }
+                if constexpr (COMPLEX) im = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, im) ^ conj_bit);
                 gr[z] = fixed_word(re), gi[z] = fixed_word(im);
+                if constexpr (COMPLEX) gn[z] = fixed_word(-im); // the digits of the negated NUMBER
             }
             planes(gr, nr), planes(gi, ni);
+            if constexpr (COMPLEX) planes(gn, nn);
             if (!FULL) { // antennas beyond nr_stations: zero digits, byte by byte
                 uint32_t mask = 0;
 #pragma unroll
                 for (uint32_t z = 0; z < 4; z++) mask |= 64u * kc + 4u * (4u * q + z) + lg < a.A ? 0xffu << (8u * z) : 0u;
 #pragma unroll
                 for (int d = 0; d < 3; d++) nr[d] &= mask, ni[d] &= mask;
+                if constexpr (COMPLEX) {
+#pragma unroll
+                    for (int d = 0; d < 3; d++) nn[d] &= mask;
+                }
             }
         };
         auto generate = [&](auto gen, auto unrolled) {
@@ -200,15 +234,23 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                     const floatx2 k4[4] = {kp[4 * q], kp[4 * q + 1], kp[4 * q + 2], kp[4 * q + 3]};
                     float g4[4] = {};
                     if constexpr (WEIGHTED) g4[0] = gw[4 * q], g4[1] = gw[4 * q + 1], g4[2] = gw[4 * q + 2], g4[3] = gw[4 * q + 3];
-                    uint32_t nr[3], ni[3];
-                    four(gen, std::false_type{}, q, k4, g4, nr, ni);
+                    uint32_t nr[3], ni[3], nn[3];
+                    four(gen, std::false_type{}, q, k4, g4, nr, ni, nn);
                     if constexpr (CHAIN) { // straight to the LDS image (component q of the chunk's six operands): the 24 registers are never held
-                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * 6u * 64u + lane) * 4u + q;
+                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * NOP * 64u + lane) * 4u + q;
 #pragma unroll
                         for (int d = 0; d < 3; d++) cw[(uint32_t)d * 256u] = beam_live ? nr[d] : 0u, cw[(3u + (uint32_t)d) * 256u] = beam_live ? ni[d] : 0u;
+                        if constexpr (COMPLEX) {
+#pragma unroll
+                            for (int d = 0; d < 3; d++) cw[(6u + (uint32_t)d) * 256u] = beam_live ? nn[d] : 0u;
+                        }
                     } else {
 #pragma unroll
                         for (int d = 0; d < 3; d++) wre[d][q] = (int)nr[d], wim[d][q] = (int)ni[d];
+                        if constexpr (COMPLEX) {
+#pragma unroll
+                            for (int d = 0; d < 3; d++) wng[d][q] = (int)nn[d];
+                        }
                     }
                 }
             } else { // the new register enters at the top while the others, and the loaded terms, move down -- no
@@ -221,17 +263,22 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
 #pragma unroll
                         for (uint32_t z = 0; z < 4; z++) g4[z] = gp[(uint64_t)min(64u * kc + 4u * (4u * q + z) + lg, a.A - 1u) * a.B];
                     }
-                    uint32_t nr[3], ni[3];
-                    four(gen, std::true_type{}, q, k4, g4, nr, ni);
+                    uint32_t nr[3], ni[3], nn[3];
+                    four(gen, std::true_type{}, q, k4, g4, nr, ni, nn);
                     if constexpr (CHAIN) {
-                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * 6u * 64u + lane) * 4u + q;
+                        uint32_t *cw = reinterpret_cast<uint32_t *>(staged) + (kc * NOP * 64u + lane) * 4u + q;
 #pragma unroll
                         for (int d = 0; d < 3; d++) cw[(uint32_t)d * 256u] = beam_live ? nr[d] : 0u, cw[(3u + (uint32_t)d) * 256u] = beam_live ? ni[d] : 0u;
+                        if constexpr (COMPLEX) {
+#pragma unroll
+                            for (int d = 0; d < 3; d++) cw[(6u + (uint32_t)d) * 256u] = beam_live ? nn[d] : 0u;
+                        }
                     } else {
 #pragma unroll
                         for (int d = 0; d < 3; d++) {
                             wre[d] = intx4{wre[d][1], wre[d][2], wre[d][3], (int)nr[d]};
                             wim[d] = intx4{wim[d][1], wim[d][2], wim[d][3], (int)ni[d]};
+                            if constexpr (COMPLEX) wng[d] = intx4{wng[d][1], wng[d][2], wng[d][3], (int)nn[d]};
                         }
                     }
 #pragma unroll
@@ -240,7 +287,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
             }
             if (!CHAIN && !beam_live) { // beams beyond nr_beams: zero coefficients (their results are not stored either)
 #pragma unroll
-                for (int d = 0; d < 3; d++) wre[d] = wim[d] = intx4{0, 0, 0, 0};
+                for (int d = 0; d < 3; d++) wre[d] = wim[d] = wng[d] = intx4{0, 0, 0, 0};
             }
         };
         if (cls == DCS_CLASS_SLOW) {
@@ -321,14 +368,29 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     // integers (s2 * 256 + s3 < 2^29: exact), converted (one rounding, far below the result's last place), and the
     // high digit enters with one fma.
     const intx4 zero = {0, 0, 0, 0};
+    // the low part of a sum: s2 * 256 + s3 as ONE fp32 rounding of the exact integer -- in int32 where that cannot wrap, with
+    // an fma of the two (exactly converted) sums in the complex product, whose |s| reaches 2^23
+    auto low_part = [](int s2, int s3) { return COMPLEX ? fmaf((float)s2, 256.0f, (float)s3) : (float)(s2 * 256 + s3); };
     auto contract = [&](const intx4 (&x)[4], floatx4 (&f)[4]) {
 #pragma unroll
         for (int v = 0; v < 4; v++) {
+            if constexpr (COMPLEX) { // plane v's own samples with re, then the other component's with +im (im planes) / -im (re planes)
+                const intx4 (&wo)[3] = (v & 1) ? wim : wng;
+                intx4 s3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wre[2], x[v], zero, 0, 0, 0);
+                intx4 s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wre[1], x[v], zero, 0, 0, 0);
+                intx4 s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wre[0], x[v], zero, 0, 0, 0);
+                s3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wo[2], x[v ^ 1], s3, 0, 0, 0);
+                s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wo[1], x[v ^ 1], s2, 0, 0, 0);
+                s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(wo[0], x[v ^ 1], s1, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; r++) f[v][r] = fmaf((float)s1[r], 65536.0f, low_part(s2[r], s3[r]));
+                continue;
+            }
             const intx4 s3 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[2] : wre[2], x[v], zero, 0, 0, 0);
             const intx4 s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[1] : wre[1], x[v], zero, 0, 0, 0);
             const intx4 s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8((v & 1) ? wim[0] : wre[0], x[v], zero, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < 4; r++) f[v][r] = fmaf((float)s1[r], 65536.0f, (float)(s2[r] * 256 + s3[r]));
+            for (int r = 0; r < 4; r++) f[v][r] = fmaf((float)s1[r], 65536.0f, low_part(s2[r], s3[r]));
         }
     };
     uint32_t nan_re = 0, nan_im = 0;     // wave-uniform: rows whose re / im plane is NaN (set once the coefficients are made)
@@ -523,15 +585,20 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         const uint64_t br = __builtin_amdgcn_ballot_w64(bad_re), bi = __builtin_amdgcn_ballot_w64(bad_im);
         nan_re = (uint32_t)((br | (br >> 16) | (br >> 32) | (br >> 48)) & 0xffffu);
         nan_im = (uint32_t)((bi | (bi >> 16) | (bi >> 32) | (bi >> 48)) & 0xffffu);
+        if constexpr (COMPLEX) nan_re = nan_im = nan_re | nan_im; // both planes depend on both components
     }
     if constexpr (STAGED) {
-        uint32_t *wx = reinterpret_cast<uint32_t *>(staged + a.share_off) + bt * (4u * 6u * 64u) + lane; // [tile][q][plane][lane]
+        uint32_t *wx = reinterpret_cast<uint32_t *>(staged + a.share_off) + bt * (4u * NOP * 64u) + lane; // [tile][q][plane][lane]
         if (shared_w && bw < a.B) {
 #pragma unroll
             for (uint32_t q = 0; q < 4; q++)
                 if ((q & (tpr - 1u)) == slot) {
 #pragma unroll
-                    for (int d = 0; d < 3; d++) wx[(q * 6u + d) * 64u] = (uint32_t)wre[d][q], wx[(q * 6u + 3u + d) * 64u] = (uint32_t)wim[d][q];
+                    for (int d = 0; d < 3; d++) wx[(q * NOP + d) * 64u] = (uint32_t)wre[d][q], wx[(q * NOP + 3u + d) * 64u] = (uint32_t)wim[d][q];
+                    if constexpr (COMPLEX) {
+#pragma unroll
+                        for (int d = 0; d < 3; d++) wx[(q * NOP + 6u + d) * 64u] = (uint32_t)wng[d][q];
+                    }
                 }
         }
         __syncthreads(); // hipcc drains the LDS-DMA (vmcnt(0)) in front of it
@@ -541,14 +608,18 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
             for (uint32_t q = 0; q < 4; q++)
                 if ((q & (tpr - 1u)) != slot) {
 #pragma unroll
-                    for (int d = 0; d < 3; d++) wre[d][q] = (int)wx[(q * 6u + d) * 64u], wim[d][q] = (int)wx[(q * 6u + 3u + d) * 64u];
+                    for (int d = 0; d < 3; d++) wre[d][q] = (int)wx[(q * NOP + d) * 64u], wim[d][q] = (int)wx[(q * NOP + 3u + d) * 64u];
+                    if constexpr (COMPLEX) {
+#pragma unroll
+                        for (int d = 0; d < 3; d++) wng[d][q] = (int)wx[(q * NOP + 6u + d) * 64u];
+                    }
                 }
         }
     } else if constexpr (CHAIN) {
-        // ---- the coefficients of this wave's chunk to LDS: [chunk][operand: re d1, d2, d3, im d1, d2, d3][lane] x 16 bytes
+        // ---- the coefficients of this wave's chunk to LDS: [chunk][operand: re d1, d2, d3, im d1, d2, d3 (complex: and -im d1, d2, d3)][lane] x 16 bytes
         intx4 *coef = reinterpret_cast<intx4 *>(staged);
-        uint32_t *nanw = reinterpret_cast<uint32_t *>(staged + 4u * 6u * 64u * 16u); // [chunk][re, im]
-        // (make_coefficients has written this wave's chunk: operand o of chunk k at coef[(k * 6 + o) * 64 + lane])
+        uint32_t *nanw = reinterpret_cast<uint32_t *>(staged + 4u * NOP * 64u * 16u); // [chunk][re, im]
+        // (make_coefficients has written this wave's chunk: operand o of chunk k at coef[(k * NOP + o) * 64 + lane])
         if (lane == 0u) nanw[2u * wave] = has_chunk ? nan_re : 0u, nanw[2u * wave + 1u] = has_chunk ? nan_im : 0u;
         float *facw = reinterpret_cast<float *>(nanw + 8); // weighted: [16] = RN(s_b * inv) of beam bw + i
         if constexpr (WEIGHTED) {
@@ -561,6 +632,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         if (idle) return;
         nan_re = nanw[0] | nanw[2] | nanw[4] | nanw[6]; // a non-finite coefficient in ANY chunk poisons the row
         nan_im = nanw[1] | nanw[3] | nanw[5] | nanw[7];
+        if constexpr (COMPLEX) nan_re = nan_im = nan_re | nan_im;
         const uint32_t n_chunks = (a.A + 63u) / 64u;
         auto run_chain = [&](auto whole) {
             // a step = (pair of this wave's blocks, antenna chunk), pair-major; two sample buffers in turn: the samples of step
@@ -582,6 +654,24 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
 #pragma unroll
                         for (int d = 0; d < 3; d++) acc[v][d] = zero;
                 }
+                if constexpr (COMPLEX) { // one operand from LDS at a time: re_d with every plane's own samples, +im_d into the im
+                                         // planes with the re samples, -im_d into the re planes with the im samples
+#pragma unroll
+                    for (int d = 0; d < 3; d++) {
+                        const intx4 w = coef[(chunk * NOP + (uint32_t)d) * 64u + lane];
+#pragma unroll
+                        for (int v = 0; v < 4; v++) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v], acc[v][d], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int half = 1; half >= 0; half--) { // operands 3 - 5 (+im: v = 1, 3), then 6 - 8 (-im: v = 0, 2)
+#pragma unroll
+                        for (int d = 0; d < 3; d++) {
+                            const intx4 w = coef[(chunk * NOP + (half ? 3u : 6u) + (uint32_t)d) * 64u + lane];
+#pragma unroll
+                            for (int v = half; v < 4; v += 2) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v ^ 1], acc[v][d], 0, 0, 0);
+                        }
+                    }
+                } else
 #pragma unroll
                 for (int half = 0; half < 2; half++) { // re planes (v = 0, 2), then im planes (v = 1, 3)
 #pragma unroll
@@ -603,7 +693,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                             }
                             floatx4 o;
 #pragma unroll
-                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * sc;
+                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, low_part(acc[v][1][r], acc[v][2][r])) * sc;
                             if (nan_re | nan_im) poison(r, o);
                             const float P = power_block_sum(o);
                             mine = m == (uint32_t)r ? P : mine;
@@ -634,7 +724,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                             }
                             floatx4 o;
 #pragma unroll
-                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * sc;
+                            for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, low_part(acc[v][1][r], acc[v][2][r])) * sc;
                             if (nan_re | nan_im) poison(r, o);
                             pk[r] = q8_pack(o, k, qa.clips != nullptr, pair_live && (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B), r, n_clip);
                             __builtin_amdgcn_sched_barrier(0);
@@ -671,7 +761,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                         }
                         floatx4 o;
 #pragma unroll
-                        for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, (float)(acc[v][1][r] * 256 + acc[v][2][r])) * sc;
+                        for (int v = 0; v < 4; v++) o[v] = fmaf((float)acc[v][0][r], 65536.0f, low_part(acc[v][1][r], acc[v][2][r])) * sc;
                         if (nan_re | nan_im) poison(r, o);
                         if (decltype(whole)::value || bb + 4u * (uint32_t)r < a.B) store(out_of(blk, r), o);
                         __builtin_amdgcn_sched_barrier(0);
@@ -709,4 +799,5 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
 #undef BF_I8_WEIGHTED
 #undef BF_I8_QUANT
 #undef BF_I8_POWER
+#undef BF_I8_COMPLEX
 

@@ -294,9 +294,12 @@ constexpr int kChainWaves = 4;
 // quant: the quantised kChain kernels take 3 -- their epilogue (four packed results held for the quad transpose, the gains, the
 // clip counts) wants 144 registers and spills 16 of them at 128, and scratch is not an option (the first launch of a
 // process would pay for it); kChain measured the same at 3 waves as at 4
-constexpr int i8_waves_per_eu(int form, bool full, bool quant = false)
+// wide: the weighted complex product's kernels with antenna masks (include/dcs_beam_complex.h; nine coefficient operands, the
+// weights' loads and the masks together) take 3 as well, kStaged too: at 128 registers kStaged spilled 2 and kChain 6
+constexpr int i8_waves_per_eu(int form, bool full, bool quant = false, bool wide = false)
 {
-    return form == kSplit ? (full ? 3 : 2) : (form == kChain ? kChainWaves - (quant ? 1 : 0) : (full || form == kStaged ? 4 : 3));
+    return form == kSplit ? (full ? 3 : 2)
+                          : (form == kChain ? kChainWaves - (quant || wide ? 1 : 0) : (wide ? 3 : (full || form == kStaged ? 4 : 3)));
 }
 
 // ---- the quantised epilogue (include/dcs_beam_quant.h): what bf_beamform_i8_q_kernel and
@@ -389,6 +392,19 @@ __device__ __forceinline__ float power_block_sum(const floatx4 o)
 #define BF_I8_POWER 1
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
+// the true complex product (include/dcs_beam_complex.h): float and detected block power out, unweighted and weighted
+#define BF_I8_COMPLEX 1
+#include "bf_beamform_i8_kernel.inc"
+#define BF_I8_COMPLEX 1
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
+#define BF_I8_COMPLEX 1
+#define BF_I8_POWER 1
+#include "bf_beamform_i8_kernel.inc"
+#define BF_I8_COMPLEX 1
+#define BF_I8_POWER 1
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
 
 // Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
 // beam), beam fastest, adding its n blocks in order -- one rounded add each, no atomics, the same sum whatever the launch
@@ -426,13 +442,24 @@ hipError_t bf_warm_module_mfma()
 }
 
 namespace {
-// One launch for the six inclusions of bf_beamform_i8_kernel.inc.  w, q, power: nullptr / false = not asked for; those
+// One launch for the ten inclusions of bf_beamform_i8_kernel.inc.  w, q, power, cx: nullptr / false = not asked for; those
 // kernels exist for the product's forms (kStaged, kChain; four waves) only, every other instantiation is the plain kernel's.
 template <int FORM, bool FULL, int NW>
 void launch_i8(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a, const bf_weights_args *w,
-               const bf_quant_args *q, bool power)
+               const bf_quant_args *q, bool power, const bf_complex_args *cx)
 {
     if constexpr (NW == 4 && (FORM == kStaged || FORM == kChain)) {
+        if (cx) { // (never with q: the launcher has refused that)
+            if (power && w)
+                hipLaunchKernelGGL((bf_beamform_i8_wcp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *cx);
+            else if (power)
+                hipLaunchKernelGGL((bf_beamform_i8_cp_kernel<FORM, FULL>), grid, block, lds, stream, a, *cx);
+            else if (w)
+                hipLaunchKernelGGL((bf_beamform_i8_wc_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *cx);
+            else
+                hipLaunchKernelGGL((bf_beamform_i8_c_kernel<FORM, FULL>), grid, block, lds, stream, a, *cx);
+            return;
+        }
         if (power && w)
             hipLaunchKernelGGL((bf_beamform_i8_wp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w);
         else if (power)
@@ -450,24 +477,24 @@ void launch_i8(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_b
 
 template <int FORM, int NW = 4>
 void launch_i8_form(bool full, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a,
-                    const bf_weights_args *w, const bf_quant_args *q, bool power)
+                    const bf_weights_args *w, const bf_quant_args *q, bool power, const bf_complex_args *cx)
 {
     if (full)
-        launch_i8<FORM, true, NW>(grid, block, lds, stream, a, w, q, power);
+        launch_i8<FORM, true, NW>(grid, block, lds, stream, a, w, q, power, cx);
     else
-        launch_i8<FORM, false, NW>(grid, block, lds, stream, a, w, q, power);
+        launch_i8<FORM, false, NW>(grid, block, lds, stream, a, w, q, power, cx);
 }
 } // namespace
 
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_args *w, const bf_quant_args *q, bool power,
-                                  hipStream_t stream)
+                                  const bf_complex_args *cx, hipStream_t stream)
 {
     bf_bacc_args a = a_in;
     if (a.A == 0 || a.B == 0 || a.C == 0 || a.nT16 == 0) return hipSuccess;
     if (a.A > 256u) return hipErrorInvalidValue; // not built
     const bool chain = a.fp32_chain != 0u;
-    if ((w || q || power) && chain) return hipErrorInvalidValue;
-    if (q && power) return hipErrorInvalidValue;
+    if ((w || q || power || cx) && chain) return hipErrorInvalidValue;
+    if (q && (power || cx)) return hipErrorInvalidValue;
     // beam tiles per workgroup: as many as the beams need; the fp32 form keeps its coefficient planes in LDS and
     // takes as many as still admit 6 workgroups per CU (26 KiB each), one tile whatever it takes beyond
     // more than 64 antennas, int8 form: one beam tile per workgroup; kChain (the product's form) or, probes build only, kSplit
@@ -521,7 +548,7 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_arg
             hipLaunchKernelGGL(bf_beamform_acc_kernel<1>, grid, block, lds, stream, a);
         return hipGetLastError();
     }
-    const bool plain = !w && !q && !power;
+    const bool plain = !w && !q && !power && !cx;
     if (!plain && (nw != 4u || (!staged_form && (!wide || split)))) return hipErrorInvalidValue; // the product's forms only
     if (q && a.tiles_per_wg / tpr > 126u) return hipErrorInvalidValue; // a lane counts its clips in bytes, 4 per pair of blocks
     const bool full = a.A % 64u == 0u; // (kStaged, kDirect: 64 antennas exactly)
@@ -529,28 +556,29 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_arg
         size_t stage_bytes = ((size_t)a.tiles_per_wg * a.A * 32u + 1023u) / 1024u * 1024u;
         if (tpr > 1u && !BACC_KNOB(a, no_share)) { // waves that own the same tile share the making of its coefficients
             a.share_off = (uint32_t)stage_bytes;
-            stage_bytes += (size_t)nbt * 4u * 6u * 64u * sizeof(uint32_t);
+            stage_bytes += (size_t)nbt * 4u * (cx ? 9u : 6u) * 64u * sizeof(uint32_t); // the complex product: nine operands
         }
 #ifdef DCS_PROBES
         if (plain && a.wg_per_cu >= 1u && a.wg_per_cu <= 5u && stage_bytes < 160u * 1024u / a.wg_per_cu) // residency cap: unused LDS
             stage_bytes = (160u * 1024u / a.wg_per_cu) & ~1023u;
         if (nw == 8u)
-            launch_i8_form<kStaged, 8>(full, grid, block, stage_bytes, stream, a, w, q, power);
+            launch_i8_form<kStaged, 8>(full, grid, block, stage_bytes, stream, a, w, q, power, cx);
         else if (nw == 16u)
-            launch_i8_form<kStaged, 16>(full, grid, block, stage_bytes, stream, a, w, q, power);
+            launch_i8_form<kStaged, 16>(full, grid, block, stage_bytes, stream, a, w, q, power, cx);
         else
 #endif
-        launch_i8_form<kStaged>(full, grid, block, stage_bytes, stream, a, w, q, power);
+        launch_i8_form<kStaged>(full, grid, block, stage_bytes, stream, a, w, q, power, cx);
 #ifdef DCS_PROBES
     } else if (a.A <= 64u) { // kDirect: the probes build's A/B form only
-        launch_i8_form<kDirect>(full, grid, block, 0, stream, a, w, q, power);
+        launch_i8_form<kDirect>(full, grid, block, 0, stream, a, w, q, power, cx);
     } else if (split) { // 2 pairs x 4 registers x 4 chunks x 64 lanes x 16 bytes of partial sums
-        launch_i8_form<kSplit>(full, grid, block, 2u * 4u * 4u * 64u * 16u, stream, a, w, q, power);
+        launch_i8_form<kSplit>(full, grid, block, 2u * 4u * 4u * 64u * 16u, stream, a, w, q, power, cx);
 #endif
     } else { // kChain: 4 chunks x 6 operands x 64 lanes x 16 bytes of coefficients + the chunks' NaN-row words, then the 16
              // beams' scale factors (weighted) and behind them their 16 gains (quantised, weighted or not)
-        const size_t coef_bytes = 4u * 6u * 64u * 16u + 8u * sizeof(uint32_t) + (q ? 32u : (w ? 16u : 0u)) * sizeof(float);
-        launch_i8_form<kChain>(full, grid, block, coef_bytes, stream, a, w, q, power);
+             // (the complex product: 9 operands, 36 KiB)
+        const size_t coef_bytes = 4u * (cx ? 9u : 6u) * 64u * 16u + 8u * sizeof(uint32_t) + (q ? 32u : (w ? 16u : 0u)) * sizeof(float);
+        launch_i8_form<kChain>(full, grid, block, coef_bytes, stream, a, w, q, power, cx);
     }
     return hipGetLastError();
 }

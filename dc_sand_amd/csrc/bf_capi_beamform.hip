@@ -1,5 +1,5 @@
-// bf_capi_beamform.hip -- both beamformers of include/dcs_beamformer.h, and their weighted, quantised and detecting
-// calls (bf_ctx_ext.h): the terms table and its class words, the terms pre-pass, the launches.  Host code only; the
+// bf_capi_beamform.hip -- both beamformers of include/dcs_beamformer.h, and their weighted, quantised, detecting and
+// complex-product calls (bf_ctx_ext.h): the terms table and its class words, the terms pre-pass, the launches.  Host code only; the
 // kernels are in bf_kernels.hip and bf_beamform_mfma.hip.
 
 #include <cstdlib>
@@ -184,11 +184,13 @@ int beamform_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, const in
 namespace {
 // What a call of the matrix-core beamformer writes to d_beams, and what it applies on the way.  kFloat: the beams, (re, im)
 // fp32 per sample; kInt8: the same quantised (include/dcs_beam_quant.h), a quarter the size; kBlockPower: one float per beam
-// and 16-sample block (include/dcs_beam_power.h), 4-byte aligned.
+// and 16-sample block (include/dcs_beam_power.h), 4-byte aligned.  complex: the true complex product instead of the
+// element-wise one (include/dcs_beam_complex.h); kFloat and kBlockPower only.
 struct bacc_output {
     enum { kFloat, kInt8, kBlockPower } kind;
     const float *d_weights; // nullptr (unweighted) or [B][A] fp32 weights in device memory (include/dcs_beam_weights.h)
     bf_quant_args quant;    // kInt8 only: the quantiser's gains and counters
+    const bf_complex_args *complex = nullptr;
     size_t block_bytes() const // per beam and 16-sample block
     {
         return kind == kBlockPower ? sizeof(float) : 32u * (kind == kInt8 ? sizeof(int8_t) : sizeof(float));
@@ -209,7 +211,7 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
     if (beams_bytes < (size_t)B * C * (nt / 16u) * out.block_bytes()) return DCS_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_beams) & out.align_mask()))
         return DCS_ERR_INVALID_ARGUMENT;
-    if ((out.d_weights || out.kind != bacc_output::kFloat) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights, no quantiser, no detector
+    if ((out.d_weights || out.kind != bacc_output::kFloat || out.complex) && (c->tune.math_mode & 8)) return DCS_ERR_UNSUPPORTED; // the fp32 fma-chain form has no weights, no quantiser, no detector, no complex product
     if (nt == 0) return DCS_OK;
     {
         const int st_range = check_dt_range(c, src, 1); // the one coefficient time, before anything is allocated
@@ -256,7 +258,7 @@ int beamform_acc_impl(dcs_bf_context *c, const dt_source &src, uint32_t nt, cons
 #endif
     const bf_weights_args wa = {out.d_weights, c->d_wnorm, c->d_wscale};
     return (int)bf_launch_beamform_acc(a, out.d_weights ? &wa : nullptr, out.kind == bacc_output::kInt8 ? &out.quant : nullptr,
-                                       out.kind == bacc_output::kBlockPower, s);
+                                       out.kind == bacc_output::kBlockPower, out.complex, s);
 }
 
 } // namespace
@@ -301,6 +303,27 @@ int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, ui
     if (!c || !d_block_power || (d_weights && !weights_ok(d_weights))) return DCS_ERR_INVALID_ARGUMENT;
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes,
                              stream, {bacc_output::kBlockPower, d_weights, {}});
+}
+
+// include/dcs_beam_complex.h, reached the same way: the float call and the detecting call with the true complex product
+int beamform_accumulated_complex_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                      size_t antenna_bytes, const float *d_weights, uint32_t flags, float *d_beams, size_t beams_bytes,
+                                      void *stream)
+{
+    if (!c || !d_beams || (d_weights && !weights_ok(d_weights)) || (flags & ~1u)) return DCS_ERR_INVALID_ARGUMENT;
+    const bf_complex_args cx = {flags & 1u};
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream,
+                             {bacc_output::kFloat, d_weights, {}, &cx});
+}
+
+int beamform_accumulated_complex_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                            const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                            float *d_block_power, size_t power_bytes, void *stream)
+{
+    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights)) || (flags & ~1u)) return DCS_ERR_INVALID_ARGUMENT;
+    const bf_complex_args cx = {flags & 1u};
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes, stream,
+                             {bacc_output::kBlockPower, d_weights, {}, &cx});
 }
 
 } // namespace bf_host

@@ -1,10 +1,10 @@
 // bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
-// (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h) and libdcs_filterbank.so
-// (include/dcs_filterbank.h).  All are built from this tree
+// (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
+// (include/dcs_filterbank.h) and libdcs_beam_complex.so (include/dcs_beam_complex.h).  All are built from this tree
 // together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
-// implementation of the weighted, the quantised and the detecting beamformer calls, of the incoherent beam and of the
-// filterbank calls; a companion checks the arguments it can check
+// implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
+// beam and of the filterbank calls; a companion checks the arguments it can check
 // without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
@@ -18,7 +18,9 @@
 // integrate_incoherent_power appended.  4 is skipped for good: tests/test_host_abi_beam_power.py hands the power companion a
 // zeroed table whose version word is 4 and expects DCS_ERR_UNSUPPORTED -- at version 4 it would call a null pointer.
 // 6: spectra_sums, filterbank_scales, filterbank_q8 appended (the tests hand foreign versions 1 to 5 only).
-#define BF_CTX_EXT_VERSION 6u
+// 7: beamform_accumulated_complex, beamform_accumulated_complex_power appended (tests/test_host_abi_beam_complex.py hands its
+// companion the foreign versions 1, 3, 5 and 6).
+#define BF_CTX_EXT_VERSION 7u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -60,6 +62,14 @@ struct bf_ctx_ext_ops {
     int (*filterbank_q8)(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
                          const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
                          uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream);
+    // the true complex product sum_a w_a x_a (include/dcs_beam_complex.h): float beams, and detected block power; d_weights:
+    // nullptr = unweighted; flags: bit 0 = DCS_BF_COMPLEX_CONJ
+    int (*beamform_accumulated_complex)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                        const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                        float *d_beams, size_t beams_bytes, void *stream);
+    int (*beamform_accumulated_complex_power)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                              const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                              float *d_block_power, size_t power_bytes, void *stream);
 };
 
 // the first member of struct dcs_bf_context

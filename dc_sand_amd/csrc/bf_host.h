@@ -131,7 +131,8 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 // bf_capi_beamform.hip: the terms table and class words (the generator's rows form writes the same table)
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
-// the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip
+// the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, and the
+// complex product's two in bf_capi_beamform.hip again
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -158,6 +159,12 @@ int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_
 int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
                        const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
                        uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream);
+int beamform_accumulated_complex_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
+                                      size_t antenna_bytes, const float *d_weights, uint32_t flags, float *d_beams, size_t beams_bytes,
+                                      void *stream);
+int beamform_accumulated_complex_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                            const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                            float *d_block_power, size_t power_bytes, void *stream);
 
 } // namespace bf_host
 

@@ -197,12 +197,18 @@ struct bf_quant_args {
     const float *gains;        // [B]: the beams' quantisation gains (device)
     unsigned long long *clips; // [B]: clipped components per beam, added to; or nullptr: no counting
 };
+// The true complex product sum_a w_a x_a instead of the element-wise one (include/dcs_beam_complex.h; DESIGN.md section
+// 5.13): a kernel argument of its own, so that bf_bacc_args -- and with it every other kernel -- stays as it is
+struct bf_complex_args {
+    uint32_t conj; // non-zero: sum_a conj(w_a) x_a
+};
 // w: nullptr, or the weights as for bf_launch_beamform; q: nullptr, or the quantiser; power: detected beam power
 // (include/dcs_beam_power.h): a.beams is then the block power tensor [C][nT16][B], one float per beam
-// and 16-sample block, written by the detecting kernels' epilogue from the floats the float kernels would have stored.
-// All three exist for the int8 form's kStaged and kChain only (a.fp32_chain must be 0), and q excludes power.
+// and 16-sample block, written by the detecting kernels' epilogue from the floats the float kernels would have stored;
+// cx: nullptr, or the complex product.  All four exist for the int8 form's kStaged and kChain only (a.fp32_chain must be
+// 0), and q excludes power and cx.
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args *q, bool power,
-                                  hipStream_t stream);
+                                  const bf_complex_args *cx, hipStream_t stream);
 // Block powers [C][nr_blocks][B] summed n at a time, in order, into spectra [nr_blocks / n][C][B]
 struct bf_pint_args {
     const float *block_power;

@@ -305,6 +305,27 @@ class SteeringCoefficientGenerator:
                                               _s(stream)),
               "dcs_bf_integrate_block_power")
 
+    # -- the true complex product, tied-array beams (include/dcs_beam_complex.h, companion library libdcs_beam_complex.so):
+    #    sum_a w_a x_a, or with ``conjugate`` sum_a conj(w_a) x_a, instead of the element-wise product; tensors as
+    #    :meth:`beamform_accumulated` and :meth:`beamform_accumulated_power`
+    def beamform_accumulated_complex(self, d_antenna, antenna_bytes: int, d_beams, beams_bytes: int, nt: int,
+                                     t_coeff: int | None = None, dt_coeff: float | None = None, d_weights=None,
+                                     conjugate: bool = False, stream=None) -> None:
+        """:meth:`beamform_accumulated` (with ``d_weights``: :meth:`beamform_accumulated_weighted`) with the complex
+        product: ``re = sum(w_re x_re - s w_im x_im)``, ``im = sum(w_re x_im + s w_im x_re)``, ``s = -1`` with ``conjugate``."""
+        fn, when, where = _coeff_time_entry("beam_complex", "dcs_bf_beamform_accumulated_complex", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), 1 if conjugate else 0,
+                 _p(d_beams), int(beams_bytes), _s(stream)), where)
+
+    def beamform_accumulated_complex_power(self, d_antenna, antenna_bytes: int, d_block_power, power_bytes: int, nt: int,
+                                           t_coeff: int | None = None, dt_coeff: float | None = None, d_weights=None,
+                                           conjugate: bool = False, stream=None) -> None:
+        """:meth:`beamform_accumulated_complex` whose epilogue detects, as :meth:`beamform_accumulated_power` does: one float
+        per (channel, block, beam) (:func:`block_power_bytes`), which :meth:`integrate_block_power` and the filterbank calls take."""
+        fn, when, where = _coeff_time_entry("beam_complex", "dcs_bf_beamform_accumulated_complex_power", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), 1 if conjugate else 0,
+                 _p(d_block_power), int(power_bytes), _s(stream)), where)
+
     # -- the incoherent beam (include/dcs_incoherent_beam.h, companion library libdcs_incoherent_beam.so): d_block_power is a
     #    device uint32 [C][nt / 16] array, d_spectra a device float [nr_blocks / blocks_per_spectrum][C] array
     def incoherent_block_power(self, d_antenna, antenna_bytes: int, d_block_power, power_bytes: int, nt: int, d_weights=None,

@@ -23,6 +23,9 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py bfpower [--rounds 5] [--shape AxBxCxNT --variant float|power|power+int]
         detected beam power: the float call (twice: its own spread) against the detecting call and the detecting call plus
         the integration, alternating, in one process                              -> profiles/r06_beam_power.md
+    python tools/measure.py bfcomplex [--rounds 5] [--shape AxBxCxNT]
+        the complex product: the float call (twice: its own spread), the complex float call plain and conjugated, the
+        detecting call and the complex detecting call, alternating, in one process -> profiles/r10_beam_complex.md
     python tools/measure.py incoh [--rounds 5] [--trace]
         the incoherent beam against the read probe (dcs_probe_reduce) over the same bytes and against the detecting call
         at 16 and 256 beams, alternating, in one process; --trace: a few launches of each kernel for
@@ -506,6 +509,52 @@ def cmd_bfpower(args):
         for d in (d_ant, d_beams, d_p, d_s):
             d.free()
     print(json.dumps({"bfpower": rows}), flush=True)
+
+
+def cmd_bfcomplex(args):
+    """The complex product (include/dcs_beam_complex.h) beside the element-wise calls of the same shape: per shape the float
+    call (twice: its own spread), the complex float call plain and conjugated, the detecting call and the complex detecting
+    call, timed in turn ``--rounds`` times in the same process on the same noise-like samples.  The bytes are the same in
+    both forms; what differs is 24 matrix instructions per pair of blocks and 64 antennas instead of 12."""
+    from dc_sand_amd.generator import block_power_bytes
+
+    shapes = [(64, 16, 32768, 256), (64, 256, 4096, 256), (256, 64, 4096, 256), (256, 64, 1024, 256)]
+    if args.shape:
+        shapes = [tuple(int(v) for v in args.shape.split("x"))]
+    rows = []
+    for A, B, C, nt in shapes:
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        ab, fb, pb = A * C * nt * 2, B * C * nt * 8, block_power_bytes(bp, nt)
+        d_ant, d_beams, d_p = device.mem_alloc(ab), device.mem_alloc(fb), device.mem_alloc(pb)
+        _noise(d_ant, ab)
+        calls = [("float", lambda: g.beamform_accumulated(d_ant, ab, d_beams, fb, nt, t_coeff=1)),
+                 ("float_again", lambda: g.beamform_accumulated(d_ant, ab, d_beams, fb, nt, t_coeff=1)),
+                 ("complex", lambda: g.beamform_accumulated_complex(d_ant, ab, d_beams, fb, nt, t_coeff=1)),
+                 ("complex_conj", lambda: g.beamform_accumulated_complex(d_ant, ab, d_beams, fb, nt, t_coeff=1, conjugate=True)),
+                 ("power", lambda: g.beamform_accumulated_power(d_ant, ab, d_p, pb, nt, t_coeff=1)),
+                 ("complex_power", lambda: g.beamform_accumulated_complex_power(d_ant, ab, d_p, pb, nt, t_coeff=1, conjugate=True))]
+        for _, fn in calls:
+            fn()
+        t = {name: [] for name, _ in calls}
+        for _ in range(args.rounds):
+            for name, fn in calls:
+                t[name].append(per_launch_ms(fn))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        spread = max(max(t["float"] + t["float_again"]) / min(t["float"] + t["float_again"]) - 1.0, abs(med["float_again"] / med["float"] - 1.0))
+        row = {"shape": f"{A}x{B}x{C}x{nt}", "form": "staged" if A <= 64 else "kChain",
+               "float_us": round(med["float"] * 1e3, 1), "float_again_us": round(med["float_again"] * 1e3, 1), "float_spread": round(spread, 4),
+               "complex_us": round(med["complex"] * 1e3, 1), "complex_ratio": round(med["complex"] / med["float"], 4),
+               "complex_conj_us": round(med["complex_conj"] * 1e3, 1), "complex_conj_ratio": round(med["complex_conj"] / med["float"], 4),
+               "power_us": round(med["power"] * 1e3, 1), "complex_power_us": round(med["complex_power"] * 1e3, 1),
+               "complex_power_ratio": round(med["complex_power"] / med["power"], 4)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        for d in (d_ant, d_beams, d_p):
+            d.free()
+    print(json.dumps({"bfcomplex": rows}), flush=True)
 
 
 def cmd_incoh(args):
@@ -1007,6 +1056,9 @@ def main():
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape, a few launches of one call (counter passes)")
     p.add_argument("--variant", default="power", choices=["float", "power", "power+int"],
                    help="with --shape: float call, detecting call, detecting call + integration")
+    p = sub.add_parser("bfcomplex")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the element-wise and the complex timings per shape")
+    p.add_argument("--shape", default="", help="AxBxCxNT: one shape only")
     p = sub.add_parser("incoh")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the new call and the read probe per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
@@ -1054,7 +1106,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
