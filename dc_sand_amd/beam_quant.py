@@ -1,7 +1,8 @@
 """Quantised int8 beam output (``include/dcs_beam_quant.h``): the host side of a deployed beamformer's per-beam
 quantisation gain and its clip counter.  :class:`BeamQuantGains` holds the ``[nr_beams]`` gains (all ones at first), their
 device copy and a device array of ``[nr_beams]`` 64-bit clip counters, which
-:meth:`dc_sand_amd.generator.SteeringCoefficientGenerator.beamform_accumulated_q8` reads and adds to when its work runs.
+:meth:`dc_sand_amd.generator.SteeringCoefficientGenerator.beamform_accumulated_q8` (and, for the complex product,
+``beamform_accumulated_complex_q8``: ``include/dcs_beam_complex_quant.h``) reads and adds to when its work runs.
 """
 from __future__ import annotations
 

@@ -63,4 +63,11 @@ COMPANIONS = {
         ("dcs_bf_beamform_accumulated_complex_power_dt", c_int,
          [_VP, c_float, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, c_size_t, _VP]),
     ]),
+    # the same product with the int8 output of beam_quant: 8-bit complex voltage beams out of the kernel's epilogue
+    "beam_complex_quant": Companion("dcs_beam_complex_quant.h", "bf_beam_complex_quant.cpp", "libdcs_beam_complex_quant.so", [
+        ("dcs_bf_beamform_accumulated_complex_q8", c_int,
+         [_VP, c_uint64, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, _VP, c_size_t, _VP, _VP]),
+        ("dcs_bf_beamform_accumulated_complex_q8_dt", c_int,
+         [_VP, c_float, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, _VP, c_size_t, _VP, _VP]),
+    ]),
 }

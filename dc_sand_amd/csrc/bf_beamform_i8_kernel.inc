@@ -1,7 +1,7 @@
-// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included ten times by bf_beamform_mfma.hip:
+// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included twelve times by bf_beamform_mfma.hip:
 // BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights); with
 // BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output), with BF_I8_POWER 1
-// bf_beamform_i8_p_kernel and bf_beamform_i8_wp_kernel (detected block power).  One text, six
+// bf_beamform_i8_p_kernel and bf_beamform_i8_wp_kernel (detected block power).  One text, twelve
 // kernels: a WEIGHTED template parameter would rename the unweighted kernels' symbols, and a body shared through an inline
 // function changes their code; compiled from this file, the unweighted kernels are, instruction for instruction, what
 // they were before weights existed, and the float kernels what they were before the quantiser.
@@ -33,6 +33,9 @@
 // not fit an int32: the low part is fmaf((float)s2, 256.0f, (float)s3) here -- both conversions exact, one rounding of the
 // same exact integer, the integer form's bits wherever that does not wrap.  A row with a non-finite coefficient in either
 // component is NaN in both planes.  Weights, factors and the detecting epilogue as in the other kernels.
+// COMPLEX with QUANT (include/dcs_beam_complex_quant.h, DESIGN.md section 5.14): bf_beamform_i8_cq_kernel and _wcq_ -- the
+// quantising epilogue above, unchanged, applied to the complex product's result registers (kChain: the gains lie behind the
+// factors, and those behind the NINE-operand coefficient image and its NaN words).
 // An inclusion defines the switches it wants as 1; the others read as 0, and all four are gone again at the end.
 #ifndef BF_I8_WEIGHTED
 #define BF_I8_WEIGHTED 0
@@ -48,7 +51,11 @@
 #endif
 template <int FORM, bool FULL, int NW = 4>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT, BF_I8_COMPLEX && BF_I8_WEIGHTED && !FULL))))
-#if BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_POWER
+#if BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_QUANT
+bf_beamform_i8_wcq_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_quant_args qa, const bf_complex_args ca)
+#elif BF_I8_COMPLEX && BF_I8_QUANT
+bf_beamform_i8_cq_kernel(const bf_bacc_args a, const bf_quant_args qa, const bf_complex_args ca)
+#elif BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_POWER
 bf_beamform_i8_wcp_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_complex_args ca)
 #elif BF_I8_COMPLEX && BF_I8_POWER
 bf_beamform_i8_cp_kernel(const bf_bacc_args a, const bf_complex_args ca)
@@ -85,7 +92,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     static_assert(!WEIGHTED || FORM == kStaged || FORM == kChain, "weights exist for the product's forms only");
     static_assert(!QUANT || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the quantiser exists for the product's forms only");
     static_assert(!BF_I8_POWER || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the detector exists for the product's forms only");
-    static_assert(!BF_I8_COMPLEX || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the complex product exists for the product's forms only");
+    static_assert(!BF_I8_COMPLEX || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the complex product exists for the product's forms only");
     constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
     extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
     uint32_t bid = BACC_LOGICAL_ID(a);

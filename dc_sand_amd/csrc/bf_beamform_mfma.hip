@@ -296,6 +296,9 @@ constexpr int kChainWaves = 4;
 // process would pay for it); kChain measured the same at 3 waves as at 4
 // wide: the weighted complex product's kernels with antenna masks (include/dcs_beam_complex.h; nine coefficient operands, the
 // weights' loads and the masks together) take 3 as well, kStaged too: at 128 registers kStaged spilled 2 and kChain 6
+// the quantised complex product (include/dcs_beam_complex_quant.h) falls under the same two rules, and they give each of its eight
+// kernels the most waves it takes without spilling (DESIGN.md section 5.14 has the table): kStaged 4 (126 - 128 registers) but for the
+// weighted one with antenna masks (8 spilled at 128; 138 at 3), kChain 3 (144; 16 - 20 spilled at 128)
 constexpr int i8_waves_per_eu(int form, bool full, bool quant = false, bool wide = false)
 {
     return form == kSplit ? (full ? 3 : 2)
@@ -405,6 +408,14 @@ __device__ __forceinline__ float power_block_sum(const floatx4 o)
 #define BF_I8_POWER 1
 #define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
+// the complex product quantised in the epilogue (include/dcs_beam_complex_quant.h): 8-bit voltage beams, unweighted and weighted
+#define BF_I8_COMPLEX 1
+#define BF_I8_QUANT 1
+#include "bf_beamform_i8_kernel.inc"
+#define BF_I8_COMPLEX 1
+#define BF_I8_QUANT 1
+#define BF_I8_WEIGHTED 1
+#include "bf_beamform_i8_kernel.inc"
 
 // Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
 // beam), beam fastest, adding its n blocks in order -- one rounded add each, no atomics, the same sum whatever the launch
@@ -442,15 +453,19 @@ hipError_t bf_warm_module_mfma()
 }
 
 namespace {
-// One launch for the ten inclusions of bf_beamform_i8_kernel.inc.  w, q, power, cx: nullptr / false = not asked for; those
+// One launch for the twelve inclusions of bf_beamform_i8_kernel.inc.  w, q, power, cx: nullptr / false = not asked for; those
 // kernels exist for the product's forms (kStaged, kChain; four waves) only, every other instantiation is the plain kernel's.
 template <int FORM, bool FULL, int NW>
 void launch_i8(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a, const bf_weights_args *w,
                const bf_quant_args *q, bool power, const bf_complex_args *cx)
 {
     if constexpr (NW == 4 && (FORM == kStaged || FORM == kChain)) {
-        if (cx) { // (never with q: the launcher has refused that)
-            if (power && w)
+        if (cx) {
+            if (q && w) // (q never with power: the launcher has refused that)
+                hipLaunchKernelGGL((bf_beamform_i8_wcq_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *q, *cx);
+            else if (q)
+                hipLaunchKernelGGL((bf_beamform_i8_cq_kernel<FORM, FULL>), grid, block, lds, stream, a, *q, *cx);
+            else if (power && w)
                 hipLaunchKernelGGL((bf_beamform_i8_wcp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *cx);
             else if (power)
                 hipLaunchKernelGGL((bf_beamform_i8_cp_kernel<FORM, FULL>), grid, block, lds, stream, a, *cx);
@@ -494,7 +509,7 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_arg
     if (a.A > 256u) return hipErrorInvalidValue; // not built
     const bool chain = a.fp32_chain != 0u;
     if ((w || q || power || cx) && chain) return hipErrorInvalidValue;
-    if (q && (power || cx)) return hipErrorInvalidValue;
+    if (q && power) return hipErrorInvalidValue;
     // beam tiles per workgroup: as many as the beams need; the fp32 form keeps its coefficient planes in LDS and
     // takes as many as still admit 6 workgroups per CU (26 KiB each), one tile whatever it takes beyond
     // more than 64 antennas, int8 form: one beam tile per workgroup; kChain (the product's form) or, probes build only, kSplit

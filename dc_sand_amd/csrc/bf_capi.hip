@@ -93,7 +93,8 @@ const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_we
                                     beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl,
                                     incoherent_block_power_impl, integrate_incoherent_power_impl,
                                     spectra_sums_impl, filterbank_scales_impl, filterbank_q8_impl,
-                                    beamform_accumulated_complex_impl, beamform_accumulated_complex_power_impl};
+                                    beamform_accumulated_complex_impl, beamform_accumulated_complex_power_impl,
+                                    beamform_accumulated_complex_q8_impl};
 }
 
 extern "C" {

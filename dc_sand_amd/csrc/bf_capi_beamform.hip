@@ -185,7 +185,7 @@ namespace {
 // What a call of the matrix-core beamformer writes to d_beams, and what it applies on the way.  kFloat: the beams, (re, im)
 // fp32 per sample; kInt8: the same quantised (include/dcs_beam_quant.h), a quarter the size; kBlockPower: one float per beam
 // and 16-sample block (include/dcs_beam_power.h), 4-byte aligned.  complex: the true complex product instead of the
-// element-wise one (include/dcs_beam_complex.h); kFloat and kBlockPower only.
+// element-wise one (include/dcs_beam_complex.h); with kInt8, include/dcs_beam_complex_quant.h.
 struct bacc_output {
     enum { kFloat, kInt8, kBlockPower } kind;
     const float *d_weights; // nullptr (unweighted) or [B][A] fp32 weights in device memory (include/dcs_beam_weights.h)
@@ -324,6 +324,20 @@ int beamform_accumulated_complex_power_impl(dcs_bf_context *c, const float *dt_c
     const bf_complex_args cx = {flags & 1u};
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes, stream,
                              {bacc_output::kBlockPower, d_weights, {}, &cx});
+}
+
+// include/dcs_beam_complex_quant.h, reached the same way: the complex product's floats quantised in the kernel's epilogue
+int beamform_accumulated_complex_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                         const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                         const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
+                                         unsigned long long *d_clip_count, void *stream)
+{
+    if (!c || !d_beams_q8 || !weights_ok(d_quant_gains) || (d_weights && !weights_ok(d_weights)) ||
+        (reinterpret_cast<uintptr_t>(d_clip_count) & 7u) || (flags & ~1u))
+        return DCS_ERR_INVALID_ARGUMENT;
+    const bf_complex_args cx = {flags & 1u};
+    return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes, stream,
+                             {bacc_output::kInt8, d_weights, {d_quant_gains, d_clip_count}, &cx});
 }
 
 } // namespace bf_host

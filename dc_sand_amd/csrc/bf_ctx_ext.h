@@ -1,7 +1,8 @@
 // bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
-// (include/dcs_filterbank.h) and libdcs_beam_complex.so (include/dcs_beam_complex.h).  All are built from this tree
+// (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h) and libdcs_beam_complex_quant.so
+// (include/dcs_beam_complex_quant.h).  All are built from this tree
 // together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
 // beam and of the filterbank calls; a companion checks the arguments it can check
@@ -20,7 +21,8 @@
 // 6: spectra_sums, filterbank_scales, filterbank_q8 appended (the tests hand foreign versions 1 to 5 only).
 // 7: beamform_accumulated_complex, beamform_accumulated_complex_power appended (tests/test_host_abi_beam_complex.py hands its
 // companion the foreign versions 1, 3, 5 and 6).
-#define BF_CTX_EXT_VERSION 7u
+// 8: beamform_accumulated_complex_q8 appended (tests/test_host_abi_beam_complex_quant.py hands its companion 1, 6 and 7).
+#define BF_CTX_EXT_VERSION 8u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -70,6 +72,11 @@ struct bf_ctx_ext_ops {
     int (*beamform_accumulated_complex_power)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
                                               const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                               float *d_block_power, size_t power_bytes, void *stream);
+    // the complex product with int8 output (include/dcs_beam_complex_quant.h): beamform_accumulated_q8's arguments and flags
+    int (*beamform_accumulated_complex_q8)(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                           const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                           const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
+                                           unsigned long long *d_clip_count, void *stream);
 };
 
 // the first member of struct dcs_bf_context

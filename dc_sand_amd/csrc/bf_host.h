@@ -132,7 +132,7 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
 // the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, and the
-// complex product's two in bf_capi_beamform.hip again
+// complex product's three in bf_capi_beamform.hip again
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -165,6 +165,10 @@ int beamform_accumulated_complex_impl(dcs_bf_context *c, const float *dt_coeff, 
 int beamform_accumulated_complex_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
                                             const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                             float *d_block_power, size_t power_bytes, void *stream);
+int beamform_accumulated_complex_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt,
+                                         const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
+                                         const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
+                                         unsigned long long *d_clip_count, void *stream);
 
 } // namespace bf_host
 

@@ -206,7 +206,7 @@ struct bf_complex_args {
 // (include/dcs_beam_power.h): a.beams is then the block power tensor [C][nT16][B], one float per beam
 // and 16-sample block, written by the detecting kernels' epilogue from the floats the float kernels would have stored;
 // cx: nullptr, or the complex product.  All four exist for the int8 form's kStaged and kChain only (a.fp32_chain must be
-// 0), and q excludes power and cx.
+// 0), and q excludes power (q with cx: include/dcs_beam_complex_quant.h).
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args *q, bool power,
                                   const bf_complex_args *cx, hipStream_t stream);
 // Block powers [C][nr_blocks][B] summed n at a time, in order, into spectra [nr_blocks / n][C][B]

@@ -326,6 +326,18 @@ class SteeringCoefficientGenerator:
         check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), 1 if conjugate else 0,
                  _p(d_block_power), int(power_bytes), _s(stream)), where)
 
+    # -- 8-bit voltage beams of the complex product (include/dcs_beam_complex_quant.h, companion library
+    #    libdcs_beam_complex_quant.so): gains, counters and the int8 tensor as :meth:`beamform_accumulated_q8`
+    def beamform_accumulated_complex_q8(self, d_antenna, antenna_bytes: int, d_quant_gains, d_beams_q8, beams_bytes: int, nt: int,
+                                        t_coeff: int | None = None, dt_coeff: float | None = None, d_weights=None,
+                                        conjugate: bool = False, d_clip_count=None, stream=None) -> None:
+        """:meth:`beamform_accumulated_complex` whose epilogue requantises every beam to int8 with its gain, as
+        :meth:`beamform_accumulated_q8` does: the bytes are the quantised floats of the complex float call, in the antenna
+        tensor's order (:func:`quantised_beams_bytes`), so they can be the ``d_antenna`` of a second beamformer."""
+        fn, when, where = _coeff_time_entry("beam_complex_quant", "dcs_bf_beamform_accumulated_complex_q8", t_coeff, dt_coeff)
+        check(fn(c_void_p(self._h), when, int(nt), _p(d_antenna), int(antenna_bytes), _p_or_null(d_weights), 1 if conjugate else 0,
+                 _p(d_quant_gains), _p(d_beams_q8), int(beams_bytes), _p_or_null(d_clip_count), _s(stream)), where)
+
     # -- the incoherent beam (include/dcs_incoherent_beam.h, companion library libdcs_incoherent_beam.so): d_block_power is a
     #    device uint32 [C][nt / 16] array, d_spectra a device float [nr_blocks / blocks_per_spectrum][C] array
     def incoherent_block_power(self, d_antenna, antenna_bytes: int, d_block_power, power_bytes: int, nt: int, d_weights=None,

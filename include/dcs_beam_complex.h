@@ -47,9 +47,9 @@
  * Accuracy: against the exact rational sum_a w_a * x_a of the fp32 coefficients,
  * |v - exact| <= 9e-8 * sum_a (|x_re| + |x_im|) + 1.8e-7 * |exact| per component.
  *
- * Out of scope: the int8-quantised output of the complex form, the fp32 fma-chain form (dcs_bf_tuning.math_mode bit 3:
- * refused with DCS_ERR_UNSUPPORTED, nothing enqueued, like the other companions' calls), and the per-sample fused
- * beamformer (dcs_bf_generate_and_beamform).
+ * The int8-quantised output of this product -- 8-bit voltage beams -- is dcs_beam_complex_quant.h.  Out of scope: the fp32
+ * fma-chain form (dcs_bf_tuning.math_mode bit 3: refused with DCS_ERR_UNSUPPORTED, nothing enqueued, like the other
+ * companions' calls), and the per-sample fused beamformer (dcs_bf_generate_and_beamform).
  *
  * Arguments refused with DCS_ERR_INVALID_ARGUMENT before the context is touched: a NULL context, a NULL output, d_beams not
  * 8-byte aligned, d_block_power or non-NULL weights not 4-byte aligned, nt % 16 != 0, a bit of flags other than

@@ -26,6 +26,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py bfcomplex [--rounds 5] [--shape AxBxCxNT]
         the complex product: the float call (twice: its own spread), the complex float call plain and conjugated, the
         detecting call and the complex detecting call, alternating, in one process -> profiles/r10_beam_complex.md
+    python tools/measure.py bfcq8 [--rounds 5] [--shape AxBxCxNT]
+        8-bit voltage beams of the complex product: the complex float call (twice: its own spread), the complex int8 call
+        and the element-wise int8 call, each without and with clip counters, alternating, in one process
+        -> profiles/r11_beam_complex_quant.md
     python tools/measure.py incoh [--rounds 5] [--trace]
         the incoherent beam against the read probe (dcs_probe_reduce) over the same bytes and against the detecting call
         at 16 and 256 beams, alternating, in one process; --trace: a few launches of each kernel for
@@ -557,6 +561,76 @@ def cmd_bfcomplex(args):
     print(json.dumps({"bfcomplex": rows}), flush=True)
 
 
+def cmd_bfcq8(args):
+    """8-bit voltage beams of the complex product (include/dcs_beam_complex_quant.h): per shape the complex float call (twice:
+    its own spread), the new call without and with clip counters, and the element-wise int8 call without and with them, all
+    conjugated where they can be, timed in turn ``--rounds`` times in the same process on the same noise-like samples.  The gains put about 1 % of
+    the components beyond the range (from the complex float output of the first channels); the clip rate printed is the
+    counters' own.  Bytes under the roofline's model: 2 A in and 8 B (float) or 2 B (int8) out per sample and channel."""
+    from dc_sand_amd.beam_quant import BeamQuantGains
+    from dc_sand_amd.generator import quantised_beams_bytes
+
+    shapes = [(64, 16, 32768, 256), (64, 256, 4096, 256), (256, 64, 4096, 256), (256, 64, 1024, 256)]
+    if args.shape:
+        shapes = [tuple(int(v) for v in args.shape.split("x"))]
+    rows = []
+    for A, B, C, nt in shapes:
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        g.upload_delays(simulate_input(bp))
+        ab, fb, qb = A * C * nt * 2, B * C * nt * 8, quantised_beams_bytes(bp, nt)
+        d_ant, d_beams, d_q = device.mem_alloc(ab), device.mem_alloc(fb), device.mem_alloc(qb)
+        _noise(d_ant, ab)
+        cf32 = lambda: g.beamform_accumulated_complex(d_ant, ab, d_beams, fb, nt, t_coeff=1, conjugate=True)  # noqa: E731
+        cf32()
+        nc = min(C, 8)  # the gains: from the first channels' complex float beams
+        v = np.empty((nc, nt // 16, B, 16, 2), dtype=np.float32)
+        device.memcpy_dtoh(v, d_beams)
+        mag = np.abs(np.moveaxis(v, 2, 0).reshape(B, -1)).astype(np.float64)
+        qg = BeamQuantGains(bp)
+        qg.host[:] = (127.5 / np.quantile(mag, 0.99, axis=1)).astype(np.float32)
+        qg.upload()
+
+        def cq8(count):
+            return lambda: g.beamform_accumulated_complex_q8(d_ant, ab, qg.device_ptr(), d_q, qb, nt, t_coeff=1, conjugate=True,
+                                                             d_clip_count=qg.clip_count_ptr() if count else None)
+
+        def q8(count):
+            return lambda: g.beamform_accumulated_q8(d_ant, ab, qg.device_ptr(), d_q, qb, nt, t_coeff=1,
+                                                     d_clip_count=qg.clip_count_ptr() if count else None)
+        cq8(True)()
+        rate = float(qg.clip_counts(reset=True).sum()) / qb
+        calls = [("cfloat", cf32), ("cfloat_again", cf32), ("cq8", cq8(False)), ("cq8_counted", cq8(True)), ("q8", q8(False)),
+                 ("q8_counted", q8(True))]
+        for _, fn in calls:
+            fn()
+        t = {name: [] for name, _ in calls}
+        for _ in range(args.rounds):
+            for name, fn in calls:
+                t[name].append(per_launch_ms(fn))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        both = t["cfloat"] + t["cfloat_again"]
+        spread = max(max(both) / min(both) - 1.0, abs(med["cfloat_again"] / med["cfloat"] - 1.0))
+        row = {"shape": f"{A}x{B}x{C}x{nt}", "form": "staged" if A <= 64 else "kChain", "byte_ratio": round((2 * A + 2 * B) / (2 * A + 8 * B), 3),
+               "cfloat_us": round(med["cfloat"] * 1e3, 1), "cfloat_again_us": round(med["cfloat_again"] * 1e3, 1), "cfloat_spread": round(spread, 4),
+               "clip_rate": round(rate, 5)}
+        for name in ("cq8", "cq8_counted", "q8", "q8_counted"):
+            row[name + "_us"] = round(med[name] * 1e3, 1)
+        row["cq8_over_cfloat"] = round(med["cq8"] / med["cfloat"], 4)
+        row["cq8_counted_over_cfloat"] = round(med["cq8_counted"] / med["cfloat"], 4)
+        row["cq8_over_q8"] = round(med["cq8"] / med["q8"], 4)
+        row["q8_counted_over_q8"] = round(med["q8_counted"] / med["q8"], 4)
+        row["cq8_frac_8TBps"] = round((2 * A + 2 * B) * C * nt / (med["cq8"] * 1e-3) / 8e12, 3)
+        row["cq8_within_spread"] = bool(med["cq8"] <= med["cfloat"] * (1.0 + spread))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        qg.free()
+        g.close()
+        for d in (d_ant, d_beams, d_q):
+            d.free()
+    print(json.dumps({"bfcq8": rows}), flush=True)
+
+
 def cmd_incoh(args):
     """The incoherent beam (include/dcs_incoherent_beam.h), read-bound: 2 A bytes per sample and channel.  Per shape, in
     turn ``--rounds`` times in one process on the same noise-like samples: the new call (events around a run of launches),
@@ -1059,6 +1133,9 @@ def main():
     p = sub.add_parser("bfcomplex")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the element-wise and the complex timings per shape")
     p.add_argument("--shape", default="", help="AxBxCxNT: one shape only")
+    p = sub.add_parser("bfcq8")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the complex float, the complex int8 and the int8 timings per shape")
+    p.add_argument("--shape", default="", help="AxBxCxNT: one shape only")
     p = sub.add_parser("incoh")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the new call and the read probe per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
@@ -1106,7 +1183,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
