@@ -1,10 +1,12 @@
-// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel, included twelve times by bf_beamform_mfma.hip:
-// BF_I8_WEIGHTED 0 makes bf_beamform_i8_kernel, 1 makes bf_beamform_i8_w_kernel (per-input beam weights); with
-// BF_I8_QUANT 1 they are bf_beamform_i8_q_kernel and bf_beamform_i8_wq_kernel (quantised int8 output), with BF_I8_POWER 1
-// bf_beamform_i8_p_kernel and bf_beamform_i8_wp_kernel (detected block power).  One text, twelve
-// kernels: a WEIGHTED template parameter would rename the unweighted kernels' symbols, and a body shared through an inline
-// function changes their code; compiled from this file, the unweighted kernels are, instruction for instruction, what
-// they were before weights existed, and the float kernels what they were before the quantiser.
+// bf_beamform_i8_kernel.inc -- the int8 matrix-core beamformer's kernel: one template, included once by bf_beamform_mfma.hip,
+// which instantiates it for every output the product has (launch_i8 there).  FORM is the way the samples reach the matrix
+// cores (kStaged, kDirect, kSplit, kChain), FULL says that nr_stations is a multiple of 64 (no antenna masks), NW is the
+// number of waves of a workgroup; the four switches below choose what is computed and written.  Each switch that needs an
+// argument of its own brings it as a further kernel parameter, in this order and only where the switch is on: w (WEIGHTED),
+// qa (QUANT), ca (COMPLEX) -- the plain kernel takes (a), the weighted quantised complex one (a, w, qa, ca).  Everything a
+// switch adds stands behind `if constexpr`: a kernel whose switches are off is, instruction for instruction, the kernel
+// this file made before that switch existed (DESIGN.md section 5.7 has the comparison, and the warning that goes with it:
+// restructuring this body, sharing an epilogue between finish and run_chain for one, moves kChain's register allocation).
 // WEIGHTED (kStaged and kChain; include/dcs_beam_weights.h, DESIGN.md section 5.7): every coefficient w is made into
 // w' = RN(ghat * w) before its digits are taken (ghat[a][b] beside the terms, same addressing), and the integer sums of a
 // beam are scaled by RN(s_b / 8355711) instead of 1 / 8355711 -- the same one multiply.  kStaged keeps its four factors in
@@ -17,15 +19,15 @@
 // bw + (lane >> 4) + 4 (lane & 3), h = (lane >> 2) & 1), and the wave writes its pair of blocks with one 16-byte store
 // per lane: 2 x 512 contiguous bytes.  kStaged keeps its four gains in registers, kChain reads them from LDS behind the
 // weighted form's factors, one register ahead.  Clipped components are counted per lane and tallied once, at the end.
-// POWER (kStaged and kChain; include/dcs_beam_power.h, DESIGN.md section 5.9): a result register's four floats -- again
-// the very floats the float kernel stores -- become |.|^2 of its two samples and their sum; three exchanges inside each
-// group of 8 lanes (power_block_sum) finish the 16-sample block's balanced pairwise sum, the same bits in all 8 lanes.
-// Lane m < 4 of a group keeps register m's sum and writes that one dword: beam bw + (lane >> 4) + 4 m of its block of the
-// tensor [c][t/16][b] -- 2 x 64 contiguous bytes per wave and pair of blocks.  The weighted form's factors as in the
-// float kernels.
+// POWER (kStaged and kChain, never with QUANT; include/dcs_beam_power.h, DESIGN.md section 5.9): a result register's four
+// floats -- again the very floats the float kernel stores -- become |.|^2 of its two samples and their sum; three exchanges
+// inside each group of 8 lanes (power_block_sum) finish the 16-sample block's balanced pairwise sum, the same bits in all 8
+// lanes.  Lane m < 4 of a group keeps register m's sum and writes that one dword: beam bw + (lane >> 4) + 4 m of its block
+// of the tensor [c][t/16][b] -- 2 x 64 contiguous bytes per wave and pair of blocks.  The weighted form's factors as in
+// the float kernels.
 // COMPLEX (kStaged and kChain; include/dcs_beam_complex.h, DESIGN.md section 5.13): the true complex product sum_a w_a x_a
-// instead of the element-wise one -- bf_beamform_i8_c_kernel, _wc_ (weighted), _cp_ and _wcp_ (detected block power).  A
-// coefficient gives NINE operands per 64 antennas instead of six: the digits of re, of sigma im and of -sigma im (sigma = -1
+// instead of the element-wise one.  A coefficient gives NINE operands per 64 antennas instead of six: the digits of re, of
+// sigma im and of -sigma im (sigma = -1
 // with bf_complex_args.conj: the sign of im is flipped before fixed_word, so the conjugate costs nothing in the loop; the
 // third operand is fixed_word(-sigma im), NOT the negated digits of the second -- a digit can be -128).  Per pair of blocks
 // and 64 antennas 24 MFMAs into the same twelve sums: re_d with all four planes' own samples, +im_d into the im planes with
@@ -33,66 +35,26 @@
 // not fit an int32: the low part is fmaf((float)s2, 256.0f, (float)s3) here -- both conversions exact, one rounding of the
 // same exact integer, the integer form's bits wherever that does not wrap.  A row with a non-finite coefficient in either
 // component is NaN in both planes.  Weights, factors and the detecting epilogue as in the other kernels.
-// COMPLEX with QUANT (include/dcs_beam_complex_quant.h, DESIGN.md section 5.14): bf_beamform_i8_cq_kernel and _wcq_ -- the
-// quantising epilogue above, unchanged, applied to the complex product's result registers (kChain: the gains lie behind the
-// factors, and those behind the NINE-operand coefficient image and its NaN words).
-// An inclusion defines the switches it wants as 1; the others read as 0, and all four are gone again at the end.
-#ifndef BF_I8_WEIGHTED
-#define BF_I8_WEIGHTED 0
-#endif
-#ifndef BF_I8_QUANT
-#define BF_I8_QUANT 0
-#endif
-#ifndef BF_I8_POWER
-#define BF_I8_POWER 0
-#endif
-#ifndef BF_I8_COMPLEX
-#define BF_I8_COMPLEX 0
-#endif
-template <int FORM, bool FULL, int NW = 4>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, BF_I8_QUANT, BF_I8_COMPLEX && BF_I8_WEIGHTED && !FULL))))
-#if BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_QUANT
-bf_beamform_i8_wcq_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_quant_args qa, const bf_complex_args ca)
-#elif BF_I8_COMPLEX && BF_I8_QUANT
-bf_beamform_i8_cq_kernel(const bf_bacc_args a, const bf_quant_args qa, const bf_complex_args ca)
-#elif BF_I8_COMPLEX && BF_I8_WEIGHTED && BF_I8_POWER
-bf_beamform_i8_wcp_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_complex_args ca)
-#elif BF_I8_COMPLEX && BF_I8_POWER
-bf_beamform_i8_cp_kernel(const bf_bacc_args a, const bf_complex_args ca)
-#elif BF_I8_COMPLEX && BF_I8_WEIGHTED
-bf_beamform_i8_wc_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_complex_args ca)
-#elif BF_I8_COMPLEX
-bf_beamform_i8_c_kernel(const bf_bacc_args a, const bf_complex_args ca)
-#elif BF_I8_WEIGHTED && BF_I8_POWER
-bf_beamform_i8_wp_kernel(const bf_bacc_args a, const bf_weights_args w)
-#elif BF_I8_POWER
-bf_beamform_i8_p_kernel(const bf_bacc_args a)
-#elif BF_I8_WEIGHTED && BF_I8_QUANT
-bf_beamform_i8_wq_kernel(const bf_bacc_args a, const bf_weights_args w, const bf_quant_args qa)
-#elif BF_I8_QUANT
-bf_beamform_i8_q_kernel(const bf_bacc_args a, const bf_quant_args qa)
-#elif BF_I8_WEIGHTED
-bf_beamform_i8_w_kernel(const bf_bacc_args a, const bf_weights_args w)
-#else
-bf_beamform_i8_kernel(const bf_bacc_args a)
-#endif
+// COMPLEX with QUANT (include/dcs_beam_complex_quant.h, DESIGN.md section 5.14): the quantising epilogue above, unchanged,
+// applied to the complex product's result registers (kChain: the gains lie behind the factors, and those behind the
+// NINE-operand coefficient image and its NaN words).
+
+template <int FORM, bool FULL, int NW = 4, bool WEIGHTED = false, bool QUANT = false, bool POWER = false, bool COMPLEX = false, class... Extra>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(i8_waves_per_eu(FORM, FULL, QUANT, COMPLEX && WEIGHTED && !FULL))))
+bf_beamform_i8_kernel(const bf_bacc_args a, const Extra... extra)
 {
-    constexpr bool WEIGHTED = BF_I8_WEIGHTED, QUANT = BF_I8_QUANT, COMPLEX = BF_I8_COMPLEX;
     constexpr uint32_t NOP = COMPLEX ? 9u : 6u; // coefficient operands per 64 antennas
-#if !BF_I8_WEIGHTED
-    const bf_weights_args w{}; // named by the (discarded) weighted branches only
-#endif
-#if !BF_I8_QUANT
-    const bf_quant_args qa{};  // named by the (discarded) quantised branches only
-#endif
-#if !BF_I8_COMPLEX
-    const bf_complex_args ca{}; // named by the (discarded) complex branches only
-#endif
+    static_assert(sizeof...(Extra) == (size_t)WEIGHTED + QUANT + COMPLEX && kernel_takes<bf_weights_args, Extra...> == WEIGHTED &&
+                      kernel_takes<bf_quant_args, Extra...> == QUANT && kernel_takes<bf_complex_args, Extra...> == COMPLEX,
+                  "the extra parameters are w, qa, ca, each exactly where its switch is on");
+    const bf_weights_args &w = kernel_extra<bf_weights_args>(extra...);
+    const bf_quant_args &qa = kernel_extra<bf_quant_args>(extra...);
+    const bf_complex_args &ca = kernel_extra<bf_complex_args>(extra...);
     static_assert(NW == 4 || ((NW == 8 || NW == 16) && FORM == kStaged), "8- and 16-wave workgroups exist for the staged form only");
     static_assert(!WEIGHTED || FORM == kStaged || FORM == kChain, "weights exist for the product's forms only");
     static_assert(!QUANT || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the quantiser exists for the product's forms only");
-    static_assert(!BF_I8_POWER || (!BF_I8_QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the detector exists for the product's forms only");
-    static_assert(!BF_I8_COMPLEX || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the complex product exists for the product's forms only");
+    static_assert(!POWER || (!QUANT && NW == 4 && (FORM == kStaged || FORM == kChain)), "the detector exists for the product's forms only");
+    static_assert(!COMPLEX || (NW == 4 && (FORM == kStaged || FORM == kChain)), "the complex product exists for the product's forms only");
     constexpr bool STAGED = FORM == kStaged, SPLIT = FORM == kSplit, CHAIN = FORM == kChain;
     extern __shared__ __attribute__((aligned(16))) char staged[]; // kStaged: the sample image (+ the coefficient exchange); kSplit: the partial sums
     uint32_t bid = BACC_LOGICAL_ID(a);
@@ -427,7 +389,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
     };
     // scale and store: lane l, register r = beam bw + (l >> 4) + 4 r, samples 2 m, 2 m + 1
     auto finish = [&](auto whole, uint32_t blk, const floatx4 (&f)[4]) {
-        if constexpr (BF_I8_POWER) { // the same floats, detected: the block sum of register m stays with lane m < 4 of each 8
+        if constexpr (POWER) { // the same floats, detected: the block sum of register m stays with lane m < 4 of each 8
             float mine = 0.0f;
 #pragma unroll
             for (int r = 0; r < 4; r++) { // beam bb + 4 r
@@ -688,7 +650,7 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
                         for (int v = half; v < 4; v += 2) acc[v][d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x[v], acc[v][d], 0, 0, 0);
                     }
                 }
-                if constexpr (BF_I8_POWER) {
+                if constexpr (POWER) {
                     if (chunk + 1u == n_chunks) { // as the float form below, each register detected and summed as it is recombined; then one dword
                         float sc_next = WEIGHTED ? facw[lg] : inv; // beam bb + 4 r's factor, one register ahead
                         float mine = 0.0f;
@@ -803,8 +765,4 @@ bf_beamform_i8_kernel(const bf_bacc_args a)
         if (qa.clips) q8_tally(qa.clips, n_clip, bb, lm, a.B);
     }
 }
-#undef BF_I8_WEIGHTED
-#undef BF_I8_QUANT
-#undef BF_I8_POWER
-#undef BF_I8_COMPLEX
 

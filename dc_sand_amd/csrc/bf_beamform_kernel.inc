@@ -1,22 +1,15 @@
-// bf_beamform_kernel.inc -- the per-sample fused beamformer's kernel, included twice by bf_kernels.hip: BF_FUSED_WEIGHTED 0
-// makes bf_beamform_kernel, 1 makes bf_beamform_w_kernel (per-input beam weights).  One text, two kernels, for the reason
-// bf_beamform_i8_kernel.inc gives: the unweighted kernels keep their symbols and, instruction for instruction, their code.
+// bf_beamform_kernel.inc -- the per-sample fused beamformer's kernel: one template, included once by bf_kernels.hip.  CH is
+// the number of channels a pass takes together.  WEIGHTED applies per-input beam weights and brings its argument as a
+// second kernel parameter, w; the unweighted kernel takes (a) alone and is, instruction for instruction, what it was before
+// weights existed (as bf_beamform_i8_kernel's switches: DESIGN.md section 5.7).
 // WEIGHTED: each coefficient w becomes w' = RN(ghat * w) (ghat[a][b] beside the terms, same addressing), the products
 // and the sums are those described in bf_kernels.hip, and the beam's sums are multiplied by s_b once, at the store.
-#ifndef BF_FUSED_WEIGHTED
-#define BF_FUSED_WEIGHTED 0
-#endif
-template <int CH>
-#if BF_FUSED_WEIGHTED
-__global__ void __launch_bounds__(kBlock) bf_beamform_w_kernel(const bf_beamform_args a, const bf_weights_args w)
-#else
-__global__ void __launch_bounds__(kBlock) bf_beamform_kernel(const bf_beamform_args a)
-#endif
+template <int CH, bool WEIGHTED = false, class... Extra>
+__global__ void __launch_bounds__(kBlock) bf_beamform_kernel(const bf_beamform_args a, const Extra... extra)
 {
-    constexpr bool WEIGHTED = BF_FUSED_WEIGHTED;
-#if !BF_FUSED_WEIGHTED
-    const bf_weights_args w{}; // named by the (discarded) weighted branches only
-#endif
+    static_assert(sizeof...(Extra) == (size_t)WEIGHTED && kernel_takes<bf_weights_args, Extra...> == WEIGHTED,
+                  "the extra parameter is w, exactly where WEIGHTED is on");
+    const bf_weights_args &w = kernel_extra<bf_weights_args>(extra...);
     extern __shared__ __attribute__((aligned(16))) float s_ant[]; // [CH][A][16][2], int8 samples converted once
 
     const uint32_t bid = blockIdx.x;
@@ -160,5 +153,4 @@ __global__ void __launch_bounds__(kBlock) bf_beamform_kernel(const bf_beamform_a
         }
     }
 }
-#undef BF_FUSED_WEIGHTED
 

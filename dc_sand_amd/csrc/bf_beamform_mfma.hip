@@ -40,6 +40,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "bf_device.h"
@@ -305,8 +306,8 @@ constexpr int i8_waves_per_eu(int form, bool full, bool quant = false, bool wide
                           : (form == kChain ? kChainWaves - (quant || wide ? 1 : 0) : (wide ? 3 : (full || form == kStaged ? 4 : 3)));
 }
 
-// ---- the quantised epilogue (include/dcs_beam_quant.h): what bf_beamform_i8_q_kernel and
-// bf_beamform_i8_wq_kernel do with a result register instead of storing its four floats.
+// ---- the quantised epilogue (include/dcs_beam_quant.h): what bf_beamform_i8_kernel's QUANT
+// instantiations do with a result register instead of storing its four floats.
 // o = {re even, im even, re odd, im odd} of one beam and one pair of samples, exactly the floats the unquantised kernel
 // stores; k the beam's gain.  Per component y = RN(o * k) (one multiply of its own), NaN -> -128, otherwise
 // clamp(rint(y), -127, 127); the four bytes are, in this order, four consecutive bytes of the int8 tensor.  Counting
@@ -365,8 +366,8 @@ __device__ __forceinline__ void q8_tally(unsigned long long *clips, uint32_t n_c
     }
 }
 
-// ---- the detecting epilogue (include/dcs_beam_power.h): what bf_beamform_i8_p_kernel and
-// bf_beamform_i8_wp_kernel do with a result register instead of storing its four floats.
+// ---- the detecting epilogue (include/dcs_beam_power.h): what bf_beamform_i8_kernel's POWER
+// instantiations do with a result register instead of storing its four floats.
 // o = {re even, im even, re odd, im odd} of one beam and samples 2 m, 2 m + 1 (m = lane & 7), exactly the floats the float
 // kernel stores.  p_t = RN(RN(re re) + RN(im im)) per sample (no fma: -ffp-contract=off), level 1 of the block's pairwise sum
 // in the lane, levels 2 - 4 with lane ^ 1, lane ^ 2 (the DPP quad permutes of q8_quad_transpose) and the other quad of the
@@ -382,39 +383,6 @@ __device__ __forceinline__ float power_block_sum(const floatx4 o)
     return s;
 }
 
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_WEIGHTED 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_QUANT 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_QUANT 1
-#define BF_I8_WEIGHTED 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_POWER 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_POWER 1
-#define BF_I8_WEIGHTED 1
-#include "bf_beamform_i8_kernel.inc"
-// the true complex product (include/dcs_beam_complex.h): float and detected block power out, unweighted and weighted
-#define BF_I8_COMPLEX 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_COMPLEX 1
-#define BF_I8_WEIGHTED 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_COMPLEX 1
-#define BF_I8_POWER 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_COMPLEX 1
-#define BF_I8_POWER 1
-#define BF_I8_WEIGHTED 1
-#include "bf_beamform_i8_kernel.inc"
-// the complex product quantised in the epilogue (include/dcs_beam_complex_quant.h): 8-bit voltage beams, unweighted and weighted
-#define BF_I8_COMPLEX 1
-#define BF_I8_QUANT 1
-#include "bf_beamform_i8_kernel.inc"
-#define BF_I8_COMPLEX 1
-#define BF_I8_QUANT 1
-#define BF_I8_WEIGHTED 1
 #include "bf_beamform_i8_kernel.inc"
 
 // Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
@@ -453,41 +421,49 @@ hipError_t bf_warm_module_mfma()
 }
 
 namespace {
-// One launch for the twelve inclusions of bf_beamform_i8_kernel.inc.  w, q, power, cx: nullptr / false = not asked for; those
-// kernels exist for the product's forms (kStaged, kChain; four waves) only, every other instantiation is the plain kernel's.
+// f(one std::bool_constant per flag): the runtime flags as template arguments
+template <class F>
+void dispatch_flags(F f)
+{
+    f();
+}
+template <class F, class... Rest>
+void dispatch_flags(F f, bool flag, Rest... rest)
+{
+    if (flag)
+        dispatch_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else
+        dispatch_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
+
+// a kernel parameter that exists only where its switch is on
+template <bool ON, class T>
+auto i8_arg(const T *p)
+{
+    if constexpr (ON)
+        return std::tuple<T>(*p);
+    else
+        return std::tuple<>();
+}
+
+// One launch for every instantiation of bf_beamform_i8_kernel.  w, q, power, cx: nullptr / false = not asked for; the switches
+// exist for the product's forms (kStaged, kChain; four waves) only, every other instantiation is the plain kernel's.
 template <int FORM, bool FULL, int NW>
 void launch_i8(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const bf_bacc_args &a, const bf_weights_args *w,
                const bf_quant_args *q, bool power, const bf_complex_args *cx)
 {
     if constexpr (NW == 4 && (FORM == kStaged || FORM == kChain)) {
-        if (cx) {
-            if (q && w) // (q never with power: the launcher has refused that)
-                hipLaunchKernelGGL((bf_beamform_i8_wcq_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *q, *cx);
-            else if (q)
-                hipLaunchKernelGGL((bf_beamform_i8_cq_kernel<FORM, FULL>), grid, block, lds, stream, a, *q, *cx);
-            else if (power && w)
-                hipLaunchKernelGGL((bf_beamform_i8_wcp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *cx);
-            else if (power)
-                hipLaunchKernelGGL((bf_beamform_i8_cp_kernel<FORM, FULL>), grid, block, lds, stream, a, *cx);
-            else if (w)
-                hipLaunchKernelGGL((bf_beamform_i8_wc_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *cx);
-            else
-                hipLaunchKernelGGL((bf_beamform_i8_c_kernel<FORM, FULL>), grid, block, lds, stream, a, *cx);
-            return;
-        }
-        if (power && w)
-            hipLaunchKernelGGL((bf_beamform_i8_wp_kernel<FORM, FULL>), grid, block, lds, stream, a, *w);
-        else if (power)
-            hipLaunchKernelGGL((bf_beamform_i8_p_kernel<FORM, FULL>), grid, block, lds, stream, a);
-        else if (q && w)
-            hipLaunchKernelGGL((bf_beamform_i8_wq_kernel<FORM, FULL>), grid, block, lds, stream, a, *w, *q);
-        else if (q)
-            hipLaunchKernelGGL((bf_beamform_i8_q_kernel<FORM, FULL>), grid, block, lds, stream, a, *q);
-        else if (w)
-            hipLaunchKernelGGL((bf_beamform_i8_w_kernel<FORM, FULL>), grid, block, lds, stream, a, *w);
-        if (power || q || w) return;
+        dispatch_flags([&](auto weighted, auto quant, auto detect, auto complex) {
+            constexpr bool W = decltype(weighted)::value, Q = decltype(quant)::value, P = decltype(detect)::value, C = decltype(complex)::value;
+            if constexpr (!(Q && P)) // (the launcher has refused that)
+                std::apply([&](const auto &...extra) {
+                    hipLaunchKernelGGL((bf_beamform_i8_kernel<FORM, FULL, NW, W, Q, P, C, std::decay_t<decltype(extra)>...>), grid, block, lds,
+                                       stream, a, extra...);
+                }, std::tuple_cat(i8_arg<W>(w), i8_arg<Q>(q), i8_arg<C>(cx)));
+        }, w != nullptr, q != nullptr, power, cx != nullptr);
+    } else {
+        hipLaunchKernelGGL((bf_beamform_i8_kernel<FORM, FULL, NW>), grid, block, lds, stream, a);
     }
-    hipLaunchKernelGGL((bf_beamform_i8_kernel<FORM, FULL, NW>), grid, block, lds, stream, a);
 }
 
 template <int FORM, int NW = 4>

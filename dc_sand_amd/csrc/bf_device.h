@@ -62,6 +62,28 @@ __device__ __forceinline__ void dispatch_fast(const bool div3, const bool lowdeg
     }
 }
 
+// A kernel template's optional parameters travel as a trailing pack, each present only where its switch is on, so every
+// instantiation's kernarg segment holds what that kernel reads and nothing else.  kernel_extra<T>(extra...) is the
+// parameter of type T among them, or a constant T of zeros where the kernel has none: then only discarded branches name it.
+// (By reference, not by value: a copy initialised from a function's result moved registers in the kChain kernels that
+// have no such parameter -- DESIGN.md section 5.7.)
+template <class T>
+__device__ __forceinline__ const T &kernel_extra()
+{
+    static constexpr T none{};
+    return none;
+}
+template <class T, class U, class... Rest>
+__device__ __forceinline__ const T &kernel_extra(const U &first, const Rest &...rest)
+{
+    if constexpr (std::is_same_v<T, U>)
+        return first;
+    else
+        return kernel_extra<T>(rest...);
+}
+template <class T, class... Extra>
+constexpr bool kernel_takes = (std::is_same_v<T, Extra> || ...);
+
 // Slow path: hardware-sequence IEEE divide and fp64 sincos rounded once to
 // fp32, i.e. the verifier's own definition (BeamformerCoefficientTest.cu:327-328).
 __device__ __forceinline__ void coeff_slow(const float fRate, const float fPhase0, const float fChan,

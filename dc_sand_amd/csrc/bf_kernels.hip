@@ -594,8 +594,6 @@ __global__ void __launch_bounds__(kBlock) bf_bform_terms_w_kernel(const bf_bform
 // independent coefficient chains (more ILP, fewer loads per product).
 constexpr uint32_t kAntChunk = 128; // antennas staged in LDS at a time (as fp32: 16 KiB per channel)
 #include "bf_beamform_kernel.inc"
-#define BF_FUSED_WEIGHTED 1
-#include "bf_beamform_kernel.inc"
 
 // ---------------------------------------------------------------------------
 // One coefficient per lane (the launch shape of the reference's
@@ -970,19 +968,19 @@ hipError_t bf_launch_beamform(const bf_beamform_args &a_in, const bf_weights_arg
     const int ch = (a.chan_per_block >= 4 && na <= 64u) ? 4 : (a.chan_per_block >= 2 ? 2 : 1);
     const size_t lds = (size_t)na * 32u * sizeof(float) * (size_t)ch;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (w) {
-        if (ch == 4)
-            hipLaunchKernelGGL(bf_beamform_w_kernel<4>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
-        else if (ch == 2)
-            hipLaunchKernelGGL(bf_beamform_w_kernel<2>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
+    auto launch = [&](auto channels) {
+        constexpr int CH = decltype(channels)::value;
+        if (w)
+            hipLaunchKernelGGL((bf_beamform_kernel<CH, true, bf_weights_args>), dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
         else
-            hipLaunchKernelGGL(bf_beamform_w_kernel<1>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a, *w);
-    } else if (ch == 4)
-        hipLaunchKernelGGL(bf_beamform_kernel<4>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
+            hipLaunchKernelGGL((bf_beamform_kernel<CH>), dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
+    };
+    if (ch == 4)
+        launch(std::integral_constant<int, 4>{});
     else if (ch == 2)
-        hipLaunchKernelGGL(bf_beamform_kernel<2>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
+        launch(std::integral_constant<int, 2>{});
     else
-        hipLaunchKernelGGL(bf_beamform_kernel<1>, dim3((uint32_t)blocks), dim3(kBlock), lds, stream, a);
+        launch(std::integral_constant<int, 1>{});
     return hipGetLastError();
 }
 

@@ -9,11 +9,18 @@ for the sites that do not instantiate what they capture.
 
 ``launches(s, fn)`` captures what ``fn()`` enqueues on ``s`` and returns the (gridDim, blockDim) of every kernel node without
 running anything: how a test proves the geometry a launcher chose instead of restating the launcher's arithmetic.  With a
-list ``others`` it also names the types of the nodes that are no kernels (a memset node, say)."""
+list ``others`` it also names the types of the nodes that are no kernels (a memset node, say).
+
+While a stream captures, Python's cyclic collector is off.  It runs wherever an allocation count happens to cross its
+threshold, and a test object it collects frees its device memory: hipFree under a global-mode capture invalidates the
+capture, and the next launch of the innocent test that captures fails with hipErrorStreamCaptureInvalidated (901)."""
 import ctypes
+import gc
 
 V = ctypes.c_void_p
 _HIP = None
+_CAPTURING = 0   # captures begun here and not yet ended
+_GC_WAS_ON = False
 
 
 class _Dim3(ctypes.Structure):
@@ -51,12 +58,22 @@ def _stream(stream):
 
 
 def begin(stream):
+    global _CAPTURING, _GC_WAS_ON
     assert _hip().hipStreamBeginCapture(_stream(stream), 0) == 0
+    if _CAPTURING == 0:
+        _GC_WAS_ON = gc.isenabled()
+        gc.disable()
+    _CAPTURING += 1
 
 
 def _end(stream):
+    global _CAPTURING
     graph = V()
-    return _hip().hipStreamEndCapture(_stream(stream), ctypes.byref(graph)), graph
+    rc = _hip().hipStreamEndCapture(_stream(stream), ctypes.byref(graph))
+    _CAPTURING -= 1
+    if _CAPTURING == 0 and _GC_WAS_ON:
+        gc.enable()
+    return rc, graph
 
 
 def end(stream):
