@@ -70,4 +70,9 @@ COMPANIONS = {
         ("dcs_bf_beamform_accumulated_complex_q8_dt", c_int,
          [_VP, c_float, c_uint32, _VP, c_size_t, _VP, c_uint32, _VP, _VP, c_size_t, _VP, _VP]),
     ]),
+    # full-Stokes detection of two polarisations' int8 beams: exact block I or I, Q, U, V, integrated like the incoherent beam
+    "stokes": Companion("dcs_stokes.h", "bf_stokes.cpp", "libdcs_stokes.so", [
+        ("dcs_bf_stokes_block", c_int, [_VP, c_uint32, _VP, _VP, c_size_t, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_integrate_stokes", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+    ]),
 }

@@ -1,7 +1,8 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
-// incoherent beam (include/dcs_incoherent_beam.h) and the search filterbanks (include/dcs_filterbank.h), each reached
-// through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its
-// device, nothing else.  Host code only; the kernels are in bf_beamform_mfma.hip, bf_incoherent.hip and bf_filterbank.hip.
+// incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h) and the Stokes
+// detection of 8-bit beams (include/dcs_stokes.h), each reached through the table at the head of every context
+// (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Host code only; the kernels
+// are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip and bf_stokes.hip.
 
 #include <cstring>
 
@@ -167,6 +168,53 @@ int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra
     a.descending = flags & 1u;
     a.level = level;
     return (int)bf_launch_filterbank_q8(a, as_stream(stream));
+}
+
+// include/dcs_stokes.h, reached the same way.  No coefficients, nothing allocated, and math_mode plays no part.
+int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
+                      uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream)
+{
+    if (!c || !d_beams_x || !d_beams_y || !d_block_stokes || (nr_stokes != 1u && nr_stokes != 4u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (misaligned(d_beams_x, 15u) || misaligned(d_beams_y, 15u) || misaligned(d_block_stokes, 4u * nr_stokes - 1u) || nt % 16u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
+    if (!holds(beams_bytes, C, nt, B, 2u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(stokes_bytes, C, nt / 16u, B, (uint64_t)nr_stokes * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_stokes_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.beams_x = d_beams_x;
+    a.beams_y = d_beams_y;
+    a.block_stokes = d_block_stokes;
+    a.rows = (uint64_t)C * (nt / 16u) * B;
+    a.nr_stokes = nr_stokes;
+    return (int)bf_launch_stokes_block(a, as_stream(stream));
+}
+
+int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
+                          uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
+                          size_t spectra_bytes, void *stream)
+{
+    if (!c || !d_block_stokes || !d_spectra || (nr_stokes != 1u && nr_stokes != 4u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (misaligned(d_block_stokes, 4u * nr_stokes - 1u) || misaligned(d_spectra, 4u * nr_stokes - 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
+    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
+    if ((uint64_t)B * nr_stokes > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
+    if (!holds(stokes_bytes, C, nr_blocks, B, (uint64_t)nr_stokes * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(spectra_bytes, n_spectra, C, B, (uint64_t)nr_stokes * sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_stokes_int_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_stokes = d_block_stokes;
+    a.spectra = d_spectra;
+    a.bs = B * nr_stokes;
+    a.total = n_spectra * C * a.bs;
+    a.C = C;
+    a.nr_blocks = nr_blocks;
+    a.n = blocks_per_spectrum;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_stokes_integrate(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -1,11 +1,11 @@
 // bf_ctx_ext.h -- the internal contract between libdcs_beamformer.so and its companions libdcs_beam_weights.so
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
-// (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h) and libdcs_beam_complex_quant.so
-// (include/dcs_beam_complex_quant.h).  All are built from this tree
+// (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
+// (include/dcs_beam_complex_quant.h) and libdcs_stokes.so (include/dcs_stokes.h).  All are built from this tree
 // together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam and of the filterbank calls; a companion checks the arguments it can check
+// beam, of the filterbank calls and of the Stokes detection; a companion checks the arguments it can check
 // without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
@@ -22,7 +22,9 @@
 // 7: beamform_accumulated_complex, beamform_accumulated_complex_power appended (tests/test_host_abi_beam_complex.py hands its
 // companion the foreign versions 1, 3, 5 and 6).
 // 8: beamform_accumulated_complex_q8 appended (tests/test_host_abi_beam_complex_quant.py hands its companion 1, 6 and 7).
-#define BF_CTX_EXT_VERSION 8u
+// 9: stokes_block, integrate_stokes appended (tests/test_host_abi_stokes.py hands its companion 1, 7 and 8; the older tests
+// hand foreign versions 1 to 7 only).
+#define BF_CTX_EXT_VERSION 9u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -77,6 +79,13 @@ struct bf_ctx_ext_ops {
                                            const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                            const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
                                            unsigned long long *d_clip_count, void *stream);
+    // full-Stokes detection (include/dcs_stokes.h): two int8 beam tensors [C][nt / 16][B][16][2] -> exact block Stokes int32
+    // [C][nt / 16][B][nr_stokes]; block Stokes [C][nr_blocks][B][nr_stokes] -> spectra [nr_blocks / blocks_per_spectrum][C][B][nr_stokes]
+    int (*stokes_block)(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
+                        uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream);
+    int (*integrate_stokes)(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
+                            uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
+                            size_t spectra_bytes, void *stream);
 };
 
 // the first member of struct dcs_bf_context

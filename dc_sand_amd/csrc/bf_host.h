@@ -131,8 +131,8 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 // bf_capi_beamform.hip: the terms table and class words (the generator's rows form writes the same table)
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
-// the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, and the
-// complex product's three in bf_capi_beamform.hip again
+// the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
+// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two in bf_capi_detect.hip
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -169,6 +169,11 @@ int beamform_accumulated_complex_q8_impl(dcs_bf_context *c, const float *dt_coef
                                          const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                          const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
                                          unsigned long long *d_clip_count, void *stream);
+int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
+                      uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream);
+int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
+                          uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
+                          size_t spectra_bytes, void *stream);
 
 } // namespace bf_host
 

@@ -246,6 +246,31 @@ struct bf_incoh_int_args {
 hipError_t bf_launch_incoherent_integrate(const bf_incoh_int_args &a, hipStream_t stream);
 hipError_t bf_warm_module_incoherent();
 
+// Full-Stokes detection (bf_stokes.hip; include/dcs_stokes.h): two int8 beam tensors as
+// rows = C * nT16 * B rows of 32 bytes each, every row pair reduced to nr_stokes exact dwords of block_stokes [C][nT16][B][nr_stokes]
+struct bf_stokes_args {
+    const int8_t *beams_x; // [rows][16][2], 16-byte aligned; polarisation x
+    const int8_t *beams_y; // the same of polarisation y; may be beams_x
+    int32_t *block_stokes; // [rows][nr_stokes], aligned to 4 * nr_stokes bytes
+    uint64_t rows;
+    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
+    uint32_t nr_stokes;    // 1 (I) or 4 (I, Q, U, V)
+};
+hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream);
+// Block Stokes [C][nr_blocks][bs] summed n at a time, exactly, into spectra [nr_blocks / n][C][bs]
+struct bf_stokes_int_args {
+    const int32_t *block_stokes;
+    float *spectra;
+    uint64_t total;      // (nr_blocks / n) * C * bs
+    uint32_t bs;         // B * nr_stokes
+    uint32_t C;
+    uint32_t nr_blocks;  // a multiple of n
+    uint32_t n;          // blocks per spectrum, >= 1
+    uint32_t accumulate; // non-zero: the rounded sums are added to what spectra holds
+};
+hipError_t bf_launch_stokes_integrate(const bf_stokes_int_args &a, hipStream_t stream);
+hipError_t bf_warm_module_stokes();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

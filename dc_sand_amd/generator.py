@@ -122,6 +122,23 @@ def incoherent_spectra_bytes(params: BeamformerParameters, nr_blocks: int, block
     return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * 4
 
 
+def block_stokes_bytes(params: BeamformerParameters, nt: int, nr_stokes: int) -> int:
+    """Size of the block Stokes tensor ``int32 [C][nt / 16][B][nr_stokes]`` of :meth:`SteeringCoefficientGenerator.stokes_block`."""
+    if nr_stokes not in (1, 4):
+        raise ValueError("nr_stokes must be 1 (I) or 4 (I, Q, U, V)")
+    return int(params.NR_CHANNELS) * (int(nt) // 16) * int(params.NR_BEAMS) * int(nr_stokes) * 4
+
+
+def stokes_spectra_bytes(params: BeamformerParameters, nr_blocks: int, blocks_per_spectrum: int, nr_stokes: int) -> int:
+    """Size of the spectra ``float [nr_blocks / blocks_per_spectrum][C][B][nr_stokes]`` of
+    :meth:`SteeringCoefficientGenerator.integrate_stokes`."""
+    if blocks_per_spectrum <= 0 or nr_blocks % blocks_per_spectrum:
+        raise ValueError("nr_blocks must be a multiple of blocks_per_spectrum >= 1")
+    if nr_stokes not in (1, 4):
+        raise ValueError("nr_stokes must be 1 (I) or 4 (I, Q, U, V)")
+    return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * int(params.NR_BEAMS) * int(nr_stokes) * 4
+
+
 def spectra_sums_bytes(params: BeamformerParameters, nr_beams: int) -> int:
     """Size of the running sums ``double [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.spectra_sums`."""
     return int(params.NR_CHANNELS) * int(nr_beams) * 16
@@ -361,8 +378,35 @@ class SteeringCoefficientGenerator:
                                                    int(spectra_bytes), _s(stream)),
               "dcs_bf_integrate_incoherent_power")
 
+    # -- full-Stokes detection of two polarisations' 8-bit beams (include/dcs_stokes.h, companion library libdcs_stokes.so):
+    #    d_beams_x and d_beams_y are device int8 [C][nt / 16][B][16][2] arrays (what beamform_accumulated_complex_q8 writes),
+    #    d_block_stokes a device int32 [C][nt / 16][B][nr_stokes] array, d_spectra a device float
+    #    [nr_blocks / blocks_per_spectrum][C][B][nr_stokes] array
+    def stokes_block(self, d_beams_x, d_beams_y, beams_bytes: int, d_block_stokes, stokes_bytes: int, nt: int, nr_stokes: int = 4,
+                     stream=None) -> None:
+        """The Stokes parameters of every 16-sample block of the beams of polarisations x and y, as exact integers
+        (:func:`block_stokes_bytes`): ``I = Pxx + Pyy`` with ``nr_stokes = 1``; ``I``, ``Q = Pxx - Pyy``,
+        ``U = 2 Re sum x conj(y)``, ``V = 2 Im sum x conj(y)``, innermost, with ``nr_stokes = 4``."""
+        sl = _lib.companion("stokes")
+        check(sl.dcs_bf_stokes_block(c_void_p(self._h), int(nt), _p(d_beams_x), _p(d_beams_y), int(beams_bytes), int(nr_stokes),
+                                     _p(d_block_stokes), int(stokes_bytes), _s(stream)),
+              "dcs_bf_stokes_block")
+
+    def integrate_stokes(self, d_block_stokes, stokes_bytes: int, nr_blocks: int, blocks_per_spectrum: int, nr_stokes: int,
+                         d_spectra, spectra_bytes: int, accumulate: bool = False, stream=None) -> None:
+        """Sums the block Stokes parameters ``[C][nr_blocks][B][nr_stokes]`` ``blocks_per_spectrum`` at a time, exactly,
+        into the spectra ``[nr_blocks / blocks_per_spectrum][C][B][nr_stokes]`` (:func:`stokes_spectra_bytes`), each sum
+        rounded to float once; with ``accumulate`` it is added to what ``d_spectra`` holds, so an integration can span
+        calls.  The spectra are those of the filterbank calls with ``nr_beams = nr_stokes * B``."""
+        sl = _lib.companion("stokes")
+        check(sl.dcs_bf_integrate_stokes(c_void_p(self._h), _p(d_block_stokes), int(stokes_bytes), int(nr_blocks),
+                                         int(blocks_per_spectrum), int(nr_stokes), 1 if accumulate else 0, _p(d_spectra),
+                                         int(spectra_bytes), _s(stream)),
+              "dcs_bf_integrate_stokes")
+
     # -- 8-bit search filterbanks (include/dcs_filterbank.h, companion library libdcs_filterbank.so): d_spectra is a device
-    #    float [nr_spectra][C][nr_beams] array -- nr_beams the context's for detected spectra, 1 for incoherent ones
+    #    float [nr_spectra][C][nr_beams] array -- nr_beams the context's for detected spectra, 1 for incoherent ones, 4 times
+    #    the context's for IQUV Stokes spectra
     def spectra_sums(self, d_spectra, spectra_bytes: int, nr_spectra: int, nr_beams: int, d_sums, sums_bytes: int,
                      accumulate: bool = False, stream=None) -> None:
         """Running fp64 sums ``{sum x, sum x^2}`` per (channel, beam) over the spectra, in time order, into ``d_sums``

@@ -34,6 +34,9 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the incoherent beam against the read probe (dcs_probe_reduce) over the same bytes and against the detecting call
         at 16 and 256 beams, alternating, in one process; --trace: a few launches of each kernel for
         `rocprofv3 --kernel-trace --stats -- python3 tools/measure.py incoh --trace`  -> profiles/r07_incoherent_beam.md
+    python tools/measure.py stokes [--rounds 5]
+        the Stokes detection of two polarisations' 8-bit beams at IQUV and at I against the incoherent beam over the same
+        bytes (the same load pattern), alternating, in one process, and the integration  -> profiles/r12_stokes.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -719,6 +722,80 @@ def cmd_incoh(args):
         print(json.dumps({"incoh": rows}), flush=True)
 
 
+def cmd_stokes(args):
+    """The Stokes detection of two polarisations' 8-bit beams (include/dcs_stokes.h), read-bound: per (beam, sample) 4 bytes
+    read and 1 (IQUV) or 0.25 (I) written.  Per shape B x C x nt, in turn ``--rounds`` times in one process on the same
+    noise-like bytes: the block call at IQUV and at I, the incoherent beam's block call over the very same bytes (x and y
+    are the halves of one buffer, which a context of min(2 B, 256) antennas reads as one sample tensor: the yardstick,
+    since it has the same load pattern), and the integration of the IQUV blocks.  Inputs above the 256 MiB Infinity
+    Cache are read from one buffer; the shape that would fit rotates over three."""
+    from dc_sand_amd.generator import (block_stokes_bytes, incoherent_block_power_bytes, quantised_beams_bytes,
+                                       stokes_spectra_bytes)
+
+    rows = []
+    for B, C, nt, nbuf in [(16, 32768, 256, 1), (256, 4096, 256, 1), (64, 4096, 256, 3)]:
+        nblk = nt // 16
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        qb = quantised_beams_bytes(bp, nt)
+        bufs = [device.mem_alloc(2 * qb) for _ in range(nbuf)]
+        for d in bufs:
+            _noise(d, 2 * qb)
+        turn = [0]
+
+        def buf():
+            turn[0] = (turn[0] + 1) % nbuf
+            return int(bufs[turn[0]])
+        g = SteeringCoefficientGenerator(bp)
+        A = min(2 * B, 256)
+        bpi = BeamformerParameters(NR_CHANNELS=C * 2 * B // A, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=nt)
+        gi = SteeringCoefficientGenerator(bpi)
+        sb4, sb1 = block_stokes_bytes(bp, nt, 4), block_stokes_bytes(bp, nt, 1)
+        pb, spb = incoherent_block_power_bytes(bpi, nt), stokes_spectra_bytes(bp, nblk, nblk, 4)
+        d_bs, d_p, d_s = device.mem_alloc(sb4), device.mem_alloc(pb), device.mem_alloc(spb)
+
+        def iquv():
+            d = buf()
+            g.stokes_block(d, d + qb, qb, d_bs, sb4, nt, nr_stokes=4)
+
+        def only_i():
+            d = buf()
+            g.stokes_block(d, d + qb, qb, d_bs, sb1, nt, nr_stokes=1)
+        incoh = lambda: gi.incoherent_block_power(buf(), 2 * qb, d_p, pb, nt)  # noqa: E731
+        integ = lambda: g.integrate_stokes(d_bs, sb4, nblk, nblk, 4, d_s, spb)  # noqa: E731
+        t = {name: [] for name in ("iquv", "i", "incoh", "incoh_again", "int")}
+        for fn in (iquv, only_i, incoh, integ):
+            fn()
+        for _ in range(args.rounds):
+            t["iquv"].append(per_launch_ms(iquv))
+            t["incoh"].append(per_launch_ms(incoh))
+            t["i"].append(per_launch_ms(only_i))
+            t["incoh_again"].append(per_launch_ms(incoh))
+        iquv()
+        for _ in range(args.rounds):
+            t["int"].append(per_launch_ms(integ))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        both = t["incoh"] + t["incoh_again"]
+        tbps = lambda nbytes, ms: round(nbytes / (ms * 1e-3) / 1e12, 2)  # noqa: E731
+        incoh_ms = float(np.median(both))
+        row = {"shape": f"{B}x{C}x{nt}", "read_MiB": (2 * qb) >> 20, "buffers": nbuf,
+               "cache": "rotated" if nbuf > 1 else "above the Infinity Cache",
+               "iquv_us": round(med["iquv"] * 1e3, 1), "iquv_moved_TBps": tbps(2 * qb + sb4, med["iquv"]),
+               "iquv_read_TBps": tbps(2 * qb, med["iquv"]),
+               "i_us": round(med["i"] * 1e3, 1), "i_moved_TBps": tbps(2 * qb + sb1, med["i"]), "i_read_TBps": tbps(2 * qb, med["i"]),
+               "incoh_us": round(incoh_ms * 1e3, 1), "incoh_read_TBps": tbps(2 * qb, incoh_ms),
+               "incoh_spread": round(max(both) / min(both) - 1.0, 4),
+               "iquv_read_rate_over_incoh": round(incoh_ms / med["iquv"], 4), "i_read_rate_over_incoh": round(incoh_ms / med["i"], 4),
+               "iquv_moved_rate_over_incoh_read": round(incoh_ms / med["iquv"] * (2 * qb + sb4) / (2 * qb), 4),
+               "int_us": round(med["int"] * 1e3, 1)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        gi.close()
+        for d in bufs + [d_bs, d_p, d_s]:
+            d.free()
+    print(json.dumps({"stokes": rows}), flush=True)
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1139,6 +1216,8 @@ def main():
     p = sub.add_parser("incoh")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the new call and the read probe per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
+    p = sub.add_parser("stokes")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the IQUV call, the I call and the incoherent beam per shape")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1183,7 +1262,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
