@@ -734,10 +734,28 @@ def test_config4_one_rank_shard_at_full_size_every_element(gpu, oracle, probes, 
     buf.free()
 
 
-@pytest.mark.parametrize("script,args", [("steering_coefficients.py", ["16", "24", "512"]), ("streaming_ticks.py", ["16", "64", "2048", "256", "20"])])
+# What each script's closing line says once it has verified itself.  tied_array_beam.py ends with its table of beams, whose
+# row of the source carries the mark; the two statistical scripts (a planted source that must stand out of the other beams)
+# keep the antenna counts of their defaults, the bit-for-bit ones take ragged counts.
+EXAMPLE_CLOSING = {
+    "steering_coefficients.py": "max ULP distance to the CPU verifier",
+    "streaming_ticks.py": "max ULP distance to the CPU verifier",
+    "detected_beams.py": "bit-identical to the contract applied to the float call's beams: True",
+    "incoherent_beam.py": "bit-identical to the integer contract: True",
+    "search_filterbank.py": "bit-identical to the model: detected beams True - incoherent beam True",
+    "tied_array_beam.py": "<- the source",
+    "hierarchical_beams.py": "stage 2, mean |beam|: beam 0:",
+    "dual_pol_stokes.py": "bit-identical to the integer contract: True",
+}
+
+
+@pytest.mark.parametrize("script,args", [("steering_coefficients.py", ["16", "24", "512"]), ("streaming_ticks.py", ["16", "64", "2048", "256", "20"]),
+                                         ("detected_beams.py", ["20", "5", "6"]), ("incoherent_beam.py", ["20", "5", "6"]),
+                                         ("search_filterbank.py", ["20", "5", "6"]), ("tied_array_beam.py", ["64", "16", "2"]),
+                                         ("hierarchical_beams.py", ["64", "8", "2"]), ("dual_pol_stokes.py", ["20", "5", "6"])])
 def test_examples_run_and_verify_themselves(gpu, script, args):
-    """examples/: the pycuda-shaped host pattern and the config-5 stream with device tables, on small shapes; each verifies
-    its own output against the oracle and exits 0."""
+    """examples/: all eight scripts on small shapes, a fresh process each; each verifies its own output (against the oracle,
+    a model, or the source it planted), says so in its closing line and exits 0."""
     import subprocess
     import sys
     from pathlib import Path
@@ -745,7 +763,7 @@ def test_examples_run_and_verify_themselves(gpu, script, args):
     root = Path(__file__).resolve().parent.parent
     res = subprocess.run([sys.executable, str(root / "examples" / script), *args], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
-    assert "max ULP distance to the CPU verifier" in res.stdout
+    assert EXAMPLE_CLOSING[script] in res.stdout, res.stdout[-1500:]
 
 
 def test_cpp_host_against_c_abi(gpu):
