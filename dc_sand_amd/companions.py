@@ -75,4 +75,11 @@ COMPANIONS = {
         ("dcs_bf_stokes_block", c_int, [_VP, c_uint32, _VP, _VP, c_size_t, c_uint32, _VP, c_size_t, _VP]),
         ("dcs_bf_integrate_stokes", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
     ]),
+    # incoherent dedispersion of the 8-bit filterbanks: the delay table of a band and DMs, and exact uint32 DM-time planes
+    "dedisperse": Companion("dcs_dedisperse.h", "bf_dedisperse.cpp", "libdcs_dedisperse.so", [
+        ("dcs_bf_dm_delays", c_int, [_VP, _VP, _VP, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_dedisperse_q8", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, _VP, c_uint32, c_uint32, _VP, _VP, c_size_t, c_uint64,
+          c_uint64, _VP]),
+    ]),
 }

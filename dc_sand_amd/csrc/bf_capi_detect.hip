@@ -1,9 +1,11 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
-// incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h) and the Stokes
-// detection of 8-bit beams (include/dcs_stokes.h), each reached through the table at the head of every context
-// (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Host code only; the kernels
-// are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip and bf_stokes.hip.
+// incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
+// detection of 8-bit beams (include/dcs_stokes.h) and the dedispersion of the filterbanks (include/dcs_dedisperse.h), each
+// reached through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and
+// its device, nothing else.  Host code only; the kernels are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip,
+// bf_stokes.hip and bf_dedisperse.hip.
 
+#include <cmath>
 #include <cstring>
 
 #include "bf_host.h"
@@ -215,6 +217,65 @@ int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size
     a.n = blocks_per_spectrum;
     a.accumulate = accumulate ? 1u : 0u;
     return (int)bf_launch_stokes_integrate(a, as_stream(stream));
+}
+
+// include/dcs_dedisperse.h, reached the same way.  No coefficients, nothing allocated, and math_mode plays no part; the band
+// is host memory and travels by value in the kernel's arguments.
+int dm_delays_impl(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
+                   size_t delays_bytes, void *stream)
+{
+    if (!c || !band || !d_dms || !d_delays || misaligned(d_dms, 7u) || misaligned(d_delays, 3u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(band->freq_first_mhz) || !std::isfinite(band->freq_step_mhz) || !std::isfinite(band->sample_time_s) ||
+        !(band->sample_time_s > 0.0) || !(band->freq_first_mhz > 0.0))
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    const double f_last = band->freq_first_mhz + (double)(C - 1u) * band->freq_step_mhz; // the kernel's own f_(C-1)
+    if (!(f_last > 0.0) || !std::isfinite(f_last)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(delays_bytes, nr_dm, C, sizeof(int32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dmdelay_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.dms = d_dms;
+    a.delays = d_delays;
+    a.total = (uint64_t)nr_dm * C;
+    a.C = C;
+    a.freq_first = band->freq_first_mhz;
+    a.freq_step = band->freq_step_mhz;
+    a.sample_time = band->sample_time_s;
+    return (int)bf_launch_dm_delays(a, as_stream(stream));
+}
+
+int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                       uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
+                       uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
+                       uint64_t out_spectra, uint64_t first_out, void *stream)
+{
+    if (!c || !d_filterbank || !d_delays || !d_dm_time || misaligned(d_filterbank, 15u) || misaligned(d_delays, 3u) ||
+        misaligned(d_dm_time, 3u) || nr_beams == 0u || max_delay > 0x7ffffffeu)
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (first_spectrum > in_spectra || (uint64_t)nr_spectra + max_delay > in_spectra - first_spectrum || first_out > out_spectra ||
+        nr_spectra > out_spectra - first_out)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(dm_time_bytes, nr_beams, nr_dm, out_spectra, sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dedisp_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.delays = d_delays;
+    a.mask = d_channel_mask;
+    a.out = d_dm_time;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.out_spectra = out_spectra;
+    a.first_out = first_out;
+    a.C = C;
+    a.B = nr_beams;
+    a.T = nr_spectra;
+    a.nr_dm = nr_dm;
+    a.max_delay = max_delay;
+    return (int)bf_launch_dedisperse(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -2,10 +2,10 @@
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
-// (include/dcs_beam_complex_quant.h) and libdcs_stokes.so (include/dcs_stokes.h).  All are built from this tree
-// together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
+// (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h) and libdcs_dedisperse.so
+// (include/dcs_dedisperse.h).  All are built from this tree together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls and of the Stokes detection; a companion checks the arguments it can check
+// beam, of the filterbank calls, of the Stokes detection and of the dedispersion; a companion checks the arguments it can check
 // without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/dcs_beamformer.h"
+#include "../../include/dcs_dedisperse.h" // dcs_bf_band
 
 // 2: beamform_accumulated_q8 appended; 3: beamform_accumulated_power, integrate_block_power appended; 5: incoherent_block_power,
 // integrate_incoherent_power appended.  4 is skipped for good: tests/test_host_abi_beam_power.py hands the power companion a
@@ -24,7 +25,9 @@
 // 8: beamform_accumulated_complex_q8 appended (tests/test_host_abi_beam_complex_quant.py hands its companion 1, 6 and 7).
 // 9: stokes_block, integrate_stokes appended (tests/test_host_abi_stokes.py hands its companion 1, 7 and 8; the older tests
 // hand foreign versions 1 to 7 only).
-#define BF_CTX_EXT_VERSION 9u
+// 10: dm_delays, dedisperse_q8 appended (tests/test_host_abi_dedisperse.py hands its companion 1, 8 and 9; no older test
+// hands a foreign version above 8).
+#define BF_CTX_EXT_VERSION 10u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -86,6 +89,14 @@ struct bf_ctx_ext_ops {
     int (*integrate_stokes)(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
                             uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
                             size_t spectra_bytes, void *stream);
+    // incoherent dedispersion (include/dcs_dedisperse.h): a band (host memory) and DMs double [nr_dm] -> delays int32
+    // [nr_dm][C]; filterbanks uint8 [nr_beams][in_spectra][C] and delays -> DM-time planes uint32 [nr_beams][nr_dm][out_spectra]
+    int (*dm_delays)(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
+                     size_t delays_bytes, void *stream);
+    int (*dedisperse_q8)(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                         uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
+                         uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
+                         uint64_t out_spectra, uint64_t first_out, void *stream);
 };
 
 // the first member of struct dcs_bf_context

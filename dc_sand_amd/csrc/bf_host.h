@@ -132,7 +132,8 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
 // the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
-// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two in bf_capi_detect.hip
+// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two and the dedispersion's two in
+// bf_capi_detect.hip
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -174,6 +175,12 @@ int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, c
 int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
                           uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
                           size_t spectra_bytes, void *stream);
+int dm_delays_impl(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
+                   size_t delays_bytes, void *stream);
+int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                       uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
+                       uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
+                       uint64_t out_spectra, uint64_t first_out, void *stream);
 
 } // namespace bf_host
 

@@ -271,6 +271,30 @@ struct bf_stokes_int_args {
 hipError_t bf_launch_stokes_integrate(const bf_stokes_int_args &a, hipStream_t stream);
 hipError_t bf_warm_module_stokes();
 
+// Incoherent dedispersion (bf_dedisperse.hip; include/dcs_dedisperse.h).
+// The delay table int32 [nr_dm][C] of a band and DMs, in fp64 rounded once per operation
+struct bf_dmdelay_args {
+    const double *dms; // [nr_dm], 8-byte aligned; read when the work runs
+    int32_t *delays;   // [nr_dm][C]
+    uint64_t total;    // nr_dm * C
+    uint32_t C;
+    double freq_first, freq_step, sample_time;
+};
+hipError_t bf_launch_dm_delays(const bf_dmdelay_args &a, hipStream_t stream);
+// Filterbanks uint8 [B][in_spectra][C] shifted by the table and summed over the columns into out uint32 [B][nr_dm][out_spectra],
+// words first_out .. first_out + T - 1 of every series
+struct bf_dedisp_args {
+    const uint8_t *in;     // 16-byte aligned
+    const int32_t *delays; // [nr_dm][C]; read when the work runs; an entry outside [0, max_delay] drops its term
+    const uint8_t *mask;   // nullptr (every column), or [C]: a zero byte drops the column
+    uint32_t *out;
+    uint64_t in_spectra, first, out_spectra, first_out;
+    uint32_t C, B, T, nr_dm, max_delay;
+    uint32_t t_tiles, dm_tiles; // filled by the launcher: tiles of output times and of DMs
+};
+hipError_t bf_launch_dedisperse(const bf_dedisp_args &a, hipStream_t stream);
+hipError_t bf_warm_module_dedisperse();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

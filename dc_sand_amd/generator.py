@@ -154,6 +154,21 @@ def filterbank_bytes(params: BeamformerParameters, nr_beams: int, out_spectra: i
     return int(nr_beams) * int(out_spectra) * int(params.NR_CHANNELS)
 
 
+def dm_delays_bytes(params: BeamformerParameters, nr_dm: int) -> int:
+    """Size of the delay table ``int32 [nr_dm][C]`` of :meth:`SteeringCoefficientGenerator.dm_delays`."""
+    return int(nr_dm) * int(params.NR_CHANNELS) * 4
+
+
+def dm_time_bytes(nr_beams: int, nr_dm: int, out_spectra: int) -> int:
+    """Size of the DM-time planes ``uint32 [nr_beams][nr_dm][out_spectra]`` of
+    :meth:`SteeringCoefficientGenerator.dedisperse_q8`."""
+    return int(nr_beams) * int(nr_dm) * int(out_spectra) * 4
+
+
+class _Band(ctypes.Structure):  # dcs_bf_band (include/dcs_dedisperse.h)
+    _fields_ = [("freq_first_mhz", ctypes.c_double), ("freq_step_mhz", ctypes.c_double), ("sample_time_s", ctypes.c_double)]
+
+
 def gpu_utilisation(params: BeamformerParameters, kernel_ms: float) -> tuple[float, float]:
     """``BeamformerCoeffTest::get_time`` model (``BeamformerCoefficientTest.cu:426-448``)."""
     out = (c_float * 2)()
@@ -437,6 +452,33 @@ class SteeringCoefficientGenerator:
                                       int(filterbank_bytes), int(out_spectra), int(first_spectrum), _p_or_null(d_clip_count),
                                       _s(stream)),
               "dcs_bf_filterbank_q8")
+
+    # -- incoherent dedispersion of those filterbanks (include/dcs_dedisperse.h, companion library libdcs_dedisperse.so):
+    #    d_delays a device int32 [nr_dm][C] array, d_dm_time a device uint32 [nr_beams][nr_dm][out_spectra] array
+    def dm_delays(self, freq_first_mhz: float, freq_step_mhz: float, sample_time_s: float, d_dms, nr_dm: int, d_delays,
+                  delays_bytes: int, stream=None) -> None:
+        """The delays, in whole spectra of ``sample_time_s``, of every filterbank column (column ``j`` at
+        ``freq_first_mhz + j * freq_step_mhz``) against the band's highest column for the DMs of the device
+        ``double [nr_dm]`` array ``d_dms``, into ``d_delays`` (:func:`dm_delays_bytes`); fp64, rounded once per operation."""
+        band = _Band(float(freq_first_mhz), float(freq_step_mhz), float(sample_time_s))
+        dl = _lib.companion("dedisperse")
+        check(dl.dcs_bf_dm_delays(c_void_p(self._h), ctypes.cast(ctypes.pointer(band), c_void_p), _p(d_dms), int(nr_dm),
+                                  _p(d_delays), int(delays_bytes), _s(stream)),
+              "dcs_bf_dm_delays")
+
+    def dedisperse_q8(self, d_filterbank, filterbank_bytes: int, in_spectra: int, first_spectrum: int, nr_spectra: int,
+                      nr_beams: int, d_delays, nr_dm: int, max_delay: int, d_dm_time, dm_time_bytes: int, out_spectra: int,
+                      first_out: int = 0, d_channel_mask=None, stream=None) -> None:
+        """Per beam, DM ``m`` and ``t < nr_spectra``: word ``first_out + t`` of series ``m`` of the planes
+        (:func:`dm_time_bytes`) becomes the exact sum over the columns ``c`` of filterbank byte
+        ``[first_spectrum + t + d_delays[m][c]][c]``; entries outside ``[0, max_delay]`` and the columns whose byte of
+        ``d_channel_mask`` (``None``, or a device ``uint8 [C]`` array) is zero drop out."""
+        dl = _lib.companion("dedisperse")
+        check(dl.dcs_bf_dedisperse_q8(c_void_p(self._h), _p(d_filterbank), int(filterbank_bytes), int(in_spectra),
+                                      int(first_spectrum), int(nr_spectra), int(nr_beams), _p(d_delays), int(nr_dm),
+                                      int(max_delay), _p_or_null(d_channel_mask), _p(d_dm_time), int(dm_time_bytes),
+                                      int(out_spectra), int(first_out), _s(stream)),
+              "dcs_bf_dedisperse_q8")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

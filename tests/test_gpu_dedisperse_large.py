@@ -1,0 +1,118 @@
+"""The dedispersion held to its 64-bit offsets (include/dcs_dedisperse.h): filterbanks and a plane past 2^32 bytes, which
+never exist on the host (helpers/large_tensor.py: the filling, the pattern whose period does not divide 2^32, the row
+reads).  A byte offset worked out in 32 bits wraps inside the same allocation, 4 GiB lower: nothing faults and no canary is
+touched, so the filterbanks hold a pattern in which the rows 4 GiB apart differ, and the plane is prefilled so that a
+wrapped store shows both above the line (the prefill stays) and below it (the prefill is spoiled).  Every other test of
+the dedispersion passes with 32-bit offsets; these two do not."""
+import numpy as np
+import pytest
+
+from helpers import large_tensor as lt
+from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
+
+pytestmark = pytest.mark.gpu
+
+CANARY = 64
+PREFILL = 0xA5
+PREFILL_WORD = 0xA5A5A5A5
+C = 64
+
+
+@pytest.fixture
+def case(gpu):
+    from dc_sand_amd import BeamformerParameters
+    from dc_sand_amd.generator import SteeringCoefficientGenerator
+
+    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1))
+    held = []
+
+    def alloc(nbytes):
+        held.append(gpu.mem_alloc(nbytes))
+        return held[-1]
+
+    yield g, alloc
+    gpu.synchronize()
+    g.close()
+    for a in held:
+        a.free()
+
+
+def test_filterbanks_past_the_line(gpu, case):
+    """B = 2, C = 64, in_spectra = 2^25 + 8192: 4,296,015,872 bytes, and row 2^25 - 8192 of beam 1 begins on the line.  4096
+    outputs of 7 DMs from windows that end below the line, straddle it and begin above it, and beam 0's alongside."""
+    from dc_sand_amd.generator import dm_time_bytes
+
+    g, alloc = case
+    B, T, in_spectra = 2, 4096, (1 << 25) + 8192
+    nbytes = B * in_spectra * C
+    line_row = (lt.LINE - in_spectra * C) // C  # of beam 1
+    assert lt.LINE < nbytes < 1.01 * lt.LINE and in_spectra * C < lt.LINE and line_row == (1 << 25) - 8192
+    table = dm_delays(C, *BAND_DESCENDING_64, DMS_40[33:])
+    nr_dm, max_delay = table.shape[0], int(table.max())
+    window = T + max_delay
+    assert 1300 < max_delay < 1340 and window < 8192
+    pattern = lt.int8_pattern(C, seed=21)
+    d_fb = alloc(nbytes)
+    lt.fill(gpu, d_fb, nbytes, pattern)
+    d_delays = alloc(table.nbytes)
+    gpu.memcpy_htod(d_delays, table)
+    pbytes = dm_time_bytes(B, nr_dm, T)
+    d_out = alloc(pbytes + CANARY)
+    firsts = [line_row - window, line_row - window // 2, line_row - 1, line_row, line_row + 100, in_spectra - window]
+    for first in firsts:
+        assert 0 <= first and first + window <= in_spectra
+        gpu.memset(d_out, PREFILL, pbytes + CANARY)
+        g.dedisperse_q8(d_fb, nbytes, in_spectra, first, T, B, d_delays, nr_dm, max_delay, d_out, pbytes, T)
+        gpu.synchronize()
+        host = np.empty(pbytes + CANARY, np.uint8)
+        gpu.memcpy_dtoh(host, d_out)
+        assert np.all(host[pbytes:] == PREFILL), "written past the plane"
+        got = host[:pbytes].view(np.uint32).reshape(B, nr_dm, T)
+        rows = first + np.arange(window, dtype=np.int64)
+        fb = np.stack([lt.rows_of(pattern, b * in_spectra + rows) for b in range(B)])  # [B][window][C] from the pattern
+        exp = dedisperse(fb, table, 0, T, max_delay)
+        assert np.unique(exp).size >= 100 and not np.array_equal(exp[0], exp[1])
+        assert np.array_equal(got, exp), (first, np.argwhere(got != exp)[:3])
+    # what the device holds is the pattern: the rows on both sides of the line, read back
+    sample = np.array([0, 1, in_spectra + line_row - 1, in_spectra + line_row, B * in_spectra - 1], dtype=np.int64)
+    assert np.array_equal(lt.read_rows(gpu, d_fb, C, sample), lt.rows_of(pattern, sample))
+
+
+def test_plane_past_the_line(gpu, case):
+    """nr_dm = 4, out_spectra = 2^28 + 4096: 4,295,032,832 bytes.  1024 outputs at the end of every series: those of DM 3
+    lie past the line, and the words 4 GiB below them -- words 15360 .. 16383 of DM 0 -- keep the prefill."""
+    from dc_sand_amd.generator import dm_time_bytes
+
+    g, alloc = case
+    B, T, nr_dm, out_spectra = 1, 1024, 4, (1 << 28) + 4096
+    first_out = out_spectra - T
+    pbytes = dm_time_bytes(B, nr_dm, out_spectra)
+    assert lt.LINE < pbytes < 1.01 * lt.LINE and (3 * out_spectra + first_out) * 4 > lt.LINE
+    table = dm_delays(C, *BAND_DESCENDING_64, DMS_40[36:])
+    assert table.shape[0] == nr_dm
+    max_delay = int(table.max())
+    fb = np.random.default_rng(22).integers(0, 256, size=(B, 3 + T + max_delay, C), dtype=np.uint8)
+    d_fb, d_delays = alloc(fb.nbytes), alloc(table.nbytes)
+    gpu.memcpy_htod(d_fb, fb)
+    gpu.memcpy_htod(d_delays, table)
+    d_out = alloc(pbytes + CANARY)
+    gpu.memset(d_out, PREFILL, pbytes + CANARY)
+    g.dedisperse_q8(d_fb, fb.nbytes, fb.shape[1], 3, T, B, d_delays, nr_dm, max_delay, d_out, pbytes, out_spectra, first_out=first_out)
+    gpu.synchronize()
+    exp = dedisperse(fb, table, 3, T, max_delay)[0]  # [nr_dm][T]
+    assert np.unique(exp).size >= 100
+    # rows of 4096 bytes = 1024 words: the written ends of the four series, the rows before them, the alias rows and the start
+    row_bytes = T * 4
+    assert (out_spectra * 4) % row_bytes == 0
+    per_series = out_spectra * 4 // row_bytes
+    written = np.array([(m + 1) * per_series - 1 for m in range(nr_dm)], dtype=np.int64)
+    alias = written[3] - lt.LINE // row_bytes
+    assert 0 <= alias < per_series - 1 and alias == 15360 * 4 // row_bytes
+    untouched = np.array(sorted({0, 1, int(alias) - 1, int(alias), int(alias) + 1, *(int(w) - 1 for w in written)}), dtype=np.int64)
+    got = lt.read_rows(gpu, d_out, row_bytes, written).view(np.uint32)
+    assert np.array_equal(got, exp), np.argwhere(got != exp)[:3]
+    kept = lt.read_rows(gpu, d_out, row_bytes, untouched).view(np.uint32)
+    assert np.all(kept == PREFILL_WORD), "a word outside [first_out, first_out + nr_spectra) was written"
+    tail = np.empty(CANARY, np.uint8)
+    gpu.memcpy_dtoh(tail, int(d_out) + pbytes)
+    assert np.all(tail == PREFILL), "written past the plane"

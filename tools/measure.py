@@ -37,6 +37,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
     python tools/measure.py stokes [--rounds 5]
         the Stokes detection of two polarisations' 8-bit beams at IQUV and at I against the incoherent beam over the same
         bytes (the same load pattern), alternating, in one process, and the integration  -> profiles/r12_stokes.md
+    python tools/measure.py dedisperse [--rounds 5] [--shape CxDMSxTxB] [--direct-shape CxDMSxTxB]
+        incoherent dedispersion of 8-bit filterbanks: time and byte-adds per second with the table dm_delays makes (the
+        staged form) and, at a smaller shape, with a seeded random table of the same max_delay (the direct form), and
+        the delay-table call                                                        -> profiles/r13_dedisperse.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -796,6 +800,56 @@ def cmd_stokes(args):
     print(json.dumps({"stokes": rows}), flush=True)
 
 
+def cmd_dedisperse(args):
+    """Incoherent dedispersion (include/dcs_dedisperse.h): nr_dm sums of C bytes per output sample, so B * nr_dm * T * C
+    byte-adds per call.  A band of 1500 MHz down to 1200 MHz in C columns, 64 us spectra and DMs 0 .. 500: delays to about 8100
+    spectra.  Noise-like bytes; ``--rounds`` timings of each call in one process.  The random table makes every chunk take the
+    direct form, which reads every term from global memory: it is timed at a smaller shape."""
+    from dc_sand_amd.generator import dm_delays_bytes, dm_time_bytes, filterbank_bytes
+
+    def parse(text):
+        C, nr_dm, T, B = (int(x) for x in text.lower().split("x"))
+        return C, nr_dm, T, B
+    rows = []
+    for kind, (C, nr_dm, T, B) in (("dm_delays table", parse(args.shape)), ("random table", parse(args.direct_shape))):
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+        g = SteeringCoefficientGenerator(bp)
+        band = (1500.0, -300.0 / C, 64e-6)
+        dms = np.linspace(0.0, 500.0, nr_dm)
+        tb, pb = dm_delays_bytes(bp, nr_dm), dm_time_bytes(B, nr_dm, T)
+        d_dms, d_delays, d_plane = device.mem_alloc(dms.nbytes), device.mem_alloc(tb), device.mem_alloc(pb)
+        device.memcpy_htod(d_dms, dms)
+        table_call = lambda: g.dm_delays(*band, d_dms, nr_dm, d_delays, tb)  # noqa: E731
+        table_call()
+        device.synchronize()
+        table = np.empty((nr_dm, C), np.int32)
+        device.memcpy_dtoh(table, d_delays)
+        max_delay = int(table.max())
+        t_table = [per_launch_ms(table_call) for _ in range(args.rounds)]
+        if kind == "random table":
+            table = np.random.default_rng(0xD15).integers(0, max_delay + 1, size=(nr_dm, C)).astype(np.int32)
+            device.memcpy_htod(d_delays, table)
+        in_spectra = T + max_delay
+        fb = filterbank_bytes(bp, B, in_spectra)
+        d_fb = device.mem_alloc(fb)
+        _noise(d_fb, fb)
+        call = lambda: g.dedisperse_q8(d_fb, fb, in_spectra, 0, T, B, d_delays, nr_dm, max_delay, d_plane, pb, T)  # noqa: E731
+        call()
+        device.synchronize()
+        t = [per_launch_ms(call, settle_ms=100.0, timed_ms=200.0) for _ in range(args.rounds)]
+        ms = float(np.median(t))
+        adds = B * nr_dm * T * C
+        row = {"table": kind, "shape": f"C={C} nr_dm={nr_dm} T={T} B={B}", "max_delay": max_delay, "filterbank_MiB": fb >> 20,
+               "ms": round(ms, 3), "spread": round(max(t) / min(t) - 1.0, 4), "byte_adds": adds,
+               "byte_adds_per_s": float(f"{adds / (ms * 1e-3):.4g}"), "dm_delays_us": round(float(np.median(t_table)) * 1e3, 1)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        for d in (d_dms, d_delays, d_plane, d_fb):
+            d.free()
+    print(json.dumps({"dedisperse": rows}), flush=True)
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1218,6 +1272,10 @@ def main():
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernel and the probe only (kernel trace)")
     p = sub.add_parser("stokes")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the IQUV call, the I call and the incoherent beam per shape")
+    p = sub.add_parser("dedisperse")
+    p.add_argument("--rounds", type=int, default=5, help="timings of each call")
+    p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB with the table dm_delays makes")
+    p.add_argument("--direct-shape", default="4096x32x2048x1", help="CxDMSxTxB with a seeded random table")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1262,7 +1320,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
