@@ -82,4 +82,15 @@ COMPANIONS = {
          [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, _VP, c_uint32, c_uint32, _VP, _VP, c_size_t, c_uint64,
           c_uint64, _VP]),
     ]),
+    # the single-pulse search on those planes: exact sums per series, boxcar peaks per width and block, and their signal-to-noise
+    "single_pulse": Companion("dcs_single_pulse.h", "bf_single_pulse.cpp", "libdcs_single_pulse.so", [
+        ("dcs_bf_dm_time_sums", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_boxcar_peaks", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, c_uint32, c_uint32, c_uint32, _VP, c_size_t,
+          c_uint64, c_uint64, _VP]),
+        ("dcs_bf_peak_snr", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, c_uint32, c_uint32, _VP, c_size_t, c_uint64,
+          _VP, c_size_t, _VP, c_size_t, _VP]),
+    ]),
 }

@@ -1,9 +1,10 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
-// detection of 8-bit beams (include/dcs_stokes.h) and the dedispersion of the filterbanks (include/dcs_dedisperse.h), each
-// reached through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and
-// its device, nothing else.  Host code only; the kernels are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip,
-// bf_stokes.hip and bf_dedisperse.hip.
+// detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h) and the
+// single-pulse search on its planes (include/dcs_single_pulse.h), each reached through the table at the head of every
+// context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Host code only; the
+// kernels are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip and
+// bf_single_pulse.hip.
 
 #include <cmath>
 #include <cstring>
@@ -276,6 +277,97 @@ int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t fi
     a.nr_dm = nr_dm;
     a.max_delay = max_delay;
     return (int)bf_launch_dedisperse(a, as_stream(stream));
+}
+
+// include/dcs_single_pulse.h, reached the same way.  Nothing allocated; of the context only its device is used.  A series is
+// one (beam, DM) pair; nr_beams * nr_dm of them fit 64 bits.
+int dm_time_sums_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
+                      uint64_t *d_sums, size_t sums_bytes, void *stream)
+{
+    if (!c || !d_dm_time || !d_sums || misaligned(d_dm_time, 3u) || misaligned(d_sums, 7u) || nr_beams == 0u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (first_spectrum > plane_spectra || nr_spectra > plane_spectra - first_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, series, 2u, sizeof(uint64_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dtsums_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.plane = d_dm_time;
+    a.sums = d_sums;
+    a.plane_spectra = plane_spectra;
+    a.first = first_spectrum;
+    a.T = nr_spectra;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_dm_time_sums(a, series, as_stream(stream));
+}
+
+int boxcar_peaks_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths,
+                      uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
+                      uint64_t peak_blocks, uint64_t first_block, void *stream)
+{
+    if (!c || !d_dm_time || !d_widths || !d_peaks || misaligned(d_dm_time, 3u) || misaligned(d_widths, 3u) ||
+        misaligned(d_peaks, 7u) || nr_beams == 0u || max_width < 1u || max_width > 4096u || block_len < 64u || block_len > 4096u ||
+        block_len % 64u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    const uint64_t nr_blocks = ((uint64_t)nr_spectra + block_len - 1u) / block_len;
+    if (first_spectrum > plane_spectra || (uint64_t)nr_spectra + (max_width - 1u) > plane_spectra - first_spectrum ||
+        first_block > peak_blocks || nr_blocks > peak_blocks - first_block)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_boxcar_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.plane = d_dm_time;
+    a.widths = d_widths;
+    a.peaks = d_peaks;
+    a.plane_spectra = plane_spectra;
+    a.first = first_spectrum;
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.T = nr_spectra;
+    a.nr_widths = nr_widths;
+    a.max_width = max_width;
+    a.block_len = block_len;
+    return (int)bf_launch_boxcar_peaks(a, series, as_stream(stream));
+}
+
+int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes, uint64_t peak_blocks, uint64_t first_block,
+                  uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
+                  uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
+                  uint32_t *d_best, size_t best_bytes, void *stream)
+{
+    if (!c || !d_peaks || !d_widths || !d_sums || !d_snr || misaligned(d_peaks, 7u) || misaligned(d_widths, 3u) ||
+        misaligned(d_sums, 7u) || misaligned(d_snr, 3u) || misaligned(d_best, 3u) || nr_beams == 0u || max_width < 1u ||
+        max_width > 4096u || first_block > peak_blocks || nr_blocks > peak_blocks - first_block || count == 0u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, series, 2u, sizeof(uint64_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(snr_bytes, series, nr_widths, peak_blocks, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (d_best && !holds(best_bytes, series, peak_blocks, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    const unsigned __int128 total = (unsigned __int128)series * nr_blocks;
+    if (total >> 64) return DCS_ERR_INVALID_ARGUMENT;
+    bf_peaksnr_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.peaks = d_peaks;
+    a.widths = d_widths;
+    a.sums = d_sums;
+    a.snr = d_snr;
+    a.best = d_best;
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.count = count;
+    a.total = (uint64_t)total;
+    a.nr_blocks = nr_blocks;
+    a.nr_widths = nr_widths;
+    a.max_width = max_width;
+    return (int)bf_launch_peak_snr(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -2,11 +2,12 @@
 // (include/dcs_beam_weights.h), libdcs_beam_quant.so (include/dcs_beam_quant.h), libdcs_beam_power.so
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
-// (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h) and libdcs_dedisperse.so
-// (include/dcs_dedisperse.h).  All are built from this tree together.  Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
+// (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
+// (include/dcs_dedisperse.h) and libdcs_single_pulse.so (include/dcs_single_pulse.h).  All are built from this tree together.
+// Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection and of the dedispersion; a companion checks the arguments it can check
-// without a device, then the table's version, and forwards.  Not a public interface.
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion and of the single-pulse search; a companion
+// checks the arguments it can check without a device, then the table's version, and forwards.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
 
@@ -27,7 +28,9 @@
 // hand foreign versions 1 to 7 only).
 // 10: dm_delays, dedisperse_q8 appended (tests/test_host_abi_dedisperse.py hands its companion 1, 8 and 9; no older test
 // hands a foreign version above 8).
-#define BF_CTX_EXT_VERSION 10u
+// 11: dm_time_sums, boxcar_peaks, peak_snr appended (tests/test_host_abi_single_pulse.py hands its companion 1, 9 and 10; no
+// older test hands a foreign version above 9).
+#define BF_CTX_EXT_VERSION 11u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -97,6 +100,20 @@ struct bf_ctx_ext_ops {
                          uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
                          uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
                          uint64_t out_spectra, uint64_t first_out, void *stream);
+    // the single-pulse search (include/dcs_single_pulse.h) on those planes: the exact sums uint64 [nr_beams][nr_dm][2] of every
+    // series; boxcar peaks uint32 [nr_beams][nr_dm][nr_widths][peak_blocks][2]; peaks and sums -> signal-to-noise float
+    // [nr_beams][nr_dm][nr_widths][peak_blocks] and the best width uint32 [nr_beams][nr_dm][peak_blocks] (nullptr = not wanted)
+    int (*dm_time_sums)(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                        uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
+                        uint64_t *d_sums, size_t sums_bytes, void *stream);
+    int (*boxcar_peaks)(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                        uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths,
+                        uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
+                        uint64_t peak_blocks, uint64_t first_block, void *stream);
+    int (*peak_snr)(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes, uint64_t peak_blocks, uint64_t first_block,
+                    uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
+                    uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
+                    uint32_t *d_best, size_t best_bytes, void *stream);
 };
 
 // the first member of struct dcs_bf_context

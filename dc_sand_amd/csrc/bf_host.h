@@ -132,8 +132,8 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
 // the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
-// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two and the dedispersion's two in
-// bf_capi_detect.hip
+// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two, the dedispersion's two and the
+// single-pulse search's three in bf_capi_detect.hip
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -181,6 +181,17 @@ int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t fi
                        uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
                        uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
                        uint64_t out_spectra, uint64_t first_out, void *stream);
+int dm_time_sums_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
+                      uint64_t *d_sums, size_t sums_bytes, void *stream);
+int boxcar_peaks_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths,
+                      uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
+                      uint64_t peak_blocks, uint64_t first_block, void *stream);
+int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes, uint64_t peak_blocks, uint64_t first_block,
+                  uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
+                  uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
+                  uint32_t *d_best, size_t best_bytes, void *stream);
 
 } // namespace bf_host
 

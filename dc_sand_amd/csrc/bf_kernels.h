@@ -295,6 +295,43 @@ struct bf_dedisp_args {
 hipError_t bf_launch_dedisperse(const bf_dedisp_args &a, hipStream_t stream);
 hipError_t bf_warm_module_dedisperse();
 
+// The single-pulse search on the DM-time planes (bf_single_pulse.hip; include/dcs_single_pulse.h).
+// A series is one (beam, DM) pair: series s begins at word s * plane_spectra of the planes.
+// {sum x, sum x^2 mod 2^64} of words first .. first + T - 1 of every series
+struct bf_dtsums_args {
+    const uint32_t *plane; // [series][plane_spectra]
+    uint64_t *sums;        // [series][2]
+    uint64_t plane_spectra, first;
+    uint32_t T;
+    uint32_t accumulate;   // non-zero: added to what sums holds
+};
+hipError_t bf_launch_dm_time_sums(const bf_dtsums_args &a, uint64_t series, hipStream_t stream);
+// Per series, width index i and block k of block_len times: {the largest boxcar sum of width widths[i], its first time} into
+// peaks [series][nr_widths][peak_blocks][2] at block first_block + k; {0, 0xffffffff} for a width outside [1, max_width]
+struct bf_boxcar_args {
+    const uint32_t *plane;  // [series][plane_spectra]; words first .. first + T + max_width - 2 of a series are read
+    const uint32_t *widths; // [nr_widths]; read when the work runs
+    uint32_t *peaks;
+    uint64_t plane_spectra, first, peak_blocks, first_block;
+    uint32_t T, nr_widths, max_width, block_len;
+    uint32_t run;           // filled by the launcher: blocks that a workgroup takes, one after the other
+    uint32_t segments;      // filled by the launcher: such runs per series
+};
+hipError_t bf_launch_boxcar_peaks(const bf_boxcar_args &a, uint64_t series, hipStream_t stream);
+// Peaks and sums -> snr [series][nr_widths][peak_blocks] and best [series][peak_blocks], blocks first_block .. + nr_blocks - 1
+struct bf_peaksnr_args {
+    const uint32_t *peaks;
+    const uint32_t *widths;
+    const uint64_t *sums;
+    float *snr;
+    uint32_t *best;         // nullptr: not wanted
+    uint64_t peak_blocks, first_block, count;
+    uint64_t total;         // series * nr_blocks
+    uint32_t nr_blocks, nr_widths, max_width;
+};
+hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream);
+hipError_t bf_warm_module_single_pulse();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

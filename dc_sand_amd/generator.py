@@ -165,6 +165,29 @@ def dm_time_bytes(nr_beams: int, nr_dm: int, out_spectra: int) -> int:
     return int(nr_beams) * int(nr_dm) * int(out_spectra) * 4
 
 
+def dm_time_sums_bytes(nr_beams: int, nr_dm: int) -> int:
+    """Size of the sums ``uint64 [nr_beams][nr_dm][2]`` of :meth:`SteeringCoefficientGenerator.dm_time_sums`."""
+    return int(nr_beams) * int(nr_dm) * 16
+
+
+def boxcar_peaks_bytes(nr_beams: int, nr_dm: int, nr_widths: int, peak_blocks: int) -> int:
+    """Size of the peak plane ``uint32 [nr_beams][nr_dm][nr_widths][peak_blocks][2]`` of
+    :meth:`SteeringCoefficientGenerator.boxcar_peaks`."""
+    return int(nr_beams) * int(nr_dm) * int(nr_widths) * int(peak_blocks) * 8
+
+
+def peak_snr_bytes(nr_beams: int, nr_dm: int, nr_widths: int, peak_blocks: int) -> int:
+    """Size of the signal-to-noise ``float [nr_beams][nr_dm][nr_widths][peak_blocks]`` of
+    :meth:`SteeringCoefficientGenerator.peak_snr`."""
+    return int(nr_beams) * int(nr_dm) * int(nr_widths) * int(peak_blocks) * 4
+
+
+def best_width_bytes(nr_beams: int, nr_dm: int, peak_blocks: int) -> int:
+    """Size of the best width indices ``uint32 [nr_beams][nr_dm][peak_blocks]`` of
+    :meth:`SteeringCoefficientGenerator.peak_snr`."""
+    return int(nr_beams) * int(nr_dm) * int(peak_blocks) * 4
+
+
 class _Band(ctypes.Structure):  # dcs_bf_band (include/dcs_dedisperse.h)
     _fields_ = [("freq_first_mhz", ctypes.c_double), ("freq_step_mhz", ctypes.c_double), ("sample_time_s", ctypes.c_double)]
 
@@ -479,6 +502,49 @@ class SteeringCoefficientGenerator:
                                       int(max_delay), _p_or_null(d_channel_mask), _p(d_dm_time), int(dm_time_bytes),
                                       int(out_spectra), int(first_out), _s(stream)),
               "dcs_bf_dedisperse_q8")
+
+    # -- the single-pulse search on those planes (include/dcs_single_pulse.h, companion library libdcs_single_pulse.so):
+    #    d_widths a device uint32 [nr_widths] array of boxcar widths, d_peaks a device uint32
+    #    [nr_beams][nr_dm][nr_widths][peak_blocks][2] array of {value, time}
+    def dm_time_sums(self, d_dm_time, dm_time_bytes: int, plane_spectra: int, first_spectrum: int, nr_spectra: int, nr_beams: int,
+                     nr_dm: int, d_sums, sums_bytes: int, accumulate: bool = False, stream=None) -> None:
+        """Per (beam, DM) series the exact ``{sum x, sum x^2 mod 2^64}`` over the words ``first_spectrum ..
+        first_spectrum + nr_spectra - 1`` into ``d_sums`` (:func:`dm_time_sums_bytes`); with ``accumulate`` they are added
+        to what ``d_sums`` holds."""
+        sl = _lib.companion("single_pulse")
+        check(sl.dcs_bf_dm_time_sums(c_void_p(self._h), _p(d_dm_time), int(dm_time_bytes), int(plane_spectra), int(first_spectrum),
+                                     int(nr_spectra), int(nr_beams), int(nr_dm), 1 if accumulate else 0, _p(d_sums),
+                                     int(sums_bytes), _s(stream)),
+              "dcs_bf_dm_time_sums")
+
+    def boxcar_peaks(self, d_dm_time, dm_time_bytes: int, plane_spectra: int, first_spectrum: int, nr_spectra: int, nr_beams: int,
+                     nr_dm: int, d_widths, nr_widths: int, max_width: int, block_len: int, d_peaks, peaks_bytes: int,
+                     peak_blocks: int, first_block: int = 0, stream=None) -> None:
+        """Per series, width ``w = d_widths[i]`` and block of ``block_len`` times ``t < nr_spectra``: the largest sum of
+        ``w`` consecutive words from ``first_spectrum + t`` (mod 2^32) and the smallest ``t`` that attains it, into block
+        ``first_block + k`` of ``d_peaks`` (:func:`boxcar_peaks_bytes`); a width outside ``[1, max_width]`` gives
+        ``{0, 0xFFFFFFFF}``.  Words up to ``first_spectrum + nr_spectra + max_width - 2`` of a series are read."""
+        sl = _lib.companion("single_pulse")
+        check(sl.dcs_bf_boxcar_peaks(c_void_p(self._h), _p(d_dm_time), int(dm_time_bytes), int(plane_spectra), int(first_spectrum),
+                                     int(nr_spectra), int(nr_beams), int(nr_dm), _p(d_widths), int(nr_widths), int(max_width),
+                                     int(block_len), _p(d_peaks), int(peaks_bytes), int(peak_blocks), int(first_block),
+                                     _s(stream)),
+              "dcs_bf_boxcar_peaks")
+
+    def peak_snr(self, d_peaks, peaks_bytes: int, peak_blocks: int, first_block: int, nr_blocks: int, nr_beams: int, nr_dm: int,
+                 d_widths, nr_widths: int, max_width: int, d_sums, sums_bytes: int, count: int, d_snr, snr_bytes: int,
+                 d_best=None, best_bytes: int = 0, stream=None) -> None:
+        """The peaks of blocks ``first_block .. first_block + nr_blocks - 1`` as signal-to-noise
+        ``(value - w * mean) / sqrt(w * variance)`` with the mean and variance of the ``count`` words behind ``d_sums``, in
+        fp64 rounded once per operation, into ``d_snr`` (:func:`peak_snr_bytes`): 0 for a series without variance,
+        ``-inf`` for a width outside ``[1, max_width]``.  ``d_best``: ``None``, or a device ``uint32`` array
+        (:func:`best_width_bytes`) for the lowest width index with the largest signal-to-noise of every block."""
+        sl = _lib.companion("single_pulse")
+        check(sl.dcs_bf_peak_snr(c_void_p(self._h), _p(d_peaks), int(peaks_bytes), int(peak_blocks), int(first_block),
+                                 int(nr_blocks), int(nr_beams), int(nr_dm), _p(d_widths), int(nr_widths), int(max_width),
+                                 _p(d_sums), int(sums_bytes), int(count), _p(d_snr), int(snr_bytes), _p_or_null(d_best),
+                                 int(best_bytes), _s(stream)),
+              "dcs_bf_peak_snr")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -41,6 +41,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         incoherent dedispersion of 8-bit filterbanks: time and byte-adds per second with the table dm_delays makes (the
         staged form) and, at a smaller shape, with a seeded random table of the same max_delay (the direct form), and
         the delay-table call                                                        -> profiles/r13_dedisperse.md
+    python tools/measure.py single_pulse [--rounds 5] [--shape CxDMSxTxB] [--block-len 256] [--buffers 3]
+        the single-pulse search on the planes of that shape: the sums, the boxcar peaks of 13 widths and the signal-to-noise,
+        the peaks' share of one read of the planes, and all three against dedisperse_q8 in the same process
+                                                                                    -> profiles/r14_single_pulse.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -850,6 +854,85 @@ def cmd_dedisperse(args):
     print(json.dumps({"dedisperse": rows}), flush=True)
 
 
+def cmd_single_pulse(args):
+    """The single-pulse search (include/dcs_single_pulse.h) on the planes the dedispersion makes, at the shape of
+    ``dedisperse``: 13 widths 1 .. 4096, blocks of 256 spectra.  The planes are made by dcs_bf_dedisperse_q8 from noise-like
+    bytes, T + max_width - 1 words per series; that call is timed at T outputs in the same process.  boxcar_peaks and
+    dm_time_sums are timed on one plane (which the Infinity Cache may hold, as it does right after the dedispersion) and
+    rotating over ``--buffers`` copies that together exceed it; the bound is one read of the plane at 6.3 TB/s."""
+    from dc_sand_amd.generator import (best_width_bytes, boxcar_peaks_bytes, dm_delays_bytes, dm_time_bytes, dm_time_sums_bytes,
+                                       filterbank_bytes, peak_snr_bytes)
+
+    C, nr_dm, T, B = (int(x) for x in args.shape.lower().split("x"))
+    widths = np.array([1 << k for k in range(13)], np.uint32)
+    max_width, block_len = 4096, args.block_len
+    bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+    g = SteeringCoefficientGenerator(bp)
+    band = (1500.0, -300.0 / C, 64e-6)
+    dms = np.linspace(0.0, 500.0, nr_dm)
+    ps = T + max_width - 1
+    tb, pb = dm_delays_bytes(bp, nr_dm), dm_time_bytes(B, nr_dm, ps)
+    d_dms, d_delays, d_widths = device.mem_alloc(dms.nbytes), device.mem_alloc(tb), device.mem_alloc(widths.nbytes)
+    planes = [device.mem_alloc(pb) for _ in range(args.buffers)]
+    device.memcpy_htod(d_dms, dms)
+    device.memcpy_htod(d_widths, widths)
+    g.dm_delays(*band, d_dms, nr_dm, d_delays, tb)
+    device.synchronize()
+    table = np.empty((nr_dm, C), np.int32)
+    device.memcpy_dtoh(table, d_delays)
+    max_delay = int(table.max())
+    in_spectra = ps + max_delay
+    fb = filterbank_bytes(bp, B, in_spectra)
+    d_fb = device.mem_alloc(fb)
+    _noise(d_fb, fb)
+    g.dedisperse_q8(d_fb, fb, in_spectra, 0, ps, B, d_delays, nr_dm, max_delay, planes[0], pb, ps)
+    device.synchronize()
+    for d in planes[1:]:
+        device.memcpy_dtod(d, planes[0], pb)
+    nb = (T + block_len - 1) // block_len
+    sb, kb = dm_time_sums_bytes(B, nr_dm), boxcar_peaks_bytes(B, nr_dm, widths.size, nb)
+    nbytes, bb = peak_snr_bytes(B, nr_dm, widths.size, nb), best_width_bytes(B, nr_dm, nb)
+    d_sums, d_peaks, d_snr, d_best = (device.mem_alloc(n) for n in (sb, kb, nbytes, bb))
+    turn = [0]
+
+    def rotated(fn):
+        def call():
+            turn[0] = (turn[0] + 1) % len(planes)
+            fn(planes[turn[0]])
+        return call
+    sums_on = lambda d: g.dm_time_sums(d, pb, ps, 0, T, B, nr_dm, d_sums, sb)  # noqa: E731
+    peaks_on = lambda d: g.boxcar_peaks(d, pb, ps, 0, T, B, nr_dm, d_widths, widths.size, max_width, block_len, d_peaks, kb, nb)  # noqa: E731
+    snr_call = lambda: g.peak_snr(d_peaks, kb, nb, 0, nb, B, nr_dm, d_widths, widths.size, max_width, d_sums, sb, T, d_snr, nbytes,  # noqa: E731
+                                  d_best, bb)
+    dedisp = lambda: g.dedisperse_q8(d_fb, fb, in_spectra, 0, T, B, d_delays, nr_dm, max_delay, planes[0], pb, ps)  # noqa: E731
+    t = {k: [] for k in ("sums", "sums_rot", "peaks", "peaks_rot", "snr", "dedisperse")}
+    for _ in range(args.rounds):
+        t["peaks"].append(per_launch_ms(lambda: peaks_on(planes[0])))
+        t["peaks_rot"].append(per_launch_ms(rotated(peaks_on)))
+        t["sums"].append(per_launch_ms(lambda: sums_on(planes[0])))
+        t["sums_rot"].append(per_launch_ms(rotated(sums_on)))
+        t["snr"].append(per_launch_ms(snr_call))
+        t["dedisperse"].append(per_launch_ms(dedisp, settle_ms=50.0, timed_ms=100.0))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    read = B * nr_dm * ps * 4
+    bound_us = read / 6.3e12 * 1e6
+    search_ms = med["sums"] + med["peaks"] + med["snr"]
+    row = {"shape": f"C={C} nr_dm={nr_dm} T={T} B={B}", "widths": widths.size, "max_width": max_width, "block_len": block_len,
+           "plane_read_MiB": read >> 20, "buffers": len(planes), "out_KiB": (kb + nbytes + bb + sb) >> 10,
+           "peaks_us": round(med["peaks"] * 1e3, 1), "peaks_rotated_us": round(med["peaks_rot"] * 1e3, 1),
+           "peaks_spread": round(max(t["peaks_rot"]) / min(t["peaks_rot"]) - 1.0, 4),
+           "plane_read_bound_us": round(bound_us, 1), "peaks_rotated_share_of_bound": round(bound_us / (med["peaks_rot"] * 1e3), 3),
+           "peaks_rotated_read_TBps": round(read / (med["peaks_rot"] * 1e-3) / 1e12, 2),
+           "sums_us": round(med["sums"] * 1e3, 1), "sums_rotated_us": round(med["sums_rot"] * 1e3, 1),
+           "sums_rotated_read_TBps": round(B * nr_dm * T * 4 / (med["sums_rot"] * 1e-3) / 1e12, 2),
+           "snr_us": round(med["snr"] * 1e3, 1), "dedisperse_ms": round(med["dedisperse"], 3),
+           "search_over_dedisperse": round(search_ms / med["dedisperse"], 4)}
+    print(json.dumps({"single_pulse": row}), flush=True)
+    g.close()
+    for d in [d_dms, d_delays, d_widths, d_fb, d_sums, d_peaks, d_snr, d_best] + planes:
+        d.free()
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1276,6 +1359,11 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="timings of each call")
     p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB with the table dm_delays makes")
     p.add_argument("--direct-shape", default="4096x32x2048x1", help="CxDMSxTxB with a seeded random table")
+    p = sub.add_parser("single_pulse")
+    p.add_argument("--rounds", type=int, default=5, help="timings of each call")
+    p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB: the shape of dedisperse")
+    p.add_argument("--block-len", type=int, default=256, help="spectra per block of the peak plane")
+    p.add_argument("--buffers", type=int, default=3, help="copies of the planes the rotated timings walk")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1320,7 +1408,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
