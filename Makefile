@@ -18,7 +18,8 @@ SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip
            dc_sand_amd/csrc/bf_capi_generate.hip \
            dc_sand_amd/csrc/bf_capi_beamform.hip dc_sand_amd/csrc/bf_capi_detect.hip dc_sand_amd/csrc/bf_capi_stream.hip
 HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h dc_sand_amd/csrc/bf_stream_ext.h \
-           dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_host.h dc_sand_amd/csrc/bf_beamform_kernel.inc \
+           dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_arg_checks.h dc_sand_amd/csrc/bf_host.h \
+           dc_sand_amd/csrc/bf_beamform_kernel.inc \
            dc_sand_amd/csrc/bf_beamform_i8_kernel.inc \
            include/dcs_beamformer.h include/dcs_stream_staging.h include/dcs_beam_weights.h include/dcs_beam_quant.h \
            include/dcs_beam_power.h include/dcs_incoherent_beam.h include/dcs_filterbank.h include/dcs_beam_complex.h \

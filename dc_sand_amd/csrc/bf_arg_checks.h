@@ -1,0 +1,180 @@
+// bf_arg_checks.h -- the checks a call behind bf_ctx_ext_ops can make without a device, each stated once: one function per
+// table entry, named after it, called by the companion's export before it reads the table and again as the first statement
+// of the *_impl behind the table.  What a function refuses is what a handle that is no context of this build gets
+// DCS_ERR_INVALID_ARGUMENT for instead of DCS_ERR_UNSUPPORTED (tests/test_host_abi_*.py); a check that needs the context's
+// sizes or its device is the _impl's own.  Host code, header-only, no HIP.  Not a public interface.
+#ifndef BF_ARG_CHECKS_H
+#define BF_ARG_CHECKS_H
+
+#include <cmath>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/dcs_beam_complex.h" // DCS_BF_COMPLEX_CONJ
+#include "../../include/dcs_beamformer.h"
+#include "../../include/dcs_dedisperse.h" // dcs_bf_band
+#include "../../include/dcs_filterbank.h" // DCS_FB_DESCENDING
+#include "../../include/dcs_stokes.h"     // DCS_BF_STOKES_I, DCS_BF_STOKES_IQUV
+
+// p is a multiple of bytes, a power of two; a null pointer passes (an optional tensor's alignment is checked the same way)
+inline bool aligned(const void *p, uintptr_t bytes) { return !(reinterpret_cast<uintptr_t>(p) & (bytes - 1u)); }
+
+// first + n <= total, without a sum that could wrap
+inline bool fits(uint64_t first, uint64_t n, uint64_t total) { return first <= total && n <= total - first; }
+
+// have >= x * y * z * w, the product taken without overflow
+inline bool holds(size_t have, uint64_t x, uint64_t y, uint64_t z, uint64_t w)
+{
+    const unsigned __int128 xy = (unsigned __int128)x * y, zw = (unsigned __int128)z * w;
+    if ((xy >> 64) || (zw >> 64)) return xy == 0 || zw == 0;
+    const unsigned __int128 need = xy * zw;
+    return !(need >> 64) && (uint64_t)need <= (uint64_t)have;
+}
+
+inline int arg_status(bool ok) { return ok ? DCS_OK : DCS_ERR_INVALID_ARGUMENT; }
+inline bool stokes_ok(uint32_t nr_stokes) { return nr_stokes == DCS_BF_STOKES_I || nr_stokes == DCS_BF_STOKES_IQUV; }
+inline bool complex_flags_ok(uint32_t flags) { return !(flags & ~(uint32_t)DCS_BF_COMPLEX_CONJ); }
+inline bool width_ok(uint32_t max_width) { return max_width >= 1u && max_width <= 4096u; }
+
+// what the three integrations share: both tensors, aligned to their elements of bytes, and whole spectra of blocks
+inline int integration_args(dcs_bf_context *c, const void *d_blocks, const void *d_spectra, uintptr_t bytes, uint32_t nr_blocks,
+                            uint32_t blocks_per_spectrum)
+{
+    return arg_status(c && d_blocks && d_spectra && aligned(d_blocks, bytes) && aligned(d_spectra, bytes) && blocks_per_spectrum != 0u &&
+                      nr_blocks % blocks_per_spectrum == 0u);
+}
+
+// include/dcs_beam_weights.h.  dt: nullptr for the times of the samples from t0 on, which begins a 16-sample block
+inline int beamform_accumulated_weighted_args(dcs_bf_context *c, uint32_t nt, const float *d_weights)
+{
+    return arg_status(c && d_weights && aligned(d_weights, 4u) && nt % 16u == 0u);
+}
+inline int generate_and_beamform_weighted_args(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const float *d_weights)
+{
+    return arg_status(!beamform_accumulated_weighted_args(c, nt, d_weights) && (dt || t0 % 16u == 0u));
+}
+
+// include/dcs_beam_quant.h
+inline int beamform_accumulated_q8_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, const float *d_quant_gains,
+                                        const unsigned long long *d_clip_count)
+{
+    return arg_status(c && d_quant_gains && aligned(d_quant_gains, 4u) && aligned(d_weights, 4u) && aligned(d_clip_count, 8u) &&
+                      nt % 16u == 0u);
+}
+
+// include/dcs_beam_power.h and include/dcs_incoherent_beam.h: block powers out, one dword each
+inline int beamform_accumulated_power_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, const void *d_block_power)
+{
+    return arg_status(c && d_block_power && aligned(d_block_power, 4u) && aligned(d_weights, 4u) && nt % 16u == 0u);
+}
+inline int integrate_block_power_args(dcs_bf_context *c, const float *d_block_power, uint32_t nr_blocks, uint32_t blocks_per_spectrum,
+                                      const float *d_spectra)
+{
+    return integration_args(c, d_block_power, d_spectra, 4u, nr_blocks, blocks_per_spectrum);
+}
+inline int incoherent_block_power_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, const uint32_t *d_block_power)
+{
+    return beamform_accumulated_power_args(c, nt, d_weights, d_block_power);
+}
+inline int integrate_incoherent_power_args(dcs_bf_context *c, const uint32_t *d_block_power, uint32_t nr_blocks,
+                                           uint32_t blocks_per_spectrum, const float *d_spectra)
+{
+    return integration_args(c, d_block_power, d_spectra, 4u, nr_blocks, blocks_per_spectrum);
+}
+
+// include/dcs_filterbank.h
+inline int spectra_sums_args(dcs_bf_context *c, const float *d_spectra, uint32_t nr_beams, const double *d_sums)
+{
+    return arg_status(c && d_spectra && d_sums && aligned(d_spectra, 4u) && aligned(d_sums, 8u) && nr_beams != 0u);
+}
+inline int filterbank_scales_args(dcs_bf_context *c, const double *d_sums, uint64_t count, uint32_t nr_beams, const float *d_scales)
+{
+    return arg_status(c && d_sums && d_scales && aligned(d_sums, 8u) && aligned(d_scales, 8u) && nr_beams != 0u && count != 0u &&
+                      count < (1ull << 53));
+}
+inline int filterbank_q8_args(dcs_bf_context *c, const float *d_spectra, uint32_t nr_spectra, uint32_t nr_beams, const float *d_scales,
+                              uint32_t flags, const uint8_t *d_filterbank, uint64_t out_spectra, uint64_t first_spectrum,
+                              const unsigned long long *d_clip_count)
+{
+    return arg_status(c && d_spectra && d_scales && d_filterbank && aligned(d_spectra, 4u) && aligned(d_scales, 8u) &&
+                      aligned(d_filterbank, 16u) && aligned(d_clip_count, 8u) && nr_beams != 0u &&
+                      !(flags & ~(uint32_t)DCS_FB_DESCENDING) && fits(first_spectrum, nr_spectra, out_spectra));
+}
+
+// include/dcs_beam_complex.h (d_beams: (re, im) fp32 pairs; d_block_power: single floats) and include/dcs_beam_complex_quant.h
+inline int beamform_accumulated_complex_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, uint32_t flags, const float *d_beams)
+{
+    return arg_status(c && d_beams && aligned(d_beams, 8u) && aligned(d_weights, 4u) && nt % 16u == 0u && complex_flags_ok(flags));
+}
+inline int beamform_accumulated_complex_power_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, uint32_t flags,
+                                                   const float *d_block_power)
+{
+    return arg_status(!beamform_accumulated_power_args(c, nt, d_weights, d_block_power) && complex_flags_ok(flags));
+}
+inline int beamform_accumulated_complex_q8_args(dcs_bf_context *c, uint32_t nt, const float *d_weights, uint32_t flags,
+                                                const float *d_quant_gains, const int8_t *d_beams_q8,
+                                                const unsigned long long *d_clip_count)
+{
+    return arg_status(!beamform_accumulated_q8_args(c, nt, d_weights, d_quant_gains, d_clip_count) && d_beams_q8 &&
+                      aligned(d_beams_q8, 8u) && complex_flags_ok(flags));
+}
+
+// include/dcs_stokes.h: a block's nr_stokes values are stored as one word or one quad
+inline int stokes_block_args(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, uint32_t nr_stokes,
+                             const int32_t *d_block_stokes)
+{
+    return arg_status(c && d_beams_x && d_beams_y && d_block_stokes && stokes_ok(nr_stokes) && aligned(d_beams_x, 16u) &&
+                      aligned(d_beams_y, 16u) && aligned(d_block_stokes, 4u * nr_stokes) && nt % 16u == 0u);
+}
+inline int integrate_stokes_args(dcs_bf_context *c, const int32_t *d_block_stokes, uint32_t nr_blocks, uint32_t blocks_per_spectrum,
+                                 uint32_t nr_stokes, const float *d_spectra)
+{
+    return arg_status(stokes_ok(nr_stokes) &&
+                      !integration_args(c, d_block_stokes, d_spectra, 4u * nr_stokes, nr_blocks, blocks_per_spectrum));
+}
+
+// include/dcs_dedisperse.h.  The band's last frequency needs the context's channel count: dm_delays_impl checks it
+inline int dm_delays_args(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, const int32_t *d_delays)
+{
+    return arg_status(c && band && d_dms && d_delays && aligned(d_dms, 8u) && aligned(d_delays, 4u) &&
+                      std::isfinite(band->freq_first_mhz) && std::isfinite(band->freq_step_mhz) && std::isfinite(band->sample_time_s) &&
+                      band->sample_time_s > 0.0 && band->freq_first_mhz > 0.0);
+}
+inline int dedisperse_q8_args(dcs_bf_context *c, const uint8_t *d_filterbank, uint64_t in_spectra, uint64_t first_spectrum,
+                              uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t max_delay,
+                              const uint32_t *d_dm_time, uint64_t out_spectra, uint64_t first_out)
+{
+    return arg_status(c && d_filterbank && d_delays && d_dm_time && aligned(d_filterbank, 16u) && aligned(d_delays, 4u) &&
+                      aligned(d_dm_time, 4u) && nr_beams != 0u && max_delay <= 0x7ffffffeu &&
+                      fits(first_spectrum, (uint64_t)nr_spectra + max_delay, in_spectra) && fits(first_out, nr_spectra, out_spectra));
+}
+
+// include/dcs_single_pulse.h.  A boxcar of max_width spectra reads max_width - 1 past the last one it starts at; a peak block
+// is block_len starts
+inline int dm_time_sums_args(dcs_bf_context *c, const uint32_t *d_dm_time, uint64_t plane_spectra, uint64_t first_spectrum,
+                             uint32_t nr_spectra, uint32_t nr_beams, const uint64_t *d_sums)
+{
+    return arg_status(c && d_dm_time && d_sums && aligned(d_dm_time, 4u) && aligned(d_sums, 8u) && nr_beams != 0u &&
+                      fits(first_spectrum, nr_spectra, plane_spectra));
+}
+inline int boxcar_peaks_args(dcs_bf_context *c, const uint32_t *d_dm_time, uint64_t plane_spectra, uint64_t first_spectrum,
+                             uint32_t nr_spectra, uint32_t nr_beams, const uint32_t *d_widths, uint32_t max_width, uint32_t block_len,
+                             const uint32_t *d_peaks, uint64_t peak_blocks, uint64_t first_block)
+{
+    if (!c || !d_dm_time || !d_widths || !d_peaks || !aligned(d_dm_time, 4u) || !aligned(d_widths, 4u) || !aligned(d_peaks, 8u) ||
+        nr_beams == 0u || !width_ok(max_width) || block_len < 64u || block_len > 4096u || block_len % 64u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    const uint64_t nr_blocks = ((uint64_t)nr_spectra + block_len - 1u) / block_len;
+    return arg_status(fits(first_spectrum, (uint64_t)nr_spectra + (max_width - 1u), plane_spectra) &&
+                      fits(first_block, nr_blocks, peak_blocks));
+}
+inline int peak_snr_args(dcs_bf_context *c, const uint32_t *d_peaks, uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks,
+                         uint32_t nr_beams, const uint32_t *d_widths, uint32_t max_width, const uint64_t *d_sums, uint64_t count,
+                         const float *d_snr, const uint32_t *d_best)
+{
+    return arg_status(c && d_peaks && d_widths && d_sums && d_snr && aligned(d_peaks, 8u) && aligned(d_widths, 4u) &&
+                      aligned(d_sums, 8u) && aligned(d_snr, 4u) && aligned(d_best, 4u) && nr_beams != 0u && width_ok(max_width) &&
+                      fits(first_block, nr_blocks, peak_blocks) && count != 0u);
+}
+
+#endif // BF_ARG_CHECKS_H

@@ -1,6 +1,8 @@
 // bf_capi_beamform.hip -- both beamformers of include/dcs_beamformer.h, and their weighted, quantised, detecting and
 // complex-product calls (bf_ctx_ext.h): the terms table and its class words, the terms pre-pass, the launches.  Host code only; the
-// kernels are in bf_kernels.hip and bf_beamform_mfma.hip.
+// kernels are in bf_kernels.hip and bf_beamform_mfma.hip.  A call behind the table begins with the device-free checks of its
+// entry (bf_arg_checks.h), the ones its companion has made already; beamform_impl and beamform_acc_impl keep all of their own,
+// since this library's exports call them directly.
 
 #include <cstdlib>
 #include <cstring>
@@ -270,8 +272,7 @@ int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream)
 {
-    if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
-    if (!dt && t0 % 16u) return DCS_ERR_INVALID_ARGUMENT; // whole 16-sample blocks
+    if (int e = generate_and_beamform_weighted_args(c, dt, t0, nt, d_weights)) return e;
     return beamform_impl(c, dt_or_index(dt, t0), nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream, d_weights);
 }
 
@@ -279,7 +280,7 @@ int beamform_accumulated_weighted_impl(dcs_bf_context *c, const float *dt_coeff,
                                        const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, float *d_beams,
                                        size_t beams_bytes, void *stream)
 {
-    if (!c || !weights_ok(d_weights)) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = beamform_accumulated_weighted_args(c, nt, d_weights)) return e;
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams, beams_bytes,
                              stream, {bacc_output::kFloat, d_weights, {}});
 }
@@ -289,8 +290,7 @@ int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint6
                                  size_t antenna_bytes, const float *d_weights, const float *d_quant_gains, int8_t *d_beams_q8,
                                  size_t beams_bytes, unsigned long long *d_clip_count, void *stream)
 {
-    if (!c || !weights_ok(d_quant_gains) || (d_weights && !weights_ok(d_weights)) || (reinterpret_cast<uintptr_t>(d_clip_count) & 7u))
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = beamform_accumulated_q8_args(c, nt, d_weights, d_quant_gains, d_clip_count)) return e;
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes,
                              stream, {bacc_output::kInt8, d_weights, {d_quant_gains, d_clip_count}});
 }
@@ -300,7 +300,7 @@ int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, ui
                                     size_t antenna_bytes, const float *d_weights, float *d_block_power, size_t power_bytes,
                                     void *stream)
 {
-    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights))) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = beamform_accumulated_power_args(c, nt, d_weights, d_block_power)) return e;
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes,
                              stream, {bacc_output::kBlockPower, d_weights, {}});
 }
@@ -310,8 +310,8 @@ int beamform_accumulated_complex_impl(dcs_bf_context *c, const float *dt_coeff, 
                                       size_t antenna_bytes, const float *d_weights, uint32_t flags, float *d_beams, size_t beams_bytes,
                                       void *stream)
 {
-    if (!c || !d_beams || (d_weights && !weights_ok(d_weights)) || (flags & ~1u)) return DCS_ERR_INVALID_ARGUMENT;
-    const bf_complex_args cx = {flags & 1u};
+    if (int e = beamform_accumulated_complex_args(c, nt, d_weights, flags, d_beams)) return e;
+    const bf_complex_args cx = {flags & DCS_BF_COMPLEX_CONJ};
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams, beams_bytes, stream,
                              {bacc_output::kFloat, d_weights, {}, &cx});
 }
@@ -320,8 +320,8 @@ int beamform_accumulated_complex_power_impl(dcs_bf_context *c, const float *dt_c
                                             const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                             float *d_block_power, size_t power_bytes, void *stream)
 {
-    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights)) || (flags & ~1u)) return DCS_ERR_INVALID_ARGUMENT;
-    const bf_complex_args cx = {flags & 1u};
+    if (int e = beamform_accumulated_complex_power_args(c, nt, d_weights, flags, d_block_power)) return e;
+    const bf_complex_args cx = {flags & DCS_BF_COMPLEX_CONJ};
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_block_power, power_bytes, stream,
                              {bacc_output::kBlockPower, d_weights, {}, &cx});
 }
@@ -332,10 +332,8 @@ int beamform_accumulated_complex_q8_impl(dcs_bf_context *c, const float *dt_coef
                                          const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
                                          unsigned long long *d_clip_count, void *stream)
 {
-    if (!c || !d_beams_q8 || !weights_ok(d_quant_gains) || (d_weights && !weights_ok(d_weights)) ||
-        (reinterpret_cast<uintptr_t>(d_clip_count) & 7u) || (flags & ~1u))
-        return DCS_ERR_INVALID_ARGUMENT;
-    const bf_complex_args cx = {flags & 1u};
+    if (int e = beamform_accumulated_complex_q8_args(c, nt, d_weights, flags, d_quant_gains, d_beams_q8, d_clip_count)) return e;
+    const bf_complex_args cx = {flags & DCS_BF_COMPLEX_CONJ};
     return beamform_acc_impl(c, dt_or_index(dt_coeff, t_coeff), nt, d_antenna, antenna_bytes, d_beams_q8, beams_bytes, stream,
                              {bacc_output::kInt8, d_weights, {d_quant_gains, d_clip_count}, &cx});
 }

@@ -2,9 +2,10 @@
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
 // detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h) and the
 // single-pulse search on its planes (include/dcs_single_pulse.h), each reached through the table at the head of every
-// context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Host code only; the
-// kernels are in bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip and
-// bf_single_pulse.hip.
+// context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Each begins with the
+// device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made already; what follows needs the
+// device or the context's sizes, or is a condition that only this side makes.  Host code only; the kernels are in
+// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip and bf_single_pulse.hip.
 
 #include <cmath>
 #include <cstring>
@@ -18,8 +19,7 @@ namespace bf_host {
 int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
                                uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream)
 {
-    if (!c || !weights_ok(d_block_power) || !weights_ok(d_spectra)) return DCS_ERR_INVALID_ARGUMENT;
-    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = integrate_block_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
@@ -43,15 +43,14 @@ int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, si
 int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
                                 uint32_t *d_block_power, size_t power_bytes, void *stream)
 {
-    if (!c || !d_block_power || (d_weights && !weights_ok(d_weights)) || (nt && !d_antenna)) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = incoherent_block_power_args(c, nt, d_weights, d_block_power)) return e;
+    if (nt && !d_antenna) return DCS_ERR_INVALID_ARGUMENT;
     DCS_CHECK_DEVICE(c);
-    if (nt % 16u) return DCS_ERR_INVALID_ARGUMENT;
     const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
     if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
     if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
     if (power_bytes < (size_t)C * (nt / 16u) * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_antenna) & 15u) || (reinterpret_cast<uintptr_t>(d_block_power) & 3u))
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (!aligned(d_antenna, 16u)) return DCS_ERR_INVALID_ARGUMENT;
     bf_incoh_args a;
     std::memset(&a, 0, sizeof(a));
     a.ant = d_antenna;
@@ -66,9 +65,7 @@ int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_p
                                     uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
                                     void *stream)
 {
-    if (!c || !d_block_power || !d_spectra || ((reinterpret_cast<uintptr_t>(d_block_power) | reinterpret_cast<uintptr_t>(d_spectra)) & 3u))
-        return DCS_ERR_INVALID_ARGUMENT;
-    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = integrate_incoherent_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
@@ -86,31 +83,12 @@ int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_p
     return (int)bf_launch_incoherent_integrate(a, as_stream(stream));
 }
 
-} // namespace bf_host
-
 // include/dcs_filterbank.h, reached the same way.  No coefficients and nothing allocated; nr_beams is the caller's, so the
 // one set of calls serves detected (the context's beams) and incoherent (1) spectra.
-namespace {
-// have >= x * y * z * w, the product taken without overflow
-bool holds(size_t have, uint64_t x, uint64_t y, uint64_t z, uint64_t w)
-{
-    const unsigned __int128 xy = (unsigned __int128)x * y, zw = (unsigned __int128)z * w;
-    if ((xy >> 64) || (zw >> 64)) return xy == 0 || zw == 0;
-    const unsigned __int128 need = xy * zw;
-    return !(need >> 64) && (uint64_t)need <= (uint64_t)have;
-}
-
-bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
-} // namespace
-
-namespace bf_host {
-
 int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
                       uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream)
 {
-    if (!c || !d_spectra || !d_sums || misaligned(d_spectra, 3u) || misaligned(d_sums, 7u) || nr_beams == 0u)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = spectra_sums_args(c, d_spectra, nr_beams, d_sums)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
@@ -128,9 +106,7 @@ int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_
 int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
                            float target_std, float *d_scales, size_t scales_bytes, void *stream)
 {
-    if (!c || !d_sums || !d_scales || misaligned(d_sums, 7u) || misaligned(d_scales, 7u) || nr_beams == 0u || count == 0u ||
-        count >= (1ull << 53))
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = filterbank_scales_args(c, d_sums, count, nr_beams, d_scales)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
@@ -149,10 +125,9 @@ int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra
                        const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
                        uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream)
 {
-    if (!c || !d_spectra || !d_scales || !d_filterbank || misaligned(d_spectra, 3u) || misaligned(d_scales, 7u) ||
-        misaligned(d_filterbank, 15u) || misaligned(d_clip_count, 7u) || nr_beams == 0u || (flags & ~1u) ||
-        first_spectrum > out_spectra || nr_spectra > out_spectra - first_spectrum)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = filterbank_q8_args(c, d_spectra, nr_spectra, nr_beams, d_scales, flags, d_filterbank, out_spectra, first_spectrum,
+                                   d_clip_count))
+        return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
@@ -168,7 +143,7 @@ int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra
     a.C = C;
     a.B = nr_beams;
     a.T = nr_spectra;
-    a.descending = flags & 1u;
+    a.descending = flags & DCS_FB_DESCENDING;
     a.level = level;
     return (int)bf_launch_filterbank_q8(a, as_stream(stream));
 }
@@ -177,9 +152,7 @@ int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra
 int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
                       uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream)
 {
-    if (!c || !d_beams_x || !d_beams_y || !d_block_stokes || (nr_stokes != 1u && nr_stokes != 4u)) return DCS_ERR_INVALID_ARGUMENT;
-    if (misaligned(d_beams_x, 15u) || misaligned(d_beams_y, 15u) || misaligned(d_block_stokes, 4u * nr_stokes - 1u) || nt % 16u)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = stokes_block_args(c, nt, d_beams_x, d_beams_y, nr_stokes, d_block_stokes)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     if (!holds(beams_bytes, C, nt, B, 2u)) return DCS_ERR_INVALID_ARGUMENT;
@@ -198,9 +171,7 @@ int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size
                           uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
                           size_t spectra_bytes, void *stream)
 {
-    if (!c || !d_block_stokes || !d_spectra || (nr_stokes != 1u && nr_stokes != 4u)) return DCS_ERR_INVALID_ARGUMENT;
-    if (misaligned(d_block_stokes, 4u * nr_stokes - 1u) || misaligned(d_spectra, 4u * nr_stokes - 1u)) return DCS_ERR_INVALID_ARGUMENT;
-    if (blocks_per_spectrum == 0u || nr_blocks % blocks_per_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = integrate_stokes_args(c, d_block_stokes, nr_blocks, blocks_per_spectrum, nr_stokes, d_spectra)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
     const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
@@ -225,10 +196,7 @@ int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size
 int dm_delays_impl(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
                    size_t delays_bytes, void *stream)
 {
-    if (!c || !band || !d_dms || !d_delays || misaligned(d_dms, 7u) || misaligned(d_delays, 3u)) return DCS_ERR_INVALID_ARGUMENT;
-    if (!std::isfinite(band->freq_first_mhz) || !std::isfinite(band->freq_step_mhz) || !std::isfinite(band->sample_time_s) ||
-        !(band->sample_time_s > 0.0) || !(band->freq_first_mhz > 0.0))
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = dm_delays_args(c, band, d_dms, d_delays)) return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     const double f_last = band->freq_first_mhz + (double)(C - 1u) * band->freq_step_mhz; // the kernel's own f_(C-1)
@@ -251,12 +219,9 @@ int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t fi
                        uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
                        uint64_t out_spectra, uint64_t first_out, void *stream)
 {
-    if (!c || !d_filterbank || !d_delays || !d_dm_time || misaligned(d_filterbank, 15u) || misaligned(d_delays, 3u) ||
-        misaligned(d_dm_time, 3u) || nr_beams == 0u || max_delay > 0x7ffffffeu)
-        return DCS_ERR_INVALID_ARGUMENT;
-    if (first_spectrum > in_spectra || (uint64_t)nr_spectra + max_delay > in_spectra - first_spectrum || first_out > out_spectra ||
-        nr_spectra > out_spectra - first_out)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = dedisperse_q8_args(c, d_filterbank, in_spectra, first_spectrum, nr_spectra, nr_beams, d_delays, max_delay, d_dm_time,
+                                   out_spectra, first_out))
+        return e;
     DCS_CHECK_DEVICE(c);
     const uint32_t C = (uint32_t)c->p.nr_channels;
     if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
@@ -285,9 +250,7 @@ int dm_time_sums_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_ti
                       uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
                       uint64_t *d_sums, size_t sums_bytes, void *stream)
 {
-    if (!c || !d_dm_time || !d_sums || misaligned(d_dm_time, 3u) || misaligned(d_sums, 7u) || nr_beams == 0u)
-        return DCS_ERR_INVALID_ARGUMENT;
-    if (first_spectrum > plane_spectra || nr_spectra > plane_spectra - first_spectrum) return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = dm_time_sums_args(c, d_dm_time, plane_spectra, first_spectrum, nr_spectra, nr_beams, d_sums)) return e;
     DCS_CHECK_DEVICE(c);
     const uint64_t series = (uint64_t)nr_beams * nr_dm;
     if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
@@ -308,14 +271,9 @@ int boxcar_peaks_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_ti
                       uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
                       uint64_t peak_blocks, uint64_t first_block, void *stream)
 {
-    if (!c || !d_dm_time || !d_widths || !d_peaks || misaligned(d_dm_time, 3u) || misaligned(d_widths, 3u) ||
-        misaligned(d_peaks, 7u) || nr_beams == 0u || max_width < 1u || max_width > 4096u || block_len < 64u || block_len > 4096u ||
-        block_len % 64u)
-        return DCS_ERR_INVALID_ARGUMENT;
-    const uint64_t nr_blocks = ((uint64_t)nr_spectra + block_len - 1u) / block_len;
-    if (first_spectrum > plane_spectra || (uint64_t)nr_spectra + (max_width - 1u) > plane_spectra - first_spectrum ||
-        first_block > peak_blocks || nr_blocks > peak_blocks - first_block)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = boxcar_peaks_args(c, d_dm_time, plane_spectra, first_spectrum, nr_spectra, nr_beams, d_widths, max_width, block_len,
+                                  d_peaks, peak_blocks, first_block))
+        return e;
     DCS_CHECK_DEVICE(c);
     const uint64_t series = (uint64_t)nr_beams * nr_dm;
     if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
@@ -341,10 +299,9 @@ int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes
                   uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
                   uint32_t *d_best, size_t best_bytes, void *stream)
 {
-    if (!c || !d_peaks || !d_widths || !d_sums || !d_snr || misaligned(d_peaks, 7u) || misaligned(d_widths, 3u) ||
-        misaligned(d_sums, 7u) || misaligned(d_snr, 3u) || misaligned(d_best, 3u) || nr_beams == 0u || max_width < 1u ||
-        max_width > 4096u || first_block > peak_blocks || nr_blocks > peak_blocks - first_block || count == 0u)
-        return DCS_ERR_INVALID_ARGUMENT;
+    if (int e = peak_snr_args(c, d_peaks, peak_blocks, first_block, nr_blocks, nr_beams, d_widths, max_width, d_sums, count, d_snr,
+                              d_best))
+        return e;
     DCS_CHECK_DEVICE(c);
     const uint64_t series = (uint64_t)nr_beams * nr_dm;
     if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;

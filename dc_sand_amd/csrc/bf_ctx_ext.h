@@ -6,8 +6,9 @@
 // (include/dcs_dedisperse.h) and libdcs_single_pulse.so (include/dcs_single_pulse.h).  All are built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion and of the single-pulse search; a companion
-// checks the arguments it can check without a device, then the table's version, and forwards.  Not a public interface.
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion and of the single-pulse search; a companion's
+// export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
+// takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
 #define BF_CTX_EXT_H
 
@@ -16,6 +17,7 @@
 
 #include "../../include/dcs_beamformer.h"
 #include "../../include/dcs_dedisperse.h" // dcs_bf_band
+#include "bf_arg_checks.h"
 
 // 2: beamform_accumulated_q8 appended; 3: beamform_accumulated_power, integrate_block_power appended; 5: incoherent_block_power,
 // integrate_incoherent_power appended.  4 is skipped for good: tests/test_host_abi_beam_power.py hands the power companion a
@@ -121,11 +123,19 @@ struct bf_ctx_ext_head {
     const bf_ctx_ext_ops *ops;
 };
 
-// a companion's way to the table, once its own checks have found c non-null: nullptr where the versions differ
+// a companion's way to the table, once the entry's checks have found c non-null: nullptr where the versions differ
 static inline const bf_ctx_ext_ops *ops_of(dcs_bf_context *c)
 {
     const bf_ctx_ext_ops *ops = reinterpret_cast<const bf_ctx_ext_head *>(c)->ops;
     return ops && ops->version == BF_CTX_EXT_VERSION ? ops : nullptr;
+}
+
+// a companion's call of one entry with the arguments a: DCS_ERR_UNSUPPORTED where the versions differ
+template <class F, class... A>
+int forward(dcs_bf_context *c, F bf_ctx_ext_ops::*entry, A... a)
+{
+    const bf_ctx_ext_ops *ops = ops_of(c);
+    return ops ? (ops->*entry)(c, a...) : DCS_ERR_UNSUPPORTED;
 }
 
 #endif // BF_CTX_EXT_H

@@ -93,9 +93,6 @@ namespace bf_host {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-// fp32 values in device memory: non-null, 4-byte aligned
-inline bool weights_ok(const float *d_weights) { return d_weights && !(reinterpret_cast<uintptr_t>(d_weights) & 3u); }
-
 // Launch geometry of the tiled form, as pick_geometry decides it (bf_capi_generate.hip)
 struct bf_geom {
     int tpb;
