@@ -93,4 +93,9 @@ COMPANIONS = {
          [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, c_uint32, c_uint32, _VP, c_size_t, c_uint64,
           _VP, c_size_t, _VP, c_size_t, _VP]),
     ]),
+    # the correlator: the exact int32 visibilities of every antenna pair of the sample tensor, integrated like the Stokes parameters
+    "correlator": Companion("dcs_correlator.h", "bf_correlator.cpp", "libdcs_correlator.so", [
+        ("dcs_bf_correlate_block", c_int, [_VP, c_uint32, _VP, c_size_t, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_integrate_visibilities", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+    ]),
 }

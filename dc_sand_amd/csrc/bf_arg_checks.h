@@ -177,4 +177,18 @@ inline int peak_snr_args(dcs_bf_context *c, const uint32_t *d_peaks, uint64_t pe
                       fits(first_block, nr_blocks, peak_blocks) && count != 0u);
 }
 
+// include/dcs_correlator.h: a visibility is blocks_per_vis whole blocks, few enough that no sum leaves int32; a baseline's
+// (re, im) is stored as one pair of words
+inline int correlate_block_args(dcs_bf_context *c, uint32_t nt, uint32_t blocks_per_vis, const int32_t *d_vis)
+{
+    return arg_status(c && d_vis && aligned(d_vis, 8u) && nt % 16u == 0u && blocks_per_vis != 0u && blocks_per_vis <= 4095u &&
+                      (nt / 16u) % blocks_per_vis == 0u);
+}
+inline int integrate_visibilities_args(dcs_bf_context *c, const int32_t *d_vis, uint32_t nr_vis, uint32_t vis_per_integration,
+                                       const float *d_out)
+{
+    return arg_status(c && d_vis && d_out && aligned(d_vis, 8u) && aligned(d_out, 4u) && vis_per_integration != 0u &&
+                      nr_vis % vis_per_integration == 0u);
+}
+
 #endif // BF_ARG_CHECKS_H

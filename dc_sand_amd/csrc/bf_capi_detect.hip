@@ -1,11 +1,11 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
-// detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h) and the
-// single-pulse search on its planes (include/dcs_single_pulse.h), each reached through the table at the head of every
+// detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h), the
+// single-pulse search on its planes (include/dcs_single_pulse.h) and the correlator (include/dcs_correlator.h), each reached through the table at the head of every
 // context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Each begins with the
 // device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made already; what follows needs the
 // device or the context's sizes, or is a condition that only this side makes.  Host code only; the kernels are in
-// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip and bf_single_pulse.hip.
+// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip and bf_correlator.hip.
 
 #include <cmath>
 #include <cstring>
@@ -325,6 +325,55 @@ int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes
     a.nr_widths = nr_widths;
     a.max_width = max_width;
     return (int)bf_launch_peak_snr(a, as_stream(stream));
+}
+
+// include/dcs_correlator.h, reached the same way.  No coefficients, nothing allocated, and math_mode plays no part.
+int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, uint32_t blocks_per_vis,
+                         int32_t *d_vis, size_t vis_bytes, void *stream)
+{
+    if (int e = correlate_block_args(c, nt, blocks_per_vis, d_vis)) return e;
+    if (nt && !d_antenna) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
+    const uint32_t nr_vis = nt / 16u / blocks_per_vis;
+    if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
+    if (!aligned(d_antenna, 16u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(antenna_bytes, C, nt, A, 2u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(vis_bytes, C, nr_vis, (uint64_t)A * (A + 1u) / 2u, 2u * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_corr_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ant = d_antenna;
+    a.vis = d_vis;
+    a.A = A;
+    a.C = C;
+    a.nT16 = nt / 16u;
+    a.n = blocks_per_vis;
+    a.nr_vis = nr_vis;
+    return (int)bf_launch_correlate(a, as_stream(stream));
+}
+
+// the integrator is the Stokes parameters': a (channel, visibility) row of 2 NB words in place of B * nr_stokes
+int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis, uint32_t vis_per_integration,
+                                uint32_t accumulate, float *d_out, size_t out_bytes, void *stream)
+{
+    if (int e = integrate_visibilities_args(c, d_vis, nr_vis, vis_per_integration, d_out)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t A = (uint64_t)c->p.nr_stations, C = (uint64_t)c->p.nr_channels;
+    const uint64_t n_out = nr_vis / vis_per_integration, bs = A * (A + 1u); // 2 NB
+    if (bs > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
+    if (!holds(vis_bytes, C, nr_vis, bs, sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(out_bytes, n_out, C, bs, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_stokes_int_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.block_stokes = d_vis;
+    a.spectra = d_out;
+    a.bs = (uint32_t)bs;
+    a.total = n_out * C * bs;
+    a.C = (uint32_t)C;
+    a.nr_blocks = nr_vis;
+    a.n = vis_per_integration;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_stokes_integrate(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -3,10 +3,11 @@
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
 // (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
-// (include/dcs_dedisperse.h) and libdcs_single_pulse.so (include/dcs_single_pulse.h).  All are built from this tree together.
+// (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h) and libdcs_correlator.so
+// (include/dcs_correlator.h).  All are built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion and of the single-pulse search; a companion's
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search and of the correlator; a companion's
 // export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
 // takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
@@ -32,7 +33,9 @@
 // hands a foreign version above 8).
 // 11: dm_time_sums, boxcar_peaks, peak_snr appended (tests/test_host_abi_single_pulse.py hands its companion 1, 9 and 10; no
 // older test hands a foreign version above 9).
-#define BF_CTX_EXT_VERSION 11u
+// 12: correlate_block, integrate_visibilities appended (tests/test_host_abi_correlator.py hands its companion 1, 10 and 11; no
+// older test hands a foreign version above 10).
+#define BF_CTX_EXT_VERSION 12u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -116,6 +119,12 @@ struct bf_ctx_ext_ops {
                     uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
                     uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
                     uint32_t *d_best, size_t best_bytes, void *stream);
+    // the correlator (include/dcs_correlator.h): the sample tensor -> exact visibilities int32 [C][nr_vis][NB][{re, im}] of
+    // the pairs b <= a, nr_vis = (nt / 16) / blocks_per_vis; visibilities -> float [nr_vis / vis_per_integration][C][NB][{re, im}]
+    int (*correlate_block)(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, uint32_t blocks_per_vis,
+                           int32_t *d_vis, size_t vis_bytes, void *stream);
+    int (*integrate_visibilities)(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis,
+                                  uint32_t vis_per_integration, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
 };
 
 // the first member of struct dcs_bf_context

@@ -129,8 +129,8 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
 // the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
-// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two, the dedispersion's two and the
-// single-pulse search's three in bf_capi_detect.hip
+// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two, the dedispersion's two, the
+// single-pulse search's three and the correlator's two in bf_capi_detect.hip
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -189,6 +189,10 @@ int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes
                   uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
                   uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
                   uint32_t *d_best, size_t best_bytes, void *stream);
+int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, uint32_t blocks_per_vis,
+                         int32_t *d_vis, size_t vis_bytes, void *stream);
+int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis,
+                                uint32_t vis_per_integration, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
 
 } // namespace bf_host
 

@@ -332,6 +332,25 @@ struct bf_peaksnr_args {
 hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream);
 hipError_t bf_warm_module_single_pulse();
 
+// The correlator (bf_correlator.hip; include/dcs_correlator.h): the sample tensor
+// [C][nT16][A][16][2] -> exact visibilities int32 [C][nr_vis][NB][2] of the pairs b <= a, each summed over n blocks
+struct bf_corr_args {
+    const int8_t *ant; // 16-byte aligned
+    int32_t *vis;      // 8-byte aligned
+    uint64_t NB;       // filled by the launcher: A (A + 1) / 2
+    uint64_t items;    // filled by the launcher: C * nr_vis * units
+    uint32_t A;        // 1 .. 256
+    uint32_t C;
+    uint32_t nT16;     // blocks of the tensor, >= nr_vis * n
+    uint32_t n;        // blocks per visibility, 1 .. 4095
+    uint32_t nr_vis;
+    uint32_t tiles;    // filled by the launcher: 16-antenna tiles
+    uint32_t st;       // filled by the launcher: squares of 4 x 4 tiles along the diagonal
+    uint32_t units;    // filled by the launcher: units (the tile pairs a wave takes at once) per (channel, visibility)
+};
+hipError_t bf_launch_correlate(const bf_corr_args &a, hipStream_t stream);
+hipError_t bf_warm_module_correlator();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

@@ -139,6 +139,29 @@ def stokes_spectra_bytes(params: BeamformerParameters, nr_blocks: int, blocks_pe
     return (int(nr_blocks) // int(blocks_per_spectrum)) * int(params.NR_CHANNELS) * int(params.NR_BEAMS) * int(nr_stokes) * 4
 
 
+def nr_baselines(nr_stations: int) -> int:
+    """``NB = A (A + 1) / 2``: the antenna pairs ``(a, b)``, ``b <= a``, of the correlator; pair ``(a, b)`` has index
+    ``a (a + 1) / 2 + b``."""
+    a = int(nr_stations)
+    return a * (a + 1) // 2
+
+
+def block_visibilities_bytes(params: BeamformerParameters, nt: int, blocks_per_vis: int) -> int:
+    """Size of the visibilities ``int32 [C][(nt / 16) / blocks_per_vis][NB][{re, im}]`` of
+    :meth:`SteeringCoefficientGenerator.correlate_block`."""
+    if not 1 <= blocks_per_vis <= 4095 or (int(nt) // 16) % blocks_per_vis:
+        raise ValueError("nt / 16 must be a multiple of blocks_per_vis, which is 1 .. 4095")
+    return int(params.NR_CHANNELS) * (int(nt) // 16 // int(blocks_per_vis)) * nr_baselines(params.NR_STATIONS) * 8
+
+
+def visibilities_bytes(params: BeamformerParameters, nr_vis: int, vis_per_integration: int) -> int:
+    """Size of the integrated visibilities ``float [nr_vis / vis_per_integration][C][NB][{re, im}]`` of
+    :meth:`SteeringCoefficientGenerator.integrate_visibilities`."""
+    if vis_per_integration <= 0 or nr_vis % vis_per_integration:
+        raise ValueError("nr_vis must be a multiple of vis_per_integration >= 1")
+    return (int(nr_vis) // int(vis_per_integration)) * int(params.NR_CHANNELS) * nr_baselines(params.NR_STATIONS) * 8
+
+
 def spectra_sums_bytes(params: BeamformerParameters, nr_beams: int) -> int:
     """Size of the running sums ``double [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.spectra_sums`."""
     return int(params.NR_CHANNELS) * int(nr_beams) * 16
@@ -545,6 +568,29 @@ class SteeringCoefficientGenerator:
                                  _p(d_sums), int(sums_bytes), int(count), _p(d_snr), int(snr_bytes), _p_or_null(d_best),
                                  int(best_bytes), _s(stream)),
               "dcs_bf_peak_snr")
+
+    # -- the correlator (include/dcs_correlator.h, companion library libdcs_correlator.so): d_vis is a device int32
+    #    [C][(nt / 16) / blocks_per_vis][NB][2] array, d_out a device float [nr_vis / vis_per_integration][C][NB][2] array
+    def correlate_block(self, d_antenna, antenna_bytes: int, d_vis, vis_bytes: int, nt: int, blocks_per_vis: int,
+                        stream=None) -> None:
+        """The visibilities ``sum_t x_a[t] conj(x_b[t])`` of every antenna pair ``b <= a`` (:func:`nr_baselines`) over every
+        ``blocks_per_vis`` (1 .. 4095) blocks of 16 samples, as exact integers ``{re, im}``
+        (:func:`block_visibilities_bytes`).  No delay table is needed."""
+        cl = _lib.companion("correlator")
+        check(cl.dcs_bf_correlate_block(c_void_p(self._h), int(nt), _p(d_antenna), int(antenna_bytes), int(blocks_per_vis),
+                                        _p(d_vis), int(vis_bytes), _s(stream)),
+              "dcs_bf_correlate_block")
+
+    def integrate_visibilities(self, d_vis, vis_bytes: int, nr_vis: int, vis_per_integration: int, d_out, out_bytes: int,
+                               accumulate: bool = False, stream=None) -> None:
+        """Sums the visibilities ``[C][nr_vis][NB][2]`` ``vis_per_integration`` at a time, exactly, into
+        ``[nr_vis / vis_per_integration][C][NB][2]`` (:func:`visibilities_bytes`), each sum rounded to float once; with
+        ``accumulate`` it is added to what ``d_out`` holds, so an integration can span calls."""
+        cl = _lib.companion("correlator")
+        check(cl.dcs_bf_integrate_visibilities(c_void_p(self._h), _p(d_vis), int(vis_bytes), int(nr_vis),
+                                               int(vis_per_integration), 1 if accumulate else 0, _p(d_out), int(out_bytes),
+                                               _s(stream)),
+              "dcs_bf_integrate_visibilities")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -45,6 +45,11 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the single-pulse search on the planes of that shape: the sums, the boxcar peaks of 13 widths and the signal-to-noise,
         the peaks' share of one read of the planes, and all three against dedisperse_q8 in the same process
                                                                                     -> profiles/r14_single_pulse.md
+    python tools/measure.py correlator [--rounds 5] [--shapes AxCxNTxN,...] [--buffers 2]
+        the correlator's block call rotating over copies of the samples that together stay above the Infinity Cache, against
+        the incoherent beam over the same bytes (the read yardstick), alternating, in one process: the time, the fraction of
+        one read of the samples at 6.3 TB/s and the matrix cores' share at their peak rate, and the integration
+                                                                                    -> profiles/r15_correlator.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -933,6 +938,67 @@ def cmd_single_pulse(args):
         d.free()
 
 
+def cmd_correlator(args):
+    """The correlator (include/dcs_correlator.h): one read of the samples (A * 32 bytes per channel and block) and
+    NB * 8 bytes written per channel and visibility.  Per shape A x C x nt x n, in turn ``--rounds`` times in one process on the
+    same noise-like samples: the block call and the incoherent beam's block call over the very same bytes (a streaming read
+    of the same tensor: the yardstick), each rotating over ``--buffers`` copies, and the integration of all visibilities of a
+    channel.  The bound is one read of the samples at 6.3 TB/s; the matrix cores' time is 4 MFMAs of 16x16x64 i8 per tile
+    pair and four blocks at 16 cycles each on 1024 SIMDs at 2.4 GHz."""
+    from dc_sand_amd.generator import block_visibilities_bytes, incoherent_block_power_bytes, nr_baselines, visibilities_bytes
+
+    rows = []
+    for shape in args.shapes.split(","):
+        A, C, nt, n = (int(x) for x in shape.split("x"))
+        nblk, nr_vis = nt // 16, nt // 16 // n
+        ab = A * C * nt * 2
+        nbuf = max(args.buffers, -(-(512 << 20) // ab))  # together at least twice the Infinity Cache
+        bufs = [device.mem_alloc(ab) for _ in range(nbuf)]
+        for d in bufs:
+            _noise(d, ab)
+        turn = [0]
+
+        def d_ant():
+            turn[0] = (turn[0] + 1) % nbuf
+            return bufs[turn[0]]
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=nt)
+        g = SteeringCoefficientGenerator(bp)
+        vb, ob, pb = block_visibilities_bytes(bp, nt, n), visibilities_bytes(bp, nr_vis, nr_vis), incoherent_block_power_bytes(bp, nt)
+        d_vis, d_out, d_p = device.mem_alloc(vb), device.mem_alloc(ob), device.mem_alloc(pb)
+        corr = lambda: g.correlate_block(d_ant(), ab, d_vis, vb, nt, n)  # noqa: E731
+        incoh = lambda: g.incoherent_block_power(d_ant(), ab, d_p, pb, nt)  # noqa: E731
+        integ = lambda: g.integrate_visibilities(d_vis, vb, nr_vis, nr_vis, d_out, ob)  # noqa: E731
+        for fn in (corr, incoh, integ):
+            fn()
+        t = {name: [] for name in ("corr", "incoh", "incoh_again", "int")}
+        for _ in range(args.rounds):
+            t["corr"].append(per_launch_ms(corr))
+            t["incoh"].append(per_launch_ms(incoh))
+            t["incoh_again"].append(per_launch_ms(incoh))
+            t["int"].append(per_launch_ms(integ))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        both = t["incoh"] + t["incoh_again"]
+        incoh_ms = float(np.median(both))
+        tiles = -(-A // 16)
+        mfmas = tiles * (tiles + 1) // 2 * 4 * C * nr_vis * -(-n // 4)
+        mfma_ms = mfmas * 16 / (1024 * 2.4e9) * 1e3
+        bound_ms = ab / 6.3e12 * 1e3
+        row = {"shape": shape, "baselines": nr_baselines(A), "read_MiB": ab >> 20, "written_MiB": round(vb / (1 << 20), 1),
+               "buffers": nbuf, "corr_us": round(med["corr"] * 1e3, 1), "corr_spread": round(max(t["corr"]) / min(t["corr"]) - 1.0, 4),
+               "corr_read_TBps": round(ab / (med["corr"] * 1e-3) / 1e12, 2),
+               "read_bound_us": round(bound_ms * 1e3, 1), "frac_of_read_bound": round(bound_ms / med["corr"], 3),
+               "mfma_peak_us": round(mfma_ms * 1e3, 1), "mfma_share_of_time": round(mfma_ms / med["corr"], 3),
+               "incoh_us": round(incoh_ms * 1e3, 1), "incoh_read_TBps": round(ab / (incoh_ms * 1e-3) / 1e12, 2),
+               "incoh_spread": round(max(both) / min(both) - 1.0, 4), "corr_over_incoh": round(med["corr"] / incoh_ms, 3),
+               "int_us": round(med["int"] * 1e3, 1)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        for d in bufs + [d_vis, d_out, d_p]:
+            d.free()
+    print(json.dumps({"correlator": rows}), flush=True)
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1364,6 +1430,10 @@ def main():
     p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB: the shape of dedisperse")
     p.add_argument("--block-len", type=int, default=256, help="spectra per block of the peak plane")
     p.add_argument("--buffers", type=int, default=3, help="copies of the planes the rotated timings walk")
+    p = sub.add_parser("correlator")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the correlator and the incoherent beam per shape")
+    p.add_argument("--shapes", default="64x4096x4096x64,256x1024x4096x64", help="AxCxNTxN, comma-separated: n blocks per visibility")
+    p.add_argument("--buffers", type=int, default=2, help="copies of the samples that the timings rotate over, at least")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1408,7 +1478,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "correlator": cmd_correlator, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
