@@ -98,4 +98,10 @@ COMPANIONS = {
         ("dcs_bf_correlate_block", c_int, [_VP, c_uint32, _VP, c_size_t, c_uint32, _VP, c_size_t, _VP]),
         ("dcs_bf_integrate_visibilities", c_int, [_VP, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP]),
     ]),
+    # the narrowband digital down-converter: mixer, FIR of up to 256 integer taps and decimation by 16 of the digitiser's stream
+    "ddc": Companion("dcs_ddc.h", "bf_ddc.cpp", "libdcs_ddc.so", [
+        ("dcs_bf_ddc_tap_digits", c_int, [_VP, _VP, c_uint32, c_uint32, _VP, c_size_t, _VP]),
+        ("dcs_bf_ddc", c_int, [_VP, c_uint32, c_uint32, _VP, c_size_t, c_uint64, _VP, c_size_t, c_uint32, c_uint32, _VP, c_uint64,
+                               _VP, c_size_t, c_uint64, _VP]),
+    ]),
 }

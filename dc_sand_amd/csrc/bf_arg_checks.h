@@ -12,6 +12,7 @@
 
 #include "../../include/dcs_beam_complex.h" // DCS_BF_COMPLEX_CONJ
 #include "../../include/dcs_beamformer.h"
+#include "../../include/dcs_ddc.h"        // dcs_ddc_band
 #include "../../include/dcs_dedisperse.h" // dcs_bf_band
 #include "../../include/dcs_filterbank.h" // DCS_FB_DESCENDING
 #include "../../include/dcs_stokes.h"     // DCS_BF_STOKES_I, DCS_BF_STOKES_IQUV
@@ -189,6 +190,34 @@ inline int integrate_visibilities_args(dcs_bf_context *c, const int32_t *d_vis, 
 {
     return arg_status(c && d_vis && d_out && aligned(d_vis, 8u) && aligned(d_out, 4u) && vis_per_integration != 0u &&
                       nr_vis % vis_per_integration == 0u);
+}
+
+// include/dcs_ddc.h: T taps in whole K steps of 64, one or two bands, the operand table of 16 T bytes
+inline bool ddc_shape_ok(uint32_t nr_taps, uint32_t nr_bands)
+{
+    return nr_taps % 64u == 0u && nr_taps >= 64u && nr_taps <= 256u && (nr_bands == 1u || nr_bands == 2u);
+}
+inline int ddc_tap_digits_args(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, const void *d_digits,
+                               size_t digits_bytes)
+{
+    return arg_status(c && d_taps && d_digits && aligned(d_taps, 4u) && aligned(d_digits, 16u) && ddc_shape_ok(nr_taps, nr_bands) &&
+                      holds(digits_bytes, 16u, nr_taps, 1u, 1u));
+}
+// a row is read from its sample 0 to 16 (nr_out - 1) + T - 1 and written from its pair 0 to nr_out - 1: the last row of either
+// tensor need not be a whole stride
+inline int ddc_args(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes,
+                    uint64_t in_stride, const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands,
+                    const dcs_ddc_band *bands, const float *d_out, size_t out_bytes, uint64_t out_stride)
+{
+    if (!(c && d_digits && bands && d_out && aligned(d_samples, 16u) && aligned(d_digits, 16u) && aligned(d_out, 8u) &&
+          ddc_shape_ok(nr_taps, nr_bands) && holds(digits_bytes, 16u, nr_taps, 1u, 1u) && in_stride % 16u == 0u && out_stride >= nr_out))
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (nr_out == 0u || nr_inputs == 0u) return DCS_OK;
+    const uint64_t row = 16u * ((uint64_t)nr_out - 1u) + nr_taps;
+    const unsigned __int128 need = (unsigned __int128)(nr_inputs - 1u) * in_stride + row;
+    const unsigned __int128 pairs = (unsigned __int128)((uint64_t)nr_bands * nr_inputs - 1u) * out_stride + nr_out; // < 2^98
+    return arg_status(d_samples && in_stride >= row && !(need >> 64) && (uint64_t)need <= (uint64_t)samples_bytes &&
+                      !(pairs >> 61) && (uint64_t)pairs * (2u * sizeof(float)) <= (uint64_t)out_bytes);
 }
 
 #endif // BF_ARG_CHECKS_H

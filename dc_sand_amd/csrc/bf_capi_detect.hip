@@ -1,11 +1,13 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
 // detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h), the
-// single-pulse search on its planes (include/dcs_single_pulse.h) and the correlator (include/dcs_correlator.h), each reached through the table at the head of every
+// single-pulse search on its planes (include/dcs_single_pulse.h), the correlator (include/dcs_correlator.h) and the digital
+// down-converter (include/dcs_ddc.h), each reached through the table at the head of every
 // context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Each begins with the
 // device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made already; what follows needs the
 // device or the context's sizes, or is a condition that only this side makes.  Host code only; the kernels are in
-// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip and bf_correlator.hip.
+// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip, bf_correlator.hip and
+// bf_ddc.hip.
 
 #include <cmath>
 #include <cstring>
@@ -374,6 +376,52 @@ int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t 
     a.n = vis_per_integration;
     a.accumulate = accumulate ? 1u : 0u;
     return (int)bf_launch_stokes_integrate(a, as_stream(stream));
+}
+
+// include/dcs_ddc.h, reached the same way.  Of the context these use the device alone: every size is an argument, and the
+// device-free checks are all the checks there are.
+int ddc_tap_digits_impl(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, void *d_digits,
+                        size_t digits_bytes, void *stream)
+{
+    if (int e = ddc_tap_digits_args(c, d_taps, nr_taps, nr_bands, d_digits, digits_bytes)) return e;
+    DCS_CHECK_DEVICE(c);
+    bf_ddc_digits_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.taps = d_taps;
+    a.digits = static_cast<int8_t *>(d_digits);
+    a.T = nr_taps;
+    a.nr_bands = nr_bands;
+    return (int)bf_launch_ddc_tap_digits(a, as_stream(stream));
+}
+
+// the oscillator of output m of the call is phase0 + 16 (first_output + m) phase_step mod 2^32: the part that does not depend on
+// m is made here, in wrapping 32-bit arithmetic
+int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes, uint64_t in_stride,
+             const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands, const dcs_ddc_band *bands,
+             uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream)
+{
+    if (int e = ddc_args(c, nr_inputs, nr_out, d_samples, samples_bytes, in_stride, d_digits, digits_bytes, nr_taps, nr_bands, bands,
+                         d_out, out_bytes, out_stride))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    if (nr_out == 0u || nr_inputs == 0u) return DCS_OK;
+    bf_ddc_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = d_samples;
+    a.digits = static_cast<const int8_t *>(d_digits);
+    a.out = d_out;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.nr_inputs = nr_inputs;
+    a.nr_out = nr_out;
+    a.T = nr_taps;
+    a.nr_bands = nr_bands;
+    for (uint32_t b = 0; b < nr_bands; b++) {
+        a.step16[b] = 16u * bands[b].phase_step;
+        a.u0[b] = bands[b].phase0 + (uint32_t)first_output * a.step16[b];
+        a.gain[b] = bands[b].gain;
+    }
+    return (int)bf_launch_ddc(a, as_stream(stream));
 }
 
 } // namespace bf_host

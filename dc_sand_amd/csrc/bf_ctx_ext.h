@@ -3,11 +3,11 @@
 // (include/dcs_beam_power.h), libdcs_incoherent_beam.so (include/dcs_incoherent_beam.h), libdcs_filterbank.so
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
 // (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
-// (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h) and libdcs_correlator.so
-// (include/dcs_correlator.h).  All are built from this tree together.
+// (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h), libdcs_correlator.so
+// (include/dcs_correlator.h) and libdcs_ddc.so (include/dcs_ddc.h).  All are built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search and of the correlator; a companion's
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator and of the down-converter; a companion's
 // export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
 // takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
@@ -35,7 +35,9 @@
 // older test hands a foreign version above 9).
 // 12: correlate_block, integrate_visibilities appended (tests/test_host_abi_correlator.py hands its companion 1, 10 and 11; no
 // older test hands a foreign version above 10).
-#define BF_CTX_EXT_VERSION 12u
+// 13: ddc_tap_digits, ddc appended (tests/test_host_abi_ddc.py hands its companion 1, 11 and 12; no older test hands a
+// foreign version above 11).
+#define BF_CTX_EXT_VERSION 13u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -125,6 +127,13 @@ struct bf_ctx_ext_ops {
                            int32_t *d_vis, size_t vis_bytes, void *stream);
     int (*integrate_visibilities)(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis,
                                   uint32_t vis_per_integration, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
+    // the digital down-converter (include/dcs_ddc.h): integer taps -> the operand table; real int8 [nr_inputs][in_stride] ->
+    // float [band][input][out_stride][{re, im}], mixed, filtered and decimated by 16
+    int (*ddc_tap_digits)(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, void *d_digits,
+                          size_t digits_bytes, void *stream);
+    int (*ddc)(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes,
+               uint64_t in_stride, const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands,
+               const dcs_ddc_band *bands, uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream);
 };
 
 // the first member of struct dcs_bf_context

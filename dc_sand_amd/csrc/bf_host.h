@@ -130,7 +130,7 @@ int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
 // the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
 // complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two, the dedispersion's two, the
-// single-pulse search's three and the correlator's two in bf_capi_detect.hip
+// single-pulse search's three, the correlator's two and the down-converter's two in bf_capi_detect.hip
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -193,6 +193,11 @@ int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna
                          int32_t *d_vis, size_t vis_bytes, void *stream);
 int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis,
                                 uint32_t vis_per_integration, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
+int ddc_tap_digits_impl(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, void *d_digits,
+                        size_t digits_bytes, void *stream);
+int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes, uint64_t in_stride,
+             const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands, const dcs_ddc_band *bands,
+             uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream);
 
 } // namespace bf_host
 

@@ -351,6 +351,34 @@ struct bf_corr_args {
 hipError_t bf_launch_correlate(const bf_corr_args &a, hipStream_t stream);
 hipError_t bf_warm_module_correlator();
 
+// The digital down-converter (bf_ddc.hip; include/dcs_ddc.h): real int8 [nr_inputs][in_stride] ->
+// float [band][input][out_stride][{re, im}], nr_out outputs per row, output m from samples 16 m .. 16 m + T - 1
+struct bf_ddc_digits_args {
+    const int32_t *taps; // [band][T][{re, im}]
+    int8_t *digits;      // 16 T bytes, 16-byte aligned
+    uint32_t T;          // 64, 128, 192, 256
+    uint32_t nr_bands;   // 1, 2
+};
+hipError_t bf_launch_ddc_tap_digits(const bf_ddc_digits_args &a, hipStream_t stream);
+struct bf_ddc_args {
+    const int8_t *x;      // 16-byte aligned
+    const int8_t *digits; // the table of bf_launch_ddc_tap_digits for (T, nr_bands)
+    float *out;           // 8-byte aligned
+    uint64_t in_stride;   // bytes, % 16 == 0, >= 16 (nr_out - 1) + T
+    uint64_t out_stride;  // pairs, >= nr_out
+    uint64_t items;       // filled by the launcher: nr_inputs * spans
+    uint32_t nr_inputs;
+    uint32_t nr_out;
+    uint32_t T;
+    uint32_t nr_bands;
+    uint32_t spans;       // filled by the launcher: the spans of outputs of a row, one workgroup each
+    uint32_t u0[2];       // per band: the phase word of output 0 of the call
+    uint32_t step16[2];   // per band: 16 phase_step, the phase step per output
+    float gain[2];
+};
+hipError_t bf_launch_ddc(const bf_ddc_args &a, hipStream_t stream);
+hipError_t bf_warm_module_ddc();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

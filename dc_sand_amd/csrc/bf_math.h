@@ -266,6 +266,37 @@ DCS_HD void dcs_sincos_fast(const float x, float *fSin, float *fCos)
     *fCos = dcs_bits_f32(dcs_xor_sign_of(uc, t30));
 }
 
+// sin and cos of the angle u / 2^32 turns, u a 32-bit phase word as a numerically controlled oscillator keeps it
+// (include/dcs_ddc.h).  The reduction is integer and exact: quadrant n = (u + 2^29) >> 30 (the nearest
+// quarter turn, mod 4) and r = (int32)(u - (n << 30)) in [-2^29, 2^29).  x = RN(RN((float)r) * k), k = RN(pi/2 * 2^-30), is
+// the reduced argument in radians, |x| <= pi/4 (1 + 2^-23): two roundings (and k's own), each 2^-24 relative.  Then the full
+// polynomials of dcs_sincos_core and the quadrant rotation of dcs_sincos_fast.  Each result is within 2^-22 absolute of the
+// true value (tests/test_ddc_model.py sweeps it against fp64).
+#define DCS_TURN32_K (DCS_PIO2_1 * 9.31322574615478515625e-10f) // RN(pi/2) * 2^-30, an exact scaling
+DCS_HD void dcs_sincos_turn32(const uint32_t u, float *fSin, float *fCos)
+{
+    const uint32_t n = (u + 0x20000000u) >> 30;
+    const int32_t ri = (int32_t)(u - (n << 30));
+    const float x = (float)ri * DCS_TURN32_K;
+    const float s = x * x;
+    float ps = dcs_fmaf(s, DCS_S4, DCS_S3);
+    ps = dcs_fmaf(ps, s, DCS_S2);
+    ps = dcs_fmaf(ps, s, DCS_S1);
+    float pc = dcs_fmaf(s, DCS_C4, DCS_C3);
+    pc = dcs_fmaf(pc, s, DCS_C2);
+    pc = dcs_fmaf(pc, s, DCS_C1);
+    pc = dcs_fmaf(pc, s, -0.5f);
+    const float sr = dcs_fmaf(s * x, ps, x);
+    const float cr = dcs_fmaf(s, pc, 1.0f);
+    // n mod 4:  0: (cr, sr)  1: (-sr, cr)  2: (-cr, -sr)  3: (sr, -cr)   as (cos, sin), as dcs_sincos_fast
+    const uint32_t t30 = n << 30, t31 = n << 31;
+    const bool swap = (int32_t)t31 < 0;
+    const uint32_t us = dcs_f32_bits(swap ? cr : sr);
+    const uint32_t uc = dcs_f32_bits(swap ? -sr : cr);
+    *fSin = dcs_bits_f32(dcs_xor_sign_of(us, t30));
+    *fCos = dcs_bits_f32(dcs_xor_sign_of(uc, t30));
+}
+
 // The quadrant on a PACKED pair p = {low half = cos r, high half = sin r}, n = q mod 4:
 //   0: (cr, sr)   1: (-sr, cr)   2: (-cr, -sr)   3: (sr, -cr)      as (cos x, sin x)
 // halves rotated by 16 * (n mod 2) with v_alignbit_b32; both sign bits from ONE 64-bit shift: the constant

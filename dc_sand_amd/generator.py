@@ -162,6 +162,21 @@ def visibilities_bytes(params: BeamformerParameters, nr_vis: int, vis_per_integr
     return (int(nr_vis) // int(vis_per_integration)) * int(params.NR_CHANNELS) * nr_baselines(params.NR_STATIONS) * 8
 
 
+def ddc_digits_bytes(nr_taps: int) -> int:
+    """Size of the operand table that :meth:`SteeringCoefficientGenerator.ddc_tap_digits` makes of ``nr_taps`` taps
+    (``DCS_DDC_DIGITS_BYTES``): 16 bytes per tap, whatever the number of bands."""
+    if nr_taps % 64 or not 64 <= nr_taps <= 256:
+        raise ValueError("nr_taps must be 64, 128, 192 or 256")
+    return 16 * int(nr_taps)
+
+
+def ddc_out_bytes(nr_inputs: int, out_stride: int, nr_bands: int = 1) -> int:
+    """Size of the output ``float [band][input][out_stride][{re, im}]`` of :meth:`SteeringCoefficientGenerator.ddc`."""
+    if nr_bands not in (1, 2):
+        raise ValueError("nr_bands must be 1 or 2")
+    return int(nr_bands) * int(nr_inputs) * int(out_stride) * 8
+
+
 def spectra_sums_bytes(params: BeamformerParameters, nr_beams: int) -> int:
     """Size of the running sums ``double [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.spectra_sums`."""
     return int(params.NR_CHANNELS) * int(nr_beams) * 16
@@ -209,6 +224,10 @@ def best_width_bytes(nr_beams: int, nr_dm: int, peak_blocks: int) -> int:
     """Size of the best width indices ``uint32 [nr_beams][nr_dm][peak_blocks]`` of
     :meth:`SteeringCoefficientGenerator.peak_snr`."""
     return int(nr_beams) * int(nr_dm) * int(peak_blocks) * 4
+
+
+class _DdcBand(ctypes.Structure):  # dcs_ddc_band (include/dcs_ddc.h)
+    _fields_ = [("phase_step", ctypes.c_uint32), ("phase0", ctypes.c_uint32), ("gain", ctypes.c_float)]
 
 
 class _Band(ctypes.Structure):  # dcs_bf_band (include/dcs_dedisperse.h)
@@ -591,6 +610,29 @@ class SteeringCoefficientGenerator:
                                                int(vis_per_integration), 1 if accumulate else 0, _p(d_out), int(out_bytes),
                                                _s(stream)),
               "dcs_bf_integrate_visibilities")
+
+    # -- the narrowband digital down-converter (include/dcs_ddc.h, companion library libdcs_ddc.so): d_samples is a device int8
+    #    [nr_inputs][in_stride] array, d_out a device float [band][input][out_stride][2] array
+    def ddc_tap_digits(self, d_taps, nr_taps: int, nr_bands: int, d_digits, digits_bytes: int, stream=None) -> None:
+        """The integer taps ``int32 [band][nr_taps][{re, im}]`` (correlation order; :func:`dc_sand_amd.ddc.band_taps`) as the
+        operand table of :meth:`ddc` (:func:`ddc_digits_bytes`): three balanced base-256 digits per tap, exact for
+        ``|tap| <= 8 355 711``."""
+        cl = _lib.companion("ddc")
+        check(cl.dcs_bf_ddc_tap_digits(c_void_p(self._h), _p(d_taps), int(nr_taps), int(nr_bands), _p(d_digits), int(digits_bytes),
+                                       _s(stream)),
+              "dcs_bf_ddc_tap_digits")
+
+    def ddc(self, d_samples, samples_bytes: int, in_stride: int, nr_inputs: int, nr_out: int, d_digits, digits_bytes: int,
+            nr_taps: int, bands, d_out, out_bytes: int, out_stride: int, first_output: int = 0, stream=None) -> None:
+        """``nr_out`` outputs per input row: output ``m`` is the exact integer sum of the taps with samples ``16 m .. 16 m +
+        nr_taps - 1``, rotated by the band's oscillator at output ``first_output + m`` and scaled by its gain.  ``bands`` is a
+        sequence of one or two ``(phase_step, phase0, gain)`` (:func:`dc_sand_amd.ddc.phase_step`), read now."""
+        cl = _lib.companion("ddc")
+        arr = (_DdcBand * len(bands))(*[_DdcBand(int(ps) & 0xFFFFFFFF, int(p0) & 0xFFFFFFFF, float(g)) for ps, p0, g in bands])
+        check(cl.dcs_bf_ddc(c_void_p(self._h), int(nr_inputs), int(nr_out), _p(d_samples), int(samples_bytes), int(in_stride),
+                            _p(d_digits), int(digits_bytes), int(nr_taps), len(bands), ctypes.cast(arr, c_void_p),
+                            int(first_output), _p(d_out), int(out_bytes), int(out_stride), _s(stream)),
+              "dcs_bf_ddc")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

@@ -1,0 +1,325 @@
+"""The digital down-converter on the GPU (include/dcs_ddc.h).  Every output is compared with the numpy
+model (helpers/ddc_model.py, anchored on the CPU by tests/test_ddc_model.py) bit for bit; the golden cases are also held to
+the reference within the CPU test's tolerance.  Strides are larger than needed: the sample rows' padding holds other data
+than the rows (a read across a row shows), the output's padding and a canary behind it are prefilled and must stay
+untouched."""
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from helpers import ddc_model as model
+from helpers import hip_graph
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = ROOT / "tests" / "golden" / "ddc"
+CANARY = 64
+PREFILL = 0xA5
+BANDS2 = [(0x0EF00000, 0x12345678, 0.75), (0xC0000001, 0xFEDCBA98, 1.0 / 3.0)]
+
+
+def row_bytes(nr_out, T):
+    return 16 * (nr_out - 1) + T
+
+
+class DCase:
+    """A context (its sizes play no part: the down-converter takes every size as an argument) and the means to run one call
+    from host arrays."""
+
+    def __init__(self, gpu):
+        from dc_sand_amd import BeamformerParameters
+        from dc_sand_amd.generator import SteeringCoefficientGenerator
+
+        self.gpu = gpu
+        self.g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=1, NR_STATIONS=1, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16))
+
+    def digits(self, taps):
+        """The device operand table of integer taps [band][T][2] (any integers: they are passed as their low 32 bits)."""
+        from dc_sand_amd.generator import ddc_digits_bytes
+
+        taps = np.ascontiguousarray(np.asarray(taps).astype(np.int64).astype(np.int32))
+        nb, T, _ = taps.shape
+        d_taps, d_digits = self.gpu.mem_alloc(taps.nbytes), self.gpu.mem_alloc(ddc_digits_bytes(T))
+        self.gpu.memcpy_htod(d_taps, taps)
+        self.g.ddc_tap_digits(d_taps, T, nb, d_digits, ddc_digits_bytes(T))
+        self.gpu.synchronize()
+        d_taps.free()
+        return d_digits
+
+    def run(self, x, taps, bands, nr_out, first_output=0, in_pad=48, out_pad=5, d_digits=None):
+        """x int8 [inputs][16 (nr_out - 1) + T] -> float32 [band][input][nr_out][2].  Every row sits in a stride of in_pad more
+        bytes, which hold the NEXT row's samples shifted (not zeros, not this row's); the last row ends where the allocation
+        ends.  The output rows are out_pad pairs longer than nr_out; what is not an output must keep its prefill."""
+        from dc_sand_amd.generator import ddc_out_bytes
+
+        x = np.asarray(x)
+        ni, T, nb = x.shape[0], np.asarray(taps).shape[1], len(bands)
+        rb = row_bytes(nr_out, T)
+        assert x.dtype == np.int8 and x.shape[1] == rb and in_pad % 16 == 0
+        in_stride, out_stride = rb + in_pad, nr_out + out_pad
+        host = np.empty((ni, in_stride), dtype=np.int8)
+        host[:, :rb] = x
+        host[:, rb:] = np.roll(x, -1, axis=0)[:, 7:7 + in_pad] ^ np.int8(0x55)
+        sbytes = (ni - 1) * in_stride + rb
+        d_x = self.gpu.mem_alloc(sbytes)
+        self.gpu.memcpy_htod(d_x, np.ascontiguousarray(host.reshape(-1)[:sbytes]))
+        obytes = ddc_out_bytes(ni, out_stride, nb)
+        d_out = self.gpu.mem_alloc(obytes + CANARY)
+        self.gpu.memset(d_out, PREFILL, obytes + CANARY)
+        own = d_digits is None
+        if own:
+            d_digits = self.digits(taps)
+        self.g.ddc(d_x, sbytes, in_stride, ni, nr_out, d_digits, 16 * T, T, bands, d_out, obytes, out_stride, first_output=first_output)
+        self.gpu.synchronize()
+        raw = np.empty(obytes + CANARY, dtype=np.uint8)
+        self.gpu.memcpy_dtoh(raw, d_out)
+        assert np.all(raw[obytes:] == PREFILL), "written past the tensor"
+        out = raw[:obytes].view(np.float32).reshape(nb, ni, out_stride, 2)
+        assert np.all(out[:, :, nr_out:].view(np.uint8) == PREFILL), "written into the padding of a row"
+        d_x.free(), d_out.free()
+        if own:
+            d_digits.free()
+        return out[:, :, :nr_out].copy()
+
+    def close(self):
+        self.g.close()
+
+
+@pytest.fixture(scope="module")
+def case(gpu):
+    c = DCase(gpu)
+    yield c
+    c.close()
+
+
+def seeded(shape, seed):
+    x = np.random.default_rng(seed).integers(-128, 128, size=shape, dtype=np.int8)
+    x.reshape(-1)[0], x.reshape(-1)[-1] = -128, 127
+    return x
+
+
+def seeded_taps(nb, T, seed, bound=model.MAX_ABS_SUM):
+    """Full three-digit taps of both signs whose |g| sum to at most ``bound`` per component."""
+    rng = np.random.default_rng(seed)
+    t = rng.integers(-(bound // T), bound // T + 1, size=(nb, T, 2))
+    assert np.abs(t).sum(axis=1).max() <= bound
+    return t
+
+
+def check(case, x, taps, bands, nr_out, **kw):
+    got = case.run(x, taps, bands, nr_out, **kw)
+    exp = model.ddc(x, taps, bands, nr_out, first_output=kw.get("first_output", 0))
+    assert model.same_bits(got, exp) is None, (x.shape, np.asarray(taps).shape, nr_out, model.same_bits(got, exp))
+    return got
+
+
+# one output; a tile less one; a tile; a tile and one (the second tile of a pair holds one output); two tiles and one (a second
+# pair).  T: every number of K steps.  One input and several; one band and two
+@pytest.mark.parametrize("nb", (1, 2))
+@pytest.mark.parametrize("ni", (1, 3))
+@pytest.mark.parametrize("T", (64, 128, 192, 256))
+def test_outputs_are_the_model_bit_for_bit(case, T, ni, nb):
+    taps = seeded_taps(nb, T, seed=T + nb)
+    assert np.abs(taps).max() > 127 * 257  # past two digits: all three digit planes
+    for nr_out in (1, 15, 16, 17, 33):
+        x = seeded((ni, row_bytes(nr_out, T)), seed=1000 * T + 10 * nr_out + ni)
+        got = check(case, x, taps, BANDS2[:nb], nr_out)
+        assert np.unique(got).size >= min(60, got.size // 2)  # no trivial expectation
+
+
+def test_several_spans_and_every_wave_of_a_workgroup(case):
+    """A workgroup takes 512 outputs, a wave 128 of them: 511, 512, 513 and 1100 outputs (a third span, a wave's ragged run)."""
+    taps = seeded_taps(2, 256, seed=9)
+    for nr_out in (511, 512, 513, 1100):
+        check(case, seeded((2, row_bytes(nr_out, 256)), seed=nr_out), taps, BANDS2, nr_out)
+
+
+def test_int32_extremes_at_the_bound(case):
+    """All -128 and all 127 against taps whose |g| sum to exactly 2^24 - 1 per component, of one sign: S = -+128 (2^24 - 1),
+    the largest magnitude a word can take, 128 below the wrap."""
+    T = 256
+    v = np.full(T, 65535)
+    v[0] += model.MAX_ABS_SUM - int(v.sum())
+    taps = np.stack([v, -v], axis=1)[None]
+    assert np.abs(taps).sum(axis=1).tolist() == [[model.MAX_ABS_SUM] * 2]
+    for sample, (re, im) in ((-128, (-128 * model.MAX_ABS_SUM, 128 * model.MAX_ABS_SUM)), (127, (127 * model.MAX_ABS_SUM, -127 * model.MAX_ABS_SUM))):
+        x = np.full((1, row_bytes(17, T)), sample, dtype=np.int8)
+        got = check(case, x, taps, [(0, 0, 1.0)], 17)
+        assert np.all(got[..., 0] == np.float32(re)) and np.all(got[..., 1] == np.float32(im))
+    assert (1 << 31) - 128 * model.MAX_ABS_SUM == 128
+
+
+def test_taps_beyond_the_bound_give_the_words_modulo_2_to_32(case):
+    T = 256
+    taps = seeded_taps(1, T, seed=77, bound=model.MAX_ABS_TAP * T)  # every tap in the digit range, the sums far past int32
+    x = np.where(taps[0, :, 0] >= 0, 127, -128).astype(np.int8)[None]  # aligned with the re taps: S_re = sum |g| |x| ~ 1.3e11
+    exact = int((taps[0, :, 0].astype(object) * x[0].astype(object)).sum())
+    assert exact > 1 << 33
+    got = check(case, x, taps, [(0, 0, 1.0)], 1)
+    assert got[0, 0, 0, 0] == np.float32(((exact + (1 << 31)) % (1 << 32)) - (1 << 31))
+
+
+def test_a_tap_beyond_the_digit_range_wraps_in_its_top_digit(case):
+    T = 64
+    taps = np.zeros((1, T, 2), dtype=np.int64)
+    taps[0, 3] = [8355712, -8421505]  # one past either end: they act as -8421504 and 8355711
+    taps[0, 40] = [12345678, (1 << 31) - 1]
+    x = np.zeros((1, row_bytes(2, T)), dtype=np.int8)
+    x[0, 3], x[0, 40], x[0, 16 + 3] = 1, 2, -3
+    got = check(case, x, taps, [(0, 0, 1.0)], 2)
+    eff = model.effective_taps(taps[0])
+    assert eff[3].tolist() == [-8421504, 8355711]
+    assert got[0, 0, 0].tolist() == [float(np.float32(eff[3, 0] + 2 * eff[40, 0])), float(np.float32(eff[3, 1] + 2 * eff[40, 1]))]
+    assert got[0, 0, 1].tolist() == [float(np.float32(-3 * eff[3, 0])), float(np.float32(-3 * eff[3, 1]))]
+
+
+@pytest.mark.parametrize("T", (64, 256))
+def test_one_hot_samples_return_the_taps(case, T):
+    """Sample 16 (m0 + 1) + k alone is 1: output m sees it at tap 16 (m0 + 1 - m) + k.  Every tap of both bands and both
+    components comes back in its place, whole (all three digit planes), for every position k inside a chunk."""
+    nb, nr_out = 2, T // 16 + 2
+    taps = seeded_taps(nb, T, seed=T)
+    taps[0, 0], taps[1, T - 1] = [model.MAX_ABS_TAP, -model.MAX_ABS_TAP], [-(1 << 16), 255]
+    for k in range(16):
+        x = np.zeros((1, row_bytes(nr_out, T)), dtype=np.int8)
+        pos = 16 * (T // 16) + k
+        x[0, pos] = 1
+        got = check(case, x, taps, [(0, 0, 1.0), (0, 0, 1.0)], nr_out)
+        for m in range(nr_out):
+            j = pos - 16 * m
+            exp = taps[:, j].astype(np.float32) if 0 <= j < T else np.zeros((nb, 2), dtype=np.float32)
+            assert np.array_equal(got[:, 0, m], exp), (k, m)
+
+
+def test_zero_phase_gives_the_exact_integers(case):
+    T, nr_out = 128, 33
+    taps = seeded_taps(2, T, seed=5, bound=1 << 16)  # |S| < 2^23: every word is a float
+    x = seeded((2, row_bytes(nr_out, T)), seed=55)
+    got = check(case, x, taps, [(0, 0, 1.0), (0, 0, 0.5)], nr_out)
+    for b, gain in ((0, 1.0), (1, 0.5)):
+        for i in range(2):
+            for comp in range(2):
+                S = model.windows(x[i], T, nr_out) @ taps[b, :, comp]
+                assert np.abs(S).max() < 1 << 24 and np.array_equal(got[b, i, :, comp].astype(np.float64), gain * S)
+
+
+@pytest.mark.parametrize("first", (0, (1 << 32) - 7, (1 << 40) + 3))
+def test_a_series_cut_in_two_is_one_series(case, first):
+    """Cut at m = 5 and at m = 16 with first_output carried: the bits of one call.  With first_output near 2^32 the product
+    16 (first_output + m) phase_step needs its wrap."""
+    T, nr_out = 192, 40
+    taps = seeded_taps(2, T, seed=first % 97)
+    x = seeded((2, row_bytes(nr_out, T)), seed=first % 89)
+    whole = check(case, x, taps, BANDS2, nr_out, first_output=first)
+    for cut in (5, 16):
+        a = check(case, np.ascontiguousarray(x[:, :row_bytes(cut, T)]), taps, BANDS2, cut, first_output=first)
+        b = check(case, np.ascontiguousarray(x[:, 16 * cut:]), taps, BANDS2, nr_out - cut, first_output=first + cut)
+        assert model.same_bits(np.concatenate([a, b], axis=2), whole) is None
+    if first:
+        assert model.same_bits(whole, model.ddc(x, taps, BANDS2, nr_out)) is not None  # the phase does depend on it
+
+
+def golden_case(name):
+    from dc_sand_amd import ddc
+
+    manifest = json.loads((GOLDEN / "manifest.json").read_text())
+    taps, case_ = np.load(GOLDEN / "taps.npz"), np.load(GOLDEN / f"{name}.npz")
+    x, y, step = case_["x"], case_["y"], int(case_["phase_step"])
+    s = manifest["scale_bits"]
+    g, gain = ddc.band_taps(taps["h107"], step, s)
+    return x, y, step, g, gain, model.reference_tolerance(x, taps["c107"], taps["h107"], g, gain, s, y)
+
+
+@pytest.mark.parametrize("name", ("random", "centre", "dual", "bandedge", "outofband"))
+def test_golden_cases_are_the_reference_within_the_cpu_tests_tolerance(case, name):
+    x, y, step, g, gain, tol = golden_case(name)
+    rb = row_bytes(y.size, 256)
+    got = check(case, np.ascontiguousarray(x[None, :rb]), g[None], [(step, 0, gain)], y.size)
+    diff = np.abs(model.as_complex(got[0, 0]) - y)
+    print(name, "largest |gpu - reference|:", diff.max(), "max ratio to the tolerance:", (diff / tol).max())
+    assert np.all(diff <= tol)
+
+
+def test_refusals_enqueue_nothing_and_empty_calls_succeed(case, gpu):
+    from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
+
+    T, ni, nr_out = 64, 2, 5
+    rb = row_bytes(nr_out, T)
+    x = seeded((ni, rb), seed=4)
+    taps = seeded_taps(1, T, seed=4)
+    d_digits = case.digits(taps)
+    d_x, d_out = gpu.mem_alloc(ni * rb + 16), gpu.mem_alloc(ni * nr_out * 8 + CANARY)
+    gpu.memcpy_htod(d_x, x)
+    gpu.memset(d_out, PREFILL, ni * nr_out * 8 + CANARY)
+    gpu.synchronize()
+    g, band = case.g, [(1, 2, 1.0)]
+    ok = dict(d_samples=d_x, samples_bytes=ni * rb, in_stride=rb, nr_inputs=ni, nr_out=nr_out, d_digits=d_digits, digits_bytes=16 * T,
+              nr_taps=T, bands=band, d_out=d_out, out_bytes=ni * nr_out * 8, out_stride=nr_out)
+    bad = [dict(samples_bytes=ni * rb - 1), dict(out_bytes=ni * nr_out * 8 - 1), dict(d_samples=int(d_x) + 8), dict(d_out=int(d_out) + 4),
+           dict(d_digits=int(d_digits) + 8), dict(digits_bytes=16 * T - 1), dict(nr_taps=32), dict(nr_taps=320), dict(bands=[]),
+           dict(bands=band * 3), dict(in_stride=rb - 16), dict(in_stride=rb + 8), dict(out_stride=nr_out - 1), dict(d_samples=0),
+           dict(nr_out=nr_out + 1, out_stride=nr_out + 1, out_bytes=ni * (nr_out + 1) * 8)]
+    for i, change in enumerate(bad):
+        with pytest.raises(DcsError) as e:
+            g.ddc(**{**ok, **change})
+        assert e.value.status == DCS_ERR_INVALID_ARGUMENT, i
+    g.ddc(**{**ok, "nr_out": 0, "d_samples": 0, "samples_bytes": 0})  # nothing to do
+    g.ddc(**{**ok, "nr_inputs": 0, "out_bytes": 0})
+    gpu.synchronize()
+    raw = np.empty(ni * nr_out * 8 + CANARY, dtype=np.uint8)
+    gpu.memcpy_dtoh(raw, d_out)
+    assert np.all(raw == PREFILL)
+    g.ddc(**ok)  # the context and the device are as usable as before
+    gpu.synchronize()
+    gpu.memcpy_dtoh(raw, d_out)
+    got = raw[:ni * nr_out * 8].view(np.float32).reshape(1, ni, nr_out, 2)
+    assert model.same_bits(got, model.ddc(x, taps, band, nr_out)) is None and np.all(raw[ni * nr_out * 8:] == PREFILL)
+    d_x.free(), d_out.free(), d_digits.free()
+
+
+def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu):
+    """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates -- replayed with new sample bytes
+    (and new taps) in the same buffers."""
+    from dc_sand_amd.generator import ddc_digits_bytes, ddc_out_bytes
+
+    c = DCase(gpu)
+    T, ni, nr_out, nb = 256, 3, 37, 2
+    rb = row_bytes(nr_out, T)
+    sets = [(seeded((ni, rb), seed=200 + i), seeded_taps(nb, T, seed=300 + i).astype(np.int32)) for i in range(3)]
+    d_x, d_taps, d_digits = gpu.mem_alloc(ni * rb), gpu.mem_alloc(nb * T * 8), gpu.mem_alloc(ddc_digits_bytes(T))
+    obytes = ddc_out_bytes(ni, nr_out, nb)
+    d_out = gpu.mem_alloc(obytes + CANARY)
+    s = gpu.Stream()
+    with hip_graph.capture(s) as graph:
+        c.g.ddc_tap_digits(d_taps, T, nb, d_digits, ddc_digits_bytes(T), stream=s.handle)
+        c.g.ddc(d_x, ni * rb, rb, ni, nr_out, d_digits, ddc_digits_bytes(T), T, BANDS2, d_out, obytes, nr_out, first_output=11, stream=s.handle)
+    raw = np.empty(obytes + CANARY, dtype=np.uint8)
+    seen = []
+    for i in (1, 2, 0):
+        x, taps = sets[i]
+        gpu.memcpy_htod(d_x, x, stream=s.handle, sync=False)
+        gpu.memcpy_htod(d_taps, taps, stream=s.handle, sync=False)
+        gpu.memset(d_out, PREFILL, obytes + CANARY, stream=s.handle)
+        graph.launch(s)
+        s.synchronize()
+        gpu.memcpy_dtoh(raw, d_out)
+        got = raw[:obytes].view(np.float32).reshape(nb, ni, nr_out, 2)
+        assert model.same_bits(got, model.ddc(x, taps, BANDS2, nr_out, first_output=11)) is None, i
+        assert np.all(raw[obytes:] == PREFILL)
+        seen.append(got.copy())
+    assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
+    graph.close()
+    for d in (d_x, d_taps, d_digits, d_out):
+        d.free()
+    c.close()
+
+
+def test_the_example_verifies_itself(gpu):
+    res = subprocess.run([sys.executable, str(ROOT / "examples" / "narrowband_ddc.py")], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "OK" in res.stdout

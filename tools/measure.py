@@ -50,6 +50,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the incoherent beam over the same bytes (the read yardstick), alternating, in one process: the time, the fraction of
         one read of the samples at 6.3 TB/s and the matrix cores' share at their peak rate, and the integration
                                                                                     -> profiles/r15_correlator.md
+    python tools/measure.py ddc [--rounds 5] [--shape INPUTSxSAMPLES] [--trace]
+        the digital down-converter at 128 inputs x 2^24 samples, 256 taps, with one band and with two, in turn in one process:
+        the time, its fraction of one read of the samples plus the write of the outputs at 8 TB/s, and the matrix cores'
+        share at their peak rate; --trace: a few launches only, for a counter run     -> profiles/r16_ddc.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -999,6 +1003,59 @@ def cmd_correlator(args):
     print(json.dumps({"correlator": rows}), flush=True)
 
 
+def cmd_ddc(args):
+    """The digital down-converter (include/dcs_ddc.h): one read of the samples and nr_bands * 8 bytes written per 16 of them.
+    At ``--shape`` inputs x samples with 256 random taps of full digit range (the time does not depend on their values), one
+    band and two in turn, ``--rounds`` times in one process on the same noise-like samples.  The bound is the read plus the
+    write at 8 TB/s; the matrix cores' time is one MFMA of 16x16x64 i8 per 64 taps and 16 outputs at 16 cycles each on
+    1024 SIMDs at 2.4 GHz (the same count for one band and two: a band is a set of rows of the operand)."""
+    from dc_sand_amd.generator import ddc_digits_bytes, ddc_out_bytes
+
+    ni, n = (int(x) for x in args.shape.split("x"))
+    T = 256
+    nr_out = (n - T) // 16 + 1
+    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=1, NR_STATIONS=1, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16))
+    d_x = device.mem_alloc(ni * n)
+    _noise(d_x, ni * n)
+    d_out = device.mem_alloc(ddc_out_bytes(ni, nr_out, 2))
+    taps = np.random.default_rng(16).integers(-60000, 60001, size=(2, T, 2)).astype(np.int32)
+    d_taps, d_digits = device.mem_alloc(taps.nbytes), [device.mem_alloc(ddc_digits_bytes(T)) for _ in range(2)]
+    device.memcpy_htod(d_taps, taps)
+    bands = [(250609664, 0, 1e-6), (0x3579BDF1, 7, 2e-6)]
+    calls = {}
+    for nb in (1, 2):
+        g.ddc_tap_digits(d_taps, T, nb, d_digits[nb - 1], ddc_digits_bytes(T))
+        calls[nb] = (lambda nb=nb: g.ddc(d_x, ni * n, n, ni, nr_out, d_digits[nb - 1], ddc_digits_bytes(T), T, bands[:nb], d_out,
+                                         ddc_out_bytes(ni, nr_out, nb), nr_out))
+    device.synchronize()
+    if args.trace:
+        for _ in range(3):
+            for nb in (1, 2):
+                calls[nb]()
+        device.synchronize()
+        return
+    t = {1: [], 2: []}
+    for _ in range(args.rounds):
+        for nb in (1, 2):
+            t[nb].append(per_launch_ms(calls[nb]))
+    rows = []
+    for nb in (1, 2):
+        ms = float(np.median(t[nb]))
+        moved = ni * n + ddc_out_bytes(ni, nr_out, nb)
+        mfma_ms = ni * -(-nr_out // 16) * (T // 64) * 16 / (1024 * 2.4e9) * 1e3
+        rows.append({"shape": args.shape, "taps": T, "bands": nb, "nr_out": nr_out, "read_MiB": ni * n >> 20,
+                     "written_MiB": ddc_out_bytes(ni, nr_out, nb) >> 20, "us": round(ms * 1e3, 1),
+                     "spread": round(max(t[nb]) / min(t[nb]) - 1.0, 4), "moved_TBps": round(moved / (ms * 1e-3) / 1e12, 2),
+                     "bound_us_at_8TBps": round(moved / 8e12 * 1e6, 1), "frac_of_bound": round(moved / 8e12 * 1e3 / ms, 3),
+                     "mfma_peak_us": round(mfma_ms * 1e3, 1), "mfma_share_of_time": round(mfma_ms / ms, 3),
+                     "Gsamples_per_s": round(ni * n / (ms * 1e-3) / 1e9, 1)})
+        print(json.dumps(rows[-1]), flush=True)
+    print(json.dumps({"ddc": rows}), flush=True)
+    g.close()
+    for d in [d_x, d_out, d_taps] + d_digits:
+        d.free()
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1434,6 +1491,10 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="alternations of the correlator and the incoherent beam per shape")
     p.add_argument("--shapes", default="64x4096x4096x64,256x1024x4096x64", help="AxCxNTxN, comma-separated: n blocks per visibility")
     p.add_argument("--buffers", type=int, default=2, help="copies of the samples that the timings rotate over, at least")
+    p = sub.add_parser("ddc")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the one-band and the two-band call")
+    p.add_argument("--shape", default="128x16777216", help="INPUTSxSAMPLES: rows of int8 samples")
+    p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1478,7 +1539,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "correlator": cmd_correlator, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "correlator": cmd_correlator, "ddc": cmd_ddc, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
