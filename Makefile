@@ -12,7 +12,8 @@ LIB     := dc_sand_amd/csrc/libdcs_beamformer.so
 # a context or a stream (bf_ctx_ext.h, bf_stream_ext.h); libdcs_NAME.so is built from bf_NAME.cpp
 COMPANIONS := $(addprefix dc_sand_amd/csrc/libdcs_,$(addsuffix .so,stream_staging beam_weights beam_quant beam_power incoherent_beam \
               filterbank beam_complex beam_complex_quant stokes dedisperse single_pulse correlator ddc))
-SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_incoherent.hip \
+SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_integrate.hip \
+           dc_sand_amd/csrc/bf_incoherent.hip \
            dc_sand_amd/csrc/bf_filterbank.hip dc_sand_amd/csrc/bf_stokes.hip dc_sand_amd/csrc/bf_dedisperse.hip \
            dc_sand_amd/csrc/bf_single_pulse.hip dc_sand_amd/csrc/bf_correlator.hip dc_sand_amd/csrc/bf_ddc.hip \
            dc_sand_amd/csrc/bf_capi.hip \

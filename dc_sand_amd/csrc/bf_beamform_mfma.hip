@@ -385,24 +385,6 @@ __device__ __forceinline__ float power_block_sum(const floatx4 o)
 
 #include "bf_beamform_i8_kernel.inc"
 
-// Block powers [C][nr_blocks][B] -> spectra [nr_blocks / n][C][B] (include/dcs_beam_power.h): one lane per (spectrum, channel,
-// beam), beam fastest, adding its n blocks in order -- one rounded add each, no atomics, the same sum whatever the launch
-// geometry.  A wave reads and writes runs of consecutive beams (and, where B < 64, of consecutive channels' runs).
-__global__ void __launch_bounds__(256) bf_power_integrate_kernel(const bf_pint_args a)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // (i * C + c) * B + b
-    if (g >= a.total) return;
-    const uint32_t b = (uint32_t)(g % a.B);
-    const uint64_t ic = g / a.B;
-    const uint32_t c = (uint32_t)(ic % a.C);
-    const uint64_t i = ic / a.C;
-    const float *p = a.block_power + (((uint64_t)c * a.nr_blocks + i * a.n) * a.B + b);
-    float acc = a.accumulate ? a.spectra[g] : p[0];
-#pragma unroll 4
-    for (uint32_t j = a.accumulate ? 0u : 1u; j < a.n; j++) acc = acc + p[(uint64_t)j * a.B];
-    a.spectra[g] = acc;
-}
-
 } // namespace
 
 // LDS bytes of one workgroup for NBT beam tiles and A antennas.
@@ -571,14 +553,5 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a_in, const bf_weights_arg
         const size_t coef_bytes = 4u * (cx ? 9u : 6u) * 64u * 16u + 8u * sizeof(uint32_t) + (q ? 32u : (w ? 16u : 0u)) * sizeof(float);
         launch_i8_form<kChain>(full, grid, block, coef_bytes, stream, a, w, q, power, cx);
     }
-    return hipGetLastError();
-}
-
-hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream)
-{
-    if (a.total == 0u) return hipSuccess;
-    const uint64_t blocks = (a.total + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bf_power_integrate_kernel, dim3((uint32_t)blocks), dim3(256u), 0, stream, a);
     return hipGetLastError();
 }

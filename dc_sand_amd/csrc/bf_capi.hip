@@ -321,6 +321,7 @@ int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
         if ((st = (int)hipGetDevice(&c->device)) != 0) break;
         if ((st = (int)bf_warm_module()) != 0) break; // load the kernels now, not in the first timed launch
         if ((st = (int)bf_warm_module_mfma()) != 0) break;
+        if ((st = (int)bf_warm_module_integrate()) != 0) break;
         if ((st = (int)bf_warm_module_incoherent()) != 0) break;
         if ((st = (int)bf_warm_module_filterbank()) != 0) break;
         if ((st = (int)bf_warm_module_stokes()) != 0) break;

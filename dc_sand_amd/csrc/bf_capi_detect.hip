@@ -6,7 +6,7 @@
 // context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Each begins with the
 // device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made already; what follows needs the
 // device or the context's sizes, or is a condition that only this side makes.  Host code only; the kernels are in
-// bf_beamform_mfma.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip, bf_correlator.hip and
+// bf_integrate.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip, bf_correlator.hip and
 // bf_ddc.hip.
 
 #include <cmath>
@@ -18,26 +18,36 @@ using namespace bf_host;
 
 namespace bf_host {
 
+// The one integration behind integrate_block_power, integrate_incoherent_power, integrate_stokes and integrate_visibilities
+// (bf_integrate.hip): blocks [C][nr_blocks][bs] of 4-byte words of the named type, n at a time, into out [nr_blocks / n][C][bs].
+// The caller has made its own device-free checks: n >= 1 divides nr_blocks.
+static int integrate_blocks(dcs_bf_context *c, bf_integrate_type type, const void *d_blocks, size_t blocks_bytes, uint64_t bs,
+                            uint32_t nr_blocks, uint32_t n, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream)
+{
+    DCS_CHECK_DEVICE(c);
+    const uint64_t C = (uint32_t)c->p.nr_channels, n_out = nr_blocks / n;
+    if (bs > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
+    if (!holds(blocks_bytes, C, nr_blocks, bs, 4u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(out_bytes, n_out, C, bs, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_integrate_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.blocks = d_blocks;
+    a.out = d_out;
+    a.total = n_out * C * bs;
+    a.bs = (uint32_t)bs;
+    a.C = (uint32_t)C;
+    a.nr_blocks = nr_blocks;
+    a.n = n;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_integrate(type, a, as_stream(stream));
+}
+
 int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
                                uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream)
 {
     if (int e = integrate_block_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
-    DCS_CHECK_DEVICE(c);
-    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
-    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
-    if (power_bytes < (size_t)C * nr_blocks * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
-    if (spectra_bytes < (size_t)n_spectra * C * B * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
-    bf_pint_args a;
-    std::memset(&a, 0, sizeof(a));
-    a.block_power = d_block_power;
-    a.spectra = d_spectra;
-    a.total = n_spectra * C * B;
-    a.B = B;
-    a.C = C;
-    a.nr_blocks = nr_blocks;
-    a.n = blocks_per_spectrum;
-    a.accumulate = accumulate ? 1u : 0u;
-    return (int)bf_launch_power_integrate(a, as_stream(stream));
+    return integrate_blocks(c, BF_INTEGRATE_F32, d_block_power, power_bytes, (uint32_t)c->p.nr_beams, nr_blocks, blocks_per_spectrum,
+                            accumulate, d_spectra, spectra_bytes, stream);
 }
 
 // include/dcs_incoherent_beam.h, reached the same way.  No coefficients: no delay table, no terms, nothing allocated, and
@@ -68,21 +78,8 @@ int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_p
                                     void *stream)
 {
     if (int e = integrate_incoherent_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
-    DCS_CHECK_DEVICE(c);
-    const uint32_t C = (uint32_t)c->p.nr_channels;
-    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
-    if (power_bytes < (size_t)C * nr_blocks * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
-    if (spectra_bytes < (size_t)n_spectra * C * sizeof(float)) return DCS_ERR_INVALID_ARGUMENT;
-    bf_incoh_int_args a;
-    std::memset(&a, 0, sizeof(a));
-    a.block_power = d_block_power;
-    a.spectra = d_spectra;
-    a.total = n_spectra * C;
-    a.C = C;
-    a.nr_blocks = nr_blocks;
-    a.n = blocks_per_spectrum;
-    a.accumulate = accumulate ? 1u : 0u;
-    return (int)bf_launch_incoherent_integrate(a, as_stream(stream));
+    return integrate_blocks(c, BF_INTEGRATE_U32, d_block_power, power_bytes, 1u, nr_blocks, blocks_per_spectrum, accumulate, d_spectra,
+                            spectra_bytes, stream);
 }
 
 // include/dcs_filterbank.h, reached the same way.  No coefficients and nothing allocated; nr_beams is the caller's, so the
@@ -174,23 +171,8 @@ int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size
                           size_t spectra_bytes, void *stream)
 {
     if (int e = integrate_stokes_args(c, d_block_stokes, nr_blocks, blocks_per_spectrum, nr_stokes, d_spectra)) return e;
-    DCS_CHECK_DEVICE(c);
-    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
-    const uint64_t n_spectra = nr_blocks / blocks_per_spectrum;
-    if ((uint64_t)B * nr_stokes > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
-    if (!holds(stokes_bytes, C, nr_blocks, B, (uint64_t)nr_stokes * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
-    if (!holds(spectra_bytes, n_spectra, C, B, (uint64_t)nr_stokes * sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
-    bf_stokes_int_args a;
-    std::memset(&a, 0, sizeof(a));
-    a.block_stokes = d_block_stokes;
-    a.spectra = d_spectra;
-    a.bs = B * nr_stokes;
-    a.total = n_spectra * C * a.bs;
-    a.C = C;
-    a.nr_blocks = nr_blocks;
-    a.n = blocks_per_spectrum;
-    a.accumulate = accumulate ? 1u : 0u;
-    return (int)bf_launch_stokes_integrate(a, as_stream(stream));
+    return integrate_blocks(c, BF_INTEGRATE_I32, d_block_stokes, stokes_bytes, (uint64_t)(uint32_t)c->p.nr_beams * nr_stokes, nr_blocks,
+                            blocks_per_spectrum, accumulate, d_spectra, spectra_bytes, stream);
 }
 
 // include/dcs_dedisperse.h, reached the same way.  No coefficients, nothing allocated, and math_mode plays no part; the band
@@ -354,28 +336,14 @@ int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna
     return (int)bf_launch_correlate(a, as_stream(stream));
 }
 
-// the integrator is the Stokes parameters': a (channel, visibility) row of 2 NB words in place of B * nr_stokes
+// a (channel, visibility) row is 2 NB = A (A + 1) words
 int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis, uint32_t vis_per_integration,
                                 uint32_t accumulate, float *d_out, size_t out_bytes, void *stream)
 {
     if (int e = integrate_visibilities_args(c, d_vis, nr_vis, vis_per_integration, d_out)) return e;
-    DCS_CHECK_DEVICE(c);
-    const uint64_t A = (uint64_t)c->p.nr_stations, C = (uint64_t)c->p.nr_channels;
-    const uint64_t n_out = nr_vis / vis_per_integration, bs = A * (A + 1u); // 2 NB
-    if (bs > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
-    if (!holds(vis_bytes, C, nr_vis, bs, sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
-    if (!holds(out_bytes, n_out, C, bs, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
-    bf_stokes_int_args a;
-    std::memset(&a, 0, sizeof(a));
-    a.block_stokes = d_vis;
-    a.spectra = d_out;
-    a.bs = (uint32_t)bs;
-    a.total = n_out * C * bs;
-    a.C = (uint32_t)C;
-    a.nr_blocks = nr_vis;
-    a.n = vis_per_integration;
-    a.accumulate = accumulate ? 1u : 0u;
-    return (int)bf_launch_stokes_integrate(a, as_stream(stream));
+    const uint64_t A = (uint32_t)c->p.nr_stations;
+    return integrate_blocks(c, BF_INTEGRATE_I32, d_vis, vis_bytes, A * (A + 1u), nr_vis, vis_per_integration, accumulate, d_out, out_bytes,
+                            stream);
 }
 
 // include/dcs_ddc.h, reached the same way.  Of the context these use the device alone: every size is an argument, and the

@@ -1,5 +1,5 @@
 // bf_correlator.cpp -- include/dcs_correlator.h, the companion library libdcs_correlator.so.  Host code only: the kernels
-// are libdcs_beamformer.so's (bf_correlator.hip, and the integrator of bf_stokes.hip), reached through the table at the head
+// are libdcs_beamformer.so's (bf_correlator.hip, bf_integrate.hip), reached through the table at the head
 // of every context it makes (bf_ctx_ext.h).  Each export makes its entry's device-free checks (bf_arg_checks.h), then forwards.
 
 #include "../../include/dcs_correlator.h"

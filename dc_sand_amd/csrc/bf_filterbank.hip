@@ -32,7 +32,7 @@
 // are counted per lane over its whole run and added to the per-beam counters with integer atomics at the end, so the
 // counts are exact; a null counter pointer skips that.  Byte offsets are 64-bit.
 //
-// The sums kernel is bf_power_integrate_kernel's layout: one lane per (channel, beam), beam fastest, walking time in
+// The sums kernel is bf_integrate_kernel's layout: one lane per (channel, beam), beam fastest, walking time in
 // order with eight loads in flight.  The order of the additions is the contract's, so the result cannot depend on the
 // launch geometry.  The scales kernel is one lane per (channel, beam) of fp64 arithmetic; -ffp-contract=off keeps every
 // operation rounded once.

@@ -1,5 +1,5 @@
 // bf_incoherent.hip -- the incoherent beam (include/dcs_incoherent_beam.h), gfx950 only: the
-// antennas' own power summed over each 16-sample block, exactly, and the integration of those block powers into spectra.
+// antennas' own power summed over each 16-sample block, exactly (bf_integrate.hip integrates those block powers).
 //
 // The sample tensor int8 [C][nt / 16][A][16][{re, im}] is R = C * nt / 16 contiguous rows of A * 32 bytes, and a row
 // reduces to one dword.  The kernel is a stream of 16-byte loads bound by the HBM read rate (2 A bytes in per sample and
@@ -21,8 +21,7 @@
 // row's end to the row's first unit (in bounds, and a line the wave fetches anyway) and flags it off; a group of rows
 // that runs over the last row repeats that row and does not store the repeats.  A < 32 leaves lanes idle instead of
 // packing several rows into one load: correct, and no production shape.
-// Byte offsets are 64-bit.  Nothing here rounds: -ffp-contract and the float flags of the build play no part except in
-// the integrator's one conversion and one add.
+// Byte offsets are 64-bit.  Nothing here rounds: -ffp-contract and the float flags of the build play no part.
 
 #include "bf_kernels.h"
 
@@ -107,22 +106,6 @@ __global__ void __launch_bounds__(kWaves * 64) bf_incoherent_power_kernel(const 
     }
 }
 
-// Block powers [C][nr_blocks] -> spectra [nr_blocks / n][C]: one lane per (spectrum, channel), channel fastest, an exact
-// 64-bit running sum of its n blocks and one conversion, RN((float)S); accumulating adds that to what the spectrum held.
-__global__ void __launch_bounds__(256) bf_incoherent_integrate_kernel(const bf_incoh_int_args a)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // i * C + c
-    if (g >= a.total) return;
-    const uint32_t c = (uint32_t)(g % a.C);
-    const uint64_t i = g / a.C;
-    const uint32_t *p = a.block_power + ((uint64_t)c * a.nr_blocks + i * a.n);
-    unsigned long long sum = 0;
-#pragma unroll 8
-    for (uint32_t j = 0; j < a.n; j++) sum += p[j];
-    const float s = (float)sum;
-    a.spectra[g] = a.accumulate ? a.spectra[g] + s : s;
-}
-
 template <uint32_t NC>
 void launch_power(const bf_incoh_args &args, hipStream_t stream)
 {
@@ -140,7 +123,7 @@ void launch_power(const bf_incoh_args &args, hipStream_t stream)
 hipError_t bf_warm_module_incoherent()
 {
     hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_incoherent_integrate_kernel));
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_incoherent_power_kernel<1>));
 }
 
 hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream)
@@ -157,14 +140,5 @@ hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream
     case 7: launch_power<7>(a, stream); break;
     default: launch_power<8>(a, stream); break;
     }
-    return hipGetLastError();
-}
-
-hipError_t bf_launch_incoherent_integrate(const bf_incoh_int_args &a, hipStream_t stream)
-{
-    if (a.total == 0u) return hipSuccess;
-    const uint64_t blocks = (a.total + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bf_incoherent_integrate_kernel, dim3((uint32_t)blocks), dim3(256u), 0, stream, a);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // bf_incoherent_beam.cpp -- include/dcs_incoherent_beam.h, the companion library libdcs_incoherent_beam.so.  Host code
-// only: the kernels are libdcs_beamformer.so's (bf_incoherent.hip), reached through the table at the head of every
+// only: the kernels are libdcs_beamformer.so's (bf_incoherent.hip, bf_integrate.hip), reached through the table at the head of every
 // context it makes (bf_ctx_ext.h).  Each export makes its entry's device-free checks (bf_arg_checks.h), then forwards.
 
 #include "../../include/dcs_incoherent_beam.h"

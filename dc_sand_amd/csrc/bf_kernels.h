@@ -209,17 +209,6 @@ struct bf_complex_args {
 // 0), and q excludes power (q with cx: include/dcs_beam_complex_quant.h).
 hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, const bf_weights_args *w, const bf_quant_args *q, bool power,
                                   const bf_complex_args *cx, hipStream_t stream);
-// Block powers [C][nr_blocks][B] summed n at a time, in order, into spectra [nr_blocks / n][C][B]
-struct bf_pint_args {
-    const float *block_power;
-    float *spectra;
-    uint64_t total;      // (nr_blocks / n) * C * B
-    uint32_t B, C;
-    uint32_t nr_blocks;  // a multiple of n
-    uint32_t n;          // blocks per spectrum, >= 1
-    uint32_t accumulate; // non-zero: the sums start from what spectra holds
-};
-hipError_t bf_launch_power_integrate(const bf_pint_args &a, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
 // The incoherent beam (bf_incoherent.hip; include/dcs_incoherent_beam.h): the sample tensor as
@@ -233,17 +222,6 @@ struct bf_incoh_args {
     uint32_t A;            // 1 .. 256
 };
 hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream);
-// Block powers [C][nr_blocks] summed n at a time, exactly, into spectra [nr_blocks / n][C]
-struct bf_incoh_int_args {
-    const uint32_t *block_power;
-    float *spectra;
-    uint64_t total;      // (nr_blocks / n) * C
-    uint32_t C;
-    uint32_t nr_blocks;  // a multiple of n
-    uint32_t n;          // blocks per spectrum, >= 1
-    uint32_t accumulate; // non-zero: the rounded sums are added to what spectra holds
-};
-hipError_t bf_launch_incoherent_integrate(const bf_incoh_int_args &a, hipStream_t stream);
 hipError_t bf_warm_module_incoherent();
 
 // Full-Stokes detection (bf_stokes.hip; include/dcs_stokes.h): two int8 beam tensors as
@@ -257,19 +235,24 @@ struct bf_stokes_args {
     uint32_t nr_stokes;    // 1 (I) or 4 (I, Q, U, V)
 };
 hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream);
-// Block Stokes [C][nr_blocks][bs] summed n at a time, exactly, into spectra [nr_blocks / n][C][bs]
-struct bf_stokes_int_args {
-    const int32_t *block_stokes;
-    float *spectra;
+hipError_t bf_warm_module_stokes();
+
+// The integrator of every post-detection output (bf_integrate.hip): blocks [C][nr_blocks][bs] summed
+// n at a time into out [nr_blocks / n][C][bs].  The element type selects the rule: float words are added in order, one rounded
+// add each; 32-bit integer words exactly, in 64 bits, and the sum converted once
+enum bf_integrate_type { BF_INTEGRATE_F32, BF_INTEGRATE_U32 /* built for bs == 1 */, BF_INTEGRATE_I32 };
+struct bf_integrate_args {
+    const void *blocks;  // words of the type the launch names
+    float *out;
     uint64_t total;      // (nr_blocks / n) * C * bs
-    uint32_t bs;         // B * nr_stokes
+    uint32_t bs;         // words per (channel, block): B; 1; B * nr_stokes; A (A + 1)
     uint32_t C;
     uint32_t nr_blocks;  // a multiple of n
-    uint32_t n;          // blocks per spectrum, >= 1
-    uint32_t accumulate; // non-zero: the rounded sums are added to what spectra holds
+    uint32_t n;          // blocks per output row, >= 1
+    uint32_t accumulate; // non-zero: float sums start from what out holds, integer sums are added to it once rounded
 };
-hipError_t bf_launch_stokes_integrate(const bf_stokes_int_args &a, hipStream_t stream);
-hipError_t bf_warm_module_stokes();
+hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &a, hipStream_t stream);
+hipError_t bf_warm_module_integrate();
 
 // Incoherent dedispersion (bf_dedisperse.hip; include/dcs_dedisperse.h).
 // The delay table int32 [nr_dm][C] of a band and DMs, in fp64 rounded once per operation

@@ -1,5 +1,5 @@
 // bf_stokes.cpp -- include/dcs_stokes.h, the companion library libdcs_stokes.so.  Host code only: the kernels are
-// libdcs_beamformer.so's (bf_stokes.hip), reached through the table at the head of every context it makes
+// libdcs_beamformer.so's (bf_stokes.hip, bf_integrate.hip), reached through the table at the head of every context it makes
 // (bf_ctx_ext.h).  Each export makes its entry's device-free checks (bf_arg_checks.h), then forwards.
 
 #include "../../include/dcs_stokes.h"

@@ -1,5 +1,5 @@
 // bf_stokes.hip -- full-Stokes detection of dual-polarisation 8-bit voltage beams (include/dcs_stokes.h; DESIGN.md section
-// 5.15), gfx950 only: the exact block Stokes parameters of two int8 beam tensors, and their integration into spectra.
+// 5.15), gfx950 only: the exact block Stokes parameters of two int8 beam tensors (bf_integrate.hip integrates them).
 // The sibling of bf_incoherent.hip: the same kind of arithmetic -- every term an integer -- on two streams instead of one.
 //
 // The two tensors int8 [C][nt / 16][B][16][{re, im}] are the same flat sequence of N = C * (nt / 16) * B rows of 32 bytes,
@@ -21,7 +21,7 @@
 //
 // A trip that runs over the last row clamps the row to N - 1 for its loads (in bounds, a line the wave fetches anyway) and
 // does not store it.  Byte offsets are 64-bit.  Nothing here rounds: -ffp-contract and the float flags of the build play
-// no part except in the integrator's one conversion and one add.
+// no part.
 
 #include "bf_kernels.h"
 
@@ -108,25 +108,6 @@ __global__ void __launch_bounds__(kWaves * 64) bf_stokes_block_kernel(const bf_s
     }
 }
 
-// Block Stokes [C][nr_blocks][bs] -> spectra [nr_blocks / n][C][bs], bs = B * nr_stokes: one lane per output element,
-// innermost index fastest, an exact signed 64-bit running sum of its n blocks and one conversion, RN((float)S);
-// accumulating adds that to what the spectrum held.
-__global__ void __launch_bounds__(256) bf_stokes_integrate_kernel(const bf_stokes_int_args a)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; // (i * C + c) * bs + e
-    if (g >= a.total) return;
-    const uint32_t e = (uint32_t)(g % a.bs);
-    const uint64_t ic = g / a.bs;
-    const uint32_t c = (uint32_t)(ic % a.C);
-    const uint64_t i = ic / a.C;
-    const int32_t *p = a.block_stokes + (((uint64_t)c * a.nr_blocks + i * a.n) * a.bs + e);
-    long long sum = 0;
-#pragma unroll 8
-    for (uint32_t j = 0; j < a.n; j++) sum += p[(uint64_t)j * a.bs];
-    const float s = (float)sum;
-    a.spectra[g] = a.accumulate ? a.spectra[g] + s : s;
-}
-
 template <uint32_t NS>
 void launch_block(const bf_stokes_args &args, hipStream_t stream)
 {
@@ -144,7 +125,7 @@ void launch_block(const bf_stokes_args &args, hipStream_t stream)
 hipError_t bf_warm_module_stokes()
 {
     hipFuncAttributes attr;
-    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_stokes_integrate_kernel));
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_stokes_block_kernel<4>));
 }
 
 hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream)
@@ -155,14 +136,5 @@ hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream)
     case 4: launch_block<4>(a, stream); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t bf_launch_stokes_integrate(const bf_stokes_int_args &a, hipStream_t stream)
-{
-    if (a.total == 0u) return hipSuccess;
-    const uint64_t blocks = (a.total + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bf_stokes_integrate_kernel, dim3((uint32_t)blocks), dim3(256u), 0, stream, a);
     return hipGetLastError();
 }

@@ -3,6 +3,9 @@ powers of the antennas whose weight is not 0, and their integration with one rou
 anchors it against plain Python-int loops; the GPU tests hold the kernels to it bit for bit."""
 import numpy as np
 
+from helpers import stokes_model
+from helpers.stokes_model import same_bits, to_float  # noqa: F401  (the tests use both through this module)
+
 
 def flags(weights, A):
     """Which antennas take part: all without weights, else those whose value != 0 (-0.0 is 0; NaN and Inf are not)."""
@@ -24,35 +27,24 @@ def block_power(ant, weights=None):
     return P.astype(np.uint32)
 
 
-def to_float(S):
-    """RN((float)S) of every exact sum: np.float32 of a Python int goes through a double, which holds a sum below 2^53
-    exactly, so the result is rounded once."""
-    S = np.asarray(S, dtype=np.int64)
-    assert S.min(initial=0) >= 0 and S.max(initial=0) < 1 << 53
-    return np.array([np.float32(int(s)) for s in S.ravel()], dtype=np.float32).reshape(S.shape)
-
-
 def integrate(P, n, prior=None):
-    """Block powers [C][nr_blocks] -> spectra float32 [nr_blocks / n][C]: S exactly in int64, RN((float)S); with
-    ``prior`` (the spectra before an accumulating call) RN(prior + RN((float)S))."""
+    """Block powers [C][nr_blocks] -> spectra float32 [nr_blocks / n][C]: the rule of stokes_model.integrate -- S exactly in
+    int64, RN((float)S), and with ``prior`` (the spectra before an accumulating call) RN(prior + that) -- on words that are
+    no less than 0, so no sum is either."""
     C, K = P.shape
-    assert n >= 1 and K % n == 0
-    S = P.astype(np.int64).reshape(C, K // n, n).sum(axis=2).T  # [K / n][C]
-    out = to_float(S)
+    assert n >= 1 and K % n == 0 and P.min(initial=0) >= 0
     if prior is not None:
         prior = np.asarray(prior, dtype=np.float32)
-        assert prior.shape == out.shape
-        out = (prior + out).astype(np.float32)  # float32 + float32: one rounded add
+        assert prior.shape == (K // n, C)
+        prior = prior.reshape(K // n, C, 1, 1)
+    out = stokes_model.integrate(P.reshape(C, K, 1, 1), n, prior=prior).reshape(K // n, C)
+    assert prior is not None or out.min(initial=0) >= 0
     return out
 
 
-def same_bits(got, exp):
-    """None if the float32 arrays agree bit for bit, else the first difference."""
-    got, exp = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
-    if got.shape != exp.shape:
-        return ("shape", got.shape, exp.shape)
-    bad = np.flatnonzero(got.view(np.uint32).ravel() != exp.view(np.uint32).ravel())
-    if bad.size == 0:
-        return None
-    i = int(bad[0])
-    return (bad.size, np.unravel_index(i, got.shape), float(got.ravel()[i]), float(exp.ravel()[i]))
+def full_range_words(C=3, K=12):
+    """Seeded block powers uint32 [C][K] over the whole 32-bit range, 0xFFFFFFFF, 0x80000000 and 0x7FFFFFFF among them: what
+    the detection never makes (it ends at 2^27) and the integration's contract covers -- words and sums that are unsigned."""
+    P = np.random.default_rng(32).integers(0, 1 << 32, size=(C, K), dtype=np.uint64).astype(np.uint32)
+    P[0, 0], P[C // 2, K // 2], P[-1, -1] = 0xFFFFFFFF, 0x80000000, 0x7FFFFFFF
+    return P

@@ -3,8 +3,6 @@ parameters of two int8 beam tensors, and their integration with one rounding.  i
 tests/test_stokes_model.py anchors it against plain Python-int arithmetic; the GPU tests hold the kernels to it bit for bit."""
 import numpy as np
 
-from helpers.incoherent_model import same_bits  # noqa: F401  (the GPU tests compare float bits with it)
-
 _CHUNK = 1 << 18  # rows (of 16 samples) taken at a time: bounds the int64 temporaries of a large tensor
 
 
@@ -51,3 +49,15 @@ def integrate(block, n, prior=None):
         with np.errstate(invalid="ignore"):
             out = (prior + out).astype(np.float32)  # float32 + float32: one rounded add
     return out
+
+
+def same_bits(got, exp):
+    """None if the float32 arrays agree bit for bit, else the first difference."""
+    got, exp = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
+    if got.shape != exp.shape:
+        return ("shape", got.shape, exp.shape)
+    bad = np.flatnonzero(got.view(np.uint32).ravel() != exp.view(np.uint32).ravel())
+    if bad.size == 0:
+        return None
+    i = int(bad[0])
+    return (bad.size, np.unravel_index(i, got.shape), float(got.ravel()[i]), float(exp.ravel()[i]))

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.incoherent_model import block_power, integrate, same_bits
+from helpers import stokes_model
+from helpers.incoherent_model import block_power, full_range_words, integrate, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +72,12 @@ class ICase:
         self.call_power(weighted=w is not None)
         gpu.synchronize()
         return self.read_power()
+
+    def set_power(self, P):
+        """The integration's input given by the test."""
+        assert P.dtype == np.uint32 and P.shape == (self.C, self.nblk)
+        self.gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        self.gpu.memcpy_htod(self.d_p, np.ascontiguousarray(P))
 
     def call_integrate(self, n, accumulate=False, stream=None):
         self.g.integrate_incoherent_power(self.d_p, self.pbytes, self.nblk, n, self.d_s, self.spectra_bytes(n),
@@ -206,6 +213,25 @@ def test_full_scale_needs_all_32_and_64_bits(gpu):
     s = c.spectra(n)
     assert s.shape == (1, 1) and float(s[0, 0]) == float(5 << 30) and 5 << 30 > 1 << 32
     assert same_bits(s, integrate(got, n)) is None
+    c.close()
+
+
+def test_words_with_bit_31_set_are_unsigned(gpu):
+    """Full-range words, which the detection never makes (it ends at 2^27): the 64-bit sum and its conversion are unsigned.
+    The same bits read as int32 give other spectra, so a signed sum or a conversion through a signed type would show."""
+    P = full_range_words()
+    C, K = P.shape
+    c = ICase(gpu, 1, C, K * 16)
+    c.set_power(P)
+    for n in (1, 2, 3, 12):
+        exp = integrate(P, n)
+        signed = stokes_model.integrate(P.view(np.int32).reshape(C, K, 1, 1), n).reshape(K // n, C)
+        assert (signed != exp).any(axis=1).all(), n
+        got = c.spectra(n)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
+        got = c.spectra(n, accumulate=True, prior=prior)
+        assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate", same_bits(got, integrate(P, n, prior=prior)))
     c.close()
 
 

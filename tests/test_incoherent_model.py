@@ -6,7 +6,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from helpers.incoherent_model import block_power, flags, integrate, same_bits, to_float
+from helpers import stokes_model
+from helpers.incoherent_model import block_power, flags, full_range_words, integrate, same_bits, to_float
 
 
 def _loop_block_power(ant, weights):
@@ -102,6 +103,27 @@ def test_integration_is_the_exact_sum_rounded_once():
     first = integrate(P[:, :12], 12)
     both = integrate(P[:, 12:], 12, prior=first)
     assert same_bits(both, (first + integrate(P[:, 12:], 12)).astype(np.float32)) is None
+
+
+def test_words_with_bit_31_set_are_unsigned():
+    """Full-range words: the exact sums are Python ints of the unsigned words, up to 12 (2^32 - 1).  The same bits read as
+    int32 give other spectra, so a signed sum would show."""
+    P = full_range_words()
+    C, K = P.shape
+    assert {0xFFFFFFFF, 0x80000000, 0x7FFFFFFF} <= set(P.ravel().tolist()) and (P >> 31).any(axis=1).all()
+    rng = np.random.default_rng(33)
+    for n in (1, 2, 3, 12):
+        got = integrate(P, n)
+        prior = rng.integers(0, 1 << 36, size=got.shape).astype(np.float32)  # integers, so prior + RN((float)S) is one exactly
+        acc = integrate(P, n, prior=prior)
+        for i in range(K // n):
+            for c in range(C):
+                s = sum(int(P[c, i * n + j]) for j in range(n))
+                assert got[i, c].tobytes() == _rn_float(s).tobytes(), (n, i, c, s)
+                assert float(prior[i, c]) == int(prior[i, c])
+                assert acc[i, c].tobytes() == _rn_float(int(prior[i, c]) + int(_rn_float(s))).tobytes(), (n, i, c)
+        signed = stokes_model.integrate(P.view(np.int32).reshape(C, K, 1, 1), n).reshape(K // n, C)
+        assert (signed != got).any(axis=1).all(), n  # every spectrum tells the two readings apart
 
 
 def test_one_rounding_differs_from_rounding_through_an_intermediate():

@@ -62,7 +62,7 @@ def kernels(lib: str, resources: dict[str, dict[str, int]] | None = None) -> dic
                 if m:
                     cur = m.group(1)
                     out.setdefault(cur, [])
-                elif cur and line.strip():
+                elif cur and line.strip() and line.strip() != "...": # (llvm-objdump's mark for the zero padding behind a kernel)
                     out[cur].append(re.sub(r"\s*//.*$", "", line.rstrip()))
             if resources is None:
                 continue
