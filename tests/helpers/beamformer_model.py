@@ -75,6 +75,28 @@ def acc_model(coef, x, scale=None):
     return recombine(*digit_sums(coef, x), scale=scale)
 
 
+def acc_model_nonfinite(coef, x, scale=None):
+    """acc_model for a (weighted) coefficient tensor that may hold NaN / Inf (the slow class: an infinite or NaN delay
+    value).  include/dcs_beamformer.h: "A coefficient that is not finite makes every sample of its beam NaN in the plane
+    concerned, as in the verifier's sum (NaN * 0 = NaN)" -- so the non-finite coefficients are zeroed for the digit sums
+    and every sample of a (channel, beam, plane) whose coefficient column (over the antennas) holds one is NaN."""
+    coef = np.asarray(coef, dtype=F32)
+    bad = ~np.isfinite(coef)  # [C][A][B][2]
+    out = acc_model(np.where(bad, F32(0), coef), x, scale=scale)
+    column = bad.any(axis=1)  # [C][B][2]
+    out[np.broadcast_to(column[:, None, :, None, :], out.shape)] = F32(np.nan)
+    return out
+
+
+def zero_weight_coefficients(coef, weights):
+    """include/dcs_beam_weights.h: "An antenna whose weight is 0 (either sign) contributes nothing, even where its delay
+    values are not finite (its coefficient is made from zero terms)": (cos 0, sin 0) = (1, 0) wherever weights[b][a] == 0.
+    coef [...][A][B][2], weights [B][A]; a copy."""
+    out = np.array(coef, dtype=F32)
+    out[..., np.asarray(weights, dtype=F32).T == 0, :] = (F32(1), F32(0))
+    return out
+
+
 def weighted_coefficients(coef, ghat):
     """w' = RN32(ghat[b][a] * w) for coef [...][A][B][2], ghat [B][A]."""
     g = np.asarray(ghat, dtype=F32).T[..., None]  # [A][B][1]
@@ -131,7 +153,9 @@ def all_pairs_fast(table, dts, nr_channels, sampling_period):
     """True when every pair at every fDeltaTime of `dts` is in a fast class, with margin: a bound on |fRotation| over
     the channels (|fRateTerm| * pi * (C - 1) / D, 0.1 % on top, + |fPhase0|) below 32000 and the rate term zero or within
     2^-60 .. 2^60 (the constant divide's range).  Only then do the beamformers (which switch a whole table, resp.
-    16-sample block, to the slow path) and the generator (which switches per wave) make coefficients the same way."""
+    16-sample block, to the slow path) and the generator (which switches per wave) make coefficients the same way from the
+    table as it is.  (Tables with a slow-class pair: pair_classes and interleave_with_filler, below, which
+    tests/test_gpu_beamformer_exact_slow.py uses to get the slow path's bits from the same generator.)"""
     d = np.float64
     denom = d(np.float32(np.float32(sampling_period) * np.float32(nr_channels)))
     scale = np.pi * max(nr_channels - 1, 0) / denom * 1.001
@@ -145,6 +169,83 @@ def all_pairs_fast(table, dts, nr_channels, sampling_period):
         if not np.all(ka * scale + np.abs(p0.astype(d)) < 32000.0):
             return False
     return True
+
+
+FAST_LOW, FAST_HIGH, SLOW, UNCLEAR = 0, 1, 2, 3
+FILLER_PHASE = 40000.0  # a filler pair: fPhase_rad = 40000, the other three values zero -- finite and plainly slow
+FILLER_PHASE_HIGH = 20000.0  # ... and one that is plainly of the full-degree fast class
+
+
+def pair_classes(table, dts, nr_channels, sampling_period):
+    """int8 [len(dts)][len(table)]: the class of every pair at every fDeltaTime -- FAST_LOW, FAST_HIGH or SLOW, as
+    dcs_pair_class (dc_sand_amd/csrc/bf_math.h) decides it from pair_terms in fp32 with the host's fRotBoundScale
+    (pi_f32 * (C - 1) / D * 1.0001, rounded to fp32) -- or UNCLEAR where a restatement should not be trusted to the bit:
+    the bound |fRateTerm| * scale + |fPhase0| within 0.5 % of 32000 or of 500, or a non-zero rate term whose exponent is
+    one of the two on either side of an edge of dcs_rate_in_fast_range (2^-61, 2^-60, 2^60, 2^61).  A non-finite term is
+    plainly SLOW.  A weighted call makes the coefficient of a pair of weight 0 from zero terms: pass flagged_table()."""
+    f, d = np.float32, np.float64
+    denom = f(f(sampling_period) * f(nr_channels))
+    with np.errstate(all="ignore"):
+        scale = f(d(nr_channels - 1) * d(f(np.pi)) / d(denom) * 1.0001)
+        if not scale >= 0:
+            scale = f(np.inf)
+    dts = np.atleast_1d(np.asarray(dts, dtype=f))
+    out = np.empty((dts.size, table.size), dtype=np.int8)
+    for i, dt in enumerate(dts):
+        with np.errstate(all="ignore"):
+            k, p0 = pair_terms(table, dt, nr_channels, sampling_period)
+            bound = ((np.abs(k) * scale).astype(f) + np.abs(p0)).astype(f)
+        e = (np.ascontiguousarray(k).view(np.uint32) >> 23) & 0xFF
+        in_range = (k == 0) | ((e >= 127 - 60) & (e <= 127 + 60))
+        cls = np.where(~in_range | ~(bound < f(32000)), SLOW, np.where(bound < f(500), FAST_LOW, FAST_HIGH)).astype(np.int8)
+        with np.errstate(invalid="ignore"):
+            near = (np.abs(bound.astype(d) - 32000.0) <= 160.0) | (np.abs(bound.astype(d) - 500.0) <= 2.5)
+        edge = (k != 0) & np.isin(e, (127 - 61, 127 - 60, 127 + 60, 127 + 61))
+        cls[near | edge] = UNCLEAR
+        out[i] = cls
+    return out
+
+
+def flagged_table(table, weights):
+    """The table [b * A + a] as a weighted call sees it: the entries of the pairs of weight 0 zeroed (terms (0, 0))."""
+    out = table.copy()
+    out[np.asarray(weights, dtype=F32).ravel() == 0] = np.zeros((), dtype=table.dtype)
+    return out
+
+
+def interleave_with_filler(table_ab, A, B, phase=FILLER_PHASE):
+    """The generator's table [a * B + b] of B beams as one of 2 B beams, [a * 2 B + b']: beam 2 b is beam b, beam 2 b + 1 a
+    filler (fPhase_rad = ``phase``, the other three values zero).  Every second pair is then slow, so every run of two or
+    more consecutive pairs holds one and every form of the generator (which decides per 64 / 128 / 256 consecutive pairs)
+    makes all its pairs with coeff_slow.  With FILLER_PHASE_HIGH every second pair is of the full-degree fast class
+    instead, and a table without a slow pair is made with the full-degree polynomials throughout -- as a beamformer makes
+    it when ONE of its pairs is of that class."""
+    assert table_ab.shape == (A * B,)
+    out = np.zeros((A, 2 * B), dtype=table_ab.dtype)
+    out[:, 0::2] = table_ab.reshape(A, B)
+    out["fPhase_rad"][:, 1::2] = F32(phase)
+    return out.ravel()
+
+
+def real_beams(coef2):
+    """[...][2 B][2] of an interleaved table -> [...][B][2] of the beams that are not fillers (a view)."""
+    assert coef2.shape[-2] % 2 == 0 and coef2.shape[-1] == 2
+    return coef2[..., 0::2, :]
+
+
+def first_difference_or_nan(got, exp):
+    """first_difference where ``exp`` may hold NaN: NaN (of any payload) in ``got`` exactly where ``exp`` has NaN, the
+    uint32 views equal everywhere else.  None, or a message."""
+    got, exp = np.ascontiguousarray(got), np.ascontiguousarray(exp)
+    assert got.shape == exp.shape and got.dtype == F32 and exp.dtype == F32, (got.shape, exp.shape, got.dtype, exp.dtype)
+    nan = np.isnan(exp)
+    wrong = np.flatnonzero((np.isnan(got) != nan).ravel())
+    if wrong.size:
+        i = int(wrong[0])
+        at = tuple(int(v) for v in np.unravel_index(i, got.shape))
+        return (f"NaN in {int(np.isnan(got).sum())} places, expected in {int(nan.sum())}; first difference at {at} "
+                f"(c, block, beam, sample, plane): got {got.ravel()[i]!r}, expected {exp.ravel()[i]!r}")
+    return first_difference(np.where(nan, F32(0), got), np.where(nan, F32(0), exp))
 
 
 def first_difference(got, exp):

@@ -7,8 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
-from helpers.beamformer_model import (FIX_SCALE, INV, acc_model, all_pairs_fast, digit_sums, digits, first_difference, fixed,
-                                      fused_model, normalise, recombine, weighted_coefficients)
+from helpers import slow_tables
+from helpers.beamformer_model import (FAST_HIGH, FAST_LOW, FILLER_PHASE_HIGH, FIX_SCALE, INV, SLOW, UNCLEAR, acc_model, acc_model_nonfinite, all_pairs_fast,
+                                      digit_sums, digits, first_difference, first_difference_or_nan, fixed, flagged_table, fused_model,
+                                      interleave_with_filler, normalise, pair_classes, real_beams, recombine, weighted_coefficients,
+                                      zero_weight_coefficients)
 
 K = FIX_SCALE
 U = Fraction(1, 2 ** 24)  # the relative error of one fp32 rounding to nearest (normal range)
@@ -266,3 +269,188 @@ def test_depth_bound_of_the_gpu_tests_is_the_pigeonhole_quotient():
     with pytest.raises(AssertionError):
         blocks_on_some_wave(16, 640, 272, (640, 2, 1), four)  # a grid that is not one-dimensional is not this kernel's
     assert all(depth >= MIN_DEPTH == 3 and nt % 16 == 0 for _, _, _, nt, depth in DEEP_SHAPES)
+
+
+# ---- what tests/test_gpu_beamformer_exact_slow.py stands on
+@pytest.fixture(scope="module")
+def lab():
+    """dc_sand_amd/csrc/bf_math.h compiled for the host (tests/numerics, as tests/test_numerics.py builds it)."""
+    import ctypes
+    import subprocess
+    from pathlib import Path
+
+    lab_dir = Path(__file__).resolve().parent / "numerics"
+    res = subprocess.run(["make", "-C", str(lab_dir)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    L = ctypes.CDLL(str(lab_dir / "libnumerics_lab.so"))
+    L.lab_generate_fast.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                    ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                    ctypes.POINTER(ctypes.c_uint64)]
+    return L
+
+
+def _class_tables():
+    """(name, table, fDeltaTime values, channels) of the tables the slow-class GPU tests use and of the boundaries' far sides."""
+    dts = np.float32([0.0, 0.3710937, 9 * 1.5e-3, 1.6])
+    A, B = 37, 21
+    edge = rand_table(A * B, seed=5)
+    edge["fDelayRate_sps"][:] = 0.0  # the zero rate term: fast whatever its exponent field says
+    edge["fDelayRate_sps"][3] = 1e-30  # the tiny one: below 2^-60, slow
+    edge["fDelayRate_sps"][4] = -1e-30
+    edge["fPhase_rad"][7] = 20000.0  # full degree
+    return [("rand_table", rand_table(A * B, seed=A + B), dts, 9),
+            ("one slow pair", slow_tables.one_slow_pair(A, B), dts, 9),
+            ("one slow pair, kChain", slow_tables.one_slow_pair(200, 20), dts, 2),
+            ("all slow", slow_tables.all_slow(A, B), dts, 3),
+            ("crossing", slow_tables.crossing(A, B), slow_tables.crossing_times(), 3),
+            ("tiny and zero rate terms", edge, dts, 64)]
+
+
+@pytest.mark.parametrize("name,table,dts,C", _class_tables(), ids=[t[0] for t in _class_tables()])
+def test_pair_classes_count_what_bf_math_counts(lab, name, table, dts, C):
+    """pair_classes against dcs_pair_terms / dcs_pair_class compiled for the host (lab_generate_fast: n_slow_pairs and
+    n_low_pairs of one time step), at every time: equal counts, and none of these tables has an unclear pair."""
+    import ctypes
+
+    cls = pair_classes(table, dts, C, slow_tables.SAMPLING_PERIOD)
+    assert cls.shape == (len(dts), table.size) and not np.any(cls == UNCLEAR)
+    d = np.ascontiguousarray(table)
+    out = np.empty((1, table.size, 2), dtype=np.float32)
+    for i, dt in enumerate(dts):
+        slow, low = ctypes.c_uint64(), ctypes.c_uint64()
+        lab.lab_generate_fast(0, d.ctypes.data, table.size, C, np.float32(slow_tables.SAMPLING_PERIOD), np.float32(dt), 0, 1,
+                              out.ctypes.data, ctypes.byref(slow), ctypes.byref(low))
+        assert (int(np.sum(cls[i] == SLOW)), int(np.sum(cls[i] == FAST_LOW))) == (slow.value, low.value), (name, i, float(dt))
+    # what each table is meant to be
+    if name == "rand_table":
+        assert np.all(cls == FAST_LOW) and all_pairs_fast(table, dts, C, slow_tables.SAMPLING_PERIOD)
+    elif name.startswith("one slow pair"):
+        assert np.all(np.sum(cls == SLOW, axis=1) == 1) and np.all(np.sum(cls == FAST_LOW, axis=1) == table.size - 1)
+        assert not all_pairs_fast(table, dts, C, slow_tables.SAMPLING_PERIOD)
+    elif name == "all slow":
+        assert np.all(cls == SLOW)
+    elif name == "crossing":
+        assert tuple(slow_tables.block_classes(cls)) == slow_tables.CROSSING_BLOCK_CLASSES
+        i = (21 // 2) * 37 + 37 // 2
+        assert np.all(cls[:16, i] == FAST_HIGH) and list(cls[16:20, i]) == [FAST_HIGH, FAST_HIGH, FAST_HIGH, SLOW] and np.all(cls[19:, i] == SLOW)
+        assert np.all(np.delete(cls, i, axis=1) == FAST_LOW)
+    else:
+        assert np.all(cls[:, [3, 4]] == SLOW) and np.all(cls[:, 7] == FAST_HIGH) and np.all(np.delete(cls, [3, 4, 7], axis=1) == FAST_LOW)
+
+
+def test_pair_classes_marks_the_neighbourhood_of_every_boundary_and_non_finite_values_slow():
+    t = np.zeros(12, dtype=rand_table(1).dtype)
+    t["fPhase_rad"][:6] = [31900.0, 32100.0, 499.0, 501.5, 31000.0, 33000.0]
+    t["fDelayRate_sps"][6:10] = [2.0 ** -61, 2.0 ** -60, 1.5 * 2.0 ** 60, 2.0 ** 61]  # (the last two: |fRotation| is huge anyway)
+    t["fDelayRate_sps"][10] = np.inf
+    t["fDelay_s"][11] = np.nan
+    cls = pair_classes(t, np.float32([0.0, 0.5]), 1, 1e-7)  # one channel: the rate term's bound is 0, its exponent still counts
+    for row in cls:
+        assert list(row) == [UNCLEAR] * 4 + [FAST_HIGH, SLOW] + [UNCLEAR] * 4 + [SLOW, SLOW]
+    # a flagged pair is made from zero terms, whatever its delay values are
+    w = np.ones((3, 4), np.float32)
+    w[2, 2], w[2, 3] = 0.0, -0.0
+    assert np.all(pair_classes(flagged_table(t, w), np.float32([0.5]), 1, 1e-7)[0, 10:] == FAST_LOW)
+    assert np.array_equal(flagged_table(t, w)[:10], t[:10])
+
+
+def test_interleaving_with_fillers_and_slicing_back_are_inverse():
+    A, B, C = 5, 3, 2
+    table_ab = rand_table(A * B, seed=11)
+    t2 = interleave_with_filler(table_ab, A, B)
+    assert t2.shape == (A * 2 * B,) and t2.dtype == table_ab.dtype
+    two = t2.reshape(A, 2 * B)
+    assert np.array_equal(two[:, 0::2].ravel(), table_ab)  # a real pair's entry is untouched, at [a * 2 B + 2 b]
+    for a in range(A):
+        for b in range(B):
+            assert t2[a * 2 * B + 2 * b] == table_ab[a * B + b]
+            assert tuple(t2[a * 2 * B + 2 * b + 1]) == (0.0, 0.0, 40000.0, 0.0)
+    # every filler is plainly slow at any time, so every run of two consecutive pairs holds a slow pair
+    cls = pair_classes(t2, np.float32([0.0, 0.37, 1.6]), C, 1e-7)
+    assert np.all(cls.reshape(3, A, 2 * B)[:, :, 1::2] == SLOW) and np.all(cls.reshape(3, A, 2 * B)[:, :, 0::2] == FAST_LOW)
+    # fillers of the full-degree fast class: the same places, the real pairs untouched
+    high = interleave_with_filler(table_ab, A, B, FILLER_PHASE_HIGH)
+    assert np.array_equal(high.reshape(A, 2 * B)[:, 0::2].ravel(), table_ab) and np.all(high["fPhase_rad"].reshape(A, 2 * B)[:, 1::2] == 20000.0)
+    cls = pair_classes(high, np.float32([0.0, 0.37, 1.6]), C, 1e-7)
+    assert np.all(cls.reshape(3, A, 2 * B)[:, :, 1::2] == FAST_HIGH) and np.all(cls.reshape(3, A, 2 * B)[:, :, 0::2] == FAST_LOW)
+    # a tensor in the generator's order [t][c][a][2 B][2] that carries its own index comes back as [t][c][a][B][2]
+    coef2 = np.arange(3 * C * A * 2 * B * 2, dtype=np.float32).reshape(3, C, A, 2 * B, 2)
+    back = real_beams(coef2)
+    assert back.shape == (3, C, A, B, 2)
+    for b in range(B):
+        assert np.array_equal(back[:, :, :, b], coef2[:, :, :, 2 * b])
+
+
+def test_non_finite_model_against_a_plain_loop():
+    """acc_model_nonfinite and first_difference_or_nan at one small case, element by element in Python: the verifier's sum
+    with a NaN coefficient is NaN whatever the samples are (NaN * 0 = NaN), the others are acc_model's."""
+    rng = np.random.default_rng(3)
+    C, A, B, nT16 = 2, 7, 4, 2
+    coef = _coefficients("trig", rng, C, A, B)
+    x = _samples("trig", rng, C, nT16, A)
+    x[:, :, 5] = 0  # the antenna of the NaN coefficient below is silent: its beam is NaN all the same
+    bad = coef.copy()
+    bad[0, 5, 1, :] = np.nan  # channel 0, beam 1, both planes
+    bad[1, 2, 3, 1] = np.inf  # channel 1, beam 3, the im plane only
+    got = acc_model_nonfinite(bad, x)
+    clean = acc_model(np.where(np.isfinite(bad), bad, np.float32(0)), x)
+    for c in range(C):
+        for t in range(nT16):
+            for b in range(B):
+                for i in range(16):
+                    for k in range(2):
+                        column_bad = any(not np.isfinite(bad[c, a, b, k]) for a in range(A))
+                        assert column_bad == ((c, b) == (0, 1) or (c, b, k) == (1, 3, 1))
+                        if column_bad:
+                            assert np.isnan(got[c, t, b, i, k])
+                        else:
+                            assert got[c, t, b, i, k].view(np.uint32) == clean[c, t, b, i, k].view(np.uint32)
+    assert first_difference(acc_model_nonfinite(coef, x), acc_model(coef, x)) is None  # finite: acc_model itself
+    # the comparison: NaN of any payload where the model has NaN, bits elsewhere
+    assert first_difference_or_nan(got, got) is None
+    other = got.copy()
+    other[0, 0, 1, 0, 0] = np.float32(-np.nan)
+    assert first_difference_or_nan(other, got) is None
+    other[0, 0, 1, 0, 0] = 0.0
+    assert "NaN in" in first_difference_or_nan(other, got)
+    other = got.copy()
+    other[1, 1, 0, 3, 0] = np.nextafter(other[1, 1, 0, 3, 0], np.float32(1e9))
+    assert "1 of" in first_difference_or_nan(other, got)
+    # weights: a flagged antenna's coefficient is made from zero terms, so its NaN goes; ghat * NaN stays NaN
+    w = np.ones((B, A), np.float32)
+    w[:, 5] = 0.0
+    s, gh = normalise(w)
+    z = zero_weight_coefficients(bad, w)
+    assert np.all(z[:, 5] == np.float32([1, 0])) and np.array_equal(np.delete(z, 5, axis=1), np.delete(bad, 5, axis=1), equal_nan=True)
+    flagged = acc_model_nonfinite(weighted_coefficients(z, gh), x, scale=s)
+    assert not np.isnan(flagged[0]).any() and np.isnan(flagged[1, :, 3, :, 1]).all() and np.isnan(flagged).sum() == nT16 * 16
+    with np.errstate(invalid="ignore"):
+        unflagged = acc_model_nonfinite(weighted_coefficients(bad, normalise(np.ones((B, A), np.float32))[1]), x, scale=s)
+    assert first_difference_or_nan(unflagged, got) is None
+    # the fused model propagates NaN by itself (a coefficient is a sine or a cosine: NaN, never Inf)
+    nans = np.where(np.isfinite(bad), bad, np.float32(np.nan))
+    with np.errstate(invalid="ignore"):
+        f = fused_model(np.broadcast_to(nans, (16 * nT16,) + bad.shape).copy(), x)
+    assert np.array_equal(np.isnan(f), np.isnan(got))
+
+
+def test_equality_sees_what_the_old_bounds_let_through():
+    """(64, 16, 2, 32), the shape tests/test_gpu_class_replay.py holds to 4e-5 * A + 1e-6: ONE unit of the middle digit of
+    one antenna's coefficients (256 / 8355711 = 3.1e-5 per unit of sample).  That antenna's samples are drawn within +-64
+    here -- at full scale, 128, the unit moves an output by 3.9e-3 and even the bound notices -- and every changed output
+    is within the bound of the unchanged one, while first_difference names the first of them."""
+    A, B, C, nt = 64, 16, 2, 32
+    rng = np.random.default_rng(64)
+    coef = _coefficients("trig", rng, C, A, B)
+    x = rng.integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+    a0 = 29
+    x[:, :, a0] = rng.integers(-64, 65, size=(C, nt // 16, 16, 2), dtype=np.int8)
+    s1, s2, s3 = digit_sums(coef, x)
+    ref = recombine(s1, s2, s3)
+    assert first_difference(ref, acc_model(coef, x)) is None
+    s2_off = s2 + x[:, :, a0].astype(np.int64)[:, :, None]  # d2 of antenna a0 one higher in every beam: [C][nT16][1][16][2]
+    off = recombine(s1, s2_off, s3)
+    err = np.abs(off.astype(np.float64) - ref.astype(np.float64))
+    assert 1.5e-3 < err.max() <= 4e-5 * A + 1e-6  # the old bound passes it ...
+    diff = first_difference(off, ref)
+    assert diff is not None and int(diff.split()[0]) > 0.8 * ref.size, diff  # ... equality does not, nearly everywhere

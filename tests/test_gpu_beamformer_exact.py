@@ -12,8 +12,10 @@ Precondition, asserted on the CPU for every case: all pairs in the fast classes 
 the beamformers switch the whole table (resp. 16-sample block) to the slow path while the generator does so per wave.
 
 Every assertion on beam values is equality of the uint32 views, the 64-byte canary behind the output untouched, all
-values finite.  Not covered here (their bound tests stay): the fp32 chain form (math_mode 8: the matrix instruction's
-internal order is not specified), the slow class, non-finite values."""
+values finite.  The slow class and non-finite delay values are held the same way, bit for bit, in
+tests/test_gpu_beamformer_exact_slow.py (the slow path's coefficient bits come from the same generator, made to take
+coeff_slow for every pair).  Not covered by either file (its bound tests stay): the fp32 chain form (math_mode 8: the
+matrix instruction's internal order is not specified)."""
 import numpy as np
 import pytest
 
@@ -50,24 +52,39 @@ class Exact(Case):
 
     def coefficient_bits(self, dts):
         """fp32 [len(dts)][C][A][B][2] from the GPU generator, asserted within 1 ULP of the oracle."""
-        gpu, oracle = self.gpu, self.oracle
         dts = np.ascontiguousarray(np.atleast_1d(np.asarray(dts, dtype=np.float32)))
         assert all_pairs_fast(self.table_ab, dts, self.C, self.bp.SAMPLING_PERIOD), "a pair outside the fast classes: change the inputs"
-        nbytes = self.gen.output_bytes(nt=dts.size)
+        return self.generated_bits(self.gen, self.op, self.table_ab, self.B, dts)[0]
+
+    def generated_bits(self, gen, op, table_ab, nr_beams, dts, not_finite=None):
+        """(fp32 [len(dts)][C][A][nr_beams][2] from the generator context ``gen``, whose table is ``table_ab``, the oracle's
+        comparison of it): the canary behind the tensor intact and every word within 1 ULP of the oracle.  ``not_finite``:
+        a mask over the pairs of table_ab whose delay values are not finite -- their words must all be NaN, and the
+        oracle compares the rest (those pairs as the zero entry's (1, 0))."""
+        gpu = self.gpu
+        nbytes = gen.output_bytes(nt=dts.size)
         buf = gpu.mem_alloc(nbytes + 64)
         gpu.memset(buf, 0xFF, nbytes + 64)
-        self.gen.generate_dt(buf, nbytes, dts)
+        gen.generate_dt(buf, nbytes, dts)
         host = np.empty(nbytes + 64, dtype=np.uint8)
         gpu.memcpy_dtoh(host, buf)
         buf.free()
         assert np.all(host[nbytes:] == 0xFF)
-        coef = host[:nbytes].view(np.float32).reshape(dts.size, self.C, self.A, self.B, 2)
-        res = oracle.compare_generated(self.op, self.table_ab, dts, 0, self.C, coef, nthreads=8)
+        coef = host[:nbytes].view(np.float32).reshape(dts.size, self.C, self.A, nr_beams, 2)
+        seen, table = coef, table_ab
+        if not_finite is not None and not_finite.any():
+            mask = not_finite.reshape(self.A, nr_beams)
+            assert np.all(np.isnan(coef[:, :, mask]))
+            seen, table = coef.copy(), table_ab.copy()
+            seen[:, :, mask] = (np.float32(1), np.float32(0))
+            table[not_finite] = np.zeros((), dtype=table.dtype)
+        res = self.oracle.compare_generated(op, table, dts, 0, self.C, seen, nthreads=8)
         assert res["max_ulp"] <= 1 and res["first_over_1ulp"] == -1 and sum(res["hist"]) == coef.size, res
-        return coef
+        return coef, res
 
-    def call(self, kind, w=None, **kw):
-        """One beamformer call into the 0xFF-filled buffer; `kw` picks the time: acc t_coeff= / dt_coeff=, fused t0= / dt=."""
+    def call(self, kind, w=None, finite=True, **kw):
+        """One beamformer call into the 0xFF-filled buffer; `kw` picks the time: acc t_coeff= / dt_coeff=, fused t0= / dt=.
+        ``finite=False`` only where the delay table holds a value that is not finite."""
         gpu, g = self.gpu, self.g
         gpu.memset(self.d_beams, 0xFF, self.nbytes + 64)
         if w is not None:
@@ -83,7 +100,7 @@ class Exact(Case):
         else:
             g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, t0=kw["t0"], nt=self.nt)
         got = self.read()  # asserts the canary
-        assert np.all(np.isfinite(got)), (kind, kw)
+        assert not finite or np.all(np.isfinite(got)), (kind, kw)
         return got
 
     def same_bits(self, got, exp, what):

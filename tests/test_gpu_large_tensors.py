@@ -10,7 +10,8 @@ bit with the numpy models of the small tests: a wrapped load gives other values,
 the line and spoils the alias row.  No tolerance anywhere; nothing on the host is proportional to a tensor.
 
 Not here: the incoherent beam's OUTPUT ([C][nt / 16] uint32) would need 32 GiB of samples to pass the line even with one
-antenna; the fp32 chain form, the slow class and non-finite values keep their small tests."""
+antenna; the fp32 chain form keeps its small bound tests, and the slow class and non-finite values are held bit for bit
+at small shapes (tests/test_gpu_beamformer_exact_slow.py)."""
 import numpy as np
 import pytest
 
