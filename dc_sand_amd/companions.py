@@ -104,4 +104,11 @@ COMPANIONS = {
         ("dcs_bf_ddc", c_int, [_VP, c_uint32, c_uint32, _VP, c_size_t, c_uint64, _VP, c_size_t, c_uint32, c_uint32, _VP, c_uint64,
                                _VP, c_size_t, c_uint64, _VP]),
     ]),
+    # the candidate sifter: the signal-to-noise planes of single_pulse as a compacted, ordered list of 32-byte records
+    "candidates": Companion("dcs_candidates.h", "bf_candidates.cpp", "libdcs_candidates.so", [
+        ("dcs_bf_candidates_workspace_bytes", c_size_t, [c_uint32, c_uint32, c_uint32]),
+        ("dcs_bf_find_candidates", c_int,
+         [_VP, _VP, c_size_t, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, c_uint32, c_float, c_uint32, c_uint32,
+          _VP, c_size_t, c_uint32, _VP, _VP, c_size_t, _VP]),
+    ]),
 }

@@ -220,4 +220,28 @@ inline int ddc_args(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, cons
                       !(pairs >> 61) && (uint64_t)pairs * (2u * sizeof(float)) <= (uint64_t)out_bytes);
 }
 
+// include/dcs_candidates.h.  The sifter's tiles are kCandTileDms DMs by kCandTileBlocks blocks (bf_candidates.hip); a segment
+// is one row of a tile, the 64 cells whose marks are one ballot.  The workspace holds per segment one 64-bit word of marks,
+// then one 32-bit count that the scan turns into the segment's place in the list, both in the order (beam, DM, tile of blocks)
+constexpr uint32_t kCandTileDms = 16u, kCandTileBlocks = 64u, kCandMaxRadius = 8u;
+inline unsigned __int128 candidates_segments(uint32_t nr_beams, uint32_t nr_dm, uint32_t nr_blocks)
+{
+    return (unsigned __int128)nr_beams * nr_dm * (((uint64_t)nr_blocks + kCandTileBlocks - 1u) / kCandTileBlocks);
+}
+inline size_t candidates_workspace_bytes(uint32_t nr_beams, uint32_t nr_dm, uint32_t nr_blocks)
+{
+    const unsigned __int128 segments = candidates_segments(nr_beams, nr_dm, nr_blocks); // < 2^90
+    const unsigned __int128 bytes = segments * 8u + (segments * 4u + 7u) / 8u * 8u;
+    return bytes > (unsigned __int128)SIZE_MAX ? SIZE_MAX : (size_t)bytes;
+}
+inline int find_candidates_args(dcs_bf_context *c, const float *d_snr, const uint32_t *d_peaks, uint64_t peak_blocks, uint64_t first_block,
+                                uint32_t nr_blocks, uint32_t nr_beams, float threshold, uint32_t dm_radius, uint32_t block_radius,
+                                const void *d_cands, uint32_t max_candidates, const uint32_t *d_count, const void *d_work)
+{
+    return arg_status(c && d_snr && d_peaks && d_count && d_work && (d_cands || max_candidates == 0u) && aligned(d_snr, 4u) &&
+                      aligned(d_peaks, 8u) && aligned(d_cands, 8u) && aligned(d_count, 4u) && aligned(d_work, 8u) && nr_beams != 0u &&
+                      dm_radius <= kCandMaxRadius && block_radius <= kCandMaxRadius && std::isfinite(threshold) &&
+                      fits(first_block, nr_blocks, peak_blocks));
+}
+
 #endif // BF_ARG_CHECKS_H

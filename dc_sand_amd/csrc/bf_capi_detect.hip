@@ -1,13 +1,13 @@
 // bf_capi_detect.hip -- what comes after detection: the integration of block powers (include/dcs_beam_power.h), the
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
 // detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h), the
-// single-pulse search on its planes (include/dcs_single_pulse.h), the correlator (include/dcs_correlator.h) and the digital
-// down-converter (include/dcs_ddc.h), each reached through the table at the head of every
-// context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing else.  Each begins with the
-// device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made already; what follows needs the
-// device or the context's sizes, or is a condition that only this side makes.  Host code only; the kernels are in
-// bf_integrate.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip, bf_single_pulse.hip, bf_correlator.hip and
-// bf_ddc.hip.
+// single-pulse search on its planes (include/dcs_single_pulse.h), the correlator (include/dcs_correlator.h), the digital
+// down-converter (include/dcs_ddc.h) and the candidate sifter (include/dcs_candidates.h), each reached through the table
+// at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing
+// else.  Each begins with the device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made
+// already; what follows needs the device or the context's sizes, or is a condition that only this side makes.  Host code
+// only; the kernels are in bf_integrate.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip,
+// bf_single_pulse.hip, bf_correlator.hip, bf_ddc.hip and bf_candidates.hip.
 
 #include <cmath>
 #include <cstring>
@@ -390,6 +390,45 @@ int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_
         a.gain[b] = bands[b].gain;
     }
     return (int)bf_launch_ddc(a, as_stream(stream));
+}
+
+// include/dcs_candidates.h, reached the same way.  Nothing allocated; of the context only its device is used.  The counts
+// and a record's block are 32-bit words: a call with 2^32 cells or more, or with a block past 2^32, is not supported.
+int find_candidates_impl(dcs_bf_context *c, const float *d_snr, size_t snr_bytes, const uint32_t *d_peaks, size_t peaks_bytes,
+                         uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm,
+                         uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
+                         size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes, void *stream)
+{
+    if (int e = find_candidates_args(c, d_snr, d_peaks, peak_blocks, first_block, nr_blocks, nr_beams, threshold, dm_radius,
+                                     block_radius, d_cands, max_candidates, d_count, d_work))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (((unsigned __int128)series * nr_blocks >> 32) || first_block + nr_blocks > (1ull << 32)) return DCS_ERR_UNSUPPORTED;
+    if (!holds(snr_bytes, series, nr_widths, peak_blocks, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cands_bytes, max_candidates, 32u, 1u, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (work_bytes < candidates_workspace_bytes(nr_beams, nr_dm, nr_blocks)) return DCS_ERR_INVALID_ARGUMENT;
+    const uint64_t segments = (uint64_t)candidates_segments(nr_beams, nr_dm, nr_blocks); // no more than the cells
+    bf_cand_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.snr = d_snr;
+    a.peaks = d_peaks;
+    a.cands = static_cast<uint32_t *>(d_cands);
+    a.count = d_count;
+    a.marks = static_cast<uint64_t *>(d_work);
+    a.places = reinterpret_cast<uint32_t *>(a.marks + segments);
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.B = nr_beams;
+    a.nr_dm = nr_dm;
+    a.nr_blocks = nr_blocks;
+    a.nr_widths = nr_widths;
+    a.dm_radius = dm_radius;
+    a.block_radius = block_radius;
+    a.max_candidates = max_candidates;
+    a.threshold = threshold;
+    return (int)bf_launch_find_candidates(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -4,10 +4,11 @@
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
 // (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
 // (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h), libdcs_correlator.so
-// (include/dcs_correlator.h) and libdcs_ddc.so (include/dcs_ddc.h).  All are built from this tree together.
+// (include/dcs_correlator.h), libdcs_ddc.so (include/dcs_ddc.h) and libdcs_candidates.so (include/dcs_candidates.h).  All are
+// built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator and of the down-converter; a companion's
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator, of the down-converter and of the candidate sifter; a companion's
 // export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
 // takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
@@ -37,7 +38,9 @@
 // older test hands a foreign version above 10).
 // 13: ddc_tap_digits, ddc appended (tests/test_host_abi_ddc.py hands its companion 1, 11 and 12; no older test hands a
 // foreign version above 11).
-#define BF_CTX_EXT_VERSION 13u
+// 14: find_candidates appended (tests/test_host_abi_candidates.py hands its companion 1, 12 and 13; no older test hands a
+// foreign version above 12).
+#define BF_CTX_EXT_VERSION 14u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -134,6 +137,13 @@ struct bf_ctx_ext_ops {
     int (*ddc)(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes,
                uint64_t in_stride, const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands,
                const dcs_ddc_band *bands, uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream);
+    // the candidate sifter (include/dcs_candidates.h): signal-to-noise float [nr_beams][nr_dm][nr_widths][peak_blocks] and the
+    // peaks behind it -> dcs_bf_candidate [max_candidates] in ascending (beam, DM, block) and d_count = {found, written}
+    int (*find_candidates)(dcs_bf_context *c, const float *d_snr, size_t snr_bytes, const uint32_t *d_peaks, size_t peaks_bytes,
+                           uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm,
+                           uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
+                           size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes,
+                           void *stream);
 };
 
 // the first member of struct dcs_bf_context

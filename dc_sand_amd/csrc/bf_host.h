@@ -198,6 +198,10 @@ int ddc_tap_digits_impl(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_ta
 int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes, uint64_t in_stride,
              const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands, const dcs_ddc_band *bands,
              uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream);
+int find_candidates_impl(dcs_bf_context *c, const float *d_snr, size_t snr_bytes, const uint32_t *d_peaks, size_t peaks_bytes,
+                         uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm,
+                         uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
+                         size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes, void *stream);
 
 } // namespace bf_host
 

@@ -237,7 +237,7 @@ struct bf_stokes_args {
 hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream);
 hipError_t bf_warm_module_stokes();
 
-// The integrator of every post-detection output (bf_integrate.hip; DESIGN.md section 5.20): blocks [C][nr_blocks][bs] summed
+// The integrator of every post-detection output (bf_integrate.hip; DESIGN.md section 5.21): blocks [C][nr_blocks][bs] summed
 // n at a time into out [nr_blocks / n][C][bs].  The element type selects the rule: float words are added in order, one rounded
 // add each; 32-bit integer words exactly, in 64 bits, and the sum converted once
 enum bf_integrate_type { BF_INTEGRATE_F32, BF_INTEGRATE_U32 /* built for bs == 1 */, BF_INTEGRATE_I32 };
@@ -361,6 +361,25 @@ struct bf_ddc_args {
 };
 hipError_t bf_launch_ddc(const bf_ddc_args &a, hipStream_t stream);
 hipError_t bf_warm_module_ddc();
+
+// The candidate sifter (bf_candidates.hip; include/dcs_candidates.h): the cells (beam, DM, block)
+// of blocks first_block .. first_block + nr_blocks - 1 at or above threshold that no cell within the two radii beats, as
+// records of eight words in ascending (beam, DM, block).  A segment is a row of a tile: kCandTileBlocks cells of one DM
+struct bf_cand_args {
+    const float *snr;      // [B][nr_dm][nr_widths][peak_blocks]
+    const uint32_t *peaks; // [B][nr_dm][nr_widths][peak_blocks][2], 8-byte aligned
+    uint32_t *cands;       // [max_candidates][8], 8-byte aligned; nullptr where max_candidates == 0
+    uint32_t *count;       // {found, written}
+    uint64_t *marks;       // the workspace: [segments] ballots of the candidates ...
+    uint32_t *places;      // ... and [segments] counts, which the scan makes the segments' first places in the list
+    uint64_t peak_blocks, first_block;
+    uint64_t segments;     // B * nr_dm * k_tiles < 2^32
+    uint32_t B, nr_dm, nr_blocks, nr_widths, dm_radius, block_radius, max_candidates;
+    float threshold;
+    uint32_t dm_tiles, k_tiles; // filled by the launcher: tiles along the DMs and along the blocks
+};
+hipError_t bf_launch_find_candidates(const bf_cand_args &a, hipStream_t stream);
+hipError_t bf_warm_module_candidates();
 
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.

@@ -226,6 +226,26 @@ def best_width_bytes(nr_beams: int, nr_dm: int, peak_blocks: int) -> int:
     return int(nr_beams) * int(nr_dm) * int(peak_blocks) * 4
 
 
+# dcs_bf_candidate (include/dcs_candidates.h): one single-pulse candidate, 32 bytes
+candidate_dtype = np.dtype([("beam", np.uint32), ("dm", np.uint32), ("width_index", np.uint32), ("block", np.uint32),
+                            ("time", np.uint32), ("value", np.uint32), ("snr", np.float32), ("members", np.uint32)])
+# The sifter's geometry (dc_sand_amd/csrc/bf_arg_checks.h, bf_candidates.hip): a tile is CANDIDATES_TILE_DMS DMs by
+# CANDIDATES_TILE_BLOCKS blocks, a segment one row of a tile; the scan takes CANDIDATES_SCAN_SPAN segments per round
+CANDIDATES_TILE_DMS, CANDIDATES_TILE_BLOCKS, CANDIDATES_MAX_RADIUS, CANDIDATES_SCAN_SPAN = 16, 64, 8, 4096
+
+
+def candidates_bytes(max_candidates: int) -> int:
+    """Size of the record array ``dcs_bf_candidate [max_candidates]`` (:data:`candidate_dtype`) of
+    :meth:`SteeringCoefficientGenerator.find_candidates`."""
+    return int(max_candidates) * candidate_dtype.itemsize
+
+
+def candidates_workspace_bytes(nr_beams: int, nr_dm: int, nr_blocks: int) -> int:
+    """``dcs_bf_candidates_workspace_bytes``: the bytes of ``d_work`` for a
+    :meth:`SteeringCoefficientGenerator.find_candidates` call of this shape.  Host only."""
+    return int(_lib.companion("candidates").dcs_bf_candidates_workspace_bytes(int(nr_beams), int(nr_dm), int(nr_blocks)))
+
+
 class _DdcBand(ctypes.Structure):  # dcs_ddc_band (include/dcs_ddc.h)
     _fields_ = [("phase_step", ctypes.c_uint32), ("phase0", ctypes.c_uint32), ("gain", ctypes.c_float)]
 
@@ -587,6 +607,25 @@ class SteeringCoefficientGenerator:
                                  _p(d_sums), int(sums_bytes), int(count), _p(d_snr), int(snr_bytes), _p_or_null(d_best),
                                  int(best_bytes), _s(stream)),
               "dcs_bf_peak_snr")
+
+    # -- the candidate sifter on that signal-to-noise (include/dcs_candidates.h, companion library libdcs_candidates.so):
+    #    d_cands a device array of candidate_dtype records, d_count a device uint32 [2] array {found, written}
+    def find_candidates(self, d_snr, snr_bytes: int, d_peaks, peaks_bytes: int, peak_blocks: int, first_block: int, nr_blocks: int,
+                        nr_beams: int, nr_dm: int, nr_widths: int, threshold: float, dm_radius: int, block_radius: int, d_cands,
+                        cands_bytes: int, max_candidates: int, d_count, d_work, work_bytes: int, stream=None) -> None:
+        """The cells (beam, DM, block) of blocks ``first_block .. first_block + nr_blocks - 1`` whose largest
+        signal-to-noise over the widths is at or above ``threshold`` and which no cell of the same beam within
+        ``dm_radius`` DMs and ``block_radius`` blocks (0 .. 8 each) beats -- the larger value, or of equal values the
+        earlier (DM, block) -- as :data:`candidate_dtype` records in ascending (beam, DM, block): the first
+        ``min(found, max_candidates)`` of ``d_cands`` (:func:`candidates_bytes`; ``None`` where ``max_candidates`` is 0)
+        and ``d_count = {found, written}``.  ``d_work``: :func:`candidates_workspace_bytes` bytes of scratch."""
+        cl = _lib.companion("candidates")
+        check(cl.dcs_bf_find_candidates(c_void_p(self._h), _p(d_snr), int(snr_bytes), _p(d_peaks), int(peaks_bytes),
+                                        int(peak_blocks), int(first_block), int(nr_blocks), int(nr_beams), int(nr_dm),
+                                        int(nr_widths), float(np.float32(threshold)), int(dm_radius), int(block_radius),
+                                        _p_or_null(d_cands), int(cands_bytes), int(max_candidates), _p(d_count), _p(d_work),
+                                        int(work_bytes), _s(stream)),
+              "dcs_bf_find_candidates")
 
     # -- the correlator (include/dcs_correlator.h, companion library libdcs_correlator.so): d_vis is a device int32
     #    [C][(nt / 16) / blocks_per_vis][NB][2] array, d_out a device float [nr_vis / vis_per_integration][C][NB][2] array

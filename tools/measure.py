@@ -45,6 +45,10 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the single-pulse search on the planes of that shape: the sums, the boxcar peaks of 13 widths and the signal-to-noise,
         the peaks' share of one read of the planes, and all three against dedisperse_q8 in the same process
                                                                                     -> profiles/r14_single_pulse.md
+    python tools/measure.py candidates [--rounds 5] [--shape CxDMSxTxB] [--block-len 64] [--threshold 6] [--max-candidates 4096]
+        the candidate sifter on the signal-to-noise of that search: find_candidates on a plane with few candidates and with
+        half the cells above the threshold, beside peak_snr and dedisperse_q8 in the same process
+                                                                                    -> profiles/r17_candidates.md
     python tools/measure.py correlator [--rounds 5] [--shapes AxCxNTxN,...] [--buffers 2]
         the correlator's block call rotating over copies of the samples that together stay above the Infinity Cache, against
         the incoherent beam over the same bytes (the read yardstick), alternating, in one process: the time, the fraction of
@@ -942,6 +946,80 @@ def cmd_single_pulse(args):
         d.free()
 
 
+def cmd_candidates(args):
+    """The candidate sifter (include/dcs_candidates.h) at the size of the search example: the signal-to-noise of 13 widths 1 ..
+    4096 and blocks of ``--block-len`` spectra, made by the chain dedisperse_q8 -> dm_time_sums -> boxcar_peaks -> peak_snr
+    from noise-like bytes.  find_candidates is timed at ``--threshold`` (on noise: few candidates, the scatter stages few
+    tiles) and at threshold 0 (about half the cells at or above it: every tile is staged twice), beside peak_snr and
+    dedisperse_q8 in the same process."""
+    from dc_sand_amd.generator import (boxcar_peaks_bytes, candidates_bytes, candidates_workspace_bytes, dm_delays_bytes, dm_time_bytes,
+                                       dm_time_sums_bytes, filterbank_bytes, peak_snr_bytes)
+
+    C, nr_dm, T, B = (int(x) for x in args.shape.lower().split("x"))
+    widths = np.array([1 << k for k in range(13)], np.uint32)
+    max_width, block_len = 4096, args.block_len
+    bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+    g = SteeringCoefficientGenerator(bp)
+    band = (1500.0, -300.0 / C, 64e-6)
+    dms = np.linspace(0.0, 500.0, nr_dm)
+    ps = T + max_width - 1
+    tb, pb = dm_delays_bytes(bp, nr_dm), dm_time_bytes(B, nr_dm, ps)
+    d_dms, d_delays, d_widths, d_plane = device.mem_alloc(dms.nbytes), device.mem_alloc(tb), device.mem_alloc(widths.nbytes), device.mem_alloc(pb)
+    device.memcpy_htod(d_dms, dms)
+    device.memcpy_htod(d_widths, widths)
+    g.dm_delays(*band, d_dms, nr_dm, d_delays, tb)
+    device.synchronize()
+    table = np.empty((nr_dm, C), np.int32)
+    device.memcpy_dtoh(table, d_delays)
+    max_delay = int(table.max())
+    in_spectra = ps + max_delay
+    fb = filterbank_bytes(bp, B, in_spectra)
+    d_fb = device.mem_alloc(fb)
+    _noise(d_fb, fb)
+    nb = (T + block_len - 1) // block_len
+    sb, kb, nbytes = dm_time_sums_bytes(B, nr_dm), boxcar_peaks_bytes(B, nr_dm, widths.size, nb), peak_snr_bytes(B, nr_dm, widths.size, nb)
+    cap = args.max_candidates
+    cb, wb = candidates_bytes(cap), candidates_workspace_bytes(B, nr_dm, nb)
+    d_sums, d_peaks, d_snr, d_cands, d_count, d_work = (device.mem_alloc(n) for n in (sb, kb, nbytes, cb, 8, wb))
+    dedisp = lambda: g.dedisperse_q8(d_fb, fb, in_spectra, 0, T, B, d_delays, nr_dm, max_delay, d_plane, pb, ps)  # noqa: E731
+    snr_call = lambda: g.peak_snr(d_peaks, kb, nb, 0, nb, B, nr_dm, d_widths, widths.size, max_width, d_sums, sb, T, d_snr, nbytes)  # noqa: E731
+    g.dedisperse_q8(d_fb, fb, in_spectra, 0, ps, B, d_delays, nr_dm, max_delay, d_plane, pb, ps)
+    g.dm_time_sums(d_plane, pb, ps, 0, T, B, nr_dm, d_sums, sb)
+    g.boxcar_peaks(d_plane, pb, ps, 0, T, B, nr_dm, d_widths, widths.size, max_width, block_len, d_peaks, kb, nb)
+    snr_call()
+
+    def find(threshold):
+        return lambda: g.find_candidates(d_snr, nbytes, d_peaks, kb, nb, 0, nb, B, nr_dm, widths.size, threshold, args.dm_radius,
+                                         args.block_radius, d_cands, cb, cap, d_count, d_work, wb)
+    found = {}
+    count = np.empty(2, np.uint32)
+    for name, threshold in (("sparse", args.threshold), ("dense", 0.0)):
+        find(threshold)()
+        device.synchronize()
+        device.memcpy_dtoh(count, d_count)
+        found[name] = count.tolist()
+    t = {k: [] for k in ("sparse", "dense", "snr", "dedisperse")}
+    for _ in range(args.rounds):
+        t["sparse"].append(per_launch_ms(find(args.threshold)))
+        t["dense"].append(per_launch_ms(find(0.0)))
+        t["snr"].append(per_launch_ms(snr_call))
+        t["dedisperse"].append(per_launch_ms(dedisp, settle_ms=50.0, timed_ms=100.0))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    row = {"shape": f"C={C} nr_dm={nr_dm} T={T} B={B}", "widths": widths.size, "block_len": block_len, "blocks": nb,
+           "snr_MiB": round(nbytes / 2**20, 1), "workspace_KiB": wb >> 10, "radii": [args.dm_radius, args.block_radius],
+           "max_candidates": cap, "threshold": args.threshold, "found": found["sparse"], "found_at_threshold_0": found["dense"],
+           "find_candidates_us": round(med["sparse"] * 1e3, 1),
+           "find_candidates_spread": round(max(t["sparse"]) / min(t["sparse"]) - 1.0, 4),
+           "find_candidates_at_threshold_0_us": round(med["dense"] * 1e3, 1),
+           "snr_read_TBps": round(nbytes / (med["sparse"] * 1e-3) / 1e12, 2),
+           "peak_snr_us": round(med["snr"] * 1e3, 1), "dedisperse_ms": round(med["dedisperse"], 3),
+           "find_candidates_over_dedisperse": round(med["sparse"] / med["dedisperse"], 5)}
+    print(json.dumps({"candidates": row}), flush=True)
+    g.close()
+    for d in (d_dms, d_delays, d_widths, d_plane, d_fb, d_sums, d_peaks, d_snr, d_cands, d_count, d_work):
+        d.free()
+
+
 def cmd_correlator(args):
     """The correlator (include/dcs_correlator.h): one read of the samples (A * 32 bytes per channel and block) and
     NB * 8 bytes written per channel and visibility.  Per shape A x C x nt x n, in turn ``--rounds`` times in one process on the
@@ -1487,6 +1565,14 @@ def main():
     p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB: the shape of dedisperse")
     p.add_argument("--block-len", type=int, default=256, help="spectra per block of the peak plane")
     p.add_argument("--buffers", type=int, default=3, help="copies of the planes the rotated timings walk")
+    p = sub.add_parser("candidates")
+    p.add_argument("--rounds", type=int, default=5, help="timings of each call")
+    p.add_argument("--shape", default="4096x512x16384x4", help="CxDMSxTxB: the shape of dedisperse")
+    p.add_argument("--block-len", type=int, default=64, help="spectra per block of the peak plane")
+    p.add_argument("--threshold", type=float, default=6.0)
+    p.add_argument("--dm-radius", type=int, default=8)
+    p.add_argument("--block-radius", type=int, default=8)
+    p.add_argument("--max-candidates", type=int, default=4096)
     p = sub.add_parser("correlator")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the correlator and the incoherent beam per shape")
     p.add_argument("--shapes", default="64x4096x4096x64,256x1024x4096x64", help="AxCxNTxN, comma-separated: n blocks per visibility")
@@ -1539,7 +1625,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "correlator": cmd_correlator, "ddc": cmd_ddc, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
