@@ -4,6 +4,7 @@ seeded random weights."""
 import numpy as np
 
 from conftest import rand_table
+from helpers.device_buffers import Context
 
 # test_beamform_accumulated_on_the_matrix_cores's shapes: staged and kChain, ragged antennas / beams, several beam groups
 # and several workgroups per channel
@@ -32,7 +33,6 @@ DEEP_SHAPES = [(64, 16, 640, 272, MIN_DEPTH), (37, 9, 640, 272, MIN_DEPTH), (64,
                (64, 16, 1280, 256, 4), (48, 72, 640, 256, 10), (130, 20, 640, 256, 4)]
 DEEPEST_SHAPES = DEEP_SHAPES[-3:]
 T_COEFF = 9
-CANARY = 64
 
 
 def blocks_on_some_wave(B, C, nt, grid, block):
@@ -47,27 +47,22 @@ def blocks_on_some_wave(B, C, nt, grid, block):
     return -(-units // waves)
 
 
-class Case:
-    """One context, its samples and output buffer (with a canary), and both beamformers with and without weights."""
+class Case(Context):
+    """One context, its samples and output buffer (0xFF with a 0xFF canary: unwritten floats read as NaN), and both
+    beamformers with and without weights."""
 
     def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu, self.oracle = gpu, oracle
-        self.A, self.B, self.C, self.nt = A, B, C, nt
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
+        super().__init__(gpu, C, A, B, NR_SAMPLES_PER_CHANNEL=nt)
+        self.oracle, self.nt = oracle, nt
         self.op = oracle.params_from(self.bp)
         self.table = rand_table(self.bp.n_pairs, seed=A + B + seed) if table is None else table  # [b*A + a]
         self.ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
-        self.g = SteeringCoefficientGenerator(self.bp)
         self.g.upload_delays(self.table)
-        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
-        gpu.memcpy_htod(self.d_ant, self.ant)
+        self.d_ant = self.upload(self.ant)
         self.shape = (C, nt // 16, B, 16, 2)
         self.nbytes = int(np.prod(self.shape)) * 4
-        self.d_beams = gpu.mem_alloc(self.nbytes + CANARY)
-        self.d_w = gpu.mem_alloc(B * A * 4)
+        self.d_beams = self.out(self.nbytes, 0xFF, 0xFF)
+        self.d_w = self.alloc(B * A * 4)
 
     def set_ant(self, ant):
         self.ant = ant
@@ -80,7 +75,7 @@ class Case:
     def run(self, kind, w=None, stream=None):
         """kind 'acc' / 'fused'; w: None (unweighted) or a [B][A] array (copied to the device first)."""
         gpu = self.gpu
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
+        self.refill(self.d_beams)
         if w is not None:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
         if kind == "acc":
@@ -95,19 +90,19 @@ class Case:
             else:
                 self.g.generate_and_beamform_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, t0=0,
                                                       nt=self.nt)
-        return self.read()
+        return self.read_beams()
 
     def floats(self, w=None, dt=None, t_coeff=T_COEFF):
         """What the float call returns (index entry point, or with dt the _dt one)."""
         gpu = self.gpu
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY)
+        self.refill(self.d_beams)
         kw = {"t_coeff": t_coeff} if dt is None else {"dt_coeff": dt}
         if w is None:
             self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, **kw)
         else:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
             self.g.beamform_accumulated_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, self.nt, **kw)
-        return self.read()
+        return self.read_beams()
 
     def enqueue_floats(self, weighted, stream):
         """The float call (by index) on ``stream`` and nothing else: what prove_depth captures."""
@@ -131,19 +126,13 @@ class Case:
                                  f"only {proven} block(s) proven on some wave, {depth} wanted -- raise the shape's channel count")
         return grid[0], block[0], proven
 
-    def read(self):
-        host = np.empty(self.nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_beams)
-        assert np.all(host[self.nbytes:] == 0xFF), "written past the output tensor"
-        return host[:self.nbytes].view(np.float32).reshape(self.shape).copy()
+    def read_beams(self):
+        return self.read(self.d_beams, self.nbytes, np.float32, self.shape)
 
     def coefficients(self, dts):
         """The oracle's fp32 coefficients [t][c][a][b][2] (the table turned to the generator's [a*B + b])."""
         t_ab = np.ascontiguousarray(self.table.reshape(self.B, self.A).T).ravel()
         return self.oracle.generate_dt(self.op, t_ab, dts)
-
-    def close(self):
-        self.g.close()
 
 
 def random_weights(rng, B, A, zero_beam=True):

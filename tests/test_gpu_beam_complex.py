@@ -7,14 +7,17 @@ model, cross-checks against the existing element-wise call that fail on a sign o
 The slow class and NaN delays are held to the fp64 complex sum of the oracle's coefficients within
 2.5e-7 * sum_a (|x_re| + |x_im|) + 2e-7 * |sum| per component: the GPU bound of DESIGN.md section 5.4 with both sample
 components.  Every call writes into an exactly sized buffer with a canary behind it."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, DEEP_SHAPES, T_COEFF, Case, random_weights
+from helpers.bacc_case import DEEP_SHAPES, T_COEFF, Case, random_weights
 from helpers.beam_complex_model import complex_model
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beamformer_model import first_difference, normalise, weighted_coefficients
+from helpers.device_buffers import CANARY, closed_after
 from test_gpu_beamformer_exact import DT_COEFF, Exact
 from test_gpu_class_replay import class_table
 
@@ -29,14 +32,14 @@ assert all(s in DEEP_SHAPES for s in DEEP)
 
 class Complex:
     """The complex calls on a Case (or Exact): the float call into the Case's own output buffer, the detecting call into a
-    block power buffer of its own (exact size + canary)."""
+    block power buffer of its own (exact size + canary), which the Case frees."""
 
     def __init__(self, case):
         self.c = c = case
         self.nblk = c.nt // 16
         self.pshape = (c.C, self.nblk, c.B)
         self.pbytes = c.C * self.nblk * c.B * 4
-        self.d_p = c.gpu.mem_alloc(self.pbytes + CANARY)
+        self.d_p = c.out(self.pbytes)
 
     def enqueue(self, conj=False, weighted=False, dt=None, t_coeff=T_COEFF, stream=None, g=None):
         c = self.c
@@ -56,28 +59,31 @@ class Complex:
 
     def floats(self, conj=False, w=None, dt=None, g=None):
         c = self.c
-        c.gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
+        c.refill(c.d_beams)
         self._weights(w)
         self.enqueue(conj, w is not None, dt, g=g)
-        return c.read()  # (synchronises; asserts the canary)
+        return c.read_beams()  # (synchronises; asserts the canary)
 
     def power(self, conj=False, w=None, dt=None):
         gpu = self.c.gpu
-        gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        self.c.refill(self.d_p)
         self._weights(w)
         self.enqueue_power(conj, w is not None, dt)
         gpu.synchronize()
         return self.read_power()
 
     def read_power(self):
-        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
-        self.c.gpu.memcpy_dtoh(host, self.d_p)
-        assert np.all(host[self.pbytes:] == 0xA5), "written past the block power tensor"
-        return host[:self.pbytes].view(np.float32).reshape(self.pshape).copy()
+        return self.c.read(self.d_p, self.pbytes, np.float32, self.pshape)
 
-    def close(self):
-        self.d_p.free()
-        self.c.close()
+
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(Case, gpu, oracle))
+
+
+@pytest.fixture
+def exact(gpu, oracle):
+    yield from closed_after(partial(Exact, gpu, oracle))
 
 
 def dt_of(c, by_index):
@@ -102,8 +108,8 @@ def check_model(x, coef, conj, w=None, dt=None, what=""):
 
 # ---- bit for bit: plain and conjugated, the index entry point and the _dt one
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_complex_product_is_the_model_bit_for_bit(gpu, oracle, A, B, C, nt):
-    x = Complex(Exact(gpu, oracle, A, B, C, nt))
+def test_complex_product_is_the_model_bit_for_bit(gpu, oracle, exact, A, B, C, nt):
+    x = Complex(exact(A, B, C, nt))
     plain = x.c.floats()
     for by_index in (True, False):
         dt_arg, dt = dt_of(x.c, by_index)
@@ -113,15 +119,14 @@ def test_complex_product_is_the_model_bit_for_bit(gpu, oracle, A, B, C, nt):
         assert np.all(np.isfinite(v)) and np.unique(v).size >= min(100, v.size // 2)
         # not the element-wise product, and the conjugate is another number in both planes
         assert first_difference(v, plain) is not None and np.any(v[..., 0] != vc[..., 0]) and np.any(v[..., 1] != vc[..., 1])
-    x.close()
 
 
 # ---- cross-checks against the existing call: no model involved
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_call(gpu, oracle, A, B, C, nt):
+def test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_call(gpu, oracle, case, A, B, C, nt):
     """x_im = 0: re = sum w_re x_re, the plain call's re plane.  x_re = 0, conjugated: re = sum w_im x_im, the plain call's
     im plane (the operand is fixed(-sigma w_im) = fixed(w_im): the same digits).  Bit for bit, both entry points."""
-    x = Complex(Case(gpu, oracle, A, B, C, nt))
+    x = Complex(case(A, B, C, nt))
     c = x.c
     ant = c.ant.copy()
     only_re, only_im = ant.copy(), ant.copy()
@@ -143,13 +148,12 @@ def test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_cal
         # (six of 2^-24 relative between the two, and the low parts' 2^31 * 2^-24 / 8355711 = 1.5e-5 each) may differ
         neg = x.floats(False, dt=dt)
         assert np.allclose(neg[..., 0], -plain[..., 1], rtol=1e-6, atol=1e-3)
-    x.close()
 
 
 # ---- weights
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_weights(gpu, oracle, A, B, C, nt):
-    x = Complex(Exact(gpu, oracle, A, B, C, nt))
+def test_weights(gpu, oracle, exact, A, B, C, nt):
+    x = Complex(exact(A, B, C, nt))
     dt_arg, dt = dt_of(x.c, True)
     coef = x.c.coefficient_bits(dt)[0]
     for conj in (False, True):
@@ -169,7 +173,6 @@ def test_weights(gpu, oracle, A, B, C, nt):
     assert np.all(np.isnan(bad[:, :, nb]))
     others = [b for b in range(B) if b != nb]
     assert first_difference(np.ascontiguousarray(bad[:, :, others]), np.ascontiguousarray(got[:, :, others])) is None
-    x.close()
 
 
 # ---- the slow class and NaN delays: against the fp64 complex sum of the oracle's coefficients
@@ -202,10 +205,10 @@ def within_fp64_bound(got, coef, ant, conj, nan_beams, what):
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(37, 21, 3, 48), (200, 20, 2, 32)])
-def test_slow_class_and_nan_delays_against_the_fp64_sum(gpu, oracle, A, B, C, nt):
+def test_slow_class_and_nan_delays_against_the_fp64_sum(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.generator import delta_times
 
-    x = Complex(Case(gpu, oracle, A, B, C, nt))
+    x = Complex(case(A, B, C, nt))
     c = x.c
     dt = delta_times(c.bp, T_COEFF, 1)
     base = c.table.copy()
@@ -229,13 +232,12 @@ def test_slow_class_and_nan_delays_against_the_fp64_sum(gpu, oracle, A, B, C, nt
         assert np.all(np.isfinite(np.delete(got, 2, axis=2)))
         p = x.power(conj)
         assert same_bits(p, block_power(got)) is None and np.all(np.isnan(p[:, :, 2]))
-    x.close()
 
 
 # ---- where a wave takes several sample blocks
 @pytest.mark.parametrize("A,B,C,nt,depth", DEEP)
-def test_several_blocks_per_wave_bit_for_bit(gpu, oracle, record_property, A, B, C, nt, depth):
-    x = Complex(Exact(gpu, oracle, A, B, C, nt))
+def test_several_blocks_per_wave_bit_for_bit(gpu, oracle, exact, record_property, A, B, C, nt, depth):
+    x = Complex(exact(A, B, C, nt))
     dt_arg, dt = dt_of(x.c, DEEP.index((A, B, C, nt, depth)) % 2 == 0)
     coef = x.c.coefficient_bits(dt)[0]
     check_model(x, coef, False, dt=dt_arg, what="deep")
@@ -246,13 +248,12 @@ def test_several_blocks_per_wave_bit_for_bit(gpu, oracle, record_property, A, B,
         p = x.power(True, dt=dt_arg)
         assert same_bits(p, block_power(v)) is None, same_bits(p, block_power(v))
         x.c.prove_depth(depth, lambda s: x.enqueue_power(True, dt=dt_arg, stream=s))
-    x.close()
 
 
 # ---- the detected form
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_block_power_is_the_model_of_the_complex_float_output(gpu, oracle, A, B, C, nt):
-    x = Complex(Case(gpu, oracle, A, B, C, nt))
+def test_block_power_is_the_model_of_the_complex_float_output(gpu, oracle, case, A, B, C, nt):
+    x = Complex(case(A, B, C, nt))
     w = random_weights(np.random.default_rng(3 * A + B), B, A, zero_beam=False)
     for conj, wt, dt in ((False, None, None), (True, None, float(DT_COEFF)), (True, w, None), (False, w, float(DT_COEFF))):
         v = x.floats(conj, wt, dt)
@@ -262,26 +263,23 @@ def test_block_power_is_the_model_of_the_complex_float_output(gpu, oracle, A, B,
         assert same_bits(got, exp) is None, (conj, wt is not None, dt, same_bits(got, exp))
     # it is not the element-wise call's power
     assert same_bits(x.power(), block_power(x.c.floats())) is not None
-    x.close()
 
 
-def test_complex_block_power_feeds_the_integration_and_the_filterbanks(gpu, oracle):
+def test_complex_block_power_feeds_the_integration_and_the_filterbanks(gpu, oracle, case):
     """complex_power -> integrate_block_power -> spectra_sums -> filterbank_scales -> filterbank_q8, each step the model of
     the step before (helpers/beam_power_model.py, helpers/filterbank_model.py)."""
     from dc_sand_amd.generator import filterbank_bytes, filterbank_scales_bytes, power_spectra_bytes, spectra_sums_bytes
     from helpers import filterbank_model as fm
 
     A, B, C, nt, n = 64, 16, 5, 256, 2
-    x = Complex(Case(gpu, oracle, A, B, C, nt))
+    x = Complex(case(A, B, C, nt))
     c, g = x.c, x.c.g
     P = x.power(True)
     assert same_bits(P, block_power(x.floats(True))) is None
     T = x.nblk // n
     sizes = {"sp": power_spectra_bytes(c.bp, x.nblk, n), "sums": spectra_sums_bytes(c.bp, B), "sc": filterbank_scales_bytes(c.bp, B),
              "fb": filterbank_bytes(c.bp, B, T)}
-    d = {k: gpu.mem_alloc(v + CANARY) for k, v in sizes.items()}
-    for k, v in sizes.items():
-        gpu.memset(d[k], 0xA5, v + CANARY)
+    d = {k: c.out(v) for k, v in sizes.items()}
     g.integrate_block_power(x.d_p, x.pbytes, x.nblk, n, d["sp"], sizes["sp"])
     g.spectra_sums(d["sp"], sizes["sp"], T, B, d["sums"], sizes["sums"])
     g.filterbank_scales(d["sums"], sizes["sums"], T, B, 24.0, d["sc"], sizes["sc"])
@@ -289,10 +287,7 @@ def test_complex_block_power_feeds_the_integration_and_the_filterbanks(gpu, orac
     gpu.synchronize()
 
     def read(k, dtype, shape):
-        host = np.empty(sizes[k] + CANARY, dtype=np.uint8)
-        gpu.memcpy_dtoh(host, d[k])
-        assert np.all(host[sizes[k]:] == 0xA5), k
-        return host[:sizes[k]].view(dtype).reshape(shape).copy()
+        return c.read(d[k], sizes[k], dtype, shape)
 
     sp = read("sp", np.float32, (T, C, B))
     assert same_bits(sp, integrate(P, n)) is None
@@ -303,20 +298,17 @@ def test_complex_block_power_feeds_the_integration_and_the_filterbanks(gpu, orac
     fb = read("fb", np.uint8, (B, T, C))
     exp, _ = fm.filterbank(sp, sc, 128.0)
     assert np.array_equal(fb, exp) and np.unique(fb).size > 20
-    for v in d.values():
-        v.free()
-    x.close()
 
 
-def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle):
+def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle, case):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
 
-    x = Complex(Case(gpu, oracle, 64, 16, 2, 32))
+    x = Complex(case(64, 16, 2, 32))
     c = x.c
     ref = x.floats(True)
     c.g.set_tuning(math_mode=8)
-    gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
-    gpu.memset(x.d_p, 0xA5, x.pbytes + CANARY)
+    c.refill(c.d_beams)
+    c.refill(x.d_p)
     gpu.memcpy_htod(c.d_w, np.ones((16, 64), np.float32))
     for call in (x.enqueue, x.enqueue_power):
         for weighted in (False, True):
@@ -325,20 +317,19 @@ def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle):
                     call(True, weighted, dt)
                 assert e.value.status == DCS_ERR_UNSUPPORTED
     gpu.synchronize()
-    assert np.all(c.read().view(np.uint32) == 0xFFFFFFFF) and np.all(x.read_power().view(np.uint32) == 0xA5A5A5A5)
+    assert np.all(c.read_beams().view(np.uint32) == 0xFFFFFFFF) and np.all(x.read_power().view(np.uint32) == 0xA5A5A5A5)
     c.g.set_tuning()
     assert first_difference(x.floats(True), ref) is None
-    x.close()
 
 
 # ---- graph replay (tests/test_gpu_class_replay.py's scheme): a table with one full-degree pair
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 2, 32), (130, 20, 2, 32)])
-def test_captured_complex_call_replayed_after_a_younger_plain_call(gpu, oracle, A, B, C, nt):
+def test_captured_complex_call_replayed_after_a_younger_plain_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
     from dc_sand_amd.generator import SteeringCoefficientGenerator
 
     table, low, where = class_table(A, B, "high")
-    x = Complex(Case(gpu, oracle, A, B, C, nt, table=table))
+    x = Complex(case(A, B, C, nt, table=table))
     c = x.c
     s = gpu.Stream()
     # a first call under capture allocates: refused, and the capture can still be ended
@@ -371,25 +362,24 @@ def test_captured_complex_call_replayed_after_a_younger_plain_call(gpu, oracle, 
         gpu.memcpy_htod(c.d_ant, ants[i])
         c.ant = ants[i]
         c.floats()  # a younger plain float call on the same context
-        gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
+        c.refill(c.d_beams)
         gpu.synchronize()
         graph.launch(s)
         s.synchronize()
-        got = c.read()
+        got = c.read_beams()
         assert first_difference(got, fresh[i]) is None, (i, first_difference(got, fresh[i]))
     graph.close()
-    x.close()
 
 
 # ---- physics: a beam steered at the source it was made for
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 2, 32), (130, 20, 2, 32)])
-def test_a_conjugate_beam_on_its_own_source_adds_coherently(gpu, oracle, A, B, C, nt):
+def test_a_conjugate_beam_on_its_own_source_adds_coherently(gpu, oracle, case, A, B, C, nt):
     """x_a(t) = rint(100 * w_{a, b0}) per component: conj(w) x = 100 |w|^2 = 100 per antenna up to the rounding of the
     sample, at most 0.5 per component -- magnitude sqrt(0.5) after the unit-modulus rotation -- so beam b0 is within
     0.7072 * A + 1e-3 of (100 * A, 0) in each component; the beamformer's own error is orders below that."""
     from dc_sand_amd.generator import delta_times
 
-    x = Complex(Case(gpu, oracle, A, B, C, nt))
+    x = Complex(case(A, B, C, nt))
     c = x.c
     b0 = B // 3
     coef = c.coefficients(delta_times(c.bp, T_COEFF, 1))[0]  # [c][a][b][2]
@@ -407,4 +397,3 @@ def test_a_conjugate_beam_on_its_own_source_adds_coherently(gpu, oracle, A, B, C
     assert np.all(p[:, :, b0] > 4 * np.delete(p, b0, axis=2).mean())
     e = c.floats()
     assert np.all(np.hypot(e[:, :, b0, :, 0], e[:, :, b0, :, 1]) < 0.9 * 100.0 * A)
-    x.close()

@@ -8,21 +8,29 @@ element-wise kernels' (float)(s2 * 256 + s3) differ, and a mix-up of re, +im and
 Every comparison is equality of uint32 or byte views against the model (helpers/beam_complex_model.py) on the GPU
 generator's coefficient bits (Exact), no tolerance anywhere; the canary behind every buffer must be intact.  "Power" is
 block_power of the model's floats bit for bit, "q8" the bytes AND clip counters of helpers/beam_quant_model.py on them."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from conftest import rand_table
 from helpers import complex_edges as ce
-from helpers.bacc_case import CANARY, T_COEFF, random_weights
+from helpers.bacc_case import T_COEFF, random_weights
 from helpers.beam_complex_model import SUM_BOUND, digit_sums, operands, recombine
 from helpers.beam_power_model import block_power, same_bits
 from helpers.beam_quant_model import gains_with_clipping, gains_without_clipping, quantise
 from helpers.beamformer_model import F32, digits, first_difference, normalise, weighted_coefficients
+from helpers.device_buffers import closed_after
 from test_gpu_beam_complex_quant import CQ, ExactQ
 from test_gpu_beam_quant import same
 from test_gpu_beamformer_exact import constant_table, full_scale_samples, one_hot_samples, weights_for
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def exactq(gpu, oracle):
+    yield from closed_after(partial(ExactQ, gpu, oracle))
 
 
 class Calls:
@@ -52,14 +60,14 @@ class Calls:
 
     def floats(self, conj, w=None):
         c = self.c
-        c.gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
+        c.refill(c.d_beams)
         c.g.beamform_accumulated_complex(c.d_ant, c.ant.nbytes, c.d_beams, c.nbytes, c.nt, d_weights=self._weights(w),
                                          conjugate=conj, **self.time)
-        return c.read()  # (synchronises; asserts the canary)
+        return c.read_beams()  # (synchronises; asserts the canary)
 
     def power(self, conj, w=None):
         x, c = self.x, self.c
-        c.gpu.memset(x.d_p, 0xA5, x.pbytes + CANARY)
+        c.refill(x.d_p)
         c.g.beamform_accumulated_complex_power(c.d_ant, c.ant.nbytes, x.d_p, x.pbytes, c.nt, d_weights=self._weights(w),
                                                conjugate=conj, **self.time)
         c.gpu.synchronize()
@@ -67,7 +75,7 @@ class Calls:
 
     def q8(self, gains, conj, w=None):
         c = self.c
-        c.gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY)
+        c.refill(c.d_q)
         c.gpu.memcpy_htod(c.d_k, np.ascontiguousarray(gains, dtype=np.float32))
         c.gpu.memset(c.d_clip, 0, c.B * 8)
         c.g.beamform_accumulated_complex_q8(c.d_ant, c.ant.nbytes, c.d_k, c.d_q, c.qbytes, c.nt, d_weights=self._weights(w),
@@ -107,7 +115,7 @@ DRIVEN = (3, 16)               # one beam of each tile
 Q8_GAIN = 127.0 / 45000.0      # the driven beams' |v| of about 41904 lands at 118
 
 
-def test_low_part_beyond_int32(gpu, oracle, record_property):
+def test_low_part_beyond_int32(gpu, oracle, exactq, record_property):
     """S2 * 256 + S3 > 2^31 - 1: the input for which the complex kernels form the low part with an fma.
 
     With every sample -128, low = 128 * (256 * P2 + P3), P_d the sum of -digit_d over the 2 * A operand digits of a plane;
@@ -133,7 +141,7 @@ def test_low_part_beyond_int32(gpu, oracle, record_property):
     A, B, C, nt = WRAP_SHAPE
     table = constant_table(A * B, ce.PHASE_REST)
     table.reshape(B, A)["fPhase_rad"][:, 0] = ce.PHASE_0
-    x = CQ(ExactQ(gpu, oracle, A, B, C, nt, table=table))
+    x = CQ(exactq(A, B, C, nt, table=table))
     c = x.c
     ant = c.ant.copy()
     ant[:, 0] = -128
@@ -179,7 +187,6 @@ def test_low_part_beyond_int32(gpu, oracle, record_property):
                 print(f"conjugate {conj}, negated: largest exact low part {int(low.max())}, smallest {int(low.min())}; beam 3: {float(exp[0, 0, 3, 0, plane])!r}")
             calls.check(conj, w, power=True, q8=(k,), what=f"the wrap inputs, sign {sign}")
     assert calls.largest_sum <= SUM_BOUND
-    x.close()
 
 
 # ---- b. full-scale samples
@@ -203,7 +210,7 @@ def full_scale_pattern(pattern, C, nt, A):
 
 
 @pytest.mark.parametrize("A,B,C,nt", FULL_SCALE_SHAPES)
-def test_full_scale_samples(gpu, oracle, A, B, C, nt):
+def test_full_scale_samples(gpu, oracle, exactq, A, B, C, nt):
     """Samples all -128, all 127, alternating by antenna, and -128 in re with 127 in im (opposite-signed products in one
     plane), against the constant tables of phase 0, fp32(pi), fp32(pi / 2), fp32(pi / 4) and the seeded random table, plain and
     conjugated: the float call always; at all -128 also power, q8 with both gain sets, and all of it weighted.
@@ -212,7 +219,7 @@ def test_full_scale_samples(gpu, oracle, A, B, C, nt):
     fp32(pi / 4), whose cos and sin both have the low digit -100, where both products of a plane have one sign (samples
     all -128: the im plane, or re conjugated).  The axis tables reach 128 * 128 * A (fp32(pi): -127 of cos = -1 and the -1 of
     sin = -8.7e-8 in one plane), the random table a random walk's few hundred thousand.  Asserted from the model."""
-    x = CQ(ExactQ(gpu, oracle, A, B, C, nt))
+    x = CQ(exactq(A, B, C, nt))
     c = x.c
     w = weights_for(A, B, A + B)
     largest = 0
@@ -232,12 +239,11 @@ def test_full_scale_samples(gpu, oracle, A, B, C, nt):
         print(f"(A, B, C, nt) = {(A, B, C, nt)}, table {name}: largest |S_d| {calls.largest_sum}")
         largest = max(largest, calls.largest_sum)
     assert largest == 2 * 128 * 100 * A, (largest, 2 * 128 * 100 * A)
-    x.close()
 
 
 # ---- c. one antenna at a time
 @pytest.mark.parametrize("A,B,C", [(37, 21, 2), (130, 20, 1), (256, 16, 1)])
-def test_one_antenna_at_a_time(gpu, oracle, A, B, C):
+def test_one_antenna_at_a_time(gpu, oracle, exactq, A, B, C):
     """one_hot_samples (nt = 16 * A: block k carries the value in antenna k's re and in antenna A - 1 - k's im, nothing
     else), values 1 and -128.  With x = (v, 0) in antenna k alone the two planes are v times the digits of F_re and of F_ip;
     with x = (0, v) they are v times the digits of F_in and of F_re: a wrong operand (re, +im, -im), a wrong digit or a wrong
@@ -246,7 +252,7 @@ def test_one_antenna_at_a_time(gpu, oracle, A, B, C):
 
     Asserted from the coefficient bits: some (antenna, beam) has a -128 among the low digits of F_ip or F_in, so "the digits
     of the negated number" are other digits than the negated ones.  Should a seed yield none, change the seed."""
-    x = CQ(ExactQ(gpu, oracle, A, B, C, 16 * A))
+    x = CQ(exactq(A, B, C, 16 * A))
     c = x.c
     dt, time = time_by_index(c)
     calls = Calls(x, c.coefficient_bits(dt)[0], **time)
@@ -262,11 +268,10 @@ def test_one_antenna_at_a_time(gpu, oracle, A, B, C):
         for wt in (None, w):
             for conj in (False, True):
                 calls.check(conj, wt, what=f"one-hot samples of {value}")
-    x.close()
 
 
 # ---- d. seeded fuzz over shapes
-def test_seeded_fuzz_bit_for_bit(gpu, oracle):
+def test_seeded_fuzz_bit_for_bit(gpu, oracle, exactq):
     """30 seeded cases in the style of tests/test_gpu_beamformer_exact.py's fuzz: antennas from the edges of the 64-antenna
     chunks or uniform in 1 .. 256, beams 1 .. 90 (mostly off the 16-beam tile), 1 .. 4 channels, 1 .. 40 sample blocks, time by
     index or by value, the conjugate flag alternating, weighted as well every third case; the float call always, power every
@@ -280,7 +285,7 @@ def test_seeded_fuzz_bit_for_bit(gpu, oracle):
         nblk = int(rng.integers(1, 41))
         if A * B * C * nblk > 600000:
             nblk = max(1, 600000 // (A * B * C))
-        x = CQ(ExactQ(gpu, oracle, A, B, C, 16 * nblk, table=rand_table(A * B, seed=7000 + case),
+        x = CQ(exactq(A, B, C, 16 * nblk, table=rand_table(A * B, seed=7000 + case),
                       ant=rng.integers(-128, 128, size=(C, nblk, A, 16, 2), dtype=np.int8)))
         if rng.integers(0, 2):
             dt = np.float32(rng.uniform(0.0, 1.5))
@@ -293,5 +298,5 @@ def test_seeded_fuzz_bit_for_bit(gpu, oracle):
                                  what=f"fuzz case {case}")
             if case % 3 == 0:
                 clipped += int(quantise(exp, gains_with_clipping(exp))[1].sum())
-        x.close()
+        x.c.close()
     assert clipped > 1000  # the clipping branch and its counters took part

@@ -5,15 +5,18 @@ applied to what the complex float call returns on the same context and inputs --
 holds to its model -- and, separately, to the model itself (helpers/beam_complex_model.py) on the generator's coefficient
 bits, so the new kernels are held to the stated arithmetic without going through the float kernels.  Every quantised call
 writes into an exactly sized buffer with a canary behind it, which must stay untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, DEEP_SHAPES, T_COEFF
+from helpers.bacc_case import DEEP_SHAPES, T_COEFF
 from helpers.beam_complex_model import complex_model
 from helpers.beam_quant_model import (expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
 from helpers.beamformer_model import first_difference, normalise, weighted_coefficients
+from helpers.device_buffers import closed_after
 from test_gpu_beam_complex import Complex, dt_of
 from test_gpu_beam_quant import QCase, same
 from test_gpu_beamformer_exact import DT_COEFF, Exact
@@ -46,7 +49,7 @@ class CQ(Complex):
     def q8(self, gains, conj=False, w=None, count=True, dt=None, zero=True):
         """One quantised call from clean buffers: (int8 beams, counters or None)."""
         c, gpu = self.c, self.c.gpu
-        gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY)
+        c.refill(c.d_q)
         gpu.memcpy_htod(c.d_k, np.ascontiguousarray(gains, dtype=np.float32))
         if zero:
             gpu.memset(c.d_clip, 0, c.B * 8)
@@ -69,22 +72,36 @@ class CQ(Complex):
         return v
 
 
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(QCase, gpu, oracle))
+
+
+@pytest.fixture
+def exactq(gpu, oracle):
+    yield from closed_after(partial(ExactQ, gpu, oracle))
+
+
+@pytest.fixture
+def exact(gpu, oracle):
+    yield from closed_after(partial(Exact, gpu, oracle))
+
+
 # ---- 1. the bytes are the quantised floats of the complex float call: plain and conjugated, both entry points
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_bytes_and_counters_are_the_quantised_complex_float_output(gpu, oracle, A, B, C, nt, weighted):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_bytes_and_counters_are_the_quantised_complex_float_output(gpu, oracle, case, A, B, C, nt, weighted):
+    x = CQ(case(A, B, C, nt))
     w = seeded_weights(B, A) if weighted else None
     for conj in (False, True):
         for dt in (None, float(DT_COEFF)):  # the index and the _dt entry points
             x.check(conj, w, dt, f"conjugate {conj}, weighted {weighted}, dt {dt}, (A, B, C, nt) = {(A, B, C, nt)}")
-    x.close()
 
 
 # ---- 2. ... and of the model on the generator's coefficient bits: the float kernels are not involved
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_bytes_are_the_quantised_model_on_the_coefficient_bits(gpu, oracle, A, B, C, nt):
-    x = CQ(ExactQ(gpu, oracle, A, B, C, nt))
+def test_bytes_are_the_quantised_model_on_the_coefficient_bits(gpu, oracle, exactq, A, B, C, nt):
+    x = CQ(exactq(A, B, C, nt))
     c = x.c
     w = seeded_weights(B, A)
     s, gh = normalise(w)
@@ -101,13 +118,12 @@ def test_bytes_are_the_quantised_model_on_the_coefficient_bits(gpu, oracle, A, B
                 what = (conj, wt is not None, by_index, expected.__name__)
                 assert same(got, exp) is None, (what, same(got, exp))
                 assert np.array_equal(n, n_exp), (what, n, n_exp)
-    x.close()
 
 
 # ---- 3. not the element-wise form
 @pytest.mark.parametrize("A,B,C,nt", SMALL)
-def test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im(gpu, oracle, A, B, C, nt):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im(gpu, oracle, case, A, B, C, nt):
+    x = CQ(case(A, B, C, nt))
     c = x.c
     k = gains_without_clipping(np.concatenate([x.floats(), c.floats()], axis=1))
     mine, _ = x.q8(k)
@@ -124,26 +140,24 @@ def test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im(gpu, 
         assert np.all(theirs[..., 1] == 0) and np.unique(theirs[..., 0]).size >= min(100, theirs.size // 8)
         assert same(np.ascontiguousarray(mine[..., 0]), np.ascontiguousarray(theirs[..., 0])) is None, dt
         assert np.any(mine[..., 1] != 0) and n_theirs.sum() > 0 and np.all(n_mine >= n_theirs)
-    x.close()
 
 
 # ---- 4. where a wave takes several sample blocks
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt,depth", DEEP)
-def test_several_blocks_per_wave(gpu, oracle, record_property, A, B, C, nt, depth, weighted):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
+    x = CQ(case(A, B, C, nt))
     w = seeded_weights(B, A) if weighted else None
     dt = float(DT_COEFF) if DEEP.index((A, B, C, nt, depth)) % 2 else None
     x.check(True, w, dt, f"deep, weighted {weighted}, (A, B, C, nt) = {(A, B, C, nt)}")
     record_property("gridDim.x, blockDim.x, blocks proven on some wave",
                     x.c.prove_depth(depth, lambda s: x.enqueue_q8(True, weighted, dt=dt, stream=s)))
-    x.close()
 
 
 # ---- 5. special gains and a NaN delay value touch their beam only
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
-def test_special_gains_and_a_nan_delay_touch_their_beam_only(gpu, oracle, A, B, C, nt):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_special_gains_and_a_nan_delay_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
+    x = CQ(case(A, B, C, nt))
     c = x.c
     v = x.floats(True)
     k = gains_with_clipping(v)
@@ -191,35 +205,31 @@ def test_special_gains_and_a_nan_delay_touch_their_beam_only(gpu, oracle, A, B, 
     assert same(got, exp1) is None and np.array_equal(n, n_exp1)
     others = [i for i in range(B) if i != nb]
     assert np.array_equal(got[:, :, others], base[:, :, others]) and np.array_equal(n[others], n_base[others])
-    x.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
-def test_null_weights_equal_all_ones_weights(gpu, oracle, A, B, C, nt):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
+    x = CQ(case(A, B, C, nt))
     k = gains_with_clipping(x.floats(True))
     plain, n_plain = x.q8(k, True)
     ones, n_ones = x.q8(k, True, np.ones((B, A), np.float32))
     assert np.array_equal(plain, ones) and np.array_equal(n_plain, n_ones) and n_plain.sum() > 0
-    x.close()
 
 
 # ---- 6. the output's alignment rule is the float call's
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
-def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, A, B, C, nt):
+def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+    x = CQ(case(A, B, C, nt))
     c = x.c
     k = gains_with_clipping(x.floats(True))
     ref, n_ref = x.q8(k, True)
-    d_big = gpu.mem_alloc(c.qbytes + CANARY + 16)
-    gpu.memset(d_big, 0xA5, c.qbytes + CANARY + 16)
+    d_big = c.out(c.qbytes + 16)
     gpu.memset(c.d_clip, 0, B * 8)
     x.enqueue_q8(True, d_out=int(d_big) + 8)
     gpu.synchronize()
-    host = np.empty(c.qbytes + CANARY + 16, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_big)
+    host = c.read(d_big)
     assert np.all(host[:8] == 0xA5) and np.all(host[8 + c.qbytes:] == 0xA5)
     assert np.array_equal(host[8:8 + c.qbytes].view(np.int8).reshape(c.shape), ref) and np.array_equal(c.counts(), n_ref)
     with pytest.raises(DcsError) as e:
@@ -228,14 +238,12 @@ def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, A, B,
     with pytest.raises(DcsError) as e:  # one byte short
         c.g.beamform_accumulated_complex_q8(c.d_ant, c.ant.nbytes, c.d_k, int(d_big), c.qbytes - 1, nt, t_coeff=T_COEFF)
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
-    d_big.free()
-    x.close()
 
 
 # ---- 7. gains are read when the work runs
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
-def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, A, B, C, nt):
-    x = CQ(QCase(gpu, oracle, A, B, C, nt))
+def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, case, A, B, C, nt):
+    x = CQ(case(A, B, C, nt))
     c = x.c
     w = seeded_weights(B, A)
     v = x.floats(True, w)
@@ -248,22 +256,21 @@ def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, A, B, C, nt):
         x.enqueue_q8(True, weighted=True, stream=s.handle)
     for k, ref, n_ref in ((k1, ref1, n1), (k2, ref2, n2), (k1, ref1, n1)):
         gpu.memcpy_htod(c.d_k, k, stream=s.handle, sync=False)
-        gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY, stream=s.handle)
+        c.refill(c.d_q, stream=s.handle)
         gpu.memset(c.d_clip, 0, B * 8, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
     graph.close()
-    x.close()
 
 
 # ---- 8. a context per beam slice, gains and counters offset
 @pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
-def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
+def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.beam_quant import BeamQuantGains
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
 
-    full = CQ(QCase(gpu, oracle, A, B, C, nt))
+    full = CQ(case(A, B, C, nt))
     fc = full.c
     k = gains_with_clipping(full.floats(True))
     ref, n_ref = full.q8(k, True)
@@ -277,31 +284,30 @@ def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
         sh = beam_range(B, 2, rank)
         lp = local_parameters(fc.bp, sh)
         local_ab = slice_table(table_ab, fc.bp, sh).reshape(A, sh.n_beams)
-        part = CQ(QCase(gpu, oracle, A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel()))
+        part = CQ(case(A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel()))
         pc = part.c
         assert pc.bp.NR_BEAMS == lp.NR_BEAMS
         pc.set_ant(fc.ant)
-        gpu.memset(pc.d_q, 0xA5, pc.qbytes + CANARY)
+        pc.refill(pc.d_q)
         part.enqueue_q8(True, d_gains=qg.device_ptr(sh.beam_lo), d_clip=qg.clip_count_ptr(sh.beam_lo))
         gpu.synchronize()
         assert np.array_equal(pc.read_q8(), ref[:, :, sh.beam_lo:sh.beam_hi]), rank
-        part.close()
+        pc.close()
     assert np.array_equal(qg.clip_counts(reset=True), n_ref)
     qg.free()
-    full.close()
 
 
 # ---- 9. the fp32 fma-chain form has no such output
-def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
+def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle, case):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
 
-    x = CQ(QCase(gpu, oracle, 64, 16, 2, 32))
+    x = CQ(case(64, 16, 2, 32))
     c = x.c
     k = gains_with_clipping(x.floats(True))
     ref, n_ref = x.q8(k, True)
     c.g.set_tuning(math_mode=8)
     s = gpu.Stream()
-    gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY)
+    c.refill(c.d_q)
     gpu.memset(c.d_clip, 0, c.B * 8)
     gpu.memcpy_htod(c.d_w, np.ones((16, 64), np.float32))
     gpu.synchronize()
@@ -312,27 +318,24 @@ def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
                     x.enqueue_q8(conj, weighted, dt=dt, stream=s.handle)
                 assert e.value.status == DCS_ERR_UNSUPPORTED
     s.synchronize()
-    host = np.empty(c.qbytes + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, c.d_q)
-    assert np.all(host == 0xA5) and np.all(c.counts() == 0)  # nothing was enqueued
+    assert np.all(c.read(c.d_q) == 0xA5) and np.all(c.counts() == 0)  # nothing was enqueued
     c.g.set_tuning()
     x.enqueue_q8(True, stream=s.handle)  # the same stream, the default form again
     s.synchronize()
     assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
-    x.close()
 
 
 # ---- 10. two stages: quantised sub-array beams are the antenna tensor of a second beamformer
-def test_quantised_beams_are_the_samples_of_a_second_beamformer(gpu, oracle):
+def test_quantised_beams_are_the_samples_of_a_second_beamformer(gpu, oracle, exact, case):
     A1, B1, B2, C, nt = 64, 32, 5, 2, 32
-    first = CQ(QCase(gpu, oracle, A1, B1, C, nt))
+    first = CQ(case(A1, B1, C, nt))
     v1 = first.floats(True)
     k = gains_without_clipping(v1)
     q1, n1 = first.q8(k, True)
     exp1, _ = quantise(v1, k)
     assert same(q1, exp1) is None and n1.sum() == 0 and np.unique(q1).size >= 100
     # the second stage reads the first stage's device tensor in place: [C][nt / 16][B1][16][2] is its [C][nt / 16][A][16][2]
-    second = Complex(Exact(gpu, oracle, B1, B2, C, nt, ant=q1))
+    second = Complex(exact(B1, B2, C, nt, ant=q1))
     c2 = second.c
     assert c2.ant.shape == q1.shape and c2.ant.nbytes == first.c.qbytes
     own = c2.d_ant
@@ -345,5 +348,3 @@ def test_quantised_beams_are_the_samples_of_a_second_beamformer(gpu, oracle):
         assert diff is None, (conj, diff)
         assert np.all(np.isfinite(got)) and np.unique(got).size >= got.size // 2
     c2.d_ant = own
-    second.close()
-    first.close()

@@ -3,13 +3,16 @@ the expectation is finite, NaN for NaN otherwise (payloads are not compared), no
 model (helpers/beam_power_model.py, anchored on the CPU by tests/test_beam_power_model.py) applied to what the float call
 returns on the same context and inputs, which tests/test_gpu_beamformer_exact.py holds to its own arithmetic.  Every call
 writes into an exactly sized buffer with a canary behind it, which must stay untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
+from helpers.bacc_case import DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beam_quant_model import SHAPES, seeded_weights
+from helpers.device_buffers import closed_after
 
 pytestmark = pytest.mark.gpu
 
@@ -25,8 +28,8 @@ class PCase(Case):
         self.nblk = nt // 16
         self.pshape = (C, self.nblk, B)
         self.pbytes = C * self.nblk * B * 4
-        self.d_p = gpu.mem_alloc(self.pbytes + CANARY)
-        self.d_s = gpu.mem_alloc(self.pbytes + CANARY)  # spectra: at most one per block
+        self.d_p = self.out(self.pbytes)
+        self.d_s = self.out(self.pbytes)  # spectra: at most one per block
 
     def call_power(self, weighted=False, dt=None, t_coeff=T_COEFF, stream=None):
         kw = {"t_coeff": t_coeff} if dt is None else {"dt_coeff": dt}
@@ -34,15 +37,12 @@ class PCase(Case):
                                           d_weights=self.d_w if weighted else None, stream=stream, **kw)
 
     def read_power(self):
-        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_p)
-        assert np.all(host[self.pbytes:] == 0xA5), "written past the block power tensor"
-        return host[:self.pbytes].view(np.float32).reshape(self.pshape).copy()
+        return self.read(self.d_p, self.pbytes, np.float32, self.pshape)
 
     def power(self, w=None, dt=None, t_coeff=T_COEFF):
         """One detecting call from a clean buffer."""
         gpu = self.gpu
-        gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        self.refill(self.d_p)
         if w is not None:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
         self.call_power(weighted=w is not None, dt=dt, t_coeff=t_coeff)
@@ -57,29 +57,30 @@ class PCase(Case):
                                      stream=stream)
 
     def read_spectra(self, n):
-        nb = self.sbytes(n)
-        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_s)
-        assert np.all(host[nb:] == 0xA5), "written past the spectra"
-        return host[:nb].view(np.float32).reshape(self.nblk // n, self.C, self.B).copy()
+        return self.read(self.d_s, self.sbytes(n), np.float32, (self.nblk // n, self.C, self.B))
 
     def spectra(self, n, accumulate=False, prior=None):
         """One integration of what d_p holds; without ``accumulate`` from a clean buffer, with ``prior`` from that."""
         gpu = self.gpu
         if not accumulate:
-            gpu.memset(self.d_s, 0xA5, self.pbytes + CANARY)
+            self.refill(self.d_s)
         if prior is not None:
-            gpu.memset(self.d_s, 0xA5, self.pbytes + CANARY)
+            self.refill(self.d_s)
             gpu.memcpy_htod(self.d_s, np.ascontiguousarray(prior, dtype=np.float32))
         self.call_integrate(n, accumulate)
         gpu.synchronize()
         return self.read_spectra(n)
 
 
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(PCase, gpu, oracle))
+
+
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt", SHAPES)
-def test_block_power_is_the_model_of_the_float_output(gpu, oracle, A, B, C, nt, weighted):
-    c = PCase(gpu, oracle, A, B, C, nt)
+def test_block_power_is_the_model_of_the_float_output(gpu, oracle, case, A, B, C, nt, weighted):
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     for dt in (None, DT_COEFF):  # the index and the _dt entry points
         v = c.floats(w, dt)
@@ -91,17 +92,16 @@ def test_block_power_is_the_model_of_the_float_output(gpu, oracle, A, B, C, nt, 
         assert np.unique(exp).size >= min(100, exp.size), (np.unique(exp).size, exp.size)
         got = c.power(w, dt)
         assert same_bits(got, exp) is None, (dt, same_bits(got, exp))
-    c.close()
 
 
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
-def test_block_power_with_several_blocks_per_wave(gpu, oracle, record_property, A, B, C, nt, depth, weighted):
+def test_block_power_with_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
     """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
     in its pairs and several pairs.  One time form per shape, in turn; then the integrator over many workgroups, every block
     its own spectrum and all blocks in one.  The launch itself, read from a captured graph, must prove `depth` blocks on
     some wave."""
-    c = PCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
     v = c.floats(w, dt)
@@ -126,12 +126,11 @@ def test_block_power_with_several_blocks_per_wave(gpu, oracle, record_property, 
         got = c.power(dt=dt)
         assert same_bits(got, block_power(v2)) is None, ("NaN pair", same_bits(got, block_power(v2)))
         assert np.all(np.isnan(got[:, :, nb]))
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
-def test_special_weights_and_delay_values_touch_their_beam_only(gpu, oracle, A, B, C, nt):
-    c = PCase(gpu, oracle, A, B, C, nt)
+def test_special_weights_and_delay_values_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     w1 = seeded_weights(B, A)
     v = c.floats(w1)
     ref = c.power(w1)
@@ -179,24 +178,22 @@ def test_special_weights_and_delay_values_touch_their_beam_only(gpu, oracle, A, 
     assert np.all(np.isnan(got[:, :, nb1]))
     others = [i for i in range(B) if i != nb1]
     assert same_bits(got[:, :, others], base[:, :, others]) is None
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
-def test_null_weights_equal_all_ones_weights(gpu, oracle, A, B, C, nt):
-    c = PCase(gpu, oracle, A, B, C, nt)
+def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     plain = c.power()
     ones = c.power(np.ones((B, A), np.float32))
     assert same_bits(plain, ones) is None and np.all(np.isfinite(plain)) and np.unique(plain).size >= min(100, plain.size)
     assert same_bits(plain, block_power(c.floats())) is None
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (37, 21, 4, 32), (192, 17, 2, 32), (130, 20, 3, 48)])
-def test_subnormal_squares_are_not_flushed(gpu, oracle, A, B, C, nt):
+def test_subnormal_squares_are_not_flushed(gpu, oracle, case, A, B, C, nt):
     """Per-beam scales that put |v|^2 of some beams below the smallest normal number: the block powers of those beams are
     sums of subnormal numbers and still the model's."""
-    c = PCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A)
     w[0::3] *= np.float32(1e-23)  # |v| ~ 1e-20: every square subnormal
     w[1::3] *= np.float32(3e-22)  # |v| ~ 1e-19: squares on both sides of the smallest normal number
@@ -210,30 +207,26 @@ def test_subnormal_squares_are_not_flushed(gpu, oracle, A, B, C, nt):
     assert np.count_nonzero(exp >= TINY) >= exp.size // 3
     got = c.power(w)
     assert same_bits(got, exp) is None, same_bits(got, exp)
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
-def test_block_power_at_an_address_that_is_4_byte_aligned_only(gpu, oracle, A, B, C, nt):
+def test_block_power_at_an_address_that_is_4_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = PCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     ref = c.power()
     assert same_bits(ref, block_power(c.floats())) is None
-    d_big = gpu.mem_alloc(c.pbytes + CANARY + 16)
-    gpu.memset(d_big, 0xA5, c.pbytes + CANARY + 16)
+    d_big = c.out(c.pbytes + 16)
     c.g.beamform_accumulated_power(c.d_ant, c.ant.nbytes, int(d_big) + 4, c.pbytes, nt, t_coeff=T_COEFF)
     gpu.synchronize()
-    host = np.empty(c.pbytes + CANARY + 16, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_big)
+    host = c.read(d_big)
     assert np.all(host[:4] == 0xA5) and np.all(host[4 + c.pbytes:] == 0xA5)
     assert same_bits(host[4:4 + c.pbytes].view(np.float32).reshape(c.pshape), ref) is None
     # ... and integrated from there, into spectra that are 4-byte aligned only
-    d_sp = gpu.mem_alloc(c.pbytes + CANARY + 16)
-    gpu.memset(d_sp, 0xA5, c.pbytes + CANARY + 16)
+    d_sp = c.out(c.pbytes + 16)
     c.g.integrate_block_power(int(d_big) + 4, c.pbytes, c.nblk, c.nblk, int(d_sp) + 4, c.sbytes(c.nblk))
     gpu.synchronize()
-    gpu.memcpy_dtoh(host, d_sp)
+    host = c.read(d_sp)
     nb = c.sbytes(c.nblk)
     assert np.all(host[:4] == 0xA5) and np.all(host[4 + nb:] == 0xA5)
     assert same_bits(host[4:4 + nb].view(np.float32).reshape(1, C, B), integrate(ref, c.nblk)) is None
@@ -249,16 +242,13 @@ def test_block_power_at_an_address_that_is_4_byte_aligned_only(gpu, oracle, A, B
     with pytest.raises(DcsError) as e:  # block powers one byte short
         c.g.integrate_block_power(int(d_big) + 4, c.pbytes - 1, c.nblk, c.nblk, int(d_sp), nb)
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
-    d_big.free()
-    d_sp.free()
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 96), (64, 16, 5, 256), (256, 33, 2, 32)])
-def test_integration_is_the_ordered_sum(gpu, oracle, A, B, C, nt):
+def test_integration_is_the_ordered_sum(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = PCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A)
     P = c.power(w)
     assert same_bits(P, block_power(c.floats(w))) is None
@@ -283,27 +273,24 @@ def test_integration_is_the_ordered_sum(gpu, oracle, A, B, C, nt):
     assert same_bits(both, integrate(np.concatenate([P1, P2], axis=1), 2 * n)) is None  # = one integration of both calls' blocks
     # a bad blocks_per_spectrum is refused, nothing is enqueued, and the stream stays usable
     s = gpu.Stream()
-    gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY)
+    c.refill(c.d_s)
     gpu.synchronize()
     for bad in (0, c.nblk + 1, 3 if c.nblk % 3 else 5):
         with pytest.raises(DcsError) as e:
             c.g.integrate_block_power(c.d_p, c.pbytes, c.nblk, bad, c.d_s, c.pbytes, stream=s.handle)
         assert e.value.status == DCS_ERR_INVALID_ARGUMENT, bad
     s.synchronize()
-    host = np.empty(c.pbytes + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, c.d_s)
-    assert np.all(host == 0xA5)
+    assert np.all(c.read(c.d_s) == 0xA5)
     c.call_integrate(2, stream=s.handle)
     s.synchronize()
     assert same_bits(c.read_spectra(2), integrate(P2, 2)) is None
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
-def test_captured_calls_pick_up_new_samples_on_replay(gpu, oracle, A, B, C, nt):
+def test_captured_calls_pick_up_new_samples_on_replay(gpu, oracle, case, A, B, C, nt):
     """Both calls in one hipGraph (the process's default queue count is left as it is), replayed with new samples in the
     same buffer."""
-    c = PCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A)
     n = 2
     ants = [c.ant] + [np.random.default_rng(100 + i).integers(-128, 128, size=c.ant.shape, dtype=np.int8) for i in range(2)]
@@ -320,24 +307,23 @@ def test_captured_calls_pick_up_new_samples_on_replay(gpu, oracle, A, B, C, nt):
         c.call_integrate(n, stream=s.handle)
     for i in (1, 2, 0, 1):
         gpu.memcpy_htod(c.d_ant, ants[i], stream=s.handle, sync=False)
-        gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY, stream=s.handle)
-        gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY, stream=s.handle)
+        c.refill(c.d_p, stream=s.handle)
+        c.refill(c.d_s, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert same_bits(c.read_power(), refs[i][0]) is None and same_bits(c.read_spectra(n), refs[i][1]) is None, i
     graph.close()
-    c.close()
 
 
-def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
+def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle, case):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
 
-    c = PCase(gpu, oracle, 64, 16, 2, 32)
+    c = case(64, 16, 2, 32)
     ref = c.power()
     assert same_bits(ref, block_power(c.floats())) is None
     c.g.set_tuning(math_mode=8)
     s = gpu.Stream()
-    gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY)
+    c.refill(c.d_p)
     gpu.synchronize()
     for weighted in (False, True):
         for dt in (None, 0.0):
@@ -345,21 +331,18 @@ def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
                 c.call_power(weighted=weighted, dt=dt, stream=s.handle)
             assert e.value.status == DCS_ERR_UNSUPPORTED
     s.synchronize()
-    host = np.empty(c.pbytes + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, c.d_p)
-    assert np.all(host == 0xA5)  # nothing was enqueued
+    assert np.all(c.read(c.d_p) == 0xA5)  # nothing was enqueued
     c.g.set_tuning()
     c.call_power(stream=s.handle)  # the same stream, the default form again
     s.synchronize()
     assert same_bits(c.read_power(), ref) is None
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
-def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
+def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
 
-    full = PCase(gpu, oracle, A, B, C, nt)
+    full = case(A, B, C, nt)
     ref = full.power()
     assert same_bits(ref, block_power(full.floats())) is None
     ref_s = integrate(ref, full.nblk)
@@ -368,10 +351,9 @@ def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
         sh = beam_range(B, 3, rank)
         lp = local_parameters(full.bp, sh)
         local_ab = slice_table(table_ab, full.bp, sh).reshape(A, sh.n_beams)
-        part = PCase(gpu, oracle, A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
+        part = case(A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
         assert part.bp.NR_BEAMS == lp.NR_BEAMS
         part.set_ant(full.ant)
         assert same_bits(part.power(), ref[:, :, sh.beam_lo:sh.beam_hi]) is None, rank
         assert same_bits(part.spectra(part.nblk), ref_s[:, :, sh.beam_lo:sh.beam_hi]) is None, rank
         part.close()
-    full.close()

@@ -3,13 +3,16 @@ byte, no tolerance: the expectation is the numpy quantiser (helpers/beam_quant_m
 tests/test_beam_quant_model.py) applied to what the float call returns on the same context and inputs, which
 tests/test_gpu_beamformer_exact.py holds to its own arithmetic.  Every quantised call writes into an exactly sized buffer
 with a canary behind it, which must stay untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
+from helpers.bacc_case import DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_quant_model import (SHAPES, expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
+from helpers.device_buffers import closed_after
 
 pytestmark = pytest.mark.gpu
 
@@ -22,9 +25,9 @@ class QCase(Case):
     def __init__(self, gpu, oracle, A, B, C, nt, **kw):
         super().__init__(gpu, oracle, A, B, C, nt, **kw)
         self.qbytes = C * nt * B * 2
-        self.d_q = gpu.mem_alloc(self.qbytes + CANARY)
-        self.d_k = gpu.mem_alloc(B * 4)
-        self.d_clip = gpu.mem_alloc(B * 8)
+        self.d_q = self.out(self.qbytes)
+        self.d_k = self.alloc(B * 4)
+        self.d_clip = self.alloc(B * 8)
 
     def call_q8(self, weighted=False, count=True, dt=None, stream=None):
         kw = {"t_coeff": T_COEFF} if dt is None else {"dt_coeff": dt}
@@ -33,10 +36,7 @@ class QCase(Case):
                                        stream=stream, **kw)
 
     def read_q8(self):
-        host = np.empty(self.qbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_q)
-        assert np.all(host[self.qbytes:] == 0xA5), "written past the int8 tensor"
-        return host[:self.qbytes].view(np.int8).reshape(self.shape).copy()
+        return self.read(self.d_q, self.qbytes, np.int8, self.shape)
 
     def counts(self):
         n = np.empty(self.B, dtype=np.uint64)
@@ -46,7 +46,7 @@ class QCase(Case):
     def q8(self, gains, w=None, count=True, dt=None, zero=True):
         """One quantised call from clean buffers: (int8 beams, counters or None)."""
         gpu = self.gpu
-        gpu.memset(self.d_q, 0xA5, self.qbytes + CANARY)
+        self.refill(self.d_q)
         gpu.memcpy_htod(self.d_k, np.ascontiguousarray(gains, dtype=np.float32))
         if zero:
             gpu.memset(self.d_clip, 0, self.B * 8)
@@ -55,6 +55,11 @@ class QCase(Case):
         self.call_q8(weighted=w is not None, count=count, dt=dt)
         gpu.synchronize()
         return self.read_q8(), (self.counts() if count else None)
+
+
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(QCase, gpu, oracle))
 
 
 def same(got, exp):
@@ -68,8 +73,8 @@ def same(got, exp):
 
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt", SHAPES)
-def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, A, B, C, nt, weighted):
-    c = QCase(gpu, oracle, A, B, C, nt)
+def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, case, A, B, C, nt, weighted):
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     for dt in (None, DT_COEFF):  # the index and the _dt entry points
         v = c.floats(w, dt)
@@ -81,16 +86,15 @@ def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, A, B, C,
             assert np.array_equal(n, n_exp), (expected.__name__, dt, n, n_exp)
             got0, _ = c.q8(k, w, count=False, dt=dt)  # no counters: the same bytes
             assert same(got0, exp) is None, (expected.__name__, dt, "no counters", same(got0, exp))
-    c.close()
 
 
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
-def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, record_property, A, B, C, nt, depth, weighted):
+def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
     """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
     in its pairs and several pairs, and its byte counters run across them.  One time form per shape, in turn.  The launch
     itself, read from a captured graph, must prove `depth` blocks on some wave."""
-    c = QCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
     v = c.floats(w, dt)
@@ -124,12 +128,11 @@ def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, record_prope
         got, n = c.q8(k, dt=dt)
         assert same(got, exp) is None, ("NaN pair", same(got, exp))
         assert np.array_equal(n, n_exp) and n[nb] == C * nt * 2 and np.all(got[:, :, nb] == -128), (n, n_exp)
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 5, 80), (64, 40, 3, 48), (130, 20, 3, 48), (256, 33, 2, 32)])
-def test_counters_add_up_and_stay_zero_without_clipping(gpu, oracle, A, B, C, nt):
-    c = QCase(gpu, oracle, A, B, C, nt)
+def test_counters_add_up_and_stay_zero_without_clipping(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     v = c.floats()
     k = gains_without_clipping(v)
     kc = gains_with_clipping(v)
@@ -146,12 +149,11 @@ def test_counters_add_up_and_stay_zero_without_clipping(gpu, oracle, A, B, C, nt
     gpu.memcpy_htod(c.d_clip, start)
     got, n = c.q8(k, zero=False)
     assert np.array_equal(n, start + n_exp)
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
-def test_special_gains_weights_and_delay_values_touch_their_beam_only(gpu, oracle, A, B, C, nt):
-    c = QCase(gpu, oracle, A, B, C, nt)
+def test_special_gains_weights_and_delay_values_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     w1 = seeded_weights(B, A)
     v = c.floats(w1)
     k = gains_with_clipping(v)
@@ -211,34 +213,30 @@ def test_special_gains_weights_and_delay_values_touch_their_beam_only(gpu, oracl
         assert np.all(got[:, :, nb1] == -128) and n[nb1] == per_beam
         others = [i for i in range(B) if i != nb1]
         assert np.array_equal(got[:, :, others], base[:, :, others]) and np.array_equal(n[others], n_base[others])
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
-def test_null_weights_equal_all_ones_weights(gpu, oracle, A, B, C, nt):
-    c = QCase(gpu, oracle, A, B, C, nt)
+def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     k = gains_with_clipping(c.floats())
     plain, n_plain = c.q8(k)
     ones, n_ones = c.q8(k, np.ones((B, A), np.float32))
     assert np.array_equal(plain, ones) and np.array_equal(n_plain, n_ones) and n_plain.sum() > 0
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
-def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, A, B, C, nt):
+def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     """d_beams_q8 has the float call's rule: 8-byte alignment is enough, 4 is refused."""
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = QCase(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     k = gains_with_clipping(c.floats())
     ref, n_ref = c.q8(k)
-    d_big = gpu.mem_alloc(c.qbytes + CANARY + 16)
-    gpu.memset(d_big, 0xA5, c.qbytes + CANARY + 16)
+    d_big = c.out(c.qbytes + 16)
     gpu.memset(c.d_clip, 0, B * 8)
     c.g.beamform_accumulated_q8(c.d_ant, c.ant.nbytes, c.d_k, int(d_big) + 8, c.qbytes, nt, t_coeff=T_COEFF, d_clip_count=c.d_clip)
     gpu.synchronize()
-    host = np.empty(c.qbytes + CANARY + 16, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_big)
+    host = c.read(d_big)
     assert np.all(host[:8] == 0xA5) and np.all(host[8 + c.qbytes:] == 0xA5)
     assert np.array_equal(host[8:8 + c.qbytes].view(np.int8).reshape(c.shape), ref) and np.array_equal(c.counts(), n_ref)
     with pytest.raises(DcsError) as e:
@@ -247,13 +245,11 @@ def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, A, B,
     with pytest.raises(DcsError) as e:  # one byte short
         c.g.beamform_accumulated_q8(c.d_ant, c.ant.nbytes, c.d_k, int(d_big), c.qbytes - 1, nt, t_coeff=T_COEFF)
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
-    d_big.free()
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
-def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, A, B, C, nt):
-    c = QCase(gpu, oracle, A, B, C, nt)
+def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     w = seeded_weights(B, A)
     v = c.floats(w)
     k1, k2 = gains_with_clipping(v), gains_without_clipping(v)
@@ -265,24 +261,23 @@ def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, A, B, C, nt):
         c.call_q8(weighted=True, stream=s.handle)
     for k, ref, n_ref in ((k1, ref1, n1), (k2, ref2, n2), (k1, ref1, n1)):
         gpu.memcpy_htod(c.d_k, k, stream=s.handle, sync=False)
-        gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY, stream=s.handle)
+        c.refill(c.d_q, stream=s.handle)
         gpu.memset(c.d_clip, 0, B * 8, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
     graph.close()
-    c.close()
 
 
-def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
+def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle, case):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
 
-    c = QCase(gpu, oracle, 64, 16, 2, 32)
+    c = case(64, 16, 2, 32)
     k = gains_with_clipping(c.floats())
     ref, n_ref = c.q8(k)
     c.g.set_tuning(math_mode=8)
     s = gpu.Stream()
-    gpu.memset(c.d_q, 0xA5, c.qbytes + CANARY)
+    c.refill(c.d_q)
     gpu.memset(c.d_clip, 0, c.B * 8)
     gpu.synchronize()
     for weighted in (False, True):
@@ -291,22 +286,19 @@ def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle):
                 c.call_q8(weighted=weighted, dt=dt, stream=s.handle)
             assert e.value.status == DCS_ERR_UNSUPPORTED
     s.synchronize()
-    host = np.empty(c.qbytes + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, c.d_q)
-    assert np.all(host == 0xA5) and np.all(c.counts() == 0)  # nothing was enqueued
+    assert np.all(c.read(c.d_q) == 0xA5) and np.all(c.counts() == 0)  # nothing was enqueued
     c.g.set_tuning()
     c.call_q8(stream=s.handle)  # the same stream, the default form again
     s.synchronize()
     assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
-def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
+def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.beam_quant import BeamQuantGains
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
 
-    full = QCase(gpu, oracle, A, B, C, nt)
+    full = case(A, B, C, nt)
     v = full.floats()
     k = gains_with_clipping(v)
     ref, n_ref = full.q8(k)
@@ -319,10 +311,10 @@ def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
         sh = beam_range(B, 3, rank)
         lp = local_parameters(full.bp, sh)
         local_ab = slice_table(table_ab, full.bp, sh).reshape(A, sh.n_beams)
-        part = QCase(gpu, oracle, A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
+        part = case(A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
         assert part.bp.NR_BEAMS == lp.NR_BEAMS
         part.set_ant(full.ant)
-        gpu.memset(part.d_q, 0xA5, part.qbytes + CANARY)
+        part.refill(part.d_q)
         part.g.beamform_accumulated_q8(part.d_ant, part.ant.nbytes, qg.device_ptr(sh.beam_lo), part.d_q, part.qbytes, nt,
                                        t_coeff=T_COEFF, d_clip_count=qg.clip_count_ptr(sh.beam_lo))
         gpu.synchronize()
@@ -331,4 +323,3 @@ def test_beam_slices_reproduce_the_full_call(gpu, oracle, A, B, C, nt):
     assert np.array_equal(qg.clip_counts(reset=True), n_ref)
     assert np.all(qg.clip_counts() == 0)
     qg.free()
-    full.close()

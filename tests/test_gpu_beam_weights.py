@@ -4,14 +4,22 @@ numerical contract -- unit weights bit-identical to the unweighted calls, 2^k we
 own beam only, random weights within the derived bounds -- and the calls' plumbing: the fp32-chain refusal, capture
 with weights changed between replays, beam shards.  Every weighted call writes into a buffer with a canary behind the
 output tensor, which must stay untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import ACC_SHAPES, CANARY, FUSED_SHAPES, T_COEFF, Case, random_weights
+from helpers.bacc_case import ACC_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import fused_model, normalise
+from helpers.device_buffers import closed_after
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(Case, gpu, oracle))
 
 
 def bits(x):
@@ -43,20 +51,19 @@ def fused_expected(case, w):
 
 
 @pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
-def test_unit_and_power_of_two_weights_on_the_matrix_cores(gpu, oracle, A, B, C, nt):
-    c = Case(gpu, oracle, A, B, C, nt)
+def test_unit_and_power_of_two_weights_on_the_matrix_cores(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     base = c.run("acc")
     ones = c.run("acc", np.ones((B, A), np.float32))
     assert np.array_equal(bits(ones), bits(base))
     for k in (0.25, 8.0):
         got = c.run("acc", np.full((B, A), k, np.float32))
         assert np.array_equal(bits(got), bits((base * np.float32(k)).astype(np.float32))), k
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", FUSED_SHAPES)
-def test_unit_and_power_of_two_weights_in_the_fused_kernel(gpu, oracle, A, B, C, nt):
-    c = Case(gpu, oracle, A, B, C, nt)
+def test_unit_and_power_of_two_weights_in_the_fused_kernel(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     base = c.run("fused")
     ones = c.run("fused", np.ones((B, A), np.float32))
     assert np.array_equal(bits(ones), bits(base))
@@ -67,14 +74,13 @@ def test_unit_and_power_of_two_weights_in_the_fused_kernel(gpu, oracle, A, B, C,
     kb = (2.0 ** (np.arange(B) % 5 - 2)).astype(np.float32)
     got = c.run("fused", np.repeat(kb[:, None], A, axis=1))
     assert np.array_equal(bits(got), bits((base * kb[None, None, :, None, None]).astype(np.float32)))
-    c.close()
 
 
 @pytest.mark.parametrize("kind", ["acc", "fused"])
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (37, 21, 4, 48), (130, 20, 2, 32), (256, 17, 2, 16), (4, 40, 3, 32)])
-def test_flagged_antennas_contribute_nothing(gpu, oracle, kind, A, B, C, nt):
+def test_flagged_antennas_contribute_nothing(gpu, oracle, case, kind, A, B, C, nt):
     rng = np.random.default_rng(A * B)
-    c = Case(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = (rng.random((B, A)) < 0.7).astype(np.float32)
     w[0, :] = 0.0   # an all-zero beam
     w[-1, :] = 1.0  # a beam with every antenna
@@ -108,13 +114,12 @@ def test_flagged_antennas_contribute_nothing(gpu, oracle, kind, A, B, C, nt):
     assert np.array_equal(bits(got), bits(finite))
     # ... while unflagged, such an antenna turns every beam to NaN (what the weights are there to prevent)
     assert np.all(np.isnan(c.run(kind, np.ones((B, A), np.float32))))
-    c.close()
 
 
 @pytest.mark.parametrize("kind", ["acc", "fused"])
-def test_a_non_finite_weight_poisons_its_beam_only(gpu, oracle, kind):
+def test_a_non_finite_weight_poisons_its_beam_only(gpu, oracle, case, kind):
     A, B, C, nt = 70, 20, 3, 32
-    c = Case(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     w = random_weights(np.random.default_rng(5), B, A, zero_beam=False)
     ref = c.run(kind, w)
     assert np.all(np.isfinite(ref))
@@ -125,71 +130,67 @@ def test_a_non_finite_weight_poisons_its_beam_only(gpu, oracle, kind):
         assert np.all(np.isnan(got[:, :, b])), (b, v)
         others = [i for i in range(B) if i != b]
         assert np.array_equal(bits(got[:, :, others]), bits(ref[:, :, others]))
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 4, 64), (37, 21, 3, 48), (129, 33, 2, 32), (256, 64, 2, 32), (1, 1, 1, 16),
                                       (64, 128, 2, 48), (192, 48, 2, 32)])
-def test_random_weights_on_the_matrix_cores_within_the_bound(gpu, oracle, A, B, C, nt):
-    c = Case(gpu, oracle, A, B, C, nt)
+def test_random_weights_on_the_matrix_cores_within_the_bound(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=B > 1)
     got = c.run("acc", w)
     assert np.all(np.isfinite(got))
     acc_bound_check(c, w, got)
-    c.close()
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 32), (37, 21, 2, 48), (130, 3, 2, 16), (258, 2, 2, 16), (1, 1, 1, 16)])
-def test_random_weights_in_the_fused_kernel_within_the_bound(gpu, oracle, A, B, C, nt):
-    c = Case(gpu, oracle, A, B, C, nt)
+def test_random_weights_in_the_fused_kernel_within_the_bound(gpu, oracle, case, A, B, C, nt):
+    c = case(A, B, C, nt)
     w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=B > 1)
     got = c.run("fused", w)
     exp = fused_expected(c, w)
     s, _ = normalise(w)
     assert np.all(np.isfinite(got))
     assert np.all(np.abs(got - exp) <= 2e-5 * A * s[None, None, :, None, None] + 1e-6)
-    c.close()
 
 
-def test_random_weights_seeded_fuzz(gpu, oracle):
+def test_random_weights_seeded_fuzz(gpu, oracle, case):
     """40 seeded cases over antennas <= 256, beams, channels and sample blocks, both beamformers, each within its bound."""
     rng = np.random.default_rng(20261016)
-    for case in range(40):
-        A = int(rng.choice([1, 3, 17, 63, 64, 65, 128, 129, 192, 200, 256])) if case % 2 else int(rng.integers(1, 257))
+    for i in range(40):
+        A = int(rng.choice([1, 3, 17, 63, 64, 65, 128, 129, 192, 200, 256])) if i % 2 else int(rng.integers(1, 257))
         B = int(rng.integers(1, 80))
         C = int(rng.integers(1, 4))
         nt = 16 * int(rng.integers(1, 6))
-        c = Case(gpu, oracle, A, B, C, nt, seed=case)
+        c = case(A, B, C, nt, seed=i)
         w = random_weights(rng, B, A, zero_beam=B > 1)
         got = c.run("acc", w)
         acc_bound_check(c, w, got)
-        if case % 4 == 0:
+        if i % 4 == 0:
             got = c.run("fused", w)
             s, _ = normalise(w)
             assert np.all(np.abs(got - fused_expected(c, w)) <= 2e-5 * A * s[None, None, :, None, None] + 1e-6), (A, B, C, nt)
         c.close()
 
 
-def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle):
+def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle, case):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
 
-    c = Case(gpu, oracle, 64, 16, 2, 32)
+    c = case(64, 16, 2, 32)
     c.g.set_tuning(math_mode=8)
     gpu.memcpy_htod(c.d_w, np.ones((16, 64), np.float32))
-    gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY)
+    c.refill(c.d_beams)
     for kw in ({"t_coeff": T_COEFF}, {"dt_coeff": 0.0}):
         with pytest.raises(DcsError) as e:
             c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, c.nt, **kw)
         assert e.value.status == DCS_ERR_UNSUPPORTED
     gpu.synchronize()
-    assert np.all(c.read().view(np.uint32) == 0xFFFFFFFF)
-    c.close()
+    assert np.all(c.read_beams().view(np.uint32) == 0xFFFFFFFF)
 
 
 @pytest.mark.parametrize("kind", ["acc", "fused"])
-def test_captured_call_picks_up_new_weights_on_replay(gpu, oracle, kind):
+def test_captured_call_picks_up_new_weights_on_replay(gpu, oracle, case, kind):
     A, B, C, nt = 130, 20, 3, 64
-    c = Case(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     rng = np.random.default_rng(3)
     w1 = random_weights(rng, B, A)
     w2 = random_weights(rng, B, A)
@@ -203,21 +204,20 @@ def test_captured_call_picks_up_new_weights_on_replay(gpu, oracle, kind):
             c.g.generate_and_beamform_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, t0=0, nt=nt, stream=s.handle)
     for w, ref in ((w1, ref1), (w2, ref2)):
         gpu.memcpy_htod(c.d_w, w, stream=s.handle, sync=False)
-        gpu.memset(c.d_beams, 0xFF, c.nbytes + CANARY, stream=s.handle)
+        c.refill(c.d_beams, stream=s.handle)
         graph.launch(s)
         s.synchronize()
-        assert np.array_equal(bits(c.read()), bits(ref))
+        assert np.array_equal(bits(c.read_beams()), bits(ref))
     graph.close()
-    c.close()
 
 
 @pytest.mark.parametrize("kind", ["acc", "fused"])
-def test_beam_shards_reproduce_the_full_call(gpu, oracle, kind):
+def test_beam_shards_reproduce_the_full_call(gpu, oracle, case, kind):
     from dc_sand_amd.beam_weights import BeamWeights
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
 
     A, B, C, nt = 65, 37, 3, 48
-    full = Case(gpu, oracle, A, B, C, nt)
+    full = case(A, B, C, nt)
     bw = BeamWeights(full.bp)
     rng = np.random.default_rng(9)
     for b in range(B):
@@ -230,32 +230,31 @@ def test_beam_shards_reproduce_the_full_call(gpu, oracle, kind):
         sh = beam_range(B, 2, rank)
         lp = local_parameters(full.bp, sh)
         local_ab = slice_table(table_ab, full.bp, sh).reshape(A, sh.n_beams)
-        part = Case(gpu, oracle, A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
+        part = case(A, sh.n_beams, C, nt, table=np.ascontiguousarray(local_ab.T).ravel())
         assert part.bp.NR_BEAMS == lp.NR_BEAMS
         part.set_ant(full.ant)
-        gpu.memset(part.d_beams, 0xFF, part.nbytes + CANARY)
+        part.refill(part.d_beams)
         if kind == "acc":
             part.g.beamform_accumulated_weighted(part.d_ant, part.ant.nbytes, bw.device_ptr(sh.beam_lo), part.d_beams, part.nbytes,
                                                  nt, t_coeff=T_COEFF)
         else:
             part.g.generate_and_beamform_weighted(part.d_ant, part.ant.nbytes, bw.device_ptr(sh.beam_lo), part.d_beams,
                                                   part.nbytes, t0=0, nt=nt)
-        got = part.read()
+        got = part.read_beams()
         assert np.array_equal(bits(got), bits(ref[:, :, sh.beam_lo:sh.beam_hi]))
         part.close()
     bw.free()
-    full.close()
 
 
-def test_weights_change_between_calls_on_one_stream(gpu, oracle):
+def test_weights_change_between_calls_on_one_stream(gpu, oracle, case):
     """d_weights is read when the work runs: a copy queued between two calls on the stream applies to the second."""
     A, B, C, nt = 64, 32, 2, 32
-    c = Case(gpu, oracle, A, B, C, nt)
+    c = case(A, B, C, nt)
     rng = np.random.default_rng(1)
     w1, w2 = random_weights(rng, B, A), random_weights(rng, B, A)
     ref2 = c.run("acc", w2)
     s = gpu.Stream()
-    d_out2 = gpu.mem_alloc(c.nbytes)
+    d_out2 = c.alloc(c.nbytes)
     gpu.memcpy_htod(c.d_w, w1, stream=s.handle, sync=False)
     c.g.beamform_accumulated_weighted(c.d_ant, c.ant.nbytes, c.d_w, c.d_beams, c.nbytes, nt, t_coeff=T_COEFF, stream=s.handle)
     gpu.memcpy_htod(c.d_w, w2, stream=s.handle, sync=False)
@@ -264,6 +263,4 @@ def test_weights_change_between_calls_on_one_stream(gpu, oracle):
     got2 = np.empty(c.shape, np.float32)
     gpu.memcpy_dtoh(got2, d_out2)
     assert np.array_equal(bits(got2), bits(ref2))
-    acc_bound_check(c, w1, c.read())
-    d_out2.free()
-    c.close()
+    acc_bound_check(c, w1, c.read_beams())

@@ -86,7 +86,7 @@ class Exact(Case):
         """One beamformer call into the 0xFF-filled buffer; `kw` picks the time: acc t_coeff= / dt_coeff=, fused t0= / dt=.
         ``finite=False`` only where the delay table holds a value that is not finite."""
         gpu, g = self.gpu, self.g
-        gpu.memset(self.d_beams, 0xFF, self.nbytes + 64)
+        self.refill(self.d_beams)
         if w is not None:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
         if kind == "acc" and w is None:
@@ -99,7 +99,7 @@ class Exact(Case):
             g.generate_and_beamform_dt(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, kw["dt"])
         else:
             g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, t0=kw["t0"], nt=self.nt)
-        got = self.read()  # asserts the canary
+        got = self.read_beams()  # asserts the canary
         assert not finite or np.all(np.isfinite(got)), (kind, kw)
         return got
 

@@ -319,7 +319,7 @@ def test_complex_product_in_the_slow_class_bit_for_bit(gpu, oracle, record_prope
         assert np.all(np.isfinite(v))
         v = check_model(x, coef, conj, w=w, what="slow class, weighted")
         assert np.all(np.isfinite(v))
-    x.close()
+    x.c.close()
 
 
 # ---- f. delay values that are not finite

@@ -2,10 +2,7 @@
 are compared with the numpy model (helpers/candidates_model.py, anchored on the CPU by tests/test_candidates_model.py) as
 words -- integers and float bits -- and so are both count words.  Every buffer is exactly sized; the records and the counts
 are prefilled with a non-zero pattern and have a 0xA5 canary behind them: a record beyond d_count[1] must stay as it was."""
-import subprocess
-import sys
 from functools import lru_cache
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,52 +10,25 @@ import pytest
 from helpers import hip_graph
 from helpers.candidates_model import CANDIDATE, collapse, expected_buffer, find_candidates, same_bits, seeded_planes
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
+from helpers.device_buffers import Context
+from helpers.examples import run_example
 from helpers.single_pulse_model import CHAIN, chain_filterbank, nr_blocks_of, peaks as model_peaks, snr as model_snr, sums as model_sums
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-CANARY = 64
 PREFILL = 0x3C
 PREFILL_WORD = 0x3C3C3C3C
 
 
-class CCase:
+class CCase(Context):
     """One context (the sifter uses none of its parameters; nr_beams is an argument) and the device buffers of its calls,
     exactly sized, outputs with a canary behind; all freed by close()."""
 
     def __init__(self, gpu):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu = gpu
-        self.bp = BeamformerParameters(NR_CHANNELS=64, NR_STATIONS=1, NR_BEAMS=1)
-        self.g = SteeringCoefficientGenerator(self.bp)
-        self.held = []
-
-    def alloc(self, nbytes):
-        a = self.gpu.mem_alloc(max(nbytes, 1))
-        self.held.append(a)
-        return a
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            self.gpu.memcpy_htod(d, a)
-        return d
+        super().__init__(gpu, 64)
 
     def out(self, nbytes):
-        d = self.alloc(nbytes + CANARY)
-        self.gpu.memset(d, PREFILL, nbytes)
-        self.gpu.memset(int(d) + nbytes, 0xA5, CANARY)
-        return d
-
-    def read(self, d, nbytes, dtype):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == 0xA5), "written past the buffer"
-        return host[:nbytes].view(dtype).copy()
+        return super().out(nbytes, PREFILL)
 
     def find(self, snr, peaks, first_block, nr_blocks, threshold, radii, max_candidates=None, d_planes=None):
         """One dcs_bf_find_candidates call into prefilled records and counts, held to the model: the records of
@@ -89,11 +59,6 @@ class CCase:
             assert bad.size == 0, (len(bad), bad[0], got[bad[0]], exp[bad[0]])
             assert same_bits(got, exp)
         return rec, count
-
-    def close(self):
-        self.g.close()
-        for a in self.held:
-            a.free()
 
 
 @pytest.fixture
@@ -304,13 +269,13 @@ def test_short_buffers_are_refused_and_nothing_is_enqueued(case, gpu):
 
 # ------------------------------------------------------------------------------------------------------------------ capture
 
-def test_captured_on_first_use_and_replayed_with_new_contents(gpu):
+def test_captured_on_first_use_and_replayed_with_new_contents(case, gpu):
     """The first call of a fresh context, captured; replayed after the planes were changed on the device: the list and
     both counts follow the new contents, a different number of candidates each time, one of them more than fit."""
     from dc_sand_amd.generator import candidates_bytes, candidates_workspace_bytes
 
     B, nr_dm, nw, pb, first_block, nr_blocks, cap = 2, 37, 3, 140, 3, 131, 1000
-    c = CCase(gpu)
+    c = case
     snr0, peaks0 = seeded_planes(B, nr_dm, nw, pb, seed=60)
     sbytes, kbytes, cbytes, wbytes = snr0.nbytes, peaks0.nbytes, candidates_bytes(cap), candidates_workspace_bytes(B, nr_dm, nr_blocks)
     d_snr, d_peaks = c.alloc(sbytes), c.alloc(kbytes)
@@ -345,7 +310,6 @@ def test_captured_on_first_use_and_replayed_with_new_contents(gpu):
         seen.append(exp_count.tolist())
     assert len({tuple(x) for x in seen}) == 3 and seen[2][0] > cap == seen[2][1] and 0 < seen[0][0] < cap
     graph.close()
-    c.close()
 
 
 # -------------------------------------------------------------------------------------------------------------------- chain
@@ -396,7 +360,5 @@ def test_the_chain_ends_in_one_record_for_the_injected_pulse(case, gpu):
 # ------------------------------------------------------------------------------------------------------------------ example
 
 def test_example_runs_and_verifies_itself(gpu):
-    res = subprocess.run([sys.executable, str(ROOT / "examples" / "candidate_list.py"), "64", "2", "32", "2048"], capture_output=True,
-                         text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
-    assert "bit-identical to the model: True" in res.stdout and "two candidates at the injected pulses: True" in res.stdout
+    out = run_example("candidate_list.py", 64, 2, 32, 2048)
+    assert "bit-identical to the model: True" in out and "two candidates at the injected pulses: True" in out

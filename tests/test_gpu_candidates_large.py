@@ -9,46 +9,38 @@ import pytest
 
 from helpers import candidates_large as cl
 from helpers.candidates_model import CANDIDATE, expected_buffer, same_bits
+from helpers.device_buffers import Context
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 PREFILL = 0x3C
 
 
 def test_planes_past_the_line(gpu):
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import (SteeringCoefficientGenerator, boxcar_peaks_bytes, candidates_bytes, candidates_workspace_bytes,
-                                       peak_snr_bytes)
+    from dc_sand_amd.generator import boxcar_peaks_bytes, candidates_bytes, candidates_workspace_bytes, peak_snr_bytes
 
     sbytes = peak_snr_bytes(cl.B, cl.NR_DM, cl.NR_WIDTHS, cl.PEAK_BLOCKS)
     kbytes = boxcar_peaks_bytes(cl.B, cl.NR_DM, cl.NR_WIDTHS, cl.PEAK_BLOCKS)
     cbytes, wbytes = candidates_bytes(cl.MAX_CANDIDATES), candidates_workspace_bytes(cl.B, cl.NR_DM, cl.NR_BLOCKS)
     assert (sbytes, kbytes) == (cl.SNR_BYTES, cl.PEAKS_BYTES)
-    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=64, NR_STATIONS=1, NR_BEAMS=1))
-    held = [gpu.mem_alloc(n) for n in (sbytes, kbytes, cbytes + CANARY, 8 + CANARY, wbytes + CANARY)]
-    d_snr, d_peaks, d_cands, d_count, d_work = held
+    c = Context(gpu, 64)
     try:
+        d_snr, d_peaks = c.alloc(sbytes), c.alloc(kbytes)
+        d_cands, d_count, d_work = (c.out(n, PREFILL) for n in (cbytes, 8, wbytes))
         gpu.memset(d_snr, cl.FILL, sbytes)
         gpu.memset(d_peaks, cl.FILL, kbytes)
-        for d, n in ((d_cands, cbytes), (d_count, 8), (d_work, wbytes)):
-            gpu.memset(d, PREFILL, n)
-            gpu.memset(int(d) + n, 0xA5, CANARY)
         snr, peaks = cl.window_planes()
         for m in range(cl.NR_DM):
             for i in range(cl.NR_WIDTHS):
                 gpu.memcpy_htod(int(d_snr) + cl.row_entry(m, i) * 4, np.ascontiguousarray(snr[0, m, i]))
                 gpu.memcpy_htod(int(d_peaks) + cl.row_entry(m, i) * 8, np.ascontiguousarray(peaks[0, m, i]))
         gpu.memcpy_htod(int(d_snr) + cl.decoy_entry() * 4, np.full(cl.NR_BLOCKS, cl.SNR_DECOY, np.float32))
-        g.find_candidates(d_snr, sbytes, d_peaks, kbytes, cl.PEAK_BLOCKS, cl.FIRST_BLOCK, cl.NR_BLOCKS, cl.B, cl.NR_DM, cl.NR_WIDTHS,
-                          cl.THRESHOLD, *cl.RADII, d_cands, cbytes, cl.MAX_CANDIDATES, d_count, d_work, wbytes)
+        c.g.find_candidates(d_snr, sbytes, d_peaks, kbytes, cl.PEAK_BLOCKS, cl.FIRST_BLOCK, cl.NR_BLOCKS, cl.B, cl.NR_DM, cl.NR_WIDTHS,
+                            cl.THRESHOLD, *cl.RADII, d_cands, cbytes, cl.MAX_CANDIDATES, d_count, d_work, wbytes)
         gpu.synchronize()
         rec, count = cl.expected()
-        got_count, got = np.empty(8 + CANARY, np.uint8), np.empty(cbytes + CANARY, np.uint8)
-        gpu.memcpy_dtoh(got_count, d_count)
-        gpu.memcpy_dtoh(got, d_cands)
-        assert np.all(got_count[8:] == 0xA5) and np.all(got[cbytes:] == 0xA5), "written past the buffer"
-        assert got_count[:8].view(np.uint32).tolist() == count.tolist()
+        got = c.read(d_cands, cbytes)
+        assert c.read(d_count, 8, np.uint32).tolist() == count.tolist()
         prefill = np.zeros(cl.MAX_CANDIDATES, CANDIDATE)
         prefill.view(np.uint8)[:] = PREFILL
         exp = expected_buffer(rec, count, prefill)
@@ -62,7 +54,4 @@ def test_planes_past_the_line(gpu):
             gpu.memcpy_dtoh(back, int(d_snr) + entry * 4)
             assert np.array_equal(back.view(np.uint32), want.view(np.uint32))
     finally:
-        gpu.synchronize()
-        g.close()
-        for a in held:
-            a.free()
+        c.close()

@@ -18,14 +18,17 @@ Per (shape, class) the sample sets, the oracle's expectations and the fresh cont
 the scenarios (they come in that order; one group is kept at a time).  The per-sample fused call of the matrix-core
 scenarios works on the first 32 samples; at the deep shapes the oracle holds the first 8 channels of its output (its
 class word is per time step and shared by every channel), (b) the whole tensor."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from conftest import rand_table
 from helpers import hip_graph
-from helpers.bacc_case import CANARY, DEEP_SHAPES, T_COEFF, Case
+from helpers.bacc_case import DEEP_SHAPES, T_COEFF, Case
 from helpers.beam_power_model import block_power, same_bits
 from helpers.beam_quant_model import quantise
+from helpers.device_buffers import closed_after
 
 pytestmark = pytest.mark.gpu
 
@@ -72,18 +75,18 @@ class RCase(Case):
     def __init__(self, gpu, oracle, A, B, C, nt, table, fnt=None):
         super().__init__(gpu, oracle, A, B, C, nt, table=table)
         self.qbytes = C * nt * B * 2
-        self.d_q = gpu.mem_alloc(self.qbytes + CANARY)
-        self.d_k = gpu.mem_alloc(B * 4)
-        self.d_clip = gpu.mem_alloc(B * 8)
+        self.d_q = self.out(self.qbytes)
+        self.d_k = self.alloc(B * 4)
+        self.d_clip = self.alloc(B * 8)
         self.pshape = (C, nt // 16, B)
         self.pbytes = C * (nt // 16) * B * 4
-        self.d_p = gpu.mem_alloc(self.pbytes + CANARY)
+        self.d_p = self.out(self.pbytes)
         self.fnt = min(nt, 32) if fnt is None else fnt
         self.fshape = (C, self.fnt // 16, B, 16, 2)
         self.fbytes = int(np.prod(self.fshape)) * 4
         self.fant_bytes = C * self.fnt * A * 2
-        self.d_fant = gpu.mem_alloc(self.fant_bytes)
-        self.d_fbeams = gpu.mem_alloc(self.fbytes + CANARY)
+        self.d_fant = self.alloc(self.fant_bytes)
+        self.d_fbeams = self.out(self.fbytes, 0xFF, 0xFF)
         self.s = gpu.Stream()
 
     def load(self, ant, w=None):
@@ -120,31 +123,25 @@ class RCase(Case):
     def clean(self, kind):
         gpu, s = self.gpu, self.s.handle
         if kind == "float":
-            gpu.memset(self.d_beams, 0xFF, self.nbytes + CANARY, stream=s)
+            self.refill(self.d_beams, stream=s)
         elif kind == "q8":
-            gpu.memset(self.d_q, 0xA5, self.qbytes + CANARY, stream=s)
+            self.refill(self.d_q, stream=s)
             gpu.memset(self.d_clip, 0, self.B * 8, stream=s)
         elif kind == "power":
-            gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY, stream=s)
+            self.refill(self.d_p, stream=s)
         else:
-            gpu.memset(self.d_fbeams, 0xFF, self.fbytes + CANARY, stream=s)
-
-    def _bytes(self, d, n, canary, what):
-        host = np.empty(n + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[n:] == canary), f"written past the {what}"
-        return host[:n]
+            self.refill(self.d_fbeams, stream=s)
 
     def fetch(self, kind):
         if kind == "float":
-            return self.read()
+            return self.read_beams()
         if kind == "q8":
             n = np.empty(self.B, dtype=np.uint64)
             self.gpu.memcpy_dtoh(n, self.d_clip)
-            return self._bytes(self.d_q, self.qbytes, 0xA5, "int8 tensor").view(np.int8).reshape(self.shape).copy(), n
+            return self.read(self.d_q, self.qbytes, np.int8, self.shape), n
         if kind == "power":
-            return self._bytes(self.d_p, self.pbytes, 0xA5, "block powers").view(np.float32).reshape(self.pshape).copy()
-        return self._bytes(self.d_fbeams, self.fbytes, 0xFF, "fused call's beams").view(np.float32).reshape(self.fshape).copy()
+            return self.read(self.d_p, self.pbytes, np.float32, self.pshape)
+        return self.read(self.d_fbeams, self.fbytes, np.float32, self.fshape)
 
     def plain(self, kind, weighted=False, g=None):
         self.clean(kind)
@@ -173,6 +170,11 @@ class RCase(Case):
         graph.launch(self.s)
         self.s.synchronize()
         return self.fetch(kind)
+
+
+@pytest.fixture
+def case(gpu, oracle):
+    yield from closed_after(partial(RCase, gpu, oracle))
 
 
 class Refs:
@@ -413,18 +415,17 @@ SCENARIOS = {
 @pytest.mark.parametrize("scenario", list(SCENARIOS))
 @pytest.mark.parametrize("cls", CLASSES)
 @pytest.mark.parametrize("A,B,C,nt,depth", MC_SHAPES)
-def test_matrix_core_calls_replayed_among_other_calls_of_their_context(gpu, oracle, A, B, C, nt, depth, cls, scenario):
+def test_matrix_core_calls_replayed_among_other_calls_of_their_context(gpu, oracle, case, A, B, C, nt, depth, cls, scenario):
     r = refs_of(oracle, A, B, C, nt, cls)
-    c = RCase(gpu, oracle, A, B, C, nt, r.table)
+    c = case(A, B, C, nt, r.table)
     SCENARIOS[scenario](c, r)
     if depth:  # (last: it captures, which the context remembers)
         c.prove_depth(depth, lambda s: c.enqueue("float", stream=s))
-    c.close()
 
 
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("cls", CLASSES + ("all",))
-def test_fused_call_of_two_chunks_replayed(gpu, oracle, cls, weighted):
+def test_fused_call_of_two_chunks_replayed(gpu, oracle, case, cls, weighted):
     """One graph is enough here: with more than 32768 pairs the terms table holds fewer than 256 time steps, so a call of
     256 is two chunks, each with its terms launch and its beamformer launch on the SAME class words.  The captured graph
     itself must show the 240 + 16 split (the terms launches have one row of workgroups per time step, one more with
@@ -432,7 +433,7 @@ def test_fused_call_of_two_chunks_replayed(gpu, oracle, cls, weighted):
     A, B, C, nt = TWO_CHUNKS
     wl = "taper" if weighted else None
     r = refs_of(oracle, A, B, C, nt, cls, fnt=nt)
-    c = RCase(gpu, oracle, A, B, C, nt, r.table, fnt=nt)
+    c = case(A, B, C, nt, r.table, fnt=nt)
     c.load(r.ant(0), r.weights(wl) if weighted else None)
     c.plain("fused", weighted)
     others = []
@@ -448,15 +449,14 @@ def test_fused_call_of_two_chunks_replayed(gpu, oracle, cls, weighted):
     for i in range(3):
         step(c, r, i, "fused", lambda: c.replay(graph, "fused"), wl=wl, what=f"replay {i + 1} of the two-chunk call")
     graph.close()
-    c.close()
 
 
 @pytest.mark.parametrize("A,B", [(64, 16), (130, 20)])
-def test_a_captured_call_is_its_two_kernels_and_the_clearing_of_its_words(gpu, oracle, A, B):
+def test_a_captured_call_is_its_two_kernels_and_the_clearing_of_its_words(gpu, oracle, case, A, B):
     """What capturing costs: the first captured call of a context is the two kernel launches of the plain call and one
     workgroup in front that clears the class words of its time steps, and so is every later one; no other node."""
     table, _, _ = class_table(A, B, "slow")
-    c = RCase(gpu, oracle, A, B, 2, 32, table)
+    c = case(A, B, 2, 32, table)
     c.load(c.ant, np.ones((B, A), np.float32))
     plain = {}
     for kind, weighted in (("float", False), ("float", True), ("q8", False), ("power", True), ("fused", False), ("fused", True)):
@@ -470,4 +470,3 @@ def test_a_captured_call_is_its_two_kernels_and_the_clearing_of_its_words(gpu, o
         got = c.plain(kind, weighted)  # after: the same bits
         for g, r in zip(got if kind == "q8" else (got,), ref if kind == "q8" else (ref,)):
             assert np.array_equal(g.view(np.uint8), r.view(np.uint8)), (kind, weighted)
-    c.close()

@@ -2,20 +2,18 @@
 compared as integers and the integrated ones as float bits with the numpy model (helpers/correlator_model.py, anchored on the
 CPU by tests/test_correlator_model.py).  The antenna tensor is exactly sized, so its last row ends where the allocation ends,
 and every output is exactly sized with a canary behind it, which must stay untouched."""
-import subprocess
-import sys
-from pathlib import Path
+from functools import partial
 
 import numpy as np
 import pytest
 
 from helpers import hip_graph
 from helpers.correlator_model import MAX_BLOCKS, baseline, integrate, nr_baselines, same_bits, visibilities
+from helpers.device_buffers import Context, closed_after
+from helpers.examples import run_example
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-CANARY = 64
 PREFILL = 0xA5
 
 
@@ -26,20 +24,15 @@ def seeded_samples(A, C, nblk, seed=0):
     return ant
 
 
-class CCase:
+class CCase(Context):
     """One context of A stations and C channels (no delay table: the correlator has no coefficients) and buffers for up to
     max_blocks sample blocks per channel."""
 
     def __init__(self, gpu, A, C, max_blocks):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu, self.A, self.C, self.NB = gpu, A, C, nr_baselines(A)
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16 * max_blocks)
-        self.g = SteeringCoefficientGenerator(self.bp)
+        super().__init__(gpu, C, A, NR_SAMPLES_PER_CHANNEL=16 * max_blocks)
+        self.NB = nr_baselines(A)
         self.max_vis_bytes = C * max_blocks * self.NB * 8
-        self.held = [gpu.mem_alloc(self.max_vis_bytes + CANARY), gpu.mem_alloc(self.max_vis_bytes + CANARY)]
-        self.d_vis, self.d_out = self.held
+        self.d_vis, self.d_out = self.out(self.max_vis_bytes), self.out(self.max_vis_bytes)
 
     def correlate(self, ant, n, stream=None):
         """The visibilities of ``ant`` from a device tensor of exactly its size and a prefilled output."""
@@ -50,25 +43,15 @@ class CCase:
         nt, nr_vis = 16 * nblk, nblk // n
         vbytes = block_visibilities_bytes(self.bp, nt, n)
         assert vbytes == C * nr_vis * self.NB * 8 <= self.max_vis_bytes
-        d_ant = self.gpu.mem_alloc(ant.nbytes)
-        self.gpu.memcpy_htod(d_ant, np.ascontiguousarray(ant))
-        self.gpu.memset(self.d_vis, PREFILL, self.max_vis_bytes + CANARY)
-        self.g.correlate_block(d_ant, ant.nbytes, self.d_vis, vbytes, nt, n, stream=stream)
+        self.refill(self.d_vis)
+        self.g.correlate_block(self.upload(ant), ant.nbytes, self.d_vis, vbytes, nt, n, stream=stream)
         self.gpu.synchronize()
-        got = self.read(self.d_vis, vbytes, np.int32, (C, nr_vis, self.NB, 2))
-        d_ant.free()
-        return got
+        return self.read(self.d_vis, vbytes, np.int32, (C, nr_vis, self.NB, 2))
 
-    def read(self, d, nbytes, dtype, shape):
-        host = np.empty(self.max_vis_bytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == PREFILL), "written past the tensor"
-        return host[:nbytes].view(dtype).reshape(shape).copy()
 
-    def close(self):
-        self.g.close()
-        for a in self.held:
-            a.free()
+@pytest.fixture
+def case(gpu):
+    yield from closed_after(partial(CCase, gpu))
 
 
 # one antenna; a few; one tile; a tile and one row; one unit of four tiles; ragged tiles in a second unit; every unit of the
@@ -78,9 +61,9 @@ BLOCKS = (1, 2, 3, 5, 8)
 
 
 @pytest.mark.parametrize("A", STATIONS)
-def test_visibilities_are_the_model(gpu, A):
+def test_visibilities_are_the_model(gpu, case, A):
     C = 3
-    c = CCase(gpu, A, C, max(BLOCKS) * 3)
+    c = case(A, C, max(BLOCKS) * 3)
     for n in BLOCKS:
         for nr_vis in (1, 3):
             ant = seeded_samples(A, C, n * nr_vis)
@@ -90,16 +73,15 @@ def test_visibilities_are_the_model(gpu, A):
             assert np.unique(exp).size >= min(100, exp.size // 3), (A, n, nr_vis)  # no trivial expectation
             for a in range(A):
                 assert not got[:, :, baseline(a, a), 1].any()
-    c.close()
 
 
-def test_one_hot_every_byte_of_a_row_reaches_its_baselines_with_its_sign(gpu):
+def test_one_hot_every_byte_of_a_row_reaches_its_baselines_with_its_sign(gpu, case):
     """A = 33 (two whole tiles and one row), n = 4.  One byte v = 3 + position of antenna a0 is non-zero, in block
     (position + a0) % 4, so every lane group's share of K is visited.  Alone: only the autocorrelation of a0 is non-zero, v^2.
     Against x = 1 + i in every other antenna: the baselines of a0 are v (1 - i) (a real part, b < a0), v (1 + i) (an imaginary
     part, b < a0) and their conjugates for a > a0, and every other word is what ones against ones or zeros give."""
     A, C, n = 33, 1, 4
-    c = CCase(gpu, A, C, n)
+    c = case(A, C, n)
     pa, pb = np.tril_indices(A)
     for a0 in (0, 1, 15, 16, 31, 32):
         for pos in range(32):
@@ -125,65 +107,56 @@ def test_one_hot_every_byte_of_a_row_reaches_its_baselines_with_its_sign(gpu):
             exp[0, 0, baseline(a0, a0)] = [v * v, 0]
             assert np.array_equal(got, exp), (a0, pos, np.argwhere(got != exp)[:4])
             assert np.array_equal(visibilities(among, n), exp)
-    c.close()
 
 
-def test_full_scale_sits_524288_below_the_wrap(gpu):
+def test_full_scale_sits_524288_below_the_wrap(gpu, case):
     A, C, n = 16, 1, MAX_BLOCKS
-    c = CCase(gpu, A, C, n)
+    c = case(A, C, n)
     ant = np.full((C, n, A, 16, 2), -128, dtype=np.int8)
     got = c.correlate(ant, n)
     exp = visibilities(ant, n)
     assert np.array_equal(got, exp)
     assert np.all(got[..., 0] == 2_146_959_360) and not got[..., 1].any() and (1 << 31) - int(got.max()) == 524_288
-    c.close()
 
 
-def test_offset_tensors_inside_larger_allocations(gpu):
+def test_offset_tensors_inside_larger_allocations(gpu, case):
     """d_antenna 48 and d_vis 8 bytes into larger, prefilled allocations: the visibilities are those of the bytes from the
     offset on, and no word before or behind the visibility tensor changes."""
     A, C, n, nr_vis = 19, 2, 3, 2
-    c = CCase(gpu, A, C, n * nr_vis)
+    c = case(A, C, n * nr_vis)
     ant = seeded_samples(A, C, n * nr_vis, seed=5)
     vbytes = C * nr_vis * c.NB * 8
-    d_ant = gpu.mem_alloc(ant.nbytes + 96)
+    d_ant = c.alloc(ant.nbytes + 96)
     gpu.memset(d_ant, 0x7F, ant.nbytes + 96)
     gpu.memcpy_htod(int(d_ant) + 48, ant)
-    d_vis = gpu.mem_alloc(vbytes + 16 + CANARY)
-    gpu.memset(d_vis, PREFILL, vbytes + 16 + CANARY)
+    d_vis = c.out(vbytes + 16)
     c.g.correlate_block(int(d_ant) + 48, ant.nbytes, int(d_vis) + 8, vbytes, 16 * n * nr_vis, n)
     gpu.synchronize()
-    host = np.empty(vbytes + 16 + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_vis)
+    host = c.read(d_vis)
     assert np.all(host[:8] == PREFILL) and np.all(host[8 + vbytes:] == PREFILL)
     got = host[8:8 + vbytes].copy().view(np.int32).reshape(C, nr_vis, c.NB, 2)
     assert np.array_equal(got, visibilities(ant, n))
     back = np.empty(ant.nbytes + 96, dtype=np.uint8)
     gpu.memcpy_dtoh(back, d_ant)
     assert np.all(back[:48] == 0x7F) and np.all(back[48 + ant.nbytes:] == 0x7F) and np.array_equal(back[48:48 + ant.nbytes].view(np.int8), ant.reshape(-1))
-    d_ant.free(), d_vis.free()
-    c.close()
 
 
-def test_the_autocorrelations_sum_to_the_incoherent_beam(gpu):
+def test_the_autocorrelations_sum_to_the_incoherent_beam(gpu, case):
     """n = 1: sum_a re V[a][a] is the incoherent beam's block power with NULL weights, both computed on the GPU, exactly."""
     from dc_sand_amd.generator import incoherent_block_power_bytes
 
     A, C, nblk = 37, 3, 5
-    c = CCase(gpu, A, C, nblk)
+    c = case(A, C, nblk)
     ant = seeded_samples(A, C, nblk, seed=9)
     vis = c.correlate(ant, 1)
     pbytes = incoherent_block_power_bytes(c.bp, 16 * nblk)
-    d_ant, d_p = gpu.mem_alloc(ant.nbytes), gpu.mem_alloc(pbytes)
-    gpu.memcpy_htod(d_ant, ant)
+    d_ant, d_p = c.upload(ant), c.alloc(pbytes)
     c.g.incoherent_block_power(d_ant, ant.nbytes, d_p, pbytes, 16 * nblk)
     gpu.synchronize()
     power = np.empty((C, nblk), dtype=np.uint32)
     gpu.memcpy_dtoh(power, d_p)
     autos = vis[:, :, [baseline(a, a) for a in range(A)], 0].astype(np.int64).sum(axis=2)
     assert np.array_equal(autos, power.astype(np.int64)) and np.unique(power).size == power.size
-    d_ant.free(), d_p.free()
-    c.close()
 
 
 def planted_visibilities(C, nr_vis, NB, seed):
@@ -195,11 +168,11 @@ def planted_visibilities(C, nr_vis, NB, seed):
 
 
 @pytest.mark.parametrize("m", (1, 3))
-def test_integration_is_the_exact_sum_rounded_once(gpu, m):
+def test_integration_is_the_exact_sum_rounded_once(gpu, case, m):
     from dc_sand_amd.generator import visibilities_bytes
 
     A, C, nr_vis = 7, 3, 6
-    c = CCase(gpu, A, C, nr_vis)
+    c = case(A, C, nr_vis)
     vis = planted_visibilities(C, nr_vis, c.NB, seed=m)
     vbytes, obytes = vis.nbytes, visibilities_bytes(c.bp, nr_vis, m)
     assert obytes == (nr_vis // m) * C * c.NB * 8
@@ -210,9 +183,9 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, m):
     prior = np.random.default_rng(m).uniform(-3e9, 3e9, size=exp.shape).astype(np.float32)
     prior.reshape(-1)[1:5] = [np.nan, np.inf, -np.inf, -0.0]
     for accumulate, want in ((False, exp), (True, integrate(vis, m, prior=prior))):
-        gpu.memset(c.d_vis, PREFILL, c.max_vis_bytes + CANARY)
+        c.refill(c.d_vis)
         gpu.memcpy_htod(c.d_vis, vis)
-        gpu.memset(c.d_out, PREFILL, c.max_vis_bytes + CANARY)
+        c.refill(c.d_out)
         if accumulate:
             gpu.memcpy_htod(c.d_out, prior)
         c.g.integrate_visibilities(c.d_vis, vbytes, nr_vis, m, c.d_out, obytes, accumulate=accumulate)
@@ -220,21 +193,20 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, m):
         got = c.read(c.d_out, obytes, np.float32, exp.shape)
         assert same_bits(got, want) is None, (m, accumulate, same_bits(got, want))
         assert np.array_equal(c.read(c.d_vis, vbytes, np.int32, vis.shape), vis)
-    c.close()
 
 
-def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu):
+def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu, case):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
     A, C, n, nr_vis = 5, 2, 2, 2
-    c = CCase(gpu, A, C, n * nr_vis)
+    c = case(A, C, n * nr_vis)
     ant = seeded_samples(A, C, n * nr_vis)
     nt, vbytes = 16 * n * nr_vis, C * nr_vis * c.NB * 8
     obytes = vbytes // 2
-    d_ant = gpu.mem_alloc(ant.nbytes + 16)
+    d_ant = c.alloc(ant.nbytes + 16)
     gpu.memcpy_htod(d_ant, ant)
-    gpu.memset(c.d_vis, PREFILL, c.max_vis_bytes + CANARY)
-    gpu.memset(c.d_out, PREFILL, c.max_vis_bytes + CANARY)
+    c.refill(c.d_vis)
+    c.refill(c.d_out)
     gpu.synchronize()
     g = c.g
     bad_calls = [
@@ -260,26 +232,22 @@ def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu):
     g.correlate_block(d_ant, 0, c.d_vis, 0, 0, 5)
     g.integrate_visibilities(c.d_vis, 0, 0, 5, c.d_out, 0)
     gpu.synchronize()
-    host = np.empty(c.max_vis_bytes + CANARY, dtype=np.uint8)
     for d in (c.d_vis, c.d_out):
-        gpu.memcpy_dtoh(host, d)
-        assert np.all(host == PREFILL)
+        assert np.all(c.read(d) == PREFILL)
     assert np.array_equal(c.correlate(ant, n), visibilities(ant, n))  # the context and the device are as usable as before
-    d_ant.free()
-    c.close()
 
 
-def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu):
+def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu, case):
     """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates, so nothing has to be run outside
     the capture first -- replayed with new bytes in the same buffers."""
     from dc_sand_amd.generator import visibilities_bytes
 
     A, C, n, nr_vis, m = 21, 3, 3, 4, 2
-    c = CCase(gpu, A, C, n * nr_vis)
+    c = case(A, C, n * nr_vis)
     nt, vbytes = 16 * n * nr_vis, C * nr_vis * c.NB * 8
     obytes = visibilities_bytes(c.bp, nr_vis, m)
     sets = [seeded_samples(A, C, n * nr_vis, seed=100 + i) for i in range(3)]
-    d_ant = gpu.mem_alloc(sets[0].nbytes)
+    d_ant = c.alloc(sets[0].nbytes)
     s = gpu.Stream()
     with hip_graph.capture(s) as graph:
         c.g.correlate_block(d_ant, sets[0].nbytes, c.d_vis, vbytes, nt, n, stream=s.handle)
@@ -288,20 +256,15 @@ def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu):
     assert not np.array_equal(refs[0], refs[1]) and not np.array_equal(refs[1], refs[2])
     for i in (1, 2, 0):
         gpu.memcpy_htod(d_ant, sets[i], stream=s.handle, sync=False)
-        gpu.memset(c.d_vis, PREFILL, c.max_vis_bytes + CANARY, stream=s.handle)
-        gpu.memset(c.d_out, PREFILL, c.max_vis_bytes + CANARY, stream=s.handle)
+        c.refill(c.d_vis, stream=s.handle)
+        c.refill(c.d_out, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read(c.d_vis, vbytes, np.int32, refs[i].shape), refs[i]), i
         want = integrate(refs[i], m)
         assert same_bits(c.read(c.d_out, obytes, np.float32, want.shape), want) is None, i
     graph.close()
-    d_ant.free()
-    c.close()
 
 
 def test_the_example_verifies_itself(gpu):
-    res = subprocess.run([sys.executable, str(ROOT / "examples" / "correlator.py"), "12", "2", "4"], capture_output=True, text=True,
-                         timeout=120)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "OK" in res.stdout
+    assert "OK" in run_example("correlator.py", 12, 2, 4, timeout=120)

@@ -9,46 +9,38 @@ import pytest
 
 from helpers import correlator_large as cl
 from helpers import large_tensor as lt
+from helpers.device_buffers import Context
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
-
 
 def run_case(gpu, k, seed):
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator, block_visibilities_bytes
+    from dc_sand_amd.generator import block_visibilities_bytes
 
     A, C, nblk, n = k["A"], k["C"], k["nblk"], k["n"]
     _, rin, rout, rows = cl.geometry(k)
-    bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16 * nblk)
-    g = SteeringCoefficientGenerator(bp)
-    abytes, vbytes = rows * rin, block_visibilities_bytes(bp, 16 * nblk, n)
+    c = Context(gpu, C, A, NR_SAMPLES_PER_CHANNEL=16 * nblk)
+    abytes, vbytes = rows * rin, block_visibilities_bytes(c.bp, 16 * nblk, n)
     assert abytes == A * C * nblk * 32 and vbytes == rows * rout
     pat = cl.pattern(k, seed)
-    d_ant, d_vis = gpu.mem_alloc(abytes), gpu.mem_alloc(vbytes + CANARY)
     try:
+        d_ant, d_vis = c.alloc(abytes), c.out(vbytes, cl.PREFILL, cl.PREFILL)
         lt.fill(gpu, d_ant, abytes, pat)
-        gpu.memset(d_vis, cl.PREFILL, vbytes + CANARY)
-        g.correlate_block(d_ant, abytes, d_vis, vbytes, 16 * nblk, n)
+        c.g.correlate_block(d_ant, abytes, d_vis, vbytes, 16 * nblk, n)
         gpu.synchronize()
         sample = cl.plan(k, seed)
         got = lt.read_rows(gpu, d_vis, rout, sample).view(np.int32).reshape(sample.size, -1, 2)
         for i, r in enumerate(sample):
             exp = cl.expected_row(k, pat, int(r))
             assert np.array_equal(got[i], exp), (int(r), np.argwhere(got[i] != exp)[:3])
-        tail = np.empty(CANARY, np.uint8)
-        gpu.memcpy_dtoh(tail, int(d_vis) + vbytes)
-        assert np.all(tail == cl.PREFILL), "written past the visibilities"
+        c.guard_untouched(d_vis)
         # what the device holds is the pattern: the sample rows on both sides of the lines, read back
         blk = A * 32
         block_rows = np.array(sorted({0, 1, abytes // blk - 1, *(x // blk + d for x in lt.lines_of(blk, abytes // blk) for d in (-1, 0))}),
                               dtype=np.int64)
         assert np.array_equal(lt.read_rows(gpu, d_ant, blk, block_rows), lt.rows_of(pat, block_rows))
     finally:
-        gpu.synchronize()
-        g.close()
-        d_ant.free(), d_vis.free()
+        c.close()
     return abytes, vbytes
 
 

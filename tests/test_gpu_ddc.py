@@ -4,8 +4,6 @@ the reference within the CPU test's tolerance.  Strides are larger than needed: 
 than the rows (a read across a row shows), the output's padding and a canary behind it are prefilled and must stay
 untouched."""
 import json
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -13,12 +11,12 @@ import pytest
 
 from helpers import ddc_model as model
 from helpers import hip_graph
+from helpers.device_buffers import Context
+from helpers.examples import run_example
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-GOLDEN = ROOT / "tests" / "golden" / "ddc"
-CANARY = 64
+GOLDEN = Path(__file__).resolve().parent / "golden" / "ddc"
 PREFILL = 0xA5
 BANDS2 = [(0x0EF00000, 0x12345678, 0.75), (0xC0000001, 0xFEDCBA98, 1.0 / 3.0)]
 
@@ -27,16 +25,12 @@ def row_bytes(nr_out, T):
     return 16 * (nr_out - 1) + T
 
 
-class DCase:
+class DCase(Context):
     """A context (its sizes play no part: the down-converter takes every size as an argument) and the means to run one call
     from host arrays."""
 
     def __init__(self, gpu):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu = gpu
-        self.g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=1, NR_STATIONS=1, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16))
+        super().__init__(gpu, 1, NR_SAMPLES_PER_CHANNEL=16)
 
     def digits(self, taps):
         """The device operand table of integer taps [band][T][2] (any integers: they are passed as their low 32 bits)."""
@@ -44,11 +38,9 @@ class DCase:
 
         taps = np.ascontiguousarray(np.asarray(taps).astype(np.int64).astype(np.int32))
         nb, T, _ = taps.shape
-        d_taps, d_digits = self.gpu.mem_alloc(taps.nbytes), self.gpu.mem_alloc(ddc_digits_bytes(T))
-        self.gpu.memcpy_htod(d_taps, taps)
-        self.g.ddc_tap_digits(d_taps, T, nb, d_digits, ddc_digits_bytes(T))
+        d_digits = self.alloc(ddc_digits_bytes(T))
+        self.g.ddc_tap_digits(self.upload(taps), T, nb, d_digits, ddc_digits_bytes(T))
         self.gpu.synchronize()
-        d_taps.free()
         return d_digits
 
     def run(self, x, taps, bands, nr_out, first_output=0, in_pad=48, out_pad=5, d_digits=None):
@@ -66,31 +58,19 @@ class DCase:
         host[:, :rb] = x
         host[:, rb:] = np.roll(x, -1, axis=0)[:, 7:7 + in_pad] ^ np.int8(0x55)
         sbytes = (ni - 1) * in_stride + rb
-        d_x = self.gpu.mem_alloc(sbytes)
-        self.gpu.memcpy_htod(d_x, np.ascontiguousarray(host.reshape(-1)[:sbytes]))
+        d_x = self.upload(host.reshape(-1)[:sbytes])
         obytes = ddc_out_bytes(ni, out_stride, nb)
-        d_out = self.gpu.mem_alloc(obytes + CANARY)
-        self.gpu.memset(d_out, PREFILL, obytes + CANARY)
-        own = d_digits is None
-        if own:
+        d_out = self.out(obytes)
+        if d_digits is None:
             d_digits = self.digits(taps)
         self.g.ddc(d_x, sbytes, in_stride, ni, nr_out, d_digits, 16 * T, T, bands, d_out, obytes, out_stride, first_output=first_output)
         self.gpu.synchronize()
-        raw = np.empty(obytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(raw, d_out)
-        assert np.all(raw[obytes:] == PREFILL), "written past the tensor"
-        out = raw[:obytes].view(np.float32).reshape(nb, ni, out_stride, 2)
+        out = self.read(d_out, obytes, np.float32, (nb, ni, out_stride, 2))
         assert np.all(out[:, :, nr_out:].view(np.uint8) == PREFILL), "written into the padding of a row"
-        d_x.free(), d_out.free()
-        if own:
-            d_digits.free()
         return out[:, :, :nr_out].copy()
 
-    def close(self):
-        self.g.close()
 
-
-@pytest.fixture(scope="module")
+@pytest.fixture
 def case(gpu):
     c = DCase(gpu)
     yield c
@@ -253,9 +233,8 @@ def test_refusals_enqueue_nothing_and_empty_calls_succeed(case, gpu):
     x = seeded((ni, rb), seed=4)
     taps = seeded_taps(1, T, seed=4)
     d_digits = case.digits(taps)
-    d_x, d_out = gpu.mem_alloc(ni * rb + 16), gpu.mem_alloc(ni * nr_out * 8 + CANARY)
+    d_x, d_out = case.alloc(ni * rb + 16), case.out(ni * nr_out * 8)
     gpu.memcpy_htod(d_x, x)
-    gpu.memset(d_out, PREFILL, ni * nr_out * 8 + CANARY)
     gpu.synchronize()
     g, band = case.g, [(1, 2, 1.0)]
     ok = dict(d_samples=d_x, samples_bytes=ni * rb, in_stride=rb, nr_inputs=ni, nr_out=nr_out, d_digits=d_digits, digits_bytes=16 * T,
@@ -271,55 +250,43 @@ def test_refusals_enqueue_nothing_and_empty_calls_succeed(case, gpu):
     g.ddc(**{**ok, "nr_out": 0, "d_samples": 0, "samples_bytes": 0})  # nothing to do
     g.ddc(**{**ok, "nr_inputs": 0, "out_bytes": 0})
     gpu.synchronize()
-    raw = np.empty(ni * nr_out * 8 + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(raw, d_out)
-    assert np.all(raw == PREFILL)
+    assert np.all(case.read(d_out) == PREFILL)
     g.ddc(**ok)  # the context and the device are as usable as before
     gpu.synchronize()
-    gpu.memcpy_dtoh(raw, d_out)
-    got = raw[:ni * nr_out * 8].view(np.float32).reshape(1, ni, nr_out, 2)
-    assert model.same_bits(got, model.ddc(x, taps, band, nr_out)) is None and np.all(raw[ni * nr_out * 8:] == PREFILL)
-    d_x.free(), d_out.free(), d_digits.free()
+    got = case.read(d_out, dtype=np.float32, shape=(1, ni, nr_out, 2))
+    assert model.same_bits(got, model.ddc(x, taps, band, nr_out)) is None
 
 
-def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu):
+def test_captured_first_calls_pick_up_new_bytes_on_replay(case, gpu):
     """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates -- replayed with new sample bytes
     (and new taps) in the same buffers."""
     from dc_sand_amd.generator import ddc_digits_bytes, ddc_out_bytes
 
-    c = DCase(gpu)
+    c = case
     T, ni, nr_out, nb = 256, 3, 37, 2
     rb = row_bytes(nr_out, T)
     sets = [(seeded((ni, rb), seed=200 + i), seeded_taps(nb, T, seed=300 + i).astype(np.int32)) for i in range(3)]
-    d_x, d_taps, d_digits = gpu.mem_alloc(ni * rb), gpu.mem_alloc(nb * T * 8), gpu.mem_alloc(ddc_digits_bytes(T))
+    d_x, d_taps, d_digits = c.alloc(ni * rb), c.alloc(nb * T * 8), c.alloc(ddc_digits_bytes(T))
     obytes = ddc_out_bytes(ni, nr_out, nb)
-    d_out = gpu.mem_alloc(obytes + CANARY)
+    d_out = c.out(obytes)
     s = gpu.Stream()
     with hip_graph.capture(s) as graph:
         c.g.ddc_tap_digits(d_taps, T, nb, d_digits, ddc_digits_bytes(T), stream=s.handle)
         c.g.ddc(d_x, ni * rb, rb, ni, nr_out, d_digits, ddc_digits_bytes(T), T, BANDS2, d_out, obytes, nr_out, first_output=11, stream=s.handle)
-    raw = np.empty(obytes + CANARY, dtype=np.uint8)
     seen = []
     for i in (1, 2, 0):
         x, taps = sets[i]
         gpu.memcpy_htod(d_x, x, stream=s.handle, sync=False)
         gpu.memcpy_htod(d_taps, taps, stream=s.handle, sync=False)
-        gpu.memset(d_out, PREFILL, obytes + CANARY, stream=s.handle)
+        c.refill(d_out, stream=s.handle)
         graph.launch(s)
         s.synchronize()
-        gpu.memcpy_dtoh(raw, d_out)
-        got = raw[:obytes].view(np.float32).reshape(nb, ni, nr_out, 2)
+        got = c.read(d_out, obytes, np.float32, (nb, ni, nr_out, 2))
         assert model.same_bits(got, model.ddc(x, taps, BANDS2, nr_out, first_output=11)) is None, i
-        assert np.all(raw[obytes:] == PREFILL)
-        seen.append(got.copy())
+        seen.append(got)
     assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
     graph.close()
-    for d in (d_x, d_taps, d_digits, d_out):
-        d.free()
-    c.close()
 
 
 def test_the_example_verifies_itself(gpu):
-    res = subprocess.run([sys.executable, str(ROOT / "examples" / "narrowband_ddc.py")], capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "OK" in res.stdout
+    assert "OK" in run_example("narrowband_ddc.py", timeout=120)

@@ -9,25 +9,22 @@ import pytest
 from helpers import ddc_large as dl
 from helpers import ddc_model as model
 from helpers import large_tensor as lt
+from helpers.device_buffers import Context
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
-
 
 def test_samples_and_outputs_past_the_line(gpu):
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator, ddc_digits_bytes
+    from dc_sand_amd.generator import ddc_digits_bytes
 
-    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=1, NR_STATIONS=1, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16))
+    c = Context(gpu, 1, NR_SAMPLES_PER_CHANNEL=16)
+    g = c.g
     pat, tp = dl.pattern(51), dl.taps(52).astype(np.int32)
     assert dl.SAMPLES_BYTES > lt.LINE and dl.OUT_BYTES > lt.LINE
-    d_x, d_out = gpu.mem_alloc(dl.SAMPLES_BYTES), gpu.mem_alloc(dl.OUT_BYTES + CANARY)
-    d_taps, d_digits = gpu.mem_alloc(tp.nbytes), gpu.mem_alloc(ddc_digits_bytes(dl.T))
     try:
+        d_x, d_out = c.alloc(dl.SAMPLES_BYTES), c.out(dl.OUT_BYTES, dl.PREFILL, dl.PREFILL)
+        d_taps, d_digits = c.upload(tp), c.alloc(ddc_digits_bytes(dl.T))
         lt.fill(gpu, d_x, dl.SAMPLES_BYTES, pat)
-        gpu.memset(d_out, dl.PREFILL, dl.OUT_BYTES + CANARY)
-        gpu.memcpy_htod(d_taps, tp)
         g.ddc_tap_digits(d_taps, dl.T, dl.NB, d_digits, ddc_digits_bytes(dl.T))
         g.ddc(d_x, dl.SAMPLES_BYTES, dl.IN_STRIDE, dl.NI, dl.NR_OUT, d_digits, ddc_digits_bytes(dl.T), dl.T, dl.BANDS, d_out, dl.OUT_BYTES,
               dl.OUT_STRIDE)
@@ -48,7 +45,4 @@ def test_samples_and_outputs_past_the_line(gpu):
         gpu.memcpy_dtoh(edge, int(d_x) + lt.LINE - 4096)
         assert np.array_equal(edge, lt.elements_of(pat, lt.LINE - 4096 + np.arange(8192)))
     finally:
-        gpu.synchronize()
-        g.close()
-        for d in (d_x, d_out, d_taps, d_digits):
-            d.free()
+        c.close()

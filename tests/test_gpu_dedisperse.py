@@ -3,9 +3,7 @@ and DM-time words are integers and are compared with the numpy model (helpers/de
 tests/test_dedisperse_model.py).  Every buffer is exactly sized: the filterbanks' last row ends where their allocation
 ends; every output has a 0xA5 canary behind it, which must stay untouched; the planes are prefilled, and every word outside
 [first_out, first_out + nr_spectra) must stay as it was."""
-import subprocess
-import sys
-from pathlib import Path
+from functools import partial
 
 import numpy as np
 import pytest
@@ -13,52 +11,19 @@ import pytest
 from helpers import hip_graph
 from helpers.dedisperse_model import (BAND_ASCENDING_100, BAND_DESCENDING_64, DMS_40, INT32_MAX, INT32_MIN, dedisperse, dm_delays,
                                       smooth_table, takes_part)
+from helpers.device_buffers import Context, closed_after
+from helpers.examples import run_example
 from helpers.filterbank_model import filterbank
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-CANARY = 64
 PREFILL = 0x3C
 PREFILL_WORD = 0x3C3C3C3C
 
 
-class DCase:
+class DCase(Context):
     """One context of C channels (no delay table: the dedispersion has no coefficients; nr_beams is an argument) and the
     device buffers of its calls, exactly sized, outputs with a canary behind; all freed by close()."""
-
-    def __init__(self, gpu, C):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu, self.C = gpu, C
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
-        self.g = SteeringCoefficientGenerator(self.bp)
-        self.held = []
-
-    def alloc(self, nbytes):
-        a = self.gpu.mem_alloc(max(nbytes, 1))
-        self.held.append(a)
-        return a
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            self.gpu.memcpy_htod(d, a)
-        return d
-
-    def out(self, nbytes, prefill=0xA5):
-        d = self.alloc(nbytes + CANARY)
-        self.gpu.memset(d, prefill, nbytes)
-        self.gpu.memset(int(d) + nbytes, 0xA5, CANARY)
-        return d
-
-    def read(self, d, nbytes, dtype, shape):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == 0xA5), "written past the tensor"
-        return host[:nbytes].view(dtype).reshape(shape).copy()
 
     def delays(self, band, dms):
         """dcs_bf_dm_delays on the device: the device table and its host copy."""
@@ -103,10 +68,10 @@ class DCase:
         assert bad.size == 0, (len(bad), bad[0], got[tuple(bad[0])], exp[tuple(bad[0])])
         return got
 
-    def close(self):
-        self.g.close()
-        for a in self.held:
-            a.free()
+
+@pytest.fixture
+def case(gpu):
+    yield from closed_after(partial(DCase, gpu))
 
 
 def seeded_bytes(B, rows, C, seed):
@@ -119,8 +84,8 @@ DMS_EDGE = np.concatenate([DMS_40[:36], [np.nan, -12.5, 1e300, -1e300]])  # 40 D
 
 
 @pytest.mark.parametrize("C", [1, 3, 64, 100])
-def test_delays_are_the_model(gpu, C):
-    c = DCase(gpu, C)
+def test_delays_are_the_model(gpu, case, C):
+    c = case(C)
     bands = [BAND_DESCENDING_64, BAND_ASCENDING_100, (1400.0, 0.0, 64e-6), (600.0, -0.25, 1e-3)]
     for band in bands:
         _, got = c.delays(band, DMS_EDGE)
@@ -136,7 +101,6 @@ def test_delays_are_the_model(gpu, C):
     c.g.dm_delays(*BAND_DESCENDING_64, d_dms, 0, d_out, 0)
     gpu.synchronize()
     assert np.all(c.read(d_out, 4 * C * 4, np.uint8, (-1,)) == 0xA5)
-    c.close()
 
 
 # ------------------------------------------------------------------------------------- planes with the tables dm_delays makes
@@ -169,8 +133,8 @@ def band_tables():
 
 
 @pytest.mark.parametrize("C,band", [(64, BAND_DESCENDING_64), (100, BAND_ASCENDING_100)])
-def test_planes_of_the_device_tables(gpu, band_tables, C, band):
-    c = DCase(gpu, C)
+def test_planes_of_the_device_tables(gpu, case, band_tables, C, band):
+    c = case(C)
     full = band_tables[C]
     assert 1300 <= full.max() <= 1340 and {int(r) for r in np.unique(full % 4)} == {0, 1, 2, 3}
     for T, B, nr_dm, first, first_out in CASES:
@@ -186,28 +150,26 @@ def test_planes_of_the_device_tables(gpu, band_tables, C, band):
     d_delays, table = c.delays(band, DMS_40[33:])
     fb = seeded_bytes(2, 6 + 700 + int(table.max()), C, seed=C)
     c.check(fb, table, 6, 700, int(table.max()), out_spectra=710, first_out=5, d_delays=d_delays)
-    c.close()
 
 
 @pytest.mark.parametrize("C", [1, 3, 17, 257])
-def test_ragged_columns_with_smooth_tables(gpu, C):
+def test_ragged_columns_with_smooth_tables(gpu, case, C):
     """Chunks that are no whole 32 columns and rows that start at any byte: C odd."""
-    c = DCase(gpu, C)
+    c = case(C)
     for nr_dm, top, T, B, first in ((7, 600, 65, 3, 1), (40, 1330, 257, 1, 6), (1, 90, 1000, 2, 0), (19, 333, 513, 1, 3)):
         table = smooth_table(C, nr_dm, top, seed=C + nr_dm)
         max_delay = int(table.max())
         fb = seeded_bytes(B, first + T + max_delay, C, seed=C * T)
         c.check(fb, table, first, T, max_delay, out_spectra=T + 9, first_out=5)
-    c.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- any table
 
-def test_any_table_and_entries_that_drop(gpu):
+def test_any_table_and_entries_that_drop(gpu, case):
     """Random entries in [0, 50000]: 6.4 MB of filterbanks that no LDS window holds.  Then the same table with entries
     outside [0, max_delay] sprinkled in, and a DM whose every term drops."""
     C, B, T, max_delay, nr_dm = 64, 2, 300, 50000, 9
-    c = DCase(gpu, C)
+    c = case(C)
     rng = np.random.default_rng(50000)
     fb = seeded_bytes(B, T + max_delay, C, seed=1)
     assert fb.nbytes >= 6_400_000
@@ -227,14 +189,13 @@ def test_any_table_and_entries_that_drop(gpu):
     smooth[5] = bad[5]
     got = c.check(fb, smooth, 0, T, max_delay)
     assert not got[:, 5].any()
-    c.close()
 
 
 # --------------------------------------------------------------------------------------------------------------------- mask
 
-def test_channel_mask(gpu):
+def test_channel_mask(gpu, case):
     C, B, T = 100, 2, 130
-    c = DCase(gpu, C)
+    c = case(C)
     table = dm_delays(C, *BAND_ASCENDING_100, DMS_40[30:37])
     max_delay = int(table.max())
     fb = seeded_bytes(B, T + max_delay, C, seed=2)
@@ -248,28 +209,26 @@ def test_channel_mask(gpu):
     assert not np.array_equal(some, plain)
     none = c.check(fb, table, 0, T, max_delay, mask=np.zeros(C, np.uint8))
     assert not none.any()
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------------------ lane overflow
 
 @pytest.mark.parametrize("C", [1030, 1024])
-def test_every_byte_255(gpu, C):
+def test_every_byte_255(gpu, case, C):
     """258 columns is the smallest count at which a 16-bit lane can wrap: every word is 255 C."""
     T, B = 100, 1
-    c = DCase(gpu, C)
+    c = case(C)
     table = np.stack([np.zeros(C, np.int32), smooth_table(C, 2, 300, seed=C)[1]])
     max_delay = int(table.max())
     assert max_delay == 300
     fb = np.full((B, T + max_delay, C), 0xFF, np.uint8)
     got = c.check(fb, table, 0, T, max_delay)
     assert np.all(got == 255 * C)
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------ capture
 
-def test_both_calls_captured_and_replayed_with_new_contents(gpu):
+def test_both_calls_captured_and_replayed_with_new_contents(gpu, case):
     """Both calls as first calls on a fresh context, captured; replayed after the DMs, the filterbank bytes and the mask
     were changed on the device: the outputs follow the new contents."""
     from dc_sand_amd.generator import dm_delays_bytes, dm_time_bytes
@@ -279,7 +238,7 @@ def test_both_calls_captured_and_replayed_with_new_contents(gpu):
     dm_sets = [DMS_40[3::6], DMS_40[20:27], DMS_40[33:]]
     max_delay = max(int(dm_delays(C, *band, d).max()) for d in dm_sets)
     in_spectra = first + T + max_delay
-    c = DCase(gpu, C)
+    c = case(C)
     tbytes, pbytes = dm_delays_bytes(c.bp, nr_dm), dm_time_bytes(B, nr_dm, out_spectra)
     d_dms, d_fb, d_mask = c.alloc(nr_dm * 8), c.alloc(B * in_spectra * C), c.alloc(C)
     d_delays, d_out = c.out(tbytes), c.out(pbytes, PREFILL)
@@ -307,16 +266,15 @@ def test_both_calls_captured_and_replayed_with_new_contents(gpu):
         seen.append(got)
     assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
     graph.close()
-    c.close()
 
 
-def test_short_buffers_and_a_band_below_zero_are_refused_and_nothing_is_enqueued(gpu):
+def test_short_buffers_and_a_band_below_zero_are_refused_and_nothing_is_enqueued(gpu, case):
     """The refusals that need the context's C: they come after the version check, with DCS_ERR_INVALID_ARGUMENT."""
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
     from dc_sand_amd.generator import dm_delays_bytes, dm_time_bytes
 
     C, B, T, nr_dm, max_delay = 64, 2, 50, 7, 30
-    c = DCase(gpu, C)
+    c = case(C)
     g = c.g
     in_spectra = T + max_delay
     fbytes, tbytes, pbytes = B * in_spectra * C, dm_delays_bytes(c.bp, nr_dm), dm_time_bytes(B, nr_dm, T)
@@ -344,12 +302,11 @@ def test_short_buffers_and_a_band_below_zero_are_refused_and_nothing_is_enqueued
     g.dedisperse_q8(d_fb, fbytes, in_spectra, 0, T, B, d_delays, 0, max_delay, d_out, 0, T)
     gpu.synchronize()
     assert np.all(c.read(d_out, pbytes, np.uint8, (-1,)) == PREFILL)
-    c.close()
 
 
 # -------------------------------------------------------------------------------------------------------------------- chain
 
-def test_filterbank_q8_descending_into_dedisperse(gpu):
+def test_filterbank_q8_descending_into_dedisperse(gpu, case):
     """Spectra whose channel c lies at f0 + c df, quantised with DCS_FB_DESCENDING: column j of the bytes is channel
     C - 1 - j, so the band is stated per column, first f0 + (C - 1) df and step -df.  The plane is the model of the chain."""
     from dc_sand_amd.generator import dm_time_bytes, filterbank_bytes, filterbank_scales_bytes
@@ -367,7 +324,7 @@ def test_filterbank_q8_descending_into_dedisperse(gpu):
     m = np.exp2(rng.uniform(-8.0, 8.0, size=(C, B))).astype(np.float32)
     x = (m[None].astype(np.float64) * (1.0 + 0.25 * rng.standard_normal((rows, C, B)))).astype(np.float32)
     sc = np.stack([m, (24.0 / (0.25 * m.astype(np.float64))).astype(np.float32)], axis=-1)
-    c = DCase(gpu, C)
+    c = case(C)
     fbytes, pbytes = filterbank_bytes(c.bp, B, rows), dm_time_bytes(B, nr_dm, T)
     assert filterbank_scales_bytes(c.bp, B) == sc.nbytes
     d_x, d_sc, d_fb = c.upload(x), c.upload(sc), c.alloc(fbytes)
@@ -382,13 +339,10 @@ def test_filterbank_q8_descending_into_dedisperse(gpu):
     got = c.read(d_out, pbytes, np.uint32, (B, nr_dm, T))
     assert np.array_equal(c.read(d_delays, table.nbytes, np.int32, table.shape), table)
     assert np.array_equal(got, exp), np.argwhere(got != exp)[:3]
-    c.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------ example
 
 def test_example_runs_and_verifies_itself(gpu):
-    res = subprocess.run([sys.executable, str(ROOT / "examples" / "dedispersed_pulse.py"), "64", "2", "24", "1024"], capture_output=True,
-                         text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
-    assert "bit-identical to the model: True" in res.stdout and "the maximum lies at the injected DM and time: True" in res.stdout
+    out = run_example("dedispersed_pulse.py", 64, 2, 24, 1024)
+    assert "bit-identical to the model: True" in out and "the maximum lies at the injected DM and time: True" in out

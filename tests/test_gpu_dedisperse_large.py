@@ -9,10 +9,10 @@ import pytest
 
 from helpers import large_tensor as lt
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
+from helpers.device_buffers import Context
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 PREFILL = 0xA5
 PREFILL_WORD = 0xA5A5A5A5
 C = 64
@@ -20,21 +20,9 @@ C = 64
 
 @pytest.fixture
 def case(gpu):
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1))
-    held = []
-
-    def alloc(nbytes):
-        held.append(gpu.mem_alloc(nbytes))
-        return held[-1]
-
-    yield g, alloc
-    gpu.synchronize()
-    g.close()
-    for a in held:
-        a.free()
+    c = Context(gpu, C)
+    yield c
+    c.close()
 
 
 def test_filterbanks_past_the_line(gpu, case):
@@ -42,7 +30,7 @@ def test_filterbanks_past_the_line(gpu, case):
     outputs of 7 DMs from windows that end below the line, straddle it and begin above it, and beam 0's alongside."""
     from dc_sand_amd.generator import dm_time_bytes
 
-    g, alloc = case
+    g, alloc = case.g, case.alloc
     B, T, in_spectra = 2, 4096, (1 << 25) + 8192
     nbytes = B * in_spectra * C
     line_row = (lt.LINE - in_spectra * C) // C  # of beam 1
@@ -54,20 +42,16 @@ def test_filterbanks_past_the_line(gpu, case):
     pattern = lt.int8_pattern(C, seed=21)
     d_fb = alloc(nbytes)
     lt.fill(gpu, d_fb, nbytes, pattern)
-    d_delays = alloc(table.nbytes)
-    gpu.memcpy_htod(d_delays, table)
+    d_delays = case.upload(table)
     pbytes = dm_time_bytes(B, nr_dm, T)
-    d_out = alloc(pbytes + CANARY)
+    d_out = case.out(pbytes)
     firsts = [line_row - window, line_row - window // 2, line_row - 1, line_row, line_row + 100, in_spectra - window]
     for first in firsts:
         assert 0 <= first and first + window <= in_spectra
-        gpu.memset(d_out, PREFILL, pbytes + CANARY)
+        case.refill(d_out)
         g.dedisperse_q8(d_fb, nbytes, in_spectra, first, T, B, d_delays, nr_dm, max_delay, d_out, pbytes, T)
         gpu.synchronize()
-        host = np.empty(pbytes + CANARY, np.uint8)
-        gpu.memcpy_dtoh(host, d_out)
-        assert np.all(host[pbytes:] == PREFILL), "written past the plane"
-        got = host[:pbytes].view(np.uint32).reshape(B, nr_dm, T)
+        got = case.read(d_out, pbytes, np.uint32, (B, nr_dm, T))
         rows = first + np.arange(window, dtype=np.int64)
         fb = np.stack([lt.rows_of(pattern, b * in_spectra + rows) for b in range(B)])  # [B][window][C] from the pattern
         exp = dedisperse(fb, table, 0, T, max_delay)
@@ -83,7 +67,7 @@ def test_plane_past_the_line(gpu, case):
     lie past the line, and the words 4 GiB below them -- words 15360 .. 16383 of DM 0 -- keep the prefill."""
     from dc_sand_amd.generator import dm_time_bytes
 
-    g, alloc = case
+    g = case.g
     B, T, nr_dm, out_spectra = 1, 1024, 4, (1 << 28) + 4096
     first_out = out_spectra - T
     pbytes = dm_time_bytes(B, nr_dm, out_spectra)
@@ -92,11 +76,8 @@ def test_plane_past_the_line(gpu, case):
     assert table.shape[0] == nr_dm
     max_delay = int(table.max())
     fb = np.random.default_rng(22).integers(0, 256, size=(B, 3 + T + max_delay, C), dtype=np.uint8)
-    d_fb, d_delays = alloc(fb.nbytes), alloc(table.nbytes)
-    gpu.memcpy_htod(d_fb, fb)
-    gpu.memcpy_htod(d_delays, table)
-    d_out = alloc(pbytes + CANARY)
-    gpu.memset(d_out, PREFILL, pbytes + CANARY)
+    d_fb, d_delays = case.upload(fb), case.upload(table)
+    d_out = case.out(pbytes)
     g.dedisperse_q8(d_fb, fb.nbytes, fb.shape[1], 3, T, B, d_delays, nr_dm, max_delay, d_out, pbytes, out_spectra, first_out=first_out)
     gpu.synchronize()
     exp = dedisperse(fb, table, 3, T, max_delay)[0]  # [nr_dm][T]
@@ -113,6 +94,4 @@ def test_plane_past_the_line(gpu, case):
     assert np.array_equal(got, exp), np.argwhere(got != exp)[:3]
     kept = lt.read_rows(gpu, d_out, row_bytes, untouched).view(np.uint32)
     assert np.all(kept == PREFILL_WORD), "a word outside [first_out, first_out + nr_spectra) was written"
-    tail = np.empty(CANARY, np.uint8)
-    gpu.memcpy_dtoh(tail, int(d_out) + pbytes)
-    assert np.all(tail == PREFILL), "written past the plane"
+    case.guard_untouched(d_out)

@@ -4,15 +4,17 @@ by tests/test_filterbank_model.py).  The tests supply the float spectra directly
 incoherent spectra of the last test but one.  Every buffer is exactly sized; every output has a 0xA5 canary behind it,
 which must stay untouched, and the filterbank rows outside [first, first + nr_spectra) are prefilled and must stay as
 they were."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers.device_buffers import Context, closed_after
 from helpers.filterbank_model import filterbank, quantise, same_bits, scales, spectra_sums
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 PREFILL = 0x3C
 TARGET_STD, LEVEL = 24.0, 128.0
 
@@ -49,41 +51,27 @@ def place_specials(x, seed=0):
     return x, mask.reshape(x.shape)
 
 
-class FCase:
+class FCase(Context):
     """One context of C channels (no delay table: the filterbank has no coefficients; nr_beams is an argument), and the
     device buffers of one (C, B, T) case, exactly sized, outputs with a canary behind."""
 
     def __init__(self, gpu, C, B, T, out_spectra=None, first=0, spectra_offset=0, stations=1):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import (SteeringCoefficientGenerator, filterbank_bytes, filterbank_scales_bytes,
-                                           spectra_sums_bytes)
+        from dc_sand_amd.generator import filterbank_bytes, filterbank_scales_bytes, spectra_sums_bytes
 
-        self.gpu, self.C, self.B, self.T, self.first = gpu, C, B, T, first
+        super().__init__(gpu, C, A=stations)
+        self.B, self.T, self.first = B, T, first
         self.out_spectra = T + first if out_spectra is None else out_spectra
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=stations, NR_BEAMS=1)
-        self.g = SteeringCoefficientGenerator(self.bp)
         self.xbytes = T * C * B * 4
         self.sums_bytes, self.scales_bytes = spectra_sums_bytes(self.bp, B), filterbank_scales_bytes(self.bp, B)
         self.fb_bytes = filterbank_bytes(self.bp, B, self.out_spectra)
         assert (self.sums_bytes, self.scales_bytes, self.fb_bytes) == (C * B * 16, C * B * 8, B * self.out_spectra * C)
-        self._x_alloc = gpu.mem_alloc(self.xbytes + spectra_offset)  # the last spectrum ends where the allocation ends
-        self.d_x = int(self._x_alloc) + spectra_offset
-        self.d_sums = gpu.mem_alloc(self.sums_bytes + CANARY)
-        self.d_scales = gpu.mem_alloc(self.scales_bytes + CANARY)
-        self.d_fb = gpu.mem_alloc(self.fb_bytes + CANARY)
-        self.d_clips = gpu.mem_alloc(B * 8 + CANARY)
-        for d, n in ((self.d_sums, self.sums_bytes), (self.d_scales, self.scales_bytes)):
-            gpu.memset(d, 0xA5, n + CANARY)
+        self.d_x = int(self.alloc(self.xbytes + spectra_offset)) + spectra_offset  # the last spectrum ends where the allocation ends
+        self.d_sums, self.d_scales = self.out(self.sums_bytes), self.out(self.scales_bytes)
+        self.d_fb, self.d_clips = self.out(self.fb_bytes, PREFILL), self.out(B * 8, 0)
         gpu.synchronize()
 
     def put(self, d, a):
         self.gpu.memcpy_htod(d, np.ascontiguousarray(a))
-
-    def _read(self, d, nbytes, dtype, shape):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == 0xA5), "written past the tensor"
-        return host[:nbytes].view(dtype).reshape(shape).copy()
 
     def call_sums(self, accumulate=False, stream=None, T=None):
         T = self.T if T is None else T
@@ -100,22 +88,20 @@ class FCase:
                              d_clip_count=self.d_clips if counters else None, stream=stream)
 
     def read_sums(self):
-        return self._read(self.d_sums, self.sums_bytes, np.float64, (self.C, self.B, 2))
+        return self.read(self.d_sums, self.sums_bytes, np.float64, (self.C, self.B, 2))
 
     def read_scales(self):
-        return self._read(self.d_scales, self.scales_bytes, np.float32, (self.C, self.B, 2))
+        return self.read(self.d_scales, self.scales_bytes, np.float32, (self.C, self.B, 2))
 
     def reset_outputs(self, stream=None):
-        self.gpu.memset(self.d_fb, PREFILL, self.fb_bytes, stream=stream)
-        self.gpu.memset(int(self.d_fb) + self.fb_bytes, 0xA5, CANARY, stream=stream)
-        self.gpu.memset(self.d_clips, 0, self.B * 8, stream=stream)
-        self.gpu.memset(int(self.d_clips) + self.B * 8, 0xA5, CANARY, stream=stream)
+        self.refill(self.d_fb, stream=stream)
+        self.refill(self.d_clips, stream=stream)
 
     def read_filterbank(self):
-        return self._read(self.d_fb, self.fb_bytes, np.uint8, (self.B, self.out_spectra, self.C))
+        return self.read(self.d_fb, self.fb_bytes, np.uint8, (self.B, self.out_spectra, self.C))
 
     def read_clips(self):
-        return self._read(self.d_clips, self.B * 8, np.uint64, (self.B,))
+        return self.read(self.d_clips, self.B * 8, np.uint64, (self.B,))
 
     def q8(self, descending=False, counters=True):
         """One call from prefilled outputs: the whole buffer and the counters (zero where none were asked for)."""
@@ -128,10 +114,10 @@ class FCase:
         prefill = np.full((self.B, self.out_spectra, self.C), PREFILL, np.uint8)
         return filterbank(x, sc, LEVEL, descending=descending, out=prefill, first=self.first)
 
-    def close(self):
-        self.g.close()
-        for d in (self._x_alloc, self.d_sums, self.d_scales, self.d_fb, self.d_clips):
-            d.free()
+
+@pytest.fixture
+def case(gpu):
+    yield from closed_after(partial(FCase, gpu))
 
 
 def check_bytes(c, x, sc, special, min_distinct=True):
@@ -164,9 +150,9 @@ SHAPES = [(1, 1, 1), (3, 5, 4), (127, 31, 3), (128, 32, 2), (129, 33, 3), (256, 
 
 
 @pytest.mark.parametrize("C,B,T", SHAPES)
-def test_sums_scales_and_bytes_are_the_model(gpu, C, B, T):
+def test_sums_scales_and_bytes_are_the_model(gpu, case, C, B, T):
     first = 3 if T > 1 else 0
-    c = FCase(gpu, C, B, T, out_spectra=T + first + (2 if first else 0), first=first)
+    c = case(C, B, T, out_spectra=T + first + (2 if first else 0), first=first)
     clean, m = seeded_spectra(C, B, T)
     c.put(c.d_x, clean)
     c.call_sums()
@@ -184,12 +170,11 @@ def test_sums_scales_and_bytes_are_the_model(gpu, C, B, T):
     c.call_sums()
     gpu.synchronize()
     assert same_bits(c.read_sums(), spectra_sums(x)) is None
-    c.close()
 
 
 @pytest.mark.parametrize("C,B,T", [(16, 4, 40), (144, 36, 33), (128, 32, 2)])
-def test_fast_shape_whose_spectra_are_4_byte_aligned_only(gpu, C, B, T):
-    c = FCase(gpu, C, B, T, out_spectra=T + 4, first=1, spectra_offset=4)
+def test_fast_shape_whose_spectra_are_4_byte_aligned_only(gpu, case, C, B, T):
+    c = case(C, B, T, out_spectra=T + 4, first=1, spectra_offset=4)
     assert c.d_x % 16 == 4
     clean, m = seeded_spectra(C, B, T, seed=1)
     x, special = place_specials(clean, seed=1)
@@ -200,16 +185,15 @@ def test_fast_shape_whose_spectra_are_4_byte_aligned_only(gpu, C, B, T):
     c.call_sums()
     gpu.synchronize()
     assert same_bits(c.read_sums(), spectra_sums(x)) is None
-    c.close()
 
 
-def test_a_workgroup_walks_several_slices_and_the_time_axis_is_split(gpu, record_property):
+def test_a_workgroup_walks_several_slices_and_the_time_axis_is_split(gpu, case, record_property):
     """From the captured launch geometry, not from the launcher's arithmetic: gridDim.y is the number of runs that the time
     axis is cut into, so a call of T spectra has a workgroup that walks at least three slices where
     2 * gridDim.y < T, and its time axis is split where gridDim.y > 1."""
     seen = {}
     for C, B, T in ((256, 64, 5), (16, 4, 40), (144, 36, 33)):
-        c = FCase(gpu, C, B, T)
+        c = case(C, B, T)
         clean, m = seeded_spectra(C, B, T, seed=2)
         x, special = place_specials(clean, seed=2)
         sc = given_scales(m)
@@ -224,15 +208,14 @@ def test_a_workgroup_walks_several_slices_and_the_time_axis_is_split(gpu, record
         record_property(f"grid of {(C, B, T)}", grid)
         seen[(C, B, T)] = (2 * grid[1] < T, grid[1] > 1)
         check_bytes(c, x, sc, special)
-        c.close()
     assert seen[(256, 64, 5)][0], "no case in which one workgroup walks at least 3 slices of an unsplit time axis"
     assert seen[(16, 4, 40)] == (True, True) and seen[(144, 36, 33)] == (True, True), seen
 
 
-def test_scale_edges(gpu):
+def test_scale_edges(gpu, case):
     """Scales given by the test: k of 0, Inf and NaN and a NaN mu; then a constant channel, which the scales call gives k = 0."""
     C, B, T = 40, 12, 6
-    c = FCase(gpu, C, B, T)
+    c = case(C, B, T)
     clean, m = seeded_spectra(C, B, T, seed=3)
     sc = given_scales(m)
     sc[1, 2, 1] = 0.0
@@ -268,13 +251,12 @@ def test_scale_edges(gpu):
     exp, _ = c.expect(x, sc)
     assert same_bits(fb, exp) is None
     assert np.all(fb[:, :, 9] == 128) and np.all(fb[5, :, 30] == 128)
-    c.close()
 
 
-def test_device_divide_and_square_root_are_the_correctly_rounded_ones(gpu):
+def test_device_divide_and_square_root_are_the_correctly_rounded_ones(gpu, case):
     """4096 seeded sums per count: the scales call against numpy's float64 divide and sqrt, which are correctly rounded."""
     C, B = 64, 64
-    c = FCase(gpu, C, B, 1)
+    c = case(C, B, 1)
     rng = np.random.default_rng(2026)
     for count in (1, 1000, (1 << 40) + 3, (1 << 53) - 1):
         m = np.exp2(rng.uniform(-20, 20, size=(C, B))) * (1 + rng.uniform(size=(C, B)))
@@ -288,21 +270,19 @@ def test_device_divide_and_square_root_are_the_correctly_rounded_ones(gpu):
         assert np.count_nonzero(exp[..., 1]) > 0.9 * C * B and np.unique(exp[..., 1]).size > 0.8 * C * B
         assert same_bits(got[..., 0], exp[..., 0]) is None, ("mu: the divide", count, same_bits(got[..., 0], exp[..., 0]))
         assert same_bits(got[..., 1], exp[..., 1]) is None, ("k: divide, sqrt, divide", count, same_bits(got[..., 1], exp[..., 1]))
-    c.close()
 
 
-def test_accumulate_over_three_calls_and_on_graph_replay(gpu):
+def test_accumulate_over_three_calls_and_on_graph_replay(gpu, case):
     C, B = 70, 9
     parts = [seeded_spectra(C, B, T, seed=10 + i)[0] for i, T in enumerate((5, 1, 11))]
     joined = np.concatenate(parts)
-    one = FCase(gpu, C, B, joined.shape[0])
+    one = case(C, B, joined.shape[0])
     one.put(one.d_x, joined)
     one.call_sums()
     gpu.synchronize()
     whole = one.read_sums()
     assert same_bits(whole, spectra_sums(joined)) is None
-    one.close()
-    c = FCase(gpu, C, B, 11)
+    c = case(C, B, 11)
     for i, part in enumerate(parts):
         c.put(c.d_x, part)
         c.call_sums(accumulate=i > 0, T=part.shape[0])
@@ -325,13 +305,12 @@ def test_accumulate_over_three_calls_and_on_graph_replay(gpu):
         running = spectra_sums(new, prior=running)
         assert same_bits(c.read_sums(), running) is None, i
     graph.close()
-    c.close()
 
 
 @pytest.mark.parametrize("C,B,T", [(48, 8, 12), (37, 3, 9)])
-def test_all_three_calls_captured_as_first_calls_on_a_fresh_context(gpu, C, B, T):
+def test_all_three_calls_captured_as_first_calls_on_a_fresh_context(gpu, case, C, B, T):
     """Nothing allocates, so nothing has to run outside the capture first; replayed with new spectra in the same buffer."""
-    c = FCase(gpu, C, B, T, out_spectra=T + 2, first=1)
+    c = case(C, B, T, out_spectra=T + 2, first=1)
     s = gpu.Stream()
     with hip_graph.capture(s) as graph:
         c.call_sums(stream=s.handle)
@@ -352,14 +331,13 @@ def test_all_three_calls_captured_as_first_calls_on_a_fresh_context(gpu, C, B, T
         assert same_bits(c.read_filterbank(), exp) is None, i
         assert np.array_equal(c.read_clips(), counts), i
     graph.close()
-    c.close()
 
 
-def test_buffers_one_byte_short_are_refused_and_nothing_is_enqueued(gpu):
+def test_buffers_one_byte_short_are_refused_and_nothing_is_enqueued(gpu, case):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
     C, B, T = 20, 6, 4
-    c = FCase(gpu, C, B, T)
+    c = case(C, B, T)
     g = c.g
     c.reset_outputs()
     gpu.synchronize()
@@ -380,26 +358,22 @@ def test_buffers_one_byte_short_are_refused_and_nothing_is_enqueued(gpu):
         assert e.value.status == DCS_ERR_INVALID_ARGUMENT, i
     gpu.synchronize()
     assert np.all(c.read_filterbank() == PREFILL) and not c.read_clips().any()
-    host = np.empty(c.sums_bytes + CANARY, np.uint8)
-    gpu.memcpy_dtoh(host, c.d_sums)
-    assert np.all(host == 0xA5)
-    c.close()
+    assert np.all(c.read(c.d_sums) == 0xA5)
 
 
-def test_incoherent_spectra_with_one_beam(gpu):
+def test_incoherent_spectra_with_one_beam(gpu, case):
     """nr_beams = 1 on real output of integrate_incoherent_power at 64 antennas and 7 channels."""
     from dc_sand_amd.generator import incoherent_block_power_bytes, incoherent_spectra_bytes
 
     A, C, n, T = 64, 7, 2, 12
     nt = 16 * n * T
-    c = FCase(gpu, C, 1, T, stations=A)
+    c = case(C, 1, T, stations=A)
     ant = np.random.default_rng(64).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
     ant[3] //= 4  # a bandpass: channel 3 is 12 dB down
-    d_ant = gpu.mem_alloc(ant.nbytes)
+    d_ant = c.upload(ant)
     pbytes, sbytes = incoherent_block_power_bytes(c.bp, nt), incoherent_spectra_bytes(c.bp, nt // 16, n)
     assert sbytes == c.xbytes
-    d_p = gpu.mem_alloc(pbytes)
-    gpu.memcpy_htod(d_ant, ant)
+    d_p = c.alloc(pbytes)
     c.g.incoherent_block_power(d_ant, ant.nbytes, d_p, pbytes, nt)
     c.g.integrate_incoherent_power(d_p, pbytes, nt // 16, n, c.d_x, sbytes)
     c.call_sums()
@@ -418,14 +392,11 @@ def test_incoherent_spectra_with_one_beam(gpu):
         exp, counts = c.expect(x, sc, descending=desc)
         assert np.unique(exp).size >= 20 and abs(float(exp.mean()) - LEVEL) < 1.0  # the bandpass is taken out
         assert same_bits(fb, exp) is None and np.array_equal(clips, counts), desc
-    d_ant.free()
-    d_p.free()
-    c.close()
 
 
 @pytest.mark.parametrize("C,B,T", [(129, 33, 3), (128, 32, 4)])
-def test_a_nan_leaves_every_other_channel_and_beam_bit_identical(gpu, C, B, T):
-    c = FCase(gpu, C, B, T)
+def test_a_nan_leaves_every_other_channel_and_beam_bit_identical(gpu, case, C, B, T):
+    c = case(C, B, T)
     clean, _ = seeded_spectra(C, B, T, seed=40)
     cc, bb = C - 2, B // 2
 
@@ -451,4 +422,3 @@ def test_a_nan_leaves_every_other_channel_and_beam_bit_identical(gpu, C, B, T):
     assert got[3][bb] == ref[3][bb] + T and np.array_equal(np.delete(got[3], bb), np.delete(ref[3], bb))
     sums = spectra_sums(x)
     assert same_bits(got[0], sums) is None and same_bits(got[1], scales(sums, T, TARGET_STD)) is None
-    c.close()

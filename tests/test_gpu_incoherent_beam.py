@@ -2,16 +2,18 @@
 powers are compared as integers and the spectra as float bits with the numpy model (helpers/incoherent_model.py, anchored
 on the CPU by tests/test_incoherent_model.py).  The sample buffer is exactly sized, so its last row ends where the
 allocation ends, and every output is exactly sized with a canary behind it, which must stay untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from helpers import hip_graph
 from helpers import stokes_model
+from helpers.device_buffers import Context, closed_after
 from helpers.incoherent_model import block_power, full_range_words, integrate, same_bits
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 SPECIALS = np.array([0.0, -0.0, np.nan, np.inf, -np.inf, 0.5, 1.0, -3.0, 1e-45], dtype=np.float32)
 
 
@@ -27,26 +29,23 @@ def seeded_flags(A, seed=0):
     return SPECIALS[rng.integers(0, SPECIALS.size, size=A)] if A > 1 else np.array([0.5], np.float32)
 
 
-class ICase:
+class ICase(Context):
     """One context of A antennas and C channels (no delay table: the incoherent beam has no coefficients), its samples
     and its two outputs."""
 
     def __init__(self, gpu, A, C, nt, seed=0):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import (SteeringCoefficientGenerator, incoherent_block_power_bytes,
-                                           incoherent_spectra_bytes)
+        from dc_sand_amd.generator import incoherent_block_power_bytes, incoherent_spectra_bytes
 
-        self.gpu, self.A, self.C, self.nt, self.nblk = gpu, A, C, nt, nt // 16
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=nt)
+        super().__init__(gpu, C, A, NR_SAMPLES_PER_CHANNEL=nt)
+        self.nt, self.nblk = nt, nt // 16
         self.spectra_bytes = lambda n: incoherent_spectra_bytes(self.bp, self.nblk, n)
-        self.g = SteeringCoefficientGenerator(self.bp)
         self.ant = seeded_samples(A, C, nt, seed)
-        self.d_ant = gpu.mem_alloc(self.ant.nbytes)
+        self.d_ant = self.alloc(self.ant.nbytes)
         self.pbytes = incoherent_block_power_bytes(self.bp, nt)
         assert self.pbytes == C * self.nblk * 4
-        self.d_p = gpu.mem_alloc(self.pbytes + CANARY)
-        self.d_s = gpu.mem_alloc(self.pbytes + CANARY)  # spectra: at most one per block
-        self.d_w = gpu.mem_alloc(A * 4)
+        self.d_p = self.out(self.pbytes)
+        self.d_s = self.out(self.pbytes)  # spectra: at most one per block
+        self.d_w = self.alloc(A * 4)
 
     def set_ant(self, ant):
         self.ant = ant
@@ -57,16 +56,13 @@ class ICase:
                                       d_weights=self.d_w if weighted else None, stream=stream)
 
     def read_power(self):
-        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_p)
-        assert np.all(host[self.pbytes:] == 0xA5), "written past the block power tensor"
-        return host[:self.pbytes].view(np.uint32).reshape(self.C, self.nblk).copy()
+        return self.read(self.d_p, self.pbytes, np.uint32, (self.C, self.nblk))
 
     def power(self, w=None):
         """One call from a clean output buffer."""
         gpu = self.gpu
         gpu.memcpy_htod(self.d_ant, self.ant)
-        gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        self.refill(self.d_p)
         if w is not None:
             gpu.memcpy_htod(self.d_w, np.ascontiguousarray(w, dtype=np.float32))
         self.call_power(weighted=w is not None)
@@ -76,7 +72,7 @@ class ICase:
     def set_power(self, P):
         """The integration's input given by the test."""
         assert P.dtype == np.uint32 and P.shape == (self.C, self.nblk)
-        self.gpu.memset(self.d_p, 0xA5, self.pbytes + CANARY)
+        self.refill(self.d_p)
         self.gpu.memcpy_htod(self.d_p, np.ascontiguousarray(P))
 
     def call_integrate(self, n, accumulate=False, stream=None):
@@ -84,25 +80,23 @@ class ICase:
                                           accumulate=accumulate, stream=stream)
 
     def read_spectra(self, n):
-        nb = self.spectra_bytes(n)
-        host = np.empty(self.pbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_s)
-        assert np.all(host[nb:] == 0xA5), "written past the spectra"
-        return host[:nb].view(np.float32).reshape(self.nblk // n, self.C).copy()
+        return self.read(self.d_s, self.spectra_bytes(n), np.float32, (self.nblk // n, self.C))
 
     def spectra(self, n, accumulate=False, prior=None):
         """One integration of what d_p holds; without ``accumulate`` from a clean buffer, with ``prior`` from that."""
         gpu = self.gpu
         if not accumulate or prior is not None:
-            gpu.memset(self.d_s, 0xA5, self.pbytes + CANARY)
+            self.refill(self.d_s)
         if prior is not None:
             gpu.memcpy_htod(self.d_s, np.ascontiguousarray(prior, dtype=np.float32))
         self.call_integrate(n, accumulate)
         gpu.synchronize()
         return self.read_spectra(n)
 
-    def close(self):
-        self.g.close()
+
+@pytest.fixture
+def case(gpu):
+    yield from closed_after(partial(ICase, gpu))
 
 
 # a single row; rows that could share a wave's load; both sides of a wave-load boundary (32 antennas); a last partial
@@ -112,8 +106,8 @@ SHAPES = [(1, 1, 16), (3, 5, 48), (8, 4, 32), (31, 3, 48), (32, 3, 48), (33, 3, 
 
 
 @pytest.mark.parametrize("A,C,nt", SHAPES)
-def test_block_power_is_the_model(gpu, A, C, nt):
-    c = ICase(gpu, A, C, nt)
+def test_block_power_is_the_model(gpu, case, A, C, nt):
+    c = case(A, C, nt)
     exp = block_power(c.ant)
     assert np.unique(exp).size >= min(100, exp.size), (np.unique(exp).size, exp.size)  # no trivial expectation
     got = c.power()
@@ -121,7 +115,6 @@ def test_block_power_is_the_model(gpu, A, C, nt):
     w = seeded_flags(A)
     got = c.power(w)
     assert np.array_equal(got, block_power(c.ant, w)), np.argwhere(got != block_power(c.ant, w))[:4]
-    c.close()
 
 
 # SHAPES have 25 groups of rows at the most, and the kernel's grid holds 2048 workgroups x 4 waves: no wave takes a second
@@ -132,10 +125,10 @@ LOOPING_SHAPES = [(32, 1283, 1040, 8), (65, 1283, 272, 2), (255, 643, 256, 1)]
 
 
 @pytest.mark.parametrize("A,C,nt,rows_per_trip", LOOPING_SHAPES)
-def test_block_power_when_a_wave_takes_a_second_trip(gpu, record_property, A, C, nt, rows_per_trip):
+def test_block_power_when_a_wave_takes_a_second_trip(gpu, case, record_property, A, C, nt, rows_per_trip):
     """The launch geometry, read from a captured graph (nothing allocates, so the capture may come first), must prove the
     second trip: its waves, each carrying `rows_per_trip` rows per trip, cannot hold the rows in one."""
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     rows = C * c.nblk
     assert rows % rows_per_trip != 0 or rows_per_trip == 1
     s = gpu.Stream()
@@ -155,14 +148,13 @@ def test_block_power_when_a_wave_takes_a_second_trip(gpu, record_property, A, C,
     exp = block_power(c.ant, w)
     got = c.power(w)
     assert np.array_equal(got, exp), np.argwhere(got != exp)[:4]
-    c.close()
 
 
-def test_integration_over_several_workgroups(gpu):
+def test_integration_over_several_workgroups(gpu, case):
     """(33, 70, 128): 560 spectra values with one block per spectrum -- three workgroups of 256 lanes, the last one partial --
     and 280 with two, plain and accumulating from a seeded prior."""
     A, C, nt = 33, 70, 128
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     P = c.power()
     assert np.array_equal(P, block_power(c.ant))
     for n, total in ((1, 560), (2, 280)):
@@ -173,12 +165,11 @@ def test_integration_over_several_workgroups(gpu):
         prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
         got = c.spectra(n, accumulate=True, prior=prior)
         assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate", same_bits(got, integrate(P, n, prior=prior)))
-    c.close()
 
 
 @pytest.mark.parametrize("A,C,nt", [(37, 2, 32), (130, 2, 32)])
-def test_weights_are_flags(gpu, A, C, nt):
-    c = ICase(gpu, A, C, nt)
+def test_weights_are_flags(gpu, case, A, C, nt):
+    c = case(A, C, nt)
     ref = block_power(c.ant)
     assert np.array_equal(c.power(), ref) and np.array_equal(c.power(np.ones(A, np.float32)), ref)  # NULL = all ones
     assert not c.power(np.zeros(A, np.float32)).any()
@@ -201,27 +192,25 @@ def test_weights_are_flags(gpu, A, C, nt):
         on = w != 0
         assert 0 < on.sum() < A and np.isnan(w).any() and np.isinf(w).any() and (w == 0.5).any() and np.signbit(w[w == 0]).any()
         assert np.array_equal(c.power(w), block_power(c.ant, w)), seed
-    c.close()
 
 
-def test_full_scale_needs_all_32_and_64_bits(gpu):
+def test_full_scale_needs_all_32_and_64_bits(gpu, case):
     A, C, nt, n = 256, 1, 640, 40
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     c.ant = np.full_like(c.ant, -128)
     got = c.power()
     assert np.all(got == 1 << 27)
     s = c.spectra(n)
     assert s.shape == (1, 1) and float(s[0, 0]) == float(5 << 30) and 5 << 30 > 1 << 32
     assert same_bits(s, integrate(got, n)) is None
-    c.close()
 
 
-def test_words_with_bit_31_set_are_unsigned(gpu):
+def test_words_with_bit_31_set_are_unsigned(gpu, case):
     """Full-range words, which the detection never makes (it ends at 2^27): the 64-bit sum and its conversion are unsigned.
     The same bits read as int32 give other spectra, so a signed sum or a conversion through a signed type would show."""
     P = full_range_words()
     C, K = P.shape
-    c = ICase(gpu, 1, C, K * 16)
+    c = case(1, C, K * 16)
     c.set_power(P)
     for n in (1, 2, 3, 12):
         exp = integrate(P, n)
@@ -232,14 +221,13 @@ def test_words_with_bit_31_set_are_unsigned(gpu):
         prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
         got = c.spectra(n, accumulate=True, prior=prior)
         assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate", same_bits(got, integrate(P, n, prior=prior)))
-    c.close()
 
 
 @pytest.mark.parametrize("A,C,nt", [(64, 5, 256), (256, 2, 96)])
-def test_integration_is_the_exact_sum_rounded_once(gpu, A, C, nt):
+def test_integration_is_the_exact_sum_rounded_once(gpu, case, A, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     P = c.power()
     assert np.array_equal(P, block_power(c.ant))
     for n in (1, 2, c.nblk):
@@ -265,8 +253,8 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, A, C, nt):
     assert same_bits(both, integrate(P2, n, prior=integrate(P, n))) is None
     # a bad blocks_per_spectrum and buffers one byte short are refused, nothing is enqueued, the stream stays usable
     s = gpu.Stream()
-    gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY)
-    gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY)
+    c.refill(c.d_s)
+    c.refill(c.d_p)
     gpu.synchronize()
     for bad in (0, c.nblk + 1, 3 if c.nblk % 3 else 5):
         with pytest.raises(DcsError) as e:
@@ -288,42 +276,36 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, A, C, nt):
         c.g.incoherent_block_power(int(c.d_ant) + 8, c.ant.nbytes, c.d_p, c.pbytes, nt, stream=s.handle)
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
     s.synchronize()
-    host = np.empty(c.pbytes + CANARY, dtype=np.uint8)
     for d in (c.d_s, c.d_p):
-        gpu.memcpy_dtoh(host, d)
-        assert np.all(host == 0xA5)
+        assert np.all(c.read(d) == 0xA5)
     c.call_power(stream=s.handle)
     c.call_integrate(2, stream=s.handle)
     s.synchronize()
     assert np.array_equal(c.read_power(), P2) and same_bits(c.read_spectra(2), integrate(P2, 2)) is None
-    c.close()
 
 
 @pytest.mark.parametrize("A,C,nt", [(64, 3, 48), (130, 2, 32)])
-def test_outputs_at_an_address_that_is_4_byte_aligned_only(gpu, A, C, nt):
+def test_outputs_at_an_address_that_is_4_byte_aligned_only(gpu, case, A, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     w = seeded_flags(A)
     gpu.memcpy_htod(c.d_ant, c.ant)
     ref = block_power(c.ant, w)
-    d_w = gpu.mem_alloc(A * 4 + 16)
+    d_w = c.alloc(A * 4 + 16)
     gpu.memcpy_htod(int(d_w) + 4, w)
-    d_big = gpu.mem_alloc(c.pbytes + CANARY + 16)
-    gpu.memset(d_big, 0xA5, c.pbytes + CANARY + 16)
+    d_big = c.out(c.pbytes + 16)
     c.g.incoherent_block_power(c.d_ant, c.ant.nbytes, int(d_big) + 4, c.pbytes, nt, d_weights=int(d_w) + 4)
     gpu.synchronize()
-    host = np.empty(c.pbytes + CANARY + 16, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_big)
+    host = c.read(d_big)
     assert np.all(host[:4] == 0xA5) and np.all(host[4 + c.pbytes:] == 0xA5)
     assert np.array_equal(host[4:4 + c.pbytes].view(np.uint32).reshape(C, c.nblk), ref)
     # ... and integrated from there, into spectra that are 4-byte aligned only
-    d_sp = gpu.mem_alloc(c.pbytes + CANARY + 16)
-    gpu.memset(d_sp, 0xA5, c.pbytes + CANARY + 16)
+    d_sp = c.out(c.pbytes + 16)
     nb = c.spectra_bytes(c.nblk)
     c.g.integrate_incoherent_power(int(d_big) + 4, c.pbytes, c.nblk, c.nblk, int(d_sp) + 4, nb)
     gpu.synchronize()
-    gpu.memcpy_dtoh(host, d_sp)
+    host = c.read(d_sp)
     assert np.all(host[:4] == 0xA5) and np.all(host[4 + nb:] == 0xA5)
     assert same_bits(host[4:4 + nb].view(np.float32).reshape(1, C), integrate(ref, c.nblk)) is None
     for args in ((int(d_big) + 2, None), (int(d_big), int(d_w) + 2)):  # 2-byte alignment is refused
@@ -334,18 +316,14 @@ def test_outputs_at_an_address_that_is_4_byte_aligned_only(gpu, A, C, nt):
         with pytest.raises(DcsError) as e:
             c.g.integrate_incoherent_power(p_in, c.pbytes, c.nblk, c.nblk, p_out, nb)
         assert e.value.status == DCS_ERR_INVALID_ARGUMENT
-    d_big.free()
-    d_sp.free()
-    d_w.free()
-    c.close()
 
 
 @pytest.mark.parametrize("A,C,nt", [(64, 3, 64), (130, 3, 64)])
-def test_captured_first_calls_pick_up_new_samples_on_replay(gpu, A, C, nt):
+def test_captured_first_calls_pick_up_new_samples_on_replay(gpu, case, A, C, nt):
     """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates, so nothing has to be run
     outside the capture first -- replayed with new samples in the same buffer (the process's default queue count is
     left as it is)."""
-    c = ICase(gpu, A, C, nt)
+    c = case(A, C, nt)
     n = 2
     w = seeded_flags(A)
     gpu.memcpy_htod(c.d_w, w)
@@ -358,11 +336,10 @@ def test_captured_first_calls_pick_up_new_samples_on_replay(gpu, A, C, nt):
     assert not np.array_equal(refs[0], refs[1])
     for i in (1, 2, 0, 1):
         gpu.memcpy_htod(c.d_ant, ants[i], stream=s.handle, sync=False)
-        gpu.memset(c.d_p, 0xA5, c.pbytes + CANARY, stream=s.handle)
-        gpu.memset(c.d_s, 0xA5, c.pbytes + CANARY, stream=s.handle)
+        c.refill(c.d_p, stream=s.handle)
+        c.refill(c.d_s, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read_power(), refs[i]), i
         assert same_bits(c.read_spectra(n), integrate(refs[i], n)) is None, i
     graph.close()
-    c.close()

@@ -23,61 +23,28 @@ from helpers.beam_complex_model import complex_model
 from helpers.beam_power_model import block_power, integrate as integrate_power
 from helpers.beam_quant_model import quantise
 from helpers.beamformer_model import (acc_model, all_pairs_fast, first_difference, fused_model, normalise, weighted_coefficients)
+from helpers.device_buffers import DeviceBuffers
 from helpers.filterbank_model import same_bits
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 PREFILL = 0xA5
 DEVICE_LIMIT = 24 << 30
 
 
-class Mem:
-    """The device memory of one test: counted, and freed whatever the test's end."""
-
-    def __init__(self, gpu, record_property):
-        self.gpu, self.record, self.held, self.total = gpu, record_property, [], 0
-
-    def alloc(self, nbytes):
-        self.total += nbytes
-        assert self.total <= DEVICE_LIMIT, self.total
-        a = self.gpu.mem_alloc(nbytes)
-        self.held.append(a)
-        return a
-
-    def filled(self, nbytes, pattern):
-        d = self.alloc(nbytes)
-        lt.fill(self.gpu, d, nbytes, pattern)
-        return d
-
-    def out(self, nbytes):
-        """Exactly sized plus the canary, prefilled."""
-        d = self.alloc(nbytes + CANARY)
-        self.gpu.memset(d, PREFILL, nbytes + CANARY)
-        return d
-
-    def close(self):
-        self.gpu.synchronize()
-        for a in self.held:
-            a.free()
-        self.record("device bytes held", self.total)
-
-
 @pytest.fixture
 def mem(gpu, record_property):
-    m = Mem(gpu, record_property)
+    """The device memory of one test: counted, and freed whatever the test's end."""
+    m = DeviceBuffers(gpu, limit=DEVICE_LIMIT)
     yield m
     m.close()
+    record_property("device bytes held", m.total)
 
 
-def prefill(gpu, d, nbytes):
-    gpu.memset(d, PREFILL, nbytes + CANARY)
-
-
-def canary_untouched(gpu, d, nbytes):
-    tail = np.empty(CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(tail, int(d) + nbytes)
-    assert np.all(tail == PREFILL), "written past the output tensor"
+def filled(mem, nbytes, pattern):
+    d = mem.alloc(nbytes)
+    lt.fill(mem.gpu, d, nbytes, pattern)
+    return d
 
 
 def not_trivial(exp):
@@ -106,7 +73,7 @@ class BF:
         self.g.upload_delays(self.table)
         self.gen.upload_delays(self.table_ab)
         self.pattern = lt.int8_pattern(self.rb_in, seed=1000 * A + seed)
-        self.d_ant = mem.filled(self.in_bytes, self.pattern)
+        self.d_ant = filled(mem, self.in_bytes, self.pattern)
         self.d_out = mem.out(self.out_bytes)
         self.d_w = mem.alloc(B * A * 4)
         self.sample = lt.plan(self.rb_in, self.rb_out, self.rows, seed=A + B + C)
@@ -118,19 +85,15 @@ class BF:
     def coefficient_bits(self, channels, dts):
         """fp32 [len(dts)][len(channels)][A][B][2] from the GPU generator, one slab per channel, each asserted within 1 ULP
         of the oracle."""
-        gpu = self.gpu
         dts = np.ascontiguousarray(np.atleast_1d(np.asarray(dts, dtype=np.float32)))
         nbytes = dts.size * self.A * self.B * 8
-        if self._buf is None or self._buf.nbytes < nbytes + 64:
-            self._buf = self.mem.alloc(nbytes + 64)
+        if self._buf is None or self._buf_bytes < nbytes:
+            self._buf, self._buf_bytes = self.mem.out(nbytes, 0xFF, 0xFF), nbytes
         out = np.empty((dts.size, len(channels), self.A, self.B, 2), dtype=np.float32)
-        host = np.empty(nbytes + 64, dtype=np.uint8)
         for i, c in enumerate(channels):
-            gpu.memset(self._buf, 0xFF, nbytes + 64)
+            self.mem.refill(self._buf)
             self.gen.generate_slab_dt(self._buf, nbytes, int(c), 1, dts)
-            gpu.memcpy_dtoh(host, self._buf)
-            assert np.all(host[nbytes:] == 0xFF)
-            coef = host[:nbytes].view(np.float32).reshape(dts.size, 1, self.A, self.B, 2)
+            coef = self.mem.read(self._buf, nbytes, np.float32, (dts.size, 1, self.A, self.B, 2))
             res = self.oracle.compare_generated(self.op, self.table_ab, dts, int(c), 1, np.ascontiguousarray(coef), nthreads=8)
             assert res["max_ulp"] <= 1 and res["first_over_1ulp"] == -1 and sum(res["hist"]) == coef.size, (int(c), res)
             out[:, i] = coef[:, 0]
@@ -161,11 +124,11 @@ class BF:
 
     def run(self, call):
         """``call(stream)`` into the prefilled output; the sampled rows' bytes, the canary checked."""
-        prefill(self.gpu, self.d_out, self.out_bytes)
+        self.mem.refill(self.d_out)
         call(None)
         self.gpu.synchronize()
         got = lt.read_rows(self.gpu, self.d_out, self.rb_out, self.sample)
-        canary_untouched(self.gpu, self.d_out, self.out_bytes)
+        self.mem.guard_untouched(self.d_out)
         return got
 
     def check_floats(self, what, call, exp):
@@ -304,11 +267,11 @@ def test_block_power_and_its_integration(gpu, oracle, mem, record_property, name
         index = np.searchsorted(members, (ch * K + group * n)[:, None] + np.arange(n)[None, :])
         exp = integrate_power(P[index], n)[0]  # [m][n][B] as [C'][blocks][B] -> [1][m][B]
         not_trivial(exp)
-        prefill(gpu, d_s, c.out_bytes)
+        mem.refill(d_s)
         c.g.integrate_block_power(c.d_out, c.out_bytes, K, n, d_s, sbytes)
         gpu.synchronize()
         got = lt.read_rows(gpu, d_s, rb, out_rows).view(np.float32)
-        canary_untouched(gpu, d_s, sbytes)
+        mem.guard_untouched(d_s, sbytes)
         assert same_bits(got, exp) is None, (n, same_bits(got, exp))
     c.close()
 
@@ -357,7 +320,7 @@ def test_stokes_block(gpu, mem):
     in_bytes = rows * rb_in
     bp, g = context(C, B=B, nt=nt)
     px, py = lt.int8_pattern(rb_in, seed=1), lt.int8_pattern(rb_in, seed=2)
-    d_x, d_y = mem.filled(in_bytes, px), mem.filled(in_bytes, py)
+    d_x, d_y = filled(mem, in_bytes, px), filled(mem, in_bytes, py)
     d_bs = mem.out(rows * B * 16)
     assert in_bytes > 2 * lt.LINE and rows * B * 16 > lt.LINE
     for ns in (4, 1):
@@ -367,11 +330,11 @@ def test_stokes_block(gpu, mem):
         y = lt.rows_of(py, sample).view(np.int8).reshape(-1, 1, B, 16, 2)
         exp = stokes_model.block_stokes(x, y, ns)
         not_trivial(exp)
-        prefill(gpu, d_bs, rows * B * 16)
+        mem.refill(d_bs)
         g.stokes_block(d_x, d_y, in_bytes, d_bs, rows * rb_out, nt, nr_stokes=ns)
         gpu.synchronize()
         got = lt.read_rows(gpu, d_bs, rb_out, sample).view(np.int32).reshape(exp.shape)
-        canary_untouched(gpu, d_bs, rows * rb_out)
+        mem.guard_untouched(d_bs, rows * rb_out)
         assert np.array_equal(got, exp), (ns, sample[np.argwhere(got != exp)[:4, 0]], np.argwhere(got != exp)[:4])
     g.close()
 
@@ -387,7 +350,7 @@ def test_integrate_stokes(gpu, mem):
     in_bytes = rows * rb
     bp, g = context(C, B=B, nt=nt)
     pattern = lt.stokes_int32_pattern(B * ns, seed=3)
-    d_bs = mem.filled(in_bytes, pattern)
+    d_bs = filled(mem, in_bytes, pattern)
     d_s = mem.out(in_bytes)
     assert in_bytes > lt.LINE
     for n in (1, 5):
@@ -406,11 +369,11 @@ def test_integrate_stokes(gpu, mem):
             S = block.astype(np.int64).sum(axis=1)
             inexact = (np.abs(S) > 1 << 24) & (exp.astype(np.float64) != S)
             assert (inexact & (S > 0)).any() and (inexact & (S < 0)).any()
-        prefill(gpu, d_s, in_bytes)
+        mem.refill(d_s)
         g.integrate_stokes(d_bs, in_bytes, K, n, ns, d_s, sbytes)
         gpu.synchronize()
         got = lt.read_rows(gpu, d_s, rb, out_rows).view(np.float32).reshape(exp.shape)
-        canary_untouched(gpu, d_s, sbytes)
+        mem.guard_untouched(d_s, sbytes)
         assert same_bits(got, exp) is None, (n, same_bits(got, exp))
     g.close()
 
@@ -424,7 +387,7 @@ def test_incoherent_block_power(gpu, mem, A, C, nt):
     assert lt.LINE < in_bytes < 1.04 * lt.LINE
     bp, g = context(C, A=A, nt=nt)
     pattern = lt.int8_pattern(rb_in, seed=A)
-    d_ant = mem.filled(in_bytes, pattern)
+    d_ant = filled(mem, in_bytes, pattern)
     d_p = mem.out(rows * 4)
     # a row is one value here: 192 seeded rows more, so that the expectation has its 100 distinct values
     sample = lt.plan(rb_in, 4, rows, seed=A, extra=np.random.default_rng(A + 1).integers(0, rows, size=192))
@@ -432,10 +395,7 @@ def test_incoherent_block_power(gpu, mem, A, C, nt):
     not_trivial(exp)
     g.incoherent_block_power(d_ant, in_bytes, d_p, rows * 4, nt)
     gpu.synchronize()
-    host = np.empty(rows * 4 + CANARY, dtype=np.uint8)
-    gpu.memcpy_dtoh(host, d_p)
-    assert np.all(host[rows * 4:] == PREFILL), "written past the output tensor"
-    got = host[:rows * 4].view(np.uint32)[sample]
+    got = mem.read(d_p, rows * 4, np.uint32)[sample]
     assert np.array_equal(got, exp), (sample[np.flatnonzero(got != exp)[:4]], got[got != exp][:4], exp[got != exp][:4])
     g.close()
 
@@ -454,15 +414,9 @@ def test_filterbank_calls_on_spectra_past_the_line(gpu, mem):
     assert lt.LINE < xbytes < 1.04 * lt.LINE
     bp, g = context(C)
     pattern = lt.spectra_pattern(NB, seed=5)  # rows (spectrum, channel) of NB floats
-    d_x = mem.filled(xbytes, pattern)
+    d_x = filled(mem, xbytes, pattern)
     ub, kb, fb = spectra_sums_bytes(bp, NB), filterbank_scales_bytes(bp, NB), filterbank_bytes(bp, NB, T)
     d_sums, d_scales, d_fb, d_clip = mem.out(ub), mem.out(kb), mem.out(fb), mem.alloc(NB * 8)
-
-    def read(d, nbytes, dtype, shape):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == PREFILL), "written past an output"
-        return host[:nbytes].view(dtype).reshape(shape)
 
     # ---- sums and scales of 258 series
     rng = np.random.default_rng(6)
@@ -473,9 +427,9 @@ def test_filterbank_calls_on_spectra_past_the_line(gpu, mem):
     g.spectra_sums(d_x, xbytes, T, NB, d_sums, ub)
     g.filterbank_scales(d_sums, ub, T, NB, TARGET_STD, d_scales, kb)
     gpu.synchronize()
-    sums = read(d_sums, ub, np.float64, (C, NB, 2))
+    sums = mem.read(d_sums, ub, np.float64, (C, NB, 2))
     assert same_bits(sums[cs, bs], exp_sums[:, 0]) is None, same_bits(sums[cs, bs], exp_sums[:, 0])
-    scales = read(d_scales, kb, np.float32, (C, NB, 2)).copy()
+    scales = mem.read(d_scales, kb, np.float32, (C, NB, 2))
     exp_scales = filterbank_model.scales(exp_sums, T, TARGET_STD)
     assert same_bits(scales[cs, bs], exp_scales[:, 0]) is None, same_bits(scales[cs, bs], exp_scales[:, 0])
     assert np.unique(exp_sums).size >= 100 and np.unique(exp_scales).size >= 100
@@ -489,12 +443,12 @@ def test_filterbank_calls_on_spectra_past_the_line(gpu, mem):
     out_rows = (np.arange(NB)[:, None] * T + ts[None, :]).ravel()
     for descending in (False, True):
         exp = np.transpose(q[:, ::-1] if descending else q, (2, 0, 1)).reshape(-1, C)
-        prefill(gpu, d_fb, fb)
+        mem.refill(d_fb)
         gpu.memset(d_clip, 0, NB * 8)
         g.filterbank_q8(d_x, xbytes, T, NB, d_scales, LEVEL, d_fb, fb, T, descending=descending, d_clip_count=d_clip)
         gpu.synchronize()
         got = lt.read_rows(gpu, d_fb, C, out_rows)
-        canary_untouched(gpu, d_fb, fb)
+        mem.guard_untouched(d_fb)
         assert same_bits(got, exp) is None, (descending, same_bits(got, exp))
         clips = np.empty(NB, dtype=np.uint64)
         gpu.memcpy_dtoh(clips, d_clip)
@@ -532,10 +486,10 @@ def test_filterbank_into_a_ring_past_the_line(gpu, mem):
         for i in np.flatnonzero(spectrum >= first):
             row = q[spectrum[i] - first, :, beam[i]]
             exp[i] = row[::-1] if descending else row
-        prefill(gpu, d_fb, fb)
+        mem.refill(d_fb)
         g.filterbank_q8(d_x, x.nbytes, T, NB, d_scales, LEVEL, d_fb, fb, out_spectra, first_spectrum=first, descending=descending)
         gpu.synchronize()
         got = lt.read_rows(gpu, d_fb, C, sample)
-        canary_untouched(gpu, d_fb, fb)
+        mem.guard_untouched(d_fb)
         assert same_bits(got, exp) is None, (descending, same_bits(got, exp), sample)
     g.close()

@@ -756,14 +756,10 @@ EXAMPLE_CLOSING = {
 def test_examples_run_and_verify_themselves(gpu, script, args):
     """examples/: all eight scripts on small shapes, a fresh process each; each verifies its own output (against the oracle,
     a model, or the source it planted), says so in its closing line and exits 0."""
-    import subprocess
-    import sys
-    from pathlib import Path
+    from helpers.examples import run_example
 
-    root = Path(__file__).resolve().parent.parent
-    res = subprocess.run([sys.executable, str(root / "examples" / script), *args], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
-    assert EXAMPLE_CLOSING[script] in res.stdout, res.stdout[-1500:]
+    out = run_example(script, *args)
+    assert EXAMPLE_CLOSING[script] in out, out[-1500:]
 
 
 def test_cpp_host_against_c_abi(gpu):

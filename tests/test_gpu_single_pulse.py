@@ -3,62 +3,31 @@ peaks are integers, the signal-to-noise is compared as float bits, all with the 
 anchored on the CPU by tests/test_single_pulse_model.py).  Every buffer is exactly sized: a plane's last word that a call
 may read ends where its allocation ends; every output has a 0xA5 canary behind it, which must stay untouched; the outputs
 are prefilled, and every word outside the blocks of the call must stay as it was."""
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from helpers import hip_graph
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
+from helpers.device_buffers import Context
+from helpers.examples import run_example
 from helpers.single_pulse_model import CHAIN, NO_TIME, chain_filterbank, nr_blocks_of, peaks, snr, sums
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-CANARY = 64
 PREFILL = 0x3C
 PREFILL_WORD = 0x3C3C3C3C
 PREFILL_FLOAT = np.frombuffer(bytes([PREFILL] * 4), np.float32)[0]
 
 
-class SCase:
+class SCase(Context):
     """One context (the search has no coefficients and uses none of its parameters; nr_beams is an argument) and the device
     buffers of its calls, exactly sized, outputs with a canary behind; all freed by close()."""
 
     def __init__(self, gpu):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-        self.gpu = gpu
-        self.bp = BeamformerParameters(NR_CHANNELS=64, NR_STATIONS=1, NR_BEAMS=1)
-        self.g = SteeringCoefficientGenerator(self.bp)
-        self.held = []
-
-    def alloc(self, nbytes):
-        a = self.gpu.mem_alloc(max(nbytes, 1))
-        self.held.append(a)
-        return a
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            self.gpu.memcpy_htod(d, a)
-        return d
+        super().__init__(gpu, 64)
 
     def out(self, nbytes, prefill=PREFILL):
-        d = self.alloc(nbytes + CANARY)
-        self.gpu.memset(d, prefill, nbytes)
-        self.gpu.memset(int(d) + nbytes, 0xA5, CANARY)
-        return d
-
-    def read(self, d, nbytes, dtype, shape):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == 0xA5), "written past the tensor"
-        return host[:nbytes].view(dtype).reshape(shape).copy()
+        return super().out(nbytes, prefill)
 
     def peaks(self, plane, first, T, widths, max_width, block_len, peak_blocks=None, first_block=0):
         """One dcs_bf_boxcar_peaks call into a prefilled peak plane, held to the model: the whole peak plane."""
@@ -115,11 +84,6 @@ class SCase:
         best = self.read(d_best, bbytes, np.uint32, (B, nr_dm, pb))
         assert np.array_equal(best, exp_best), np.argwhere(best != exp_best)[:3]
         return got, best
-
-    def close(self):
-        self.g.close()
-        for a in self.held:
-            a.free()
 
 
 def seeded_plane(B, nr_dm, spectra, seed, top=1 << 20):
@@ -322,7 +286,7 @@ def test_short_buffers_are_refused_and_nothing_is_enqueued(case, gpu):
 
 # ------------------------------------------------------------------------------------------------------------------ capture
 
-def test_three_calls_captured_and_replayed_with_new_contents(gpu):
+def test_three_calls_captured_and_replayed_with_new_contents(case, gpu):
     """All three as first calls on a fresh context, captured; replayed after the plane words, the width list and the sums
     that the signal-to-noise reads were changed on the device: the outputs follow the new contents."""
     from dc_sand_amd.generator import best_width_bytes, boxcar_peaks_bytes, dm_time_bytes, dm_time_sums_bytes, peak_snr_bytes
@@ -330,7 +294,7 @@ def test_three_calls_captured_and_replayed_with_new_contents(gpu):
     B, nr_dm, T, nw, max_width, block_len, first, first_block, pb = 2, 3, 700, 4, 50, 128, 2, 1, 8
     ps = first + T + max_width - 1
     nb = nr_blocks_of(T, block_len)
-    c = SCase(gpu)
+    c = case
     pbytes, sbytes = dm_time_bytes(B, nr_dm, ps), dm_time_sums_bytes(B, nr_dm)
     kbytes, nbytes, bbytes = boxcar_peaks_bytes(B, nr_dm, nw, pb), peak_snr_bytes(B, nr_dm, nw, pb), best_width_bytes(B, nr_dm, pb)
     d_plane, d_widths, d_sums_in = c.alloc(pbytes), c.alloc(nw * 4), c.alloc(sbytes)
@@ -367,7 +331,6 @@ def test_three_calls_captured_and_replayed_with_new_contents(gpu):
         seen.append((got, got_snr))
     assert not np.array_equal(seen[0][0], seen[1][0]) and not np.array_equal(seen[1][1], seen[2][1])
     graph.close()
-    c.close()
 
 
 # -------------------------------------------------------------------------------------------------------------------- chain
@@ -417,7 +380,5 @@ def test_the_chain_recovers_the_injected_pulse(case, gpu):
 # ------------------------------------------------------------------------------------------------------------------ example
 
 def test_example_runs_and_verifies_itself(gpu):
-    res = subprocess.run([sys.executable, str(ROOT / "examples" / "single_pulse_search.py"), "64", "2", "24", "1024"], capture_output=True,
-                         text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
-    assert "bit-identical to the model: True" in res.stdout and "the pulse is recovered: True" in res.stdout
+    out = run_example("single_pulse_search.py", 64, 2, 24, 1024)
+    assert "bit-identical to the model: True" in out and "the pulse is recovered: True" in out

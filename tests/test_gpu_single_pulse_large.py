@@ -9,47 +9,20 @@ import pytest
 
 from helpers import large_tensor as lt
 from helpers import single_pulse_large as sl
+from helpers.device_buffers import Context
 from helpers.single_pulse_model import nr_blocks_of, peaks, snr, sums
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 PREFILL = 0xA5
 PREFILL_WORD = 0xA5A5A5A5
 
 
 @pytest.fixture
 def case(gpu):
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator
-
-    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=64, NR_STATIONS=1, NR_BEAMS=1))
-    held = []
-
-    def alloc(nbytes, fill=None):
-        held.append(gpu.mem_alloc(nbytes))
-        if fill is not None:
-            gpu.memset(held[-1], fill, nbytes)
-        return held[-1]
-
-    def upload(a):
-        a = np.ascontiguousarray(a)
-        d = alloc(a.nbytes)
-        gpu.memcpy_htod(d, a)
-        return d
-
-    yield g, alloc, upload
-    gpu.synchronize()
-    g.close()
-    for a in held:
-        a.free()
-
-
-def read(gpu, d, nbytes, dtype, shape):
-    host = np.empty(nbytes + CANARY, np.uint8)
-    gpu.memcpy_dtoh(host, d)
-    assert np.all(host[nbytes:] == PREFILL), "written past the tensor"
-    return host[:nbytes].view(dtype).reshape(shape)
+    c = Context(gpu, 64)
+    yield c
+    c.close()
 
 
 def test_plane_past_the_line(gpu, case):
@@ -57,7 +30,7 @@ def test_plane_past_the_line(gpu, case):
     and the peaks of 5000 times from windows that end below the line, straddle it and begin above it, all four series at once."""
     from dc_sand_amd.generator import boxcar_peaks_bytes, dm_time_bytes, dm_time_sums_bytes
 
-    g, alloc, upload = case
+    g, alloc, upload = case.g, case.alloc, case.upload
     k = sl.PLANE
     B, nr_dm, ps, T, max_width, block_len = k["B"], k["nr_dm"], k["plane_spectra"], k["T"], k["max_width"], k["block_len"]
     widths = np.array(k["widths"], np.uint32)
@@ -69,20 +42,20 @@ def test_plane_past_the_line(gpu, case):
     d_widths = upload(widths)
     nb = nr_blocks_of(T, block_len)
     sbytes, kbytes = dm_time_sums_bytes(B, nr_dm), boxcar_peaks_bytes(B, nr_dm, widths.size, nb)
-    d_sums, d_peaks = alloc(sbytes + CANARY), alloc(kbytes + CANARY)
+    d_sums, d_peaks = case.out(sbytes), case.out(kbytes)
     for first in sl.plane_firsts():
         assert 0 <= first and first + sl.PLANE_WINDOW <= ps
-        gpu.memset(d_sums, PREFILL, sbytes + CANARY)
-        gpu.memset(d_peaks, PREFILL, kbytes + CANARY)
+        case.refill(d_sums)
+        case.refill(d_peaks)
         g.dm_time_sums(d_plane, nbytes, ps, first, T, B, nr_dm, d_sums, sbytes)
         g.boxcar_peaks(d_plane, nbytes, ps, first, T, B, nr_dm, d_widths, widths.size, max_width, block_len, d_peaks, kbytes, nb)
         gpu.synchronize()
         window = sl.plane_window(pattern, first)  # [1][4][T + max_width - 1] from the pattern
         exp_sums, exp_peaks = sums(window, 0, T), peaks(window, 0, T, widths, max_width, block_len)
         assert np.unique(exp_peaks[..., 1]).size >= 50 and not np.array_equal(exp_peaks[0, 0], exp_peaks[0, 3])
-        got_sums = read(gpu, d_sums, sbytes, np.uint64, exp_sums.shape)
+        got_sums = case.read(d_sums, sbytes, np.uint64, exp_sums.shape)
         assert np.array_equal(got_sums, exp_sums), (first, got_sums, exp_sums)
-        got = read(gpu, d_peaks, kbytes, np.uint32, exp_peaks.shape)
+        got = case.read(d_peaks, kbytes, np.uint32, exp_peaks.shape)
         assert np.array_equal(got, exp_peaks), (first, np.argwhere(got != exp_peaks)[:3])
     # what the device holds is the pattern: the words on both sides of the line, read back
     rows = np.array([0, 1, lt.LINE // 4096 - 1, lt.LINE // 4096, nbytes // 4096 - 1], dtype=np.int64)
@@ -94,7 +67,7 @@ def test_peak_plane_past_the_line(gpu, case):
     width) row: those of the last row lie past the line, and the entries 4 GiB below them keep the prefill."""
     from dc_sand_amd.generator import boxcar_peaks_bytes
 
-    g, alloc, upload = case
+    g, upload = case.g, case.upload
     k = sl.PEAKS_OUT
     B, nr_dm, pb, T, block_len, max_width = k["B"], k["nr_dm"], k["peak_blocks"], k["T"], k["block_len"], k["max_width"]
     widths = np.array(sl.WIDTHS_OUT, np.uint32)
@@ -103,7 +76,7 @@ def test_peak_plane_past_the_line(gpu, case):
     assert lt.LINE < kbytes < 1.01 * lt.LINE and written[-1] * row_bytes > lt.LINE and alias.size == 1
     plane = np.random.default_rng(32).integers(0, 1 << 20, size=(B, nr_dm, 3 + T + max_width - 1), dtype=np.uint32)
     d_plane, d_widths = upload(plane), upload(widths)
-    d_peaks = alloc(kbytes + CANARY, PREFILL)
+    d_peaks = case.out(kbytes)
     g.boxcar_peaks(d_plane, plane.nbytes, plane.shape[2], 3, T, B, nr_dm, d_widths, widths.size, max_width, block_len, d_peaks, kbytes,
                    pb, first_block=pb - sl.ROW_BLOCKS)
     gpu.synchronize()
@@ -114,9 +87,7 @@ def test_peak_plane_past_the_line(gpu, case):
     assert not set(untouched.tolist()) & set(written.tolist())
     kept = lt.read_rows(gpu, d_peaks, row_bytes, untouched).view(np.uint32)
     assert np.all(kept == PREFILL_WORD), "a block outside [first_block, first_block + nr_blocks) was written"
-    tail = np.empty(CANARY, np.uint8)
-    gpu.memcpy_dtoh(tail, int(d_peaks) + kbytes)
-    assert np.all(tail == PREFILL), "written past the peak plane"
+    case.guard_untouched(d_peaks)
 
 
 def test_signal_to_noise_past_the_line_from_peaks_past_two(gpu, case):
@@ -124,7 +95,7 @@ def test_signal_to_noise_past_the_line_from_peaks_past_two(gpu, case):
     blocks of every (DM, width) row.  The peaks elsewhere hold the prefill, so an entry read 4 or 8 GiB low gives other figures."""
     from dc_sand_amd.generator import best_width_bytes, boxcar_peaks_bytes, peak_snr_bytes
 
-    g, alloc, upload = case
+    g, alloc, upload = case.g, case.alloc, case.upload
     k = sl.SNR_OUT
     B, nr_dm, pb, count, max_width = k["B"], k["nr_dm"], k["peak_blocks"], k["count"], k["max_width"]
     widths = np.array(sl.WIDTHS_OUT, np.uint32)
@@ -137,7 +108,8 @@ def test_signal_to_noise_past_the_line_from_peaks_past_two(gpu, case):
     plane = np.random.default_rng(33).integers(0, 1 << 20, size=(B, nr_dm, nblk * 64 + max_width - 1), dtype=np.uint32)
     pk = peaks(plane, 0, nblk * 64, widths, max_width, 64)  # [1][4][4][16][2]
     sm = sums(plane, 0, count)
-    d_peaks, d_snr, d_best = alloc(kbytes, PREFILL), alloc(nbytes + CANARY, PREFILL), alloc(bbytes + CANARY, PREFILL)
+    d_peaks, d_snr, d_best = alloc(kbytes), case.out(nbytes), case.out(bbytes)
+    gpu.memset(d_peaks, PREFILL, kbytes)
     for row, values in zip(pwritten, pk.reshape(-1, nblk * 2)):
         gpu.memcpy_htod(int(d_peaks) + int(row) * prow, np.ascontiguousarray(values))
     d_widths, d_sums = upload(widths), upload(sm)
@@ -157,7 +129,5 @@ def test_signal_to_noise_past_the_line_from_peaks_past_two(gpu, case):
     bwritten = np.array([(m + 1) * per - 1 for m in range(nr_dm)], dtype=np.int64)
     assert np.array_equal(lt.read_rows(gpu, d_best, brow, bwritten).view(np.uint32), exp_best.reshape(nr_dm, nblk))
     assert np.all(lt.read_rows(gpu, d_best, brow, bwritten - 1).view(np.uint32) == PREFILL_WORD)
-    for d, n in ((d_snr, nbytes), (d_best, bbytes)):
-        tail = np.empty(CANARY, np.uint8)
-        gpu.memcpy_dtoh(tail, int(d) + n)
-        assert np.all(tail == PREFILL), "written past the tensor"
+    case.guard_untouched(d_snr)
+    case.guard_untouched(d_best)

@@ -3,17 +3,19 @@ tolerance anywhere: the block Stokes parameters are compared as integers and the
 (helpers/stokes_model.py, anchored on the CPU by tests/test_stokes_model.py).  Both beam tensors are exactly sized, so their
 last row ends where the allocation ends, and every output is exactly sized with a canary behind it, which must stay
 untouched."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from conftest import rand_table
 from helpers import filterbank_model, hip_graph
+from helpers.device_buffers import Context, closed_after
 from helpers.filterbank_model import same_bits  # bit for bit; two NaNs agree (their payload is the implementation's)
 from helpers.stokes_model import block_stokes, integrate
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 64
 BOTH = (4, 1)
 
 
@@ -33,29 +35,27 @@ def filled(shape, re, im):
     return a
 
 
-class SCase:
+class SCase(Context):
     """One context of B beams and C channels (no delay table: the detection has no coefficients), the two beam tensors
     and the two outputs, sized for IQUV; with nr_stokes = 1 the canary begins where the smaller tensor ends."""
 
     def __init__(self, gpu, B, C, nt, seed=0, same_pointer=False):
-        from dc_sand_amd import BeamformerParameters
-        from dc_sand_amd.generator import SteeringCoefficientGenerator, block_stokes_bytes, quantised_beams_bytes, stokes_spectra_bytes
+        from dc_sand_amd.generator import block_stokes_bytes, quantised_beams_bytes, stokes_spectra_bytes
 
-        self.gpu, self.B, self.C, self.nt, self.nblk = gpu, B, C, nt, nt // 16
-        self.bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
-        self.g = SteeringCoefficientGenerator(self.bp)
+        super().__init__(gpu, C, B=B, NR_SAMPLES_PER_CHANNEL=nt)
+        self.nt, self.nblk = nt, nt // 16
         self.x, self.y = seeded_beams(B, C, nt, seed)
         self.bbytes = quantised_beams_bytes(self.bp, nt)
         assert self.bbytes == self.x.nbytes == C * nt * B * 2
-        self.d_x = gpu.mem_alloc(self.bbytes)
-        self.d_y = self.d_x if same_pointer else gpu.mem_alloc(self.bbytes)
+        self.d_x = self.alloc(self.bbytes)
+        self.d_y = self.d_x if same_pointer else self.alloc(self.bbytes)
         self.sbytes = lambda ns: block_stokes_bytes(self.bp, nt, ns)
         self.spectra_bytes = lambda n, ns: stokes_spectra_bytes(self.bp, self.nblk, n, ns)
         assert self.sbytes(4) == C * self.nblk * B * 16 and self.sbytes(1) == C * self.nblk * B * 4
-        self.d_bs = gpu.mem_alloc(self.sbytes(4) + CANARY)
-        self.d_s = gpu.mem_alloc(self.sbytes(4) + CANARY)  # spectra: at most one per block
+        self.d_bs = self.out(self.sbytes(4))
+        self.d_s = self.out(self.sbytes(4))  # spectra: at most one per block
 
-    def upload(self):
+    def put_beams(self):
         self.gpu.memcpy_htod(self.d_x, self.x)
         if self.d_y is not self.d_x:
             self.gpu.memcpy_htod(self.d_y, self.y)
@@ -64,15 +64,12 @@ class SCase:
         self.g.stokes_block(self.d_x, self.d_y, self.bbytes, self.d_bs, self.sbytes(ns), self.nt, nr_stokes=ns, stream=stream)
 
     def read_block(self, ns):
-        host = np.empty(self.sbytes(4) + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_bs)
-        assert np.all(host[self.sbytes(ns):] == 0xA5), "written past the block Stokes tensor"
-        return host[:self.sbytes(ns)].view(np.int32).reshape(self.C, self.nblk, self.B, ns).copy()
+        return self.read(self.d_bs, self.sbytes(ns), np.int32, (self.C, self.nblk, self.B, ns))
 
     def block(self, ns):
         """One call from a clean output buffer."""
-        self.upload()
-        self.gpu.memset(self.d_bs, 0xA5, self.sbytes(4) + CANARY)
+        self.put_beams()
+        self.refill(self.d_bs)
         self.call_block(ns)
         self.gpu.synchronize()
         return self.read_block(ns)
@@ -81,7 +78,7 @@ class SCase:
         """The integration's input given by the test."""
         ns = block.shape[-1]
         assert block.dtype == np.int32 and block.nbytes == self.sbytes(ns)
-        self.gpu.memset(self.d_bs, 0xA5, self.sbytes(4) + CANARY)
+        self.refill(self.d_bs)
         self.gpu.memcpy_htod(self.d_bs, np.ascontiguousarray(block))
 
     def call_integrate(self, n, ns, accumulate=False, stream=None):
@@ -89,15 +86,11 @@ class SCase:
                                 accumulate=accumulate, stream=stream)
 
     def read_spectra(self, n, ns):
-        nb = self.spectra_bytes(n, ns)
-        host = np.empty(self.sbytes(4) + CANARY, dtype=np.uint8)
-        self.gpu.memcpy_dtoh(host, self.d_s)
-        assert np.all(host[nb:] == 0xA5), "written past the spectra"
-        return host[:nb].view(np.float32).reshape(self.nblk // n, self.C, self.B, ns).copy()
+        return self.read(self.d_s, self.spectra_bytes(n, ns), np.float32, (self.nblk // n, self.C, self.B, ns))
 
     def spectra(self, n, ns, prior=None):
         """One integration of what d_bs holds from a clean buffer, accumulating where there is a ``prior``."""
-        self.gpu.memset(self.d_s, 0xA5, self.sbytes(4) + CANARY)
+        self.refill(self.d_s)
         if prior is not None:
             self.gpu.memcpy_htod(self.d_s, np.ascontiguousarray(prior, dtype=np.float32))
         self.call_integrate(n, ns, accumulate=prior is not None)
@@ -113,8 +106,15 @@ class SCase:
             assert got.dtype == want.dtype and np.array_equal(got, want), (what, ns, np.argwhere(got != want)[:4])
         return exp
 
-    def close(self):
-        self.g.close()
+
+@pytest.fixture
+def case(gpu):
+    yield from closed_after(partial(SCase, gpu))
+
+
+@pytest.fixture
+def context(gpu):
+    yield from closed_after(partial(Context, gpu))
 
 
 # one row; a few; exactly one wave of rows and one more; one workgroup of lanes and one more; N = 105, odd and no multiple
@@ -123,11 +123,10 @@ SHAPES = [(1, 1, 16), (3, 5, 48), (64, 1, 16), (65, 1, 16), (257, 1, 16), (7, 3,
 
 
 @pytest.mark.parametrize("B,C,nt", SHAPES)
-def test_block_stokes_is_the_model(gpu, B, C, nt):
-    c = SCase(gpu, B, C, nt)
+def test_block_stokes_is_the_model(gpu, case, B, C, nt):
+    c = case(B, C, nt)
     exp = c.check_block()
     assert np.unique(exp).size >= min(100, exp.size), (np.unique(exp).size, exp.size)  # no trivial expectation
-    c.close()
 
 
 # The kernel's grid is capped at 2048 workgroups of 4 waves, and a wave carries 128 rows (2 per lane) per trip: 512 rows per
@@ -138,14 +137,14 @@ def test_block_stokes_is_the_model(gpu, B, C, nt):
 LOOPING_SHAPE = (64, 8, 32784)
 
 
-def test_block_stokes_when_a_wave_takes_a_second_trip(gpu, record_property):
+def test_block_stokes_when_a_wave_takes_a_second_trip(gpu, case, record_property):
     B, C, nt = LOOPING_SHAPE
-    c = SCase(gpu, B, C, nt)
+    c = case(B, C, nt)
     rows = C * c.nblk * B
     assert c.bbytes < 64 << 20
     exp = block_stokes(c.x, c.y, 4)
     assert np.unique(exp).size >= 100
-    c.upload()
+    c.put_beams()
     for ns in BOTH:
         s = gpu.Stream()
         nodes = hip_graph.launches(s, lambda: c.call_block(ns, stream=s.handle))
@@ -156,28 +155,26 @@ def test_block_stokes_when_a_wave_takes_a_second_trip(gpu, record_property):
         record_property(f"nr_stokes {ns}: gridDim.x, blockDim.x, rows", (grid[0], block[0], rows))
         # 2 rows per lane per trip is the kernel's; with fewer the second trip is only surer
         assert grid[0] * block[0] * 2 < rows, f"{grid[0]} workgroups of {block[0]} lanes take {rows} rows in one trip: raise nt"
-        gpu.memset(c.d_bs, 0xA5, c.sbytes(4) + CANARY)
+        c.refill(c.d_bs)
         c.call_block(ns)
         gpu.synchronize()
         got = c.read_block(ns)
         assert np.array_equal(got, exp[..., :ns]), (ns, np.argwhere(got != exp[..., :ns])[:4])
-    c.close()
 
 
 EDGE = (3, 2, 32)
 
 
-def test_all_minus_128(gpu):
-    c = SCase(gpu, *EDGE)
+def test_all_minus_128(gpu, case):
+    c = case(*EDGE)
     c.x = np.full_like(c.x, -128)
     c.y = np.full_like(c.y, -128)
     exp = c.check_block()
     assert np.all(exp == np.array([1 << 20, 0, 1 << 20, 0], dtype=np.int32))
-    c.close()
 
 
-def test_the_pair_that_makes_ci_extreme(gpu):
-    c = SCase(gpu, *EDGE)
+def test_the_pair_that_makes_ci_extreme(gpu, case):
+    c = case(*EDGE)
     c.x, c.y = filled(c.x.shape, -128, 127), filled(c.x.shape, 127, -128)
     exp = c.check_block()
     p = 16 * (128 * 128 + 127 * 127)
@@ -187,31 +184,28 @@ def test_the_pair_that_makes_ci_extreme(gpu):
     assert np.all(c.check_block() == np.array([1 << 19, 0, 0, 1 << 19], dtype=np.int32))
     c.x, c.y = c.y, c.x
     assert np.all(c.check_block() == np.array([1 << 19, 0, 0, -(1 << 19)], dtype=np.int32))
-    c.close()
 
 
-def test_the_sign_of_v(gpu):
-    c = SCase(gpu, *EDGE)
+def test_the_sign_of_v(gpu, case):
+    c = case(*EDGE)
     c.x, c.y = filled(c.x.shape, 0, 1), filled(c.x.shape, 1, 0)  # x = i, y = 1: V = +2 per sample
     assert np.all(c.check_block() == np.array([32, 0, 0, 32], dtype=np.int32))
-    c.close()
 
 
-def test_both_polarisations_the_same_pointer(gpu):
-    c = SCase(gpu, *EDGE, same_pointer=True)
+def test_both_polarisations_the_same_pointer(gpu, case):
+    c = case(*EDGE, same_pointer=True)
     c.y = c.x
     exp = c.check_block()
     pxx = (c.x.astype(np.int64) ** 2).sum(axis=(3, 4))
     assert np.array_equal(exp[..., 0], 2 * pxx) and np.array_equal(exp[..., 2], 2 * pxx)
     assert not exp[..., 1].any() and not exp[..., 3].any() and np.unique(pxx).size == pxx.size
-    c.close()
 
 
-def test_one_hot_every_byte_of_a_row_is_used_once_with_its_partner(gpu):
+def test_one_hot_every_byte_of_a_row_is_used_once_with_its_partner(gpu, case):
     """x one-hot against y all ones, and the other way round, for each of the 32 byte positions of one row in the middle:
     the hot byte v = 3 + position shows as v^2 in I and Q, as v in U, and in V with the sign of its place ((re, im) of x:
     (-, +); of y: (+, -)); every other row stays what all ones against zeros give."""
-    c = SCase(gpu, *EDGE)
+    c = case(*EDGE)
     rows = c.C * c.nblk * c.B
     hot_row = rows // 2 + 1
     for pos in range(32):
@@ -227,7 +221,6 @@ def test_one_hot_every_byte_of_a_row_is_used_once_with_its_partner(gpu):
             assert exp[hot_row].tolist() == [v * v + 32, q_sign * (v * v - 32), 2 * v, 2 * v_sign * v], (pos, exp[hot_row])
             others = np.delete(exp, hot_row, axis=0)
             assert np.all(others == np.array([32, -32 * q_sign, 0, 0])), pos
-    c.close()
 
 
 def planted_block(C, nblk, B, ns, seed):
@@ -241,11 +234,11 @@ def planted_block(C, nblk, B, ns, seed):
 
 
 @pytest.mark.parametrize("ns", BOTH)
-def test_integration_is_the_exact_sum_rounded_once(gpu, ns):
+def test_integration_is_the_exact_sum_rounded_once(gpu, case, ns):
     """(B, C, nblk) = (7, 3, 12): with IQUV 1008, 504, 336 and 84 output elements for n = 1, 2, 3 and 12 -- three workgroups
     of 256 lanes and a partial fourth, one and a partial second, a partial one -- and a quarter of that with I."""
     B, C, nt = 7, 3, 192
-    c = SCase(gpu, B, C, nt)
+    c = case(B, C, nt)
     block = planted_block(C, c.nblk, B, ns, seed=ns)
     c.set_block(block)
     for n in (1, 2, 3, c.nblk):
@@ -272,16 +265,15 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, ns):
     prior = np.full((1, C, B, ns), -0.0, dtype=np.float32)
     got = c.spectra(c.nblk, ns, prior=prior)
     assert same_bits(got, integrate(zeros, c.nblk, prior=prior)) is None and not np.signbit(got).any()
-    c.close()
 
 
-def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu):
+def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu, case):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
-    c = SCase(gpu, 3, 2, 32)
-    c.upload()
-    gpu.memset(c.d_bs, 0xA5, c.sbytes(4) + CANARY)
-    gpu.memset(c.d_s, 0xA5, c.sbytes(4) + CANARY)
+    c = case(3, 2, 32)
+    c.put_beams()
+    c.refill(c.d_bs)
+    c.refill(c.d_s)
     gpu.synchronize()
     g = c.g
     bad_calls = []
@@ -313,20 +305,17 @@ def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu):
         g.stokes_block(c.d_x, c.d_y, 0, c.d_bs, 0, 0, nr_stokes=ns)
         g.integrate_stokes(c.d_bs, 0, 0, 5, ns, c.d_s, 0)
     gpu.synchronize()
-    host = np.empty(c.sbytes(4) + CANARY, dtype=np.uint8)
     for d in (c.d_bs, c.d_s):
-        gpu.memcpy_dtoh(host, d)
-        assert np.all(host == 0xA5)
+        assert np.all(c.read(d) == 0xA5)
     c.check_block()  # the context and the device are as usable as before
-    c.close()
 
 
 @pytest.mark.parametrize("ns", BOTH)
-def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu, ns):
+def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu, case, ns):
     """Both calls in one hipGraph as the first calls on a fresh context -- nothing allocates, so nothing has to be run outside
     the capture first -- replayed with new bytes in the same buffers."""
     B, C, nt, n = 5, 3, 64, 2
-    c = SCase(gpu, B, C, nt)
+    c = case(B, C, nt)
     s = gpu.Stream()
     with hip_graph.capture(s) as graph:
         c.call_block(ns, stream=s.handle)
@@ -337,41 +326,37 @@ def test_captured_first_calls_pick_up_new_bytes_on_replay(gpu, ns):
     for i in (1, 2, 0):
         gpu.memcpy_htod(c.d_x, pairs[i][0], stream=s.handle, sync=False)
         gpu.memcpy_htod(c.d_y, pairs[i][1], stream=s.handle, sync=False)
-        gpu.memset(c.d_bs, 0xA5, c.sbytes(4) + CANARY, stream=s.handle)
-        gpu.memset(c.d_s, 0xA5, c.sbytes(4) + CANARY, stream=s.handle)
+        c.refill(c.d_bs, stream=s.handle)
+        c.refill(c.d_s, stream=s.handle)
         graph.launch(s)
         s.synchronize()
         assert np.array_equal(c.read_block(ns), refs[i]), i
         assert same_bits(c.read_spectra(n, ns), integrate(refs[i], n)) is None, i
     graph.close()
-    c.close()
 
 
-def test_end_to_end_from_two_antenna_tensors_to_stokes_filterbanks(gpu):
+def test_end_to_end_from_two_antenna_tensors_to_stokes_filterbanks(gpu, context):
     """Two complex-product 8-bit beamformer calls on different antenna tensors with shared gains; the block Stokes parameters
     of the very bytes they wrote; the spectra; and the 8-bit filterbanks of the 4 B = 12 series, series 4 b + s Stokes s of
     beam b, against helpers/filterbank_model.py bit for bit."""
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import (SteeringCoefficientGenerator, block_stokes_bytes, filterbank_bytes, filterbank_scales_bytes,
-                                       quantised_beams_bytes, spectra_sums_bytes, stokes_spectra_bytes)
+    from dc_sand_amd.generator import (block_stokes_bytes, filterbank_bytes, filterbank_scales_bytes, quantised_beams_bytes,
+                                       spectra_sums_bytes, stokes_spectra_bytes)
 
     A, B, C, nt, ns, n = 8, 3, 2, 32, 4, 1
     nblk, T, NB = nt // 16, nt // 16 // n, ns * B
-    bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B, NR_SAMPLES_PER_CHANNEL=nt)
-    g = SteeringCoefficientGenerator(bp)
+    c = context(C, A, B, NR_SAMPLES_PER_CHANNEL=nt)
+    bp, g, read = c.bp, c.g, c.read
     g.upload_delays(rand_table(bp.n_pairs, seed=A + B))
     rng = np.random.default_rng(7)
     ants = [rng.integers(-128, 128, size=(C, nblk, A, 16, 2), dtype=np.int8) for _ in range(2)]
     # |sum_a w_a x_a| <= A * 128 * sqrt(2) with |w| = 1: this gain cannot clip, and spreads the beams over the int8 range
     gains = np.full(B, 127.0 / (A * 128 * 1.5), dtype=np.float32)
-    d_k = gpu.mem_alloc(B * 4)
-    gpu.memcpy_htod(d_k, gains)
+    d_k = c.upload(gains)
     qbytes = quantised_beams_bytes(bp, nt)
     d_ant, d_q, q = [], [], []
     for ant in ants:
-        d_ant.append(gpu.mem_alloc(ant.nbytes))
-        gpu.memcpy_htod(d_ant[-1], ant)
-        d_q.append(gpu.mem_alloc(qbytes))
+        d_ant.append(c.upload(ant))
+        d_q.append(c.alloc(qbytes))
         g.beamform_accumulated_complex_q8(d_ant[-1], ant.nbytes, d_k, d_q[-1], qbytes, nt, t_coeff=9)
         gpu.synchronize()
         host = np.empty((C, nblk, B, 16, 2), dtype=np.int8)
@@ -379,20 +364,9 @@ def test_end_to_end_from_two_antenna_tensors_to_stokes_filterbanks(gpu):
         q.append(host)
     assert np.unique(q[0]).size >= 30 and np.unique(q[1]).size >= 30 and not np.array_equal(q[0], q[1])
 
-    def out_buffer(nbytes):
-        d = gpu.mem_alloc(nbytes + CANARY)
-        gpu.memset(d, 0xA5, nbytes + CANARY)
-        return d
-
-    def read(d, nbytes, dtype, shape):
-        host = np.empty(nbytes + CANARY, dtype=np.uint8)
-        gpu.memcpy_dtoh(host, d)
-        assert np.all(host[nbytes:] == 0xA5), "written past an output"
-        return host[:nbytes].view(dtype).reshape(shape).copy()
-
     sb, pb = block_stokes_bytes(bp, nt, ns), stokes_spectra_bytes(bp, nblk, n, ns)
     ub, kb, fb = spectra_sums_bytes(bp, NB), filterbank_scales_bytes(bp, NB), filterbank_bytes(bp, NB, T)
-    d_bs, d_s, d_sums, d_scales, d_fb = (out_buffer(x) for x in (sb, pb, ub, kb, fb))
+    d_bs, d_s, d_sums, d_scales, d_fb = (c.out(x) for x in (sb, pb, ub, kb, fb))
     g.stokes_block(d_q[0], d_q[1], qbytes, d_bs, sb, nt, nr_stokes=ns)
     g.integrate_stokes(d_bs, sb, nblk, n, ns, d_s, pb)
     g.spectra_sums(d_s, pb, T, NB, d_sums, ub)
@@ -417,4 +391,3 @@ def test_end_to_end_from_two_antenna_tensors_to_stokes_filterbanks(gpu):
     for b in range(B):
         for s in range(ns):
             assert np.array_equal(got_fb[ns * b + s], by_beam_and_stokes[:, :, b, s]), (b, s)
-    g.close()
