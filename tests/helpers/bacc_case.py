@@ -47,6 +47,29 @@ def blocks_on_some_wave(B, C, nt, grid, block):
     return -(-units // waves)
 
 
+def passes_of_fused_launch(A, B, C, nt16, grid_x, shared_bytes):
+    """(channels per workgroup, channels per pass CH, live channels in the last pass of the last workgroup) of ONE launch of
+    the fused per-sample beamformer over nt16 sample blocks, from its geometry alone.  The kernel stages CH channels of
+    min(A, 128) antennas, 16 samples and (re, im) as fp32, so its dynamic LDS is CH * min(A, 128) * 128 bytes; a workgroup
+    takes one 16-beam tile, one sample block and one group of channels, so gridDim.x = ceil(B / 16) * nt16 * n_cblocks with
+    n_cblocks = ceil(C / cpb).  Nothing of the launcher's decision is restated (which cpb it prefers, when it narrows the
+    pass): if it comes to choose otherwise, the tests that assert this triple fail instead of testing nothing.  A geometry
+    that is not this kernel's, or a shape at which two values of cpb give the same grid, is an AssertionError."""
+    row = min(A, 128) * 128
+    assert shared_bytes % row == 0 and shared_bytes // row in (1, 2, 4), \
+        f"{shared_bytes} bytes of LDS are not 1, 2 or 4 channels of {row} bytes"
+    ch = shared_bytes // row
+    per_cblock = -(-B // 16) * nt16
+    assert grid_x % per_cblock == 0, f"{grid_x} workgroups are no whole number of channel groups ({per_cblock} workgroups each)"
+    n_cblocks = grid_x // per_cblock
+    fits = [cpb for cpb in (1, 2, 4) if -(-C // cpb) == n_cblocks]
+    assert len(fits) == 1, f"{n_cblocks} channel groups of {C} channels: channels per workgroup {fits or 'none'} of 1, 2, 4"
+    cpb = fits[0]
+    last = C - (n_cblocks - 1) * cpb  # channels of the last workgroup: 1 .. cpb
+    live = last - (-(-last // ch) - 1) * ch
+    return cpb, ch, live
+
+
 class Case(Context):
     """One context, its samples and output buffer (0xFF with a 0xFF canary: unwritten floats read as NaN), and both
     beamformers with and without weights."""
@@ -125,6 +148,34 @@ class Case(Context):
         assert proven >= depth, (f"(A, B, C, nt) = {(self.A, self.B, self.C, self.nt)} launches {grid[0]} workgroups of {block[0]} lanes: "
                                  f"only {proven} block(s) proven on some wave, {depth} wanted -- raise the shape's channel count")
         return grid[0], block[0], proven
+
+    def enqueue_fused(self, weighted, stream, dts=None):
+        """The fused call (from time index 0, or at the fDeltaTime values dts) on ``stream`` and nothing else: what
+        prove_passes captures.  Weighted, it reads the weights the last weighted call left in d_w."""
+        kw = {"t0": 0, "nt": self.nt} if dts is None else {"dt": dts}
+        if weighted:
+            self.g.generate_and_beamform_weighted(self.d_ant, self.ant.nbytes, self.d_w, self.d_beams, self.nbytes, stream=stream, **kw)
+        elif dts is None:
+            self.g.generate_and_beamform(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, stream=stream, **kw)
+        else:
+            self.g.generate_and_beamform_dt(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, dts, stream=stream)
+
+    def prove_passes(self, passes, call):
+        """Asserts that the fused beamformer launch of ``call(stream)`` is ``passes`` = (channels per workgroup, channels per
+        pass, live channels in the last workgroup's last pass), read from the launch (passes_of_fused_launch); ``call``
+        must have been made once already, since a first call allocates, and covers at most 256 time steps (one launch: a
+        longer call refuses the capture).  Nothing runs.  Returns the proven triple."""
+        from helpers import hip_graph
+
+        s = self.gpu.Stream()
+        nodes = hip_graph.launches(s, lambda: call(s.handle), shared=True)
+        s.synchronize()
+        grid, block, shared_bytes = hip_graph.largest_launch(nodes)  # asserts that the maximum is unique
+        assert grid[1] == grid[2] == 1 and block[1] == block[2] == 1, (grid, block)
+        proven = passes_of_fused_launch(self.A, self.B, self.C, self.nt // 16, grid[0], shared_bytes)
+        assert proven == tuple(passes), (f"(A, B, C, nt) = {(self.A, self.B, self.C, self.nt)} launches {grid[0]} workgroups with {shared_bytes} "
+                                         f"bytes of LDS: (cpb, CH, live in the last pass) = {proven}, {tuple(passes)} wanted")
+        return proven
 
     def read_beams(self):
         return self.read(self.d_beams, self.nbytes, np.float32, self.shape)

@@ -9,7 +9,9 @@ for the sites that do not instantiate what they capture.
 
 ``launches(s, fn)`` captures what ``fn()`` enqueues on ``s`` and returns the (gridDim, blockDim) of every kernel node without
 running anything: how a test proves the geometry a launcher chose instead of restating the launcher's arithmetic.  With a
-list ``others`` it also names the types of the nodes that are no kernels (a memset node, say).
+list ``others`` it also names the types of the nodes that are no kernels (a memset node, say).  With ``shared=True`` every
+kernel node is (gridDim, blockDim, sharedMemBytes): the dynamic LDS a launcher asked for tells which instantiation of a
+kernel template it took where the grid alone does not.
 
 While a stream captures, Python's cyclic collector is off.  It runs wherever an allocation count happens to cross its
 threshold, and a test object it collects frees its device memory: hipFree under a global-mode capture invalidates the
@@ -115,9 +117,10 @@ class capture:
         destroy(self._graph)
 
 
-def kernel_nodes(graph, others=None):
+def kernel_nodes(graph, others=None, shared=False):
     """[((grid x, y, z), (block x, y, z))] of every kernel node of a captured (not instantiated) graph; read-only.  The
-    hipGraphNodeType of every other node is appended to ``others`` where a list is given."""
+    hipGraphNodeType of every other node is appended to ``others`` where a list is given.  ``shared=True``: every entry is
+    ((grid x, y, z), (block x, y, z), sharedMemBytes), the dynamic LDS of the launch in bytes."""
     hip = _hip()
     n = ctypes.c_size_t(0)
     assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
@@ -136,13 +139,15 @@ def kernel_nodes(graph, others=None):
         assert rc == 0, f"hipGraphKernelNodeGetParams: {rc}"
         g, b = p.gridDim, p.blockDim
         assert g.x >= 1 and g.y >= 1 and g.z >= 1 and 1 <= b.x * b.y * b.z <= 1024, ((g.x, g.y, g.z), (b.x, b.y, b.z))
-        out.append(((g.x, g.y, g.z), (b.x, b.y, b.z)))
+        dims = ((g.x, g.y, g.z), (b.x, b.y, b.z))
+        out.append(dims + (int(p.sharedMemBytes),) if shared else dims)
     return out
 
 
-def launches(stream, fn, others=None):
+def launches(stream, fn, others=None, shared=False):
     """The kernel launches ``fn()`` enqueues on ``stream``, captured and thrown away: nothing runs.  ``fn`` must only
-    launch (a call that allocates on first use is made once, plainly, beforehand).  ``others``: as kernel_nodes takes it."""
+    launch (a call that allocates on first use is made once, plainly, beforehand).  ``others``, ``shared``: as kernel_nodes
+    takes them."""
     begin(stream)
     try:
         fn()
@@ -153,7 +158,7 @@ def launches(stream, fn, others=None):
         raise
     graph = end(stream)
     try:
-        return kernel_nodes(graph, others)
+        return kernel_nodes(graph, others, shared)
     finally:
         destroy(graph)
 
@@ -162,8 +167,10 @@ def largest_launch(nodes):
     """The rule that names a call's main kernel among its launches: the node with the most workgroups.  (A beamformer
     call is the small kernel that makes the table's terms, one lane per pair, and the beamformer itself, whose every
     workgroup takes a few sample blocks of one channel: at the shapes that use this rule it has at least five times the
-    terms kernel's workgroups, and the caller asserts that the maximum is unique.)"""
+    terms kernel's workgroups, and the caller asserts that the maximum is unique.  The fused beamformer's shapes that use
+    it launch 2048 workgroups and more against the 514 at the most of their terms kernel, which has a row of workgroups
+    per time step.)  The nodes as kernel_nodes returns them, with or without their sharedMemBytes."""
     assert nodes, "no kernel node was captured"
-    sizes = sorted((g[0] * g[1] * g[2] for g, _ in nodes), reverse=True)
+    sizes = sorted((n[0][0] * n[0][1] * n[0][2] for n in nodes), reverse=True)
     assert len(sizes) == 1 or sizes[0] > sizes[1], nodes
     return max(nodes, key=lambda n: n[0][0] * n[0][1] * n[0][2])

@@ -271,6 +271,45 @@ def test_depth_bound_of_the_gpu_tests_is_the_pigeonhole_quotient():
     assert all(depth >= MIN_DEPTH == 3 and nt % 16 == 0 for _, _, _, nt, depth in DEEP_SHAPES)
 
 
+def test_passes_of_a_fused_launch_read_from_its_geometry():
+    """helpers/bacc_case.py: passes_of_fused_launch, what the GPU tests of the fused kernel's 2- and 4-channel passes read
+    from a captured launch, on geometries worked by hand."""
+    from helpers.bacc_case import passes_of_fused_launch
+
+    # 511 channels in groups of 4 are 128 groups, the last of 3; one beam tile, 16 blocks: 2048 workgroups.  5 antennas are
+    # 640 bytes a channel
+    assert passes_of_fused_launch(5, 3, 511, 16, 2048, 4 * 640) == (4, 4, 3)
+    assert passes_of_fused_launch(5, 3, 511, 16, 2048, 2 * 640) == (4, 2, 1)  # the last group: a pass of 2, a pass of 1
+    assert passes_of_fused_launch(5, 3, 511, 16, 2048, 640) == (4, 1, 1)
+    assert passes_of_fused_launch(5, 3, 512, 16, 2048, 4 * 640) == (4, 4, 4)  # a whole last pass
+    assert passes_of_fused_launch(5, 3, 510, 16, 2048, 2 * 640) == (4, 2, 2)  # a last group of 2: one whole pass of 2
+    assert passes_of_fused_launch(5, 3, 511, 16, 4096, 2 * 640) == (2, 2, 1)  # 256 groups: 2 channels each
+    assert passes_of_fused_launch(5, 3, 511, 16, 8176, 640) == (1, 1, 1)
+    assert passes_of_fused_launch(5, 3, 511, 16, 8176, 2 * 640) == (1, 2, 1)  # a pass wider than the group: one live channel
+    assert passes_of_fused_launch(7, 20, 254, 16, 2048, 4 * 7 * 128) == (4, 4, 2)  # two beam tiles, 64 groups
+    assert passes_of_fused_launch(7, 20, 254, 3, 2 * 3 * 127, 2 * 7 * 128) == (2, 2, 2)
+    # more than 128 antennas are staged 128 at a time: 16 KiB a channel
+    assert passes_of_fused_launch(129, 2, 511, 16, 2048, 32768) == (4, 2, 1)
+    assert passes_of_fused_launch(300, 2, 511, 16, 2048, 16384) == (4, 1, 1)
+    assert passes_of_fused_launch(64, 3, 509, 16, 2048, 32768) == (4, 4, 1)
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 2, 16, 16, 2 * 640)  # ambiguous: one group of 2 channels is ceil(2 / 2) and ceil(2 / 4)
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 1, 16, 16, 640)  # ambiguous: one channel is one group whatever cpb
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 511, 16, 2047, 4 * 640)  # no whole number of channel groups
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(7, 20, 254, 16, 2048 + 16, 4 * 7 * 128)  # whole groups of ONE beam tile only
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 511, 16, 2048, 3 * 640)  # 3 channels per pass: no form of the kernel
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 511, 16, 2048, 4 * 640 + 4)  # no whole number of channels
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(129, 2, 511, 16, 2048, 2 * 129 * 128)  # sized for 129 antennas, not for the staged 128
+    with pytest.raises(AssertionError):
+        passes_of_fused_launch(5, 3, 511, 16, 16 * 100, 4 * 640)  # 100 groups: no cpb of 1, 2, 4
+
+
 # ---- what tests/test_gpu_beamformer_exact_slow.py stands on
 @pytest.fixture(scope="module")
 def lab():

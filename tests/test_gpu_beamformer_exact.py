@@ -195,9 +195,11 @@ def test_matrix_core_form_with_several_blocks_per_wave_bit_for_bit(gpu, oracle, 
     c.close()
 
 
-# ---- b. the fused per-sample kernel.  FUSED_SHAPES plus: three LDS chunks of antennas with a partial last one; odd channel
-# counts with enough workgroups (>= 2048) for the launcher to keep 4 channels per pass (<= 64 antennas) and 2 (> 64), so
-# that the last pass of a workgroup is a partial one
+# ---- b. the fused per-sample kernel.  FUSED_SHAPES plus: three LDS chunks of antennas with a partial last one;
+# (4, 512, 5, 512), one launch of 4 channels per pass whose last pass has one live channel; (65, 512, 3, 512), whose 33 280
+# pairs leave the terms table 252 time steps: THREE launches (240, 240 and 32 steps: the offsets tex0 and nt16_total, the
+# staged fDeltaTime values), each with too few workgroups for more than ONE channel per pass.  Every other shape of this
+# list is one launch of one channel per pass as well; FUSED_PASS_SHAPES, below, are the shapes of 2 and 4.
 FUSED_EXACT_SHAPES = FUSED_SHAPES + [(300, 7, 3, 32), (4, 512, 5, 512), (65, 512, 3, 512)]
 
 
@@ -205,6 +207,47 @@ FUSED_EXACT_SHAPES = FUSED_SHAPES + [(300, 7, 3, 32), (4, 512, 5, 512), (65, 512
 def test_fused_kernel_is_the_verifiers_sum_bit_for_bit(gpu, oracle, A, B, C, nt):
     c = Exact(gpu, oracle, A, B, C, nt)
     c.check_fused(weights=(None, weights_for(A, B, A + 7 * B)), t0=0)
+    c.close()
+
+
+# ---- b'. the passes of 2 and 4 channels.  A workgroup walks cpb channels, CH at a time: (A, B, C, nt, (cpb, CH, live channels
+# in the last pass of the last workgroup)), the triple as Case.prove_passes reads it from the launch.  Each shape launches
+# 2048 workgroups, the fewest at which the launcher keeps the form, with few beams (the dead lanes of a 16-beam tile cost
+# the model nothing) and 256 time steps, the most a captured call takes.
+#   CH = 4: three live channels in the last pass; two beam tiles with a ragged second and two live; 64 antennas, the last
+#           count with 4 channels per pass (32 KiB of LDS), and one live
+#   CH = 2 of cpb = 4 (a workgroup makes TWO passes, the last workgroup a whole and a partial one): 65 antennas, the first
+#           count with 2; 129, across two LDS chunks of antennas, the second holding one antenna
+#   CH = 2 of cpb = 2: 5 antennas; 64 (where cpb = 4 would have meant CH = 4); 130, two LDS chunks
+FUSED_PASS_SHAPES = [(5, 3, 511, 256, (4, 4, 3)), (7, 20, 254, 256, (4, 4, 2)), (64, 3, 509, 256, (4, 4, 1)),
+                     (65, 3, 511, 256, (4, 2, 1)), (129, 2, 511, 256, (4, 2, 1)),
+                     (5, 3, 255, 256, (2, 2, 1)), (64, 3, 255, 256, (2, 2, 1)), (130, 3, 255, 256, (2, 2, 1))]
+
+
+def prove_fused_passes(c, record_property, passes, dts=None):
+    """The form of the unweighted and of the weighted call, read from a captured launch (nothing runs), asserted to be
+    ``passes`` and recorded.  Behind the calls themselves: a first call allocates, and d_w holds the weights."""
+    for weighted in (False, True):
+        record_property(f"{'weighted' if weighted else 'unweighted'}{'' if dts is None else ', dt by value'}: "
+                        "channels per workgroup, channels per pass, live channels in the last pass",
+                        c.prove_passes(passes, lambda s: c.enqueue_fused(weighted, s, dts=dts)))
+
+
+@pytest.mark.parametrize("A,B,C,nt,passes", FUSED_PASS_SHAPES)
+def test_fused_kernel_passes_of_two_and_four_channels_bit_for_bit(gpu, oracle, record_property, A, B, C, nt, passes):
+    c = Exact(gpu, oracle, A, B, C, nt)
+    c.check_fused(weights=(None, weights_for(A, B, A + 7 * B)), t0=0)
+    prove_fused_passes(c, record_property, passes)
+    c.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt,passes", [FUSED_PASS_SHAPES[3], FUSED_PASS_SHAPES[0]])
+def test_fused_kernel_passes_of_two_and_four_channels_times_by_value(gpu, oracle, record_property, A, B, C, nt, passes):
+    """Off the time-index grid and descending, as test_fused_kernel_time_offset_and_times_by_value makes them."""
+    c = Exact(gpu, oracle, A, B, C, nt)
+    dts = np.sort(np.random.default_rng(A).uniform(0.0, 1.5, nt)).astype(np.float32)[::-1]
+    c.check_fused(weights=(None, weights_for(A, B, 3 * A + B)), dts=dts)
+    prove_fused_passes(c, record_property, passes, dts=dts)
     c.close()
 
 

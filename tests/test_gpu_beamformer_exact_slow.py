@@ -35,7 +35,8 @@ from helpers.beamformer_model import (FAST_HIGH, FAST_LOW, FILLER_PHASE, FILLER_
                                       first_difference_or_nan, flagged_table, fused_model, interleave_with_filler, normalise,
                                       real_beams, weighted_coefficients, zero_weight_coefficients)
 from test_gpu_beam_complex import Complex, check_model
-from test_gpu_beamformer_exact import DT_COEFF, FUSED_EXACT_SHAPES, PAIRS_PER_SLICE, Exact, weights_for
+from test_gpu_beamformer_exact import (DT_COEFF, FUSED_EXACT_SHAPES, FUSED_PASS_SHAPES, PAIRS_PER_SLICE, Exact, prove_fused_passes,
+                                       weights_for)
 from test_gpu_class_replay import CHAIN_DEEP, STAGED_DEEP
 
 pytestmark = pytest.mark.gpu
@@ -268,12 +269,24 @@ def test_a_table_that_is_slow_throughout(gpu, oracle, record_property, A, B, C, 
     c.close()
 
 
-# ---- d. the fused per-sample kernel: the shapes of its fast-class twin (passes of 1, 2 and 4 channels, a partial last
-# pass, three LDS chunks of antennas), the table with ONE slow pair
+# ---- d. the fused per-sample kernel: the shapes of its fast-class twin (three LDS chunks of antennas; (4, 512, 5, 512), 4
+# channels per pass with one live in the last; (65, 512, 3, 512), three launches; every launch of the others, and of
+# that one, takes ONE channel per pass), the table with ONE slow pair
 @pytest.mark.parametrize("A,B,C,nt", FUSED_EXACT_SHAPES)
 def test_fused_kernel_in_the_slow_class_bit_for_bit(gpu, oracle, record_property, A, B, C, nt):
     c = SlowExact(gpu, oracle, A, B, C, nt, slow_tables.one_slow_pair(A, B), record_property)
     c.check_fused_slow(weights=(None, slow_weights_for(A, B, A + 7 * B)), t0=0)
+    c.close()
+
+
+# ---- d''. the slow branch ("channel outermost and unrolled") at 4 and 2 channels per pass, the form read from the launch
+# (test_gpu_beamformer_exact.py: FUSED_PASS_SHAPES): 4 with three live channels in the last pass and with two beam tiles;
+# 2 in a workgroup of two passes (65 antennas) and in one of a single pass
+@pytest.mark.parametrize("A,B,C,nt,passes", [FUSED_PASS_SHAPES[i] for i in (0, 1, 3, 5)])
+def test_fused_kernel_passes_of_two_and_four_channels_in_the_slow_class(gpu, oracle, record_property, A, B, C, nt, passes):
+    c = SlowExact(gpu, oracle, A, B, C, nt, slow_tables.one_slow_pair(A, B), record_property)
+    c.check_fused_slow(weights=(None, slow_weights_for(A, B, A + 7 * B)), t0=0)
+    prove_fused_passes(c, record_property, passes)
     c.close()
 
 
@@ -288,6 +301,17 @@ def test_fused_kernel_class_changing_during_a_call(gpu, oracle, record_property)
     c = SlowExact(gpu, oracle, A, B, C, nt, slow_tables.crossing(A, B), record_property)
     c.check_fused_slow(weights=(None, slow_weights_for(A, B, 3 * A + B)), dts=slow_tables.crossing_times(),
                        block_classes=slow_tables.CROSSING_BLOCK_CLASSES)
+    c.close()
+
+
+@pytest.mark.parametrize("A,B,C,nt,passes", [(5, 21, 1366, 48, (4, 4, 2)), (5, 21, 683, 48, (2, 2, 1))])
+def test_fused_kernel_class_changing_during_a_call_with_several_channels_per_pass(gpu, oracle, record_property, A, B, C, nt, passes):
+    """The same three blocks (full degree, slow, slow) where a pass takes 4 and 2 channels: 2052 workgroups of two beam
+    tiles, the form read from the launch; two live channels in the last pass of 4, one in the last pass of 2."""
+    c = SlowExact(gpu, oracle, A, B, C, nt, slow_tables.crossing(A, B), record_property)
+    dts = slow_tables.crossing_times()
+    c.check_fused_slow(weights=(None, slow_weights_for(A, B, 3 * A + B)), dts=dts, block_classes=slow_tables.CROSSING_BLOCK_CLASSES)
+    prove_fused_passes(c, record_property, passes, dts=dts)
     c.close()
 
 
