@@ -111,4 +111,13 @@ COMPANIONS = {
          [_VP, _VP, c_size_t, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, c_uint32, c_float, c_uint32, c_uint32,
           _VP, c_size_t, c_uint32, _VP, _VP, c_size_t, _VP]),
     ]),
+    # the polyphase channeliser: the down-converter's float series into the int8 sample tensor (FIR, FFT, gains, corner turn)
+    "channeliser": Companion("dcs_channeliser.h", "bf_channeliser.cpp", "libdcs_channeliser.so", [
+        ("dcs_bf_channelise", c_int,
+         [_VP, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, c_uint64, _VP, _VP, c_uint32, _VP, c_size_t, c_uint64, c_uint64,
+          c_uint32, c_uint32, _VP]),
+        ("dcs_bf_channelise_q8", c_int,
+         [_VP, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, c_uint64, _VP, _VP, c_uint32, _VP, _VP, c_size_t, c_uint64,
+          c_uint64, c_uint32, c_uint32, _VP, _VP]),
+    ]),
 }

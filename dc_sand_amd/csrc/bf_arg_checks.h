@@ -244,4 +244,35 @@ inline int find_candidates_args(dcs_bf_context *c, const float *d_snr, const uin
                       fits(first_block, nr_blocks, peak_blocks));
 }
 
+// include/dcs_channeliser.h: N a power of two in [64, 2048], 1 .. 16 taps per branch, whole blocks of 16 spectra.  A row is read
+// from its pair 0 to (nr_spectra + P - 1) N - 1; the output is the whole tensor [N][out_blocks][out_inputs][16][2] of words of
+// elem bytes (4: float, 1: int8), of which the call writes blocks first_block .. and inputs first_input ..
+inline int channelise_args(dcs_bf_context *c, uint32_t N, uint32_t P, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                           size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
+                           const void *d_out, uint32_t elem, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
+                           uint32_t out_inputs, uint32_t first_input)
+{
+    const bool empty = nr_spectra == 0u || nr_inputs == 0u;
+    if (!c || (!empty && !(d_in && d_taps && d_twiddles && d_out))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!(aligned(d_in, 8u) && aligned(d_taps, 4u) && aligned(d_twiddles, 8u) && aligned(d_out, 16u))) return DCS_ERR_INVALID_ARGUMENT;
+    if (N < 64u || N > 2048u || (N & (N - 1u)) || P < 1u || P > 16u || nr_spectra % 16u != 0u || order > 1u)
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (empty) return DCS_OK;
+    const uint64_t row = ((uint64_t)nr_spectra + P - 1u) * N;                                   // < 2^44
+    const unsigned __int128 need = (unsigned __int128)(nr_inputs - 1u) * in_stride + row;      // < 2^97
+    return arg_status(in_stride >= row && !(need >> 61) && (uint64_t)need * (2u * sizeof(float)) <= (uint64_t)in_bytes &&
+                      fits(first_block, nr_spectra / 16u, out_blocks) && fits(first_input, nr_inputs, out_inputs) &&
+                      holds(out_bytes, N, out_blocks, out_inputs, 32u * elem));
+}
+inline int channelise_q8_args(dcs_bf_context *c, uint32_t N, uint32_t P, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                              size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
+                              const float *d_gains, const int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
+                              uint32_t out_inputs, uint32_t first_input, const unsigned long long *d_clip_count)
+{
+    const bool empty = nr_spectra == 0u || nr_inputs == 0u;
+    if (!c || (!empty && !d_gains) || !aligned(d_gains, 4u) || !aligned(d_clip_count, 8u)) return DCS_ERR_INVALID_ARGUMENT;
+    return channelise_args(c, N, P, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order, d_out_q8, 1u, out_bytes,
+                           out_blocks, first_block, out_inputs, first_input);
+}
+
 #endif // BF_ARG_CHECKS_H

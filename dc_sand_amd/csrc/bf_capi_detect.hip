@@ -2,12 +2,12 @@
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
 // detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h), the
 // single-pulse search on its planes (include/dcs_single_pulse.h), the correlator (include/dcs_correlator.h), the digital
-// down-converter (include/dcs_ddc.h) and the candidate sifter (include/dcs_candidates.h), each reached through the table
-// at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing
+// down-converter (include/dcs_ddc.h), the candidate sifter (include/dcs_candidates.h) and the polyphase channeliser
+// (include/dcs_channeliser.h), each reached through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing
 // else.  Each begins with the device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made
 // already; what follows needs the device or the context's sizes, or is a condition that only this side makes.  Host code
 // only; the kernels are in bf_integrate.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip,
-// bf_single_pulse.hip, bf_correlator.hip, bf_ddc.hip and bf_candidates.hip.
+// bf_single_pulse.hip, bf_correlator.hip, bf_ddc.hip, bf_candidates.hip and bf_channeliser.hip.
 
 #include <cmath>
 #include <cstring>
@@ -429,6 +429,60 @@ int find_candidates_impl(dcs_bf_context *c, const float *d_snr, size_t snr_bytes
     a.max_candidates = max_candidates;
     a.threshold = threshold;
     return (int)bf_launch_find_candidates(a, as_stream(stream));
+}
+
+// include/dcs_channeliser.h, reached the same way.  Of the context these use the device alone: every size is an argument, and
+// the device-free checks are all the checks there are.  Nothing allocated: one launch each.
+static int channelise_launch(dcs_bf_context *c, uint32_t N, uint32_t P, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                             uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order, const float *d_gains,
+                             float *d_out, int8_t *d_out_q8, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs,
+                             uint32_t first_input, unsigned long long *d_clip_count, void *stream)
+{
+    DCS_CHECK_DEVICE(c);
+    if (nr_spectra == 0u || nr_inputs == 0u) return DCS_OK;
+    bf_chan_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_in;
+    a.taps = d_taps;
+    a.twiddles = d_twiddles;
+    a.gains = d_gains;
+    a.out = d_out;
+    a.out_q8 = d_out_q8;
+    a.clip_count = d_clip_count;
+    a.in_stride = in_stride;
+    a.out_blocks = out_blocks;
+    a.first_block = first_block;
+    a.N = N;
+    a.P = P;
+    a.nr_inputs = nr_inputs;
+    a.nr_spectra = nr_spectra;
+    a.order = order;
+    a.out_inputs = out_inputs;
+    a.first_input = first_input;
+    return (int)bf_launch_channelise(a, as_stream(stream));
+}
+
+int channelise_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                    size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order, float *d_out,
+                    size_t out_bytes, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs, uint32_t first_input, void *stream)
+{
+    if (int e = channelise_args(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order,
+                                d_out, 4u, out_bytes, out_blocks, first_block, out_inputs, first_input))
+        return e;
+    return channelise_launch(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_stride, d_taps, d_twiddles, order, nullptr, d_out,
+                             nullptr, out_blocks, first_block, out_inputs, first_input, nullptr, stream);
+}
+
+int channelise_q8_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra,
+                       const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
+                       const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
+                       uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count, void *stream)
+{
+    if (int e = channelise_q8_args(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order,
+                                   d_gains, d_out_q8, out_bytes, out_blocks, first_block, out_inputs, first_input, d_clip_count))
+        return e;
+    return channelise_launch(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_stride, d_taps, d_twiddles, order, d_gains, nullptr,
+                             d_out_q8, out_blocks, first_block, out_inputs, first_input, d_clip_count, stream);
 }
 
 } // namespace bf_host

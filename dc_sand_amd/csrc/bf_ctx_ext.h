@@ -4,11 +4,11 @@
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
 // (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
 // (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h), libdcs_correlator.so
-// (include/dcs_correlator.h), libdcs_ddc.so (include/dcs_ddc.h) and libdcs_candidates.so (include/dcs_candidates.h).  All are
-// built from this tree together.
+// (include/dcs_correlator.h), libdcs_ddc.so (include/dcs_ddc.h), libdcs_candidates.so (include/dcs_candidates.h) and
+// libdcs_channeliser.so (include/dcs_channeliser.h).  All are built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator, of the down-converter and of the candidate sifter; a companion's
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator, of the down-converter, of the candidate sifter and of the channeliser; a companion's
 // export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
 // takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
@@ -40,7 +40,9 @@
 // foreign version above 11).
 // 14: find_candidates appended (tests/test_host_abi_candidates.py hands its companion 1, 12 and 13; no older test hands a
 // foreign version above 12).
-#define BF_CTX_EXT_VERSION 14u
+// 15: channelise, channelise_q8 appended (tests/test_host_abi_channeliser.py hands its companion 1, 13 and 14; no older test
+// hands a foreign version above 13).
+#define BF_CTX_EXT_VERSION 15u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -144,6 +146,18 @@ struct bf_ctx_ext_ops {
                            uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
                            size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes,
                            void *stream);
+    // the polyphase channeliser (include/dcs_channeliser.h): float [nr_inputs][in_stride][{re, im}] -> the spectra of a FIR of
+    // nr_taps rows of nr_channels pairs and an nr_channels-point butterfly network, [nr_channels][out_blocks][out_inputs][16][{re, im}]
+    // as floats, or quantised with gains float [nr_inputs][nr_channels]; d_clip_count: nullptr = no counting
+    int (*channelise)(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra,
+                      const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles,
+                      uint32_t order, float *d_out, size_t out_bytes, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs,
+                      uint32_t first_input, void *stream);
+    int (*channelise_q8)(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra,
+                         const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles,
+                         uint32_t order, const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks,
+                         uint64_t first_block, uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count,
+                         void *stream);
 };
 
 // the first member of struct dcs_bf_context

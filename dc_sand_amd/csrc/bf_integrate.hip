@@ -1,4 +1,4 @@
-// bf_integrate.hip -- the integrator of every post-detection output (DESIGN.md section 5.21), gfx950 only: n consecutive
+// bf_integrate.hip -- the integrator of every post-detection output (DESIGN.md section 5.22), gfx950 only: n consecutive
 // blocks of a [C][nr_blocks][bs] tensor reduced to one row of spectra [nr_blocks / n][C][bs].  One kernel for detected power
 // (float, bs = B), the incoherent beam (uint32, bs = 1), the Stokes parameters (int32, bs = B * nr_stokes) and the
 // visibilities (int32, bs = A (A + 1)); the element type selects the reduction rule and nothing else.
@@ -7,7 +7,7 @@
 // bs < 64, of consecutive channels' runs), and a lane walks its n blocks bs words apart.  No atomics and no cross-lane step,
 // so the result does not depend on the launch geometry.  Offsets are 64-bit.  Where bs is 1 a lane's n words are consecutive
 // and the stride is worth knowing when compiling: the loads merge four to an instruction, and 128 MiB of block powers
-// integrate in 32 us instead of 193 (DESIGN.md section 5.21).  A unit of its own, so that an edit here recompiles 20 lines and
+// integrate in 32 us instead of 193 (DESIGN.md section 5.22).  A unit of its own, so that an edit here recompiles 20 lines and
 // not the matrix-core beamformer.
 
 #include "bf_kernels.h"
@@ -65,7 +65,7 @@ hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &
     const dim3 grid((uint32_t)blocks), block(256u);
     switch (type) {
     case BF_INTEGRATE_F32: hipLaunchKernelGGL(bf_integrate_kernel<float>, grid, block, 0, stream, a); break;
-    case BF_INTEGRATE_U32: // a lane's n words are consecutive, and the unit-stride form reads them four to a load (section 5.21)
+    case BF_INTEGRATE_U32: // a lane's n words are consecutive, and the unit-stride form reads them four to a load (section 5.22)
         if (a.bs != 1u) return hipErrorInvalidValue; // not built: no call has unsigned words more than one to a block
         hipLaunchKernelGGL((bf_integrate_kernel<uint32_t, true>), grid, block, 0, stream, a);
         break;

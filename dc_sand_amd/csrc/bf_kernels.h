@@ -237,7 +237,7 @@ struct bf_stokes_args {
 hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream);
 hipError_t bf_warm_module_stokes();
 
-// The integrator of every post-detection output (bf_integrate.hip; DESIGN.md section 5.21): blocks [C][nr_blocks][bs] summed
+// The integrator of every post-detection output (bf_integrate.hip; DESIGN.md section 5.22): blocks [C][nr_blocks][bs] summed
 // n at a time into out [nr_blocks / n][C][bs].  The element type selects the rule: float words are added in order, one rounded
 // add each; 32-bit integer words exactly, in 64 bits, and the sum converted once
 enum bf_integrate_type { BF_INTEGRATE_F32, BF_INTEGRATE_U32 /* built for bs == 1 */, BF_INTEGRATE_I32 };
@@ -380,6 +380,26 @@ struct bf_cand_args {
 };
 hipError_t bf_launch_find_candidates(const bf_cand_args &a, hipStream_t stream);
 hipError_t bf_warm_module_candidates();
+
+// The polyphase channeliser (bf_channeliser.hip; include/dcs_channeliser.h): float [nr_inputs][in_stride][2]
+// -> FIR of P rows of N pairs, N-point butterfly network -> [N][out_blocks][out_inputs][16][2] as floats (out) or quantised
+// (out_q8, with gains and counters); exactly one of out and out_q8 is set
+struct bf_chan_args {
+    const float *in;       // 8-byte aligned
+    const float *taps;     // [P][N]
+    const float *twiddles; // [N / 2][2], 8-byte aligned
+    const float *gains;    // out_q8 only: [nr_inputs][N]
+    float *out;            // 16-byte aligned, or nullptr
+    int8_t *out_q8;        // 16-byte aligned, or nullptr
+    unsigned long long *clip_count; // out_q8 only: [nr_inputs], or nullptr
+    uint64_t in_stride;    // pairs, >= (nr_spectra + P - 1) N
+    uint64_t out_blocks, first_block;
+    uint64_t items;        // filled by the launcher
+    uint32_t N, P, nr_inputs, nr_spectra, order, out_inputs, first_input;
+    uint32_t groups;       // filled by the launcher: the groups of inputs that share an item
+};
+hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream);
+hipError_t bf_warm_module_channeliser();
 
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.

@@ -177,6 +177,30 @@ def ddc_out_bytes(nr_inputs: int, out_stride: int, nr_bands: int = 1) -> int:
     return int(nr_bands) * int(nr_inputs) * int(out_stride) * 8
 
 
+def _channeliser_shape(nr_channels: int, nr_taps: int = 1) -> None:
+    if not 64 <= nr_channels <= 2048 or nr_channels & (nr_channels - 1):
+        raise ValueError("nr_channels must be a power of two in [64, 2048]")
+    if not 1 <= nr_taps <= 16:
+        raise ValueError("nr_taps must be in [1, 16]")
+
+
+def channeliser_in_pairs(nr_channels: int, nr_taps: int, nr_spectra: int) -> int:
+    """The pairs of a row that :meth:`SteeringCoefficientGenerator.channelise` reads for ``nr_spectra`` spectra
+    (``DCS_CHAN_IN_PAIRS``): ``(nr_spectra + nr_taps - 1) nr_channels``, the least ``in_stride``."""
+    _channeliser_shape(int(nr_channels), int(nr_taps))
+    if nr_spectra < 0 or nr_spectra % 16:
+        raise ValueError("nr_spectra must be a multiple of 16")
+    return (int(nr_spectra) + int(nr_taps) - 1) * int(nr_channels)
+
+
+def channelised_bytes(nr_channels: int, out_blocks: int, out_inputs: int, q8: bool = False) -> int:
+    """Size of the output ``[nr_channels][out_blocks][out_inputs][16][{re, im}]`` of
+    :meth:`SteeringCoefficientGenerator.channelise` (floats) or, with ``q8``, ``.channelise_q8`` (int8: the sample tensor of
+    ``nr_channels`` channels, ``out_inputs`` stations and ``16 out_blocks`` samples)."""
+    _channeliser_shape(int(nr_channels))
+    return int(nr_channels) * int(out_blocks) * int(out_inputs) * 32 * (1 if q8 else 4)
+
+
 def spectra_sums_bytes(params: BeamformerParameters, nr_beams: int) -> int:
     """Size of the running sums ``double [C][nr_beams][2]`` of :meth:`SteeringCoefficientGenerator.spectra_sums`."""
     return int(params.NR_CHANNELS) * int(nr_beams) * 16
@@ -672,6 +696,38 @@ class SteeringCoefficientGenerator:
                             _p(d_digits), int(digits_bytes), int(nr_taps), len(bands), ctypes.cast(arr, c_void_p),
                             int(first_output), _p(d_out), int(out_bytes), int(out_stride), _s(stream)),
               "dcs_bf_ddc")
+
+    # -- the polyphase channeliser behind it (include/dcs_channeliser.h, companion library libdcs_channeliser.so): d_in is a
+    #    device float [nr_inputs][in_stride][2] array (one band of ddc's output), d_out a device [nr_channels][out_blocks]
+    #    [out_inputs][16][2] array of floats, d_out_q8 the same of int8: the sample tensor
+    def channelise(self, d_in, in_bytes: int, in_stride: int, nr_inputs: int, nr_spectra: int, nr_channels: int, nr_taps: int,
+                   d_taps, d_twiddles, d_out, out_bytes: int, out_blocks: int, out_inputs: int, first_block: int = 0,
+                   first_input: int = 0, order: int = 0, stream=None) -> None:
+        """``nr_spectra`` (a multiple of 16) spectra per input row: spectrum ``n`` is the FIR of the ``nr_taps`` rows of
+        ``nr_channels`` pairs from pair ``n nr_channels`` on with ``d_taps`` (:func:`dc_sand_amd.channeliser.pfb_taps`) through
+        the butterfly network of ``d_twiddles`` (:func:`dc_sand_amd.channeliser.twiddles`), written as floats to blocks
+        ``first_block ..`` and inputs ``first_input ..`` of ``d_out`` (:func:`channelised_bytes`).  ``order`` 1 gives channels
+        that ascend in frequency (:func:`dc_sand_amd.channeliser.channel_of`)."""
+        cl = _lib.companion("channeliser")
+        check(cl.dcs_bf_channelise(c_void_p(self._h), int(nr_channels), int(nr_taps), int(nr_inputs), int(nr_spectra), _p_or_null(d_in),
+                                   int(in_bytes), int(in_stride), _p_or_null(d_taps), _p_or_null(d_twiddles), int(order),
+                                   _p_or_null(d_out), int(out_bytes), int(out_blocks), int(first_block), int(out_inputs),
+                                   int(first_input), _s(stream)),
+              "dcs_bf_channelise")
+
+    def channelise_q8(self, d_in, in_bytes: int, in_stride: int, nr_inputs: int, nr_spectra: int, nr_channels: int, nr_taps: int,
+                      d_taps, d_twiddles, d_gains, d_out_q8, out_bytes: int, out_blocks: int, out_inputs: int,
+                      first_block: int = 0, first_input: int = 0, order: int = 0, d_clip_count=None, stream=None) -> None:
+        """:meth:`channelise` quantised to int8 with the gains ``float [nr_inputs][nr_channels]`` (by input of the call and output
+        channel), by the quantiser of :meth:`beamform_accumulated_q8`: exactly the float call's values times the gain, rounded
+        to nearest even and clamped to +-127, NaN as -128.  ``d_clip_count``: ``None``, or a device ``uint64 [nr_inputs]`` array
+        that grows by each input's clipped components."""
+        cl = _lib.companion("channeliser")
+        check(cl.dcs_bf_channelise_q8(c_void_p(self._h), int(nr_channels), int(nr_taps), int(nr_inputs), int(nr_spectra),
+                                      _p_or_null(d_in), int(in_bytes), int(in_stride), _p_or_null(d_taps), _p_or_null(d_twiddles),
+                                      int(order), _p_or_null(d_gains), _p_or_null(d_out_q8), int(out_bytes), int(out_blocks),
+                                      int(first_block), int(out_inputs), int(first_input), _p_or_null(d_clip_count), _s(stream)),
+              "dcs_bf_channelise_q8")
 
     TUNING_FIELDS = ("form", "nontemporal", "chan_per_block", "tiles_per_block", "waves_per_block", "rows_per_wave",
                      "xcd_remap", "rows_same_tile", "math_mode", "wg_per_cu")

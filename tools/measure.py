@@ -58,6 +58,11 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         the digital down-converter at 128 inputs x 2^24 samples, 256 taps, with one band and with two, in turn in one process:
         the time, its fraction of one read of the samples plus the write of the outputs at 8 TB/s, and the matrix cores'
         share at their peak rate; --trace: a few launches only, for a counter run     -> profiles/r16_ddc.md
+    python tools/measure.py channeliser [--rounds 5] [--shapes INPUTSxNxPxSPECTRA,...] [--trace]
+        the polyphase channeliser's quantised and float calls per shape, in turn in one process on seeded float series of
+        small integers, beside a device-to-device copy of the input's bytes in the same process: the time, the floor of the
+        bytes it must move at 8 TB/s and the fraction of it reached; --trace: a few launches only, for a counter run
+                                                                                    -> profiles/r18_channeliser.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -1134,6 +1139,68 @@ def cmd_ddc(args):
         d.free()
 
 
+def cmd_channeliser(args):
+    """The polyphase channeliser (include/dcs_channeliser.h).  Per shape (inputs x N x P x spectra) the quantised call, the
+    float call and a device-to-device copy of the input's bytes (the copy figure of the same session), in turn ``--rounds``
+    times in one process.  The floor is the bytes the call must move -- inputs (spectra + P - 1) N 8 read, inputs spectra N 2
+    (int8) or 8 (float) written -- at the 8 TB/s HBM peak.  The input is a seeded series of small integers as floats (a 32 MiB
+    block repeated), the taps pfb_taps, the gains 2^-3: the time does not depend on the values."""
+    from dc_sand_amd import _lib, channeliser
+    from dc_sand_amd.generator import channelised_bytes, channeliser_in_pairs
+
+    g = SteeringCoefficientGenerator(BeamformerParameters(NR_CHANNELS=1, NR_STATIONS=1, NR_BEAMS=1, NR_SAMPLES_PER_CHANNEL=16))
+    rows = []
+    for shape in args.shapes.split(","):
+        ni, N, P, ns = (int(x) for x in shape.split("x"))
+        pairs = channeliser_in_pairs(N, P, ns)
+        in_bytes, fbytes, qbytes = ni * pairs * 8, channelised_bytes(N, ns // 16, ni), channelised_bytes(N, ns // 16, ni, q8=True)
+        d_in, d_f, d_q = device.mem_alloc(in_bytes), device.mem_alloc(max(fbytes, in_bytes)), device.mem_alloc(qbytes)
+        blk = min(in_bytes, 32 << 20)
+        device.memcpy_htod(d_in, np.random.default_rng(18).integers(-100, 101, size=blk // 4).astype(np.float32))
+        off = blk
+        while off < in_bytes:
+            n = min(off, in_bytes - off)
+            device.memcpy_dtod(int(d_in) + off, d_in, n)
+            off += n
+        taps, tw = channeliser.pfb_taps(N, P), channeliser.twiddles(N)
+        gains = np.full((ni, N), 0.125, dtype=np.float32)
+        d_taps, d_tw, d_g, d_n = (device.mem_alloc(b) for b in (taps.nbytes, tw.nbytes, gains.nbytes, 8 * ni))
+        device.memcpy_htod(d_taps, taps)
+        device.memcpy_htod(d_tw, tw)
+        device.memcpy_htod(d_g, gains)
+        device.memset(d_n, 0, 8 * ni)
+        calls = {
+            "q8": lambda: g.channelise_q8(d_in, in_bytes, pairs, ni, ns, N, P, d_taps, d_tw, d_g, d_q, qbytes, ns // 16, ni, d_clip_count=d_n),
+            "float": lambda: g.channelise(d_in, in_bytes, pairs, ni, ns, N, P, d_taps, d_tw, d_f, fbytes, ns // 16, ni),
+            "copy": lambda: _lib.check(_lib.lib().dcs_memcpy_dtod(ctypes.c_void_p(int(d_f)), ctypes.c_void_p(int(d_in)), in_bytes, None), "dtod"),
+        }
+        device.synchronize()
+        if args.trace:
+            for _ in range(3):
+                calls["q8"]()
+                calls["float"]()
+            device.synchronize()
+        else:
+            t = {k: [] for k in calls}
+            for _ in range(args.rounds):
+                for k in calls:
+                    t[k].append(per_launch_ms(calls[k]))
+            copy_ms = float(np.median(t["copy"]))
+            for k, wbytes in (("q8", qbytes), ("float", fbytes)):
+                ms = float(np.median(t[k]))
+                floor_ms = (in_bytes + wbytes) / 8e12 * 1e3
+                rows.append({"shape": shape, "call": k, "read_MiB": in_bytes >> 20, "written_MiB": wbytes >> 20, "ms": round(ms, 4),
+                             "spread": round(max(t[k]) / min(t[k]) - 1.0, 4), "floor_ms_at_8TBps": round(floor_ms, 4),
+                             "frac_of_floor": round(floor_ms / ms, 3), "moved_TBps": round((in_bytes + wbytes) / (ms * 1e-3) / 1e12, 2),
+                             "copy_of_the_input_ms": round(copy_ms, 4), "copy_TBps_read_plus_write": round(2 * in_bytes / (copy_ms * 1e-3) / 1e12, 2),
+                             "Gpairs_per_s": round(ni * ns * N / (ms * 1e-3) / 1e9, 1)})
+                print(json.dumps(rows[-1]), flush=True)
+        for d in (d_in, d_f, d_q, d_taps, d_tw, d_g, d_n):
+            d.free()
+    print(json.dumps({"channeliser": rows}), flush=True)
+    g.close()
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1581,6 +1648,10 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="alternations of the one-band and the two-band call")
     p.add_argument("--shape", default="128x16777216", help="INPUTSxSAMPLES: rows of int8 samples")
     p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
+    p = sub.add_parser("channeliser")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the quantised call, the float call and the copy per shape")
+    p.add_argument("--shapes", default="64x1024x8x8192,64x64x4x131072,64x2048x16x4096", help="INPUTSxNxPxSPECTRA, comma-separated")
+    p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1625,7 +1696,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "channeliser": cmd_channeliser, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
