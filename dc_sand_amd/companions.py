@@ -4,7 +4,7 @@ every function of ``signatures`` its ``(name, restype, argtypes)``.  Needs no bu
 """
 from __future__ import annotations
 
-from ctypes import POINTER, c_float, c_int, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_float, c_int, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 from typing import NamedTuple
 
 _VP = c_void_p
@@ -119,5 +119,16 @@ COMPANIONS = {
         ("dcs_bf_channelise_q8", c_int,
          [_VP, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, c_uint64, _VP, _VP, c_uint32, _VP, _VP, c_size_t, c_uint64,
           c_uint64, c_uint32, c_uint32, _VP, _VP]),
+    ]),
+    # the RFI flagger between the filterbanks and the dedispersion: exact statistics, cell / channel / spectrum flags, cleaned bytes
+    "rfi": Companion("dcs_rfi.h", "bf_rfi.cpp", "libdcs_rfi.so", [
+        ("dcs_bf_rfi_moments", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP, c_size_t, _VP]),
+        ("dcs_bf_rfi_flags", c_int,
+         [_VP, _VP, c_size_t, _VP, c_size_t, c_uint32, c_uint32, c_uint32, _VP, _VP, c_size_t, _VP, c_size_t, _VP, c_size_t, _VP,
+          c_size_t, _VP]),
+        ("dcs_bf_rfi_clean_q8", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, _VP, _VP, c_uint8, _VP, c_size_t, c_uint64,
+          c_uint64, _VP, _VP]),
     ]),
 }

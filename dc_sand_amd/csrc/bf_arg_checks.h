@@ -15,6 +15,7 @@
 #include "../../include/dcs_ddc.h"        // dcs_ddc_band
 #include "../../include/dcs_dedisperse.h" // dcs_bf_band
 #include "../../include/dcs_filterbank.h" // DCS_FB_DESCENDING
+#include "../../include/dcs_rfi.h"        // dcs_bf_rfi_thresholds
 #include "../../include/dcs_stokes.h"     // DCS_BF_STOKES_I, DCS_BF_STOKES_IQUV
 
 // p is a multiple of bytes, a power of two; a null pointer passes (an optional tensor's alignment is checked the same way)
@@ -273,6 +274,48 @@ inline int channelise_q8_args(dcs_bf_context *c, uint32_t N, uint32_t P, uint32_
     if (!c || (!empty && !d_gains) || !aligned(d_gains, 4u) || !aligned(d_clip_count, 8u)) return DCS_ERR_INVALID_ARGUMENT;
     return channelise_args(c, N, P, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order, d_out_q8, 1u, out_bytes,
                            out_blocks, first_block, out_inputs, first_input);
+}
+
+// include/dcs_rfi.h: a window of nr_blocks blocks of 1 .. 65536 spectra, at most 2^32 - 1 spectra in all.  The buffers whose
+// sizes need no C are checked here (a product past 64 bits holds in no buffer); those that need it are the _impl's
+inline bool rfi_window_ok(uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams)
+{
+    return nr_beams != 0u && block_len >= 1u && block_len <= 65536u && (uint64_t)nr_blocks * block_len <= 0xffffffffull;
+}
+inline bool rfi_threshold_ok(double v) { return std::isfinite(v) && v >= 0.0; }
+inline int rfi_moments_args(dcs_bf_context *c, const uint8_t *d_filterbank, uint64_t in_spectra, uint64_t first_spectrum,
+                            uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint32_t *d_cell_sums,
+                            const uint32_t *d_zero_dm, size_t zero_dm_bytes)
+{
+    return arg_status(c && d_filterbank && d_cell_sums && aligned(d_filterbank, 16u) && aligned(d_cell_sums, 8u) &&
+                      aligned(d_zero_dm, 4u) && rfi_window_ok(nr_blocks, block_len, nr_beams) &&
+                      fits(first_spectrum, (uint64_t)nr_blocks * block_len, in_spectra) &&
+                      (!d_zero_dm || holds(zero_dm_bytes, nr_beams, (uint64_t)nr_blocks * block_len, sizeof(uint32_t), 1u)));
+}
+inline int rfi_flags_args(dcs_bf_context *c, const uint32_t *d_cell_sums, const uint32_t *d_zero_dm, size_t zero_dm_bytes,
+                          uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr,
+                          const uint8_t *d_cell_flags, const uint8_t *d_channel_mask, const uint8_t *d_spectrum_flags,
+                          size_t spectrum_flags_bytes, const uint32_t *d_counts, size_t counts_bytes)
+{
+    if (!(c && d_cell_sums && thr && d_cell_flags && d_channel_mask && d_counts && aligned(d_cell_sums, 8u) && aligned(d_zero_dm, 4u) &&
+          aligned(d_counts, 4u) && rfi_window_ok(nr_blocks, block_len, nr_beams)))
+        return DCS_ERR_INVALID_ARGUMENT;
+    if (!(rfi_threshold_ok(thr->mean_thr) && rfi_threshold_ok(thr->mean_floor) && rfi_threshold_ok(thr->var_thr) &&
+          rfi_threshold_ok(thr->var_floor) && rfi_threshold_ok(thr->zero_dm_thr) && rfi_threshold_ok(thr->zero_dm_floor)))
+        return DCS_ERR_INVALID_ARGUMENT;
+    const uint64_t window = (uint64_t)nr_blocks * block_len;
+    return arg_status(!d_zero_dm == !d_spectrum_flags && holds(counts_bytes, nr_beams, 3u, sizeof(uint32_t), 1u) &&
+                      (!d_zero_dm || (holds(zero_dm_bytes, nr_beams, window, sizeof(uint32_t), 1u) &&
+                                      holds(spectrum_flags_bytes, nr_beams, window, 1u, 1u))));
+}
+inline int rfi_clean_q8_args(dcs_bf_context *c, const uint8_t *d_filterbank, uint64_t in_spectra, uint64_t first_spectrum,
+                             uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_out, uint64_t out_spectra,
+                             uint64_t first_out, const unsigned long long *d_replaced)
+{
+    return arg_status(c && d_filterbank && d_out && aligned(d_filterbank, 16u) && aligned(d_out, 16u) && aligned(d_replaced, 8u) &&
+                      rfi_window_ok(nr_blocks, block_len, nr_beams) &&
+                      fits(first_spectrum, (uint64_t)nr_blocks * block_len, in_spectra) &&
+                      fits(first_out, (uint64_t)nr_blocks * block_len, out_spectra));
 }
 
 #endif // BF_ARG_CHECKS_H

@@ -2,12 +2,12 @@
 // incoherent beam (include/dcs_incoherent_beam.h), the search filterbanks (include/dcs_filterbank.h), the Stokes
 // detection of 8-bit beams (include/dcs_stokes.h), the dedispersion of the filterbanks (include/dcs_dedisperse.h), the
 // single-pulse search on its planes (include/dcs_single_pulse.h), the correlator (include/dcs_correlator.h), the digital
-// down-converter (include/dcs_ddc.h), the candidate sifter (include/dcs_candidates.h) and the polyphase channeliser
-// (include/dcs_channeliser.h), each reached through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing
+// down-converter (include/dcs_ddc.h), the candidate sifter (include/dcs_candidates.h), the polyphase channeliser
+// (include/dcs_channeliser.h) and the RFI flagger (include/dcs_rfi.h), each reached through the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters and its device, nothing
 // else.  Each begins with the device-free checks of its table entry (bf_arg_checks.h), the ones its companion has made
 // already; what follows needs the device or the context's sizes, or is a condition that only this side makes.  Host code
 // only; the kernels are in bf_integrate.hip, bf_incoherent.hip, bf_filterbank.hip, bf_stokes.hip, bf_dedisperse.hip,
-// bf_single_pulse.hip, bf_correlator.hip, bf_ddc.hip, bf_candidates.hip and bf_channeliser.hip.
+// bf_single_pulse.hip, bf_correlator.hip, bf_ddc.hip, bf_candidates.hip, bf_channeliser.hip and bf_rfi.hip.
 
 #include <cmath>
 #include <cstring>
@@ -483,6 +483,100 @@ int channelise_q8_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps
         return e;
     return channelise_launch(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_stride, d_taps, d_twiddles, order, d_gains, nullptr,
                              d_out_q8, out_blocks, first_block, out_inputs, first_input, d_clip_count, stream);
+}
+
+// include/dcs_rfi.h, reached the same way.  Nothing allocated; of the context the channel count and the device are used.  The
+// sizes that need C are checked here; the thresholds are host memory and travel by value in the kernels' arguments.
+int rfi_moments_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                     uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, uint32_t *d_cell_sums, size_t cell_sums_bytes,
+                     uint32_t *d_zero_dm, size_t zero_dm_bytes, void *stream)
+{
+    if (int e = rfi_moments_args(c, d_filterbank, in_spectra, first_spectrum, nr_blocks, block_len, nr_beams, d_cell_sums, d_zero_dm,
+                                 zero_dm_bytes))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cell_sums_bytes, nr_beams, nr_blocks, C, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_moments_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.cell_sums = d_cell_sums;
+    a.zero_dm = d_zero_dm;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    return (int)bf_launch_rfi_moments(a, as_stream(stream));
+}
+
+int rfi_flags_impl(dcs_bf_context *c, const uint32_t *d_cell_sums, size_t cell_sums_bytes, const uint32_t *d_zero_dm, size_t zero_dm_bytes,
+                   uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr, uint8_t *d_cell_flags,
+                   size_t cell_flags_bytes, uint8_t *d_channel_mask, size_t channel_mask_bytes, uint8_t *d_spectrum_flags,
+                   size_t spectrum_flags_bytes, uint32_t *d_counts, size_t counts_bytes, void *stream)
+{
+    if (int e = rfi_flags_args(c, d_cell_sums, d_zero_dm, zero_dm_bytes, nr_blocks, block_len, nr_beams, thr, d_cell_flags, d_channel_mask,
+                               d_spectrum_flags, spectrum_flags_bytes, d_counts, counts_bytes))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(cell_sums_bytes, nr_beams, nr_blocks, C, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cell_flags_bytes, nr_beams, nr_blocks, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(channel_mask_bytes, nr_beams, C, 1u, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_flags_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.cell_sums = d_cell_sums;
+    a.zero_dm = d_zero_dm;
+    a.cell_flags = d_cell_flags;
+    a.channel_mask = d_channel_mask;
+    a.spectrum_flags = d_spectrum_flags;
+    a.counts = d_counts;
+    a.mean_thr = thr->mean_thr;
+    a.mean_floor = thr->mean_floor;
+    a.var_thr = thr->var_thr;
+    a.var_floor = thr->var_floor;
+    a.zero_dm_thr = thr->zero_dm_thr;
+    a.zero_dm_floor = thr->zero_dm_floor;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    a.max_bad_blocks = thr->max_bad_blocks;
+    return (int)bf_launch_rfi_flags(a, as_stream(stream));
+}
+
+int rfi_clean_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                      uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_cell_flags, const uint8_t *d_channel_mask,
+                      const uint8_t *d_spectrum_flags, uint8_t fill, uint8_t *d_out, size_t out_bytes, uint64_t out_spectra,
+                      uint64_t first_out, unsigned long long *d_replaced, void *stream)
+{
+    if (int e = rfi_clean_q8_args(c, d_filterbank, in_spectra, first_spectrum, nr_blocks, block_len, nr_beams, d_out, out_spectra, first_out,
+                                  d_replaced))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(out_bytes, nr_beams, out_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_clean_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.out = d_out;
+    a.cell_flags = d_cell_flags;
+    a.channel_mask = d_channel_mask;
+    a.spectrum_flags = d_spectrum_flags;
+    a.replaced = d_replaced;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.out_spectra = out_spectra;
+    a.first_out = first_out;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    a.fill = fill;
+    return (int)bf_launch_rfi_clean(a, as_stream(stream));
 }
 
 } // namespace bf_host

@@ -4,11 +4,11 @@
 // (include/dcs_filterbank.h), libdcs_beam_complex.so (include/dcs_beam_complex.h), libdcs_beam_complex_quant.so
 // (include/dcs_beam_complex_quant.h), libdcs_stokes.so (include/dcs_stokes.h), libdcs_dedisperse.so
 // (include/dcs_dedisperse.h), libdcs_single_pulse.so (include/dcs_single_pulse.h), libdcs_correlator.so
-// (include/dcs_correlator.h), libdcs_ddc.so (include/dcs_ddc.h), libdcs_candidates.so (include/dcs_candidates.h) and
-// libdcs_channeliser.so (include/dcs_channeliser.h).  All are built from this tree together.
+// (include/dcs_correlator.h), libdcs_ddc.so (include/dcs_ddc.h), libdcs_candidates.so (include/dcs_candidates.h),
+// libdcs_channeliser.so (include/dcs_channeliser.h) and libdcs_rfi.so (include/dcs_rfi.h).  All are built from this tree together.
 // Every dcs_bf_context begins with a bf_ctx_ext_head whose table points at the product library's
 // implementation of the weighted, the quantised, the detecting and the complex-product beamformer calls, of the incoherent
-// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator, of the down-converter, of the candidate sifter and of the channeliser; a companion's
+// beam, of the filterbank calls, of the Stokes detection, of the dedispersion, of the single-pulse search, of the correlator, of the down-converter, of the candidate sifter, of the channeliser and of the RFI flagger; a companion's
 // export is two statements: the entry's device-free checks (bf_arg_checks.h, where the implementation behind the table
 // takes them from too), then forward(), which checks the table's version and calls the entry.  Not a public interface.
 #ifndef BF_CTX_EXT_H
@@ -42,7 +42,9 @@
 // foreign version above 12).
 // 15: channelise, channelise_q8 appended (tests/test_host_abi_channeliser.py hands its companion 1, 13 and 14; no older test
 // hands a foreign version above 13).
-#define BF_CTX_EXT_VERSION 15u
+// 16: rfi_moments, rfi_flags, rfi_clean_q8 appended (tests/test_host_abi_rfi.py hands its companion 1, 14 and 15; no older test
+// hands a foreign version above 14).
+#define BF_CTX_EXT_VERSION 16u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -158,6 +160,21 @@ struct bf_ctx_ext_ops {
                          uint32_t order, const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks,
                          uint64_t first_block, uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count,
                          void *stream);
+    // the RFI flagger (include/dcs_rfi.h): filterbanks uint8 [nr_beams][in_spectra][C] -> {sum x, sum x^2} uint32
+    // [nr_beams][nr_blocks][C][2] and the zero-DM series uint32 [nr_beams][nr_blocks * block_len] (nullptr = not wanted); those ->
+    // cell flags uint8 [nr_beams][nr_blocks][C], channel masks uint8 [nr_beams][C], spectrum flags uint8 [nr_beams][nr_blocks *
+    // block_len] and counts uint32 [nr_beams][3]; filterbanks and any of the flags (nullptr = none) -> the cleaned filterbanks
+    int (*rfi_moments)(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                       uint64_t first_spectrum, uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, uint32_t *d_cell_sums,
+                       size_t cell_sums_bytes, uint32_t *d_zero_dm, size_t zero_dm_bytes, void *stream);
+    int (*rfi_flags)(dcs_bf_context *c, const uint32_t *d_cell_sums, size_t cell_sums_bytes, const uint32_t *d_zero_dm,
+                     size_t zero_dm_bytes, uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr,
+                     uint8_t *d_cell_flags, size_t cell_flags_bytes, uint8_t *d_channel_mask, size_t channel_mask_bytes,
+                     uint8_t *d_spectrum_flags, size_t spectrum_flags_bytes, uint32_t *d_counts, size_t counts_bytes, void *stream);
+    int (*rfi_clean_q8)(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                        uint64_t first_spectrum, uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_cell_flags,
+                        const uint8_t *d_channel_mask, const uint8_t *d_spectrum_flags, uint8_t fill, uint8_t *d_out, size_t out_bytes,
+                        uint64_t out_spectra, uint64_t first_out, unsigned long long *d_replaced, void *stream);
 };
 
 // the first member of struct dcs_bf_context

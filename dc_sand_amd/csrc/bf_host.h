@@ -209,6 +209,17 @@ int channelise_q8_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps
                        const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
                        const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
                        uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count, void *stream);
+int rfi_moments_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                     uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, uint32_t *d_cell_sums, size_t cell_sums_bytes,
+                     uint32_t *d_zero_dm, size_t zero_dm_bytes, void *stream);
+int rfi_flags_impl(dcs_bf_context *c, const uint32_t *d_cell_sums, size_t cell_sums_bytes, const uint32_t *d_zero_dm, size_t zero_dm_bytes,
+                   uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr, uint8_t *d_cell_flags,
+                   size_t cell_flags_bytes, uint8_t *d_channel_mask, size_t channel_mask_bytes, uint8_t *d_spectrum_flags,
+                   size_t spectrum_flags_bytes, uint32_t *d_counts, size_t counts_bytes, void *stream);
+int rfi_clean_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                      uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_cell_flags, const uint8_t *d_channel_mask,
+                      const uint8_t *d_spectrum_flags, uint8_t fill, uint8_t *d_out, size_t out_bytes, uint64_t out_spectra,
+                      uint64_t first_out, unsigned long long *d_replaced, void *stream);
 
 } // namespace bf_host
 

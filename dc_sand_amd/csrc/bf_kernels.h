@@ -401,6 +401,45 @@ struct bf_chan_args {
 hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream);
 hipError_t bf_warm_module_channeliser();
 
+// The RFI flagger (bf_rfi.hip; include/dcs_rfi.h) on the filterbanks uint8 [B][in_spectra][C].  The
+// window is rows first .. first + nr_blocks * block_len - 1 of every beam, nr_blocks blocks of block_len rows.
+// {sum x, sum x^2} per (beam, block, channel), and the sum over the channels of every row of the window
+struct bf_rfi_moments_args {
+    const uint8_t *in;   // 16-byte aligned
+    uint32_t *cell_sums; // [B][nr_blocks][C][2]
+    uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]: zeroed by the launcher, added to by the kernel
+    uint64_t in_spectra, first;
+    uint32_t C, B, nr_blocks, block_len;
+    uint32_t lanes, tiles; // filled by the launcher: lanes of 16 channels per row (a power of two <= 64), channel tiles per row
+};
+hipError_t bf_launch_rfi_moments(const bf_rfi_moments_args &a, hipStream_t stream);
+// cell sums and the zero-DM series -> cell flags, channel masks, spectrum flags, counts; the thresholds by value
+struct bf_rfi_flags_args {
+    const uint32_t *cell_sums; // [B][nr_blocks][C][2]
+    const uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]
+    uint8_t *cell_flags;       // [B][nr_blocks][C]
+    uint8_t *channel_mask;     // [B][C]
+    uint8_t *spectrum_flags;   // nullptr with zero_dm, or [B][nr_blocks * block_len]
+    uint32_t *counts;          // [B][3]
+    double mean_thr, mean_floor, var_thr, var_floor, zero_dm_thr, zero_dm_floor;
+    uint32_t C, B, nr_blocks, block_len, max_bad_blocks;
+};
+hipError_t bf_launch_rfi_flags(const bf_rfi_flags_args &a, hipStream_t stream);
+// the window with every flagged byte replaced by fill, into rows first_out .. of out uint8 [B][out_spectra][C]
+struct bf_rfi_clean_args {
+    const uint8_t *in;             // 16-byte aligned
+    uint8_t *out;                  // 16-byte aligned; may be in where the rows are the same ones
+    const uint8_t *cell_flags;     // nullptr (none), or [B][nr_blocks][C]
+    const uint8_t *channel_mask;   // nullptr (none), or [B][C]: a zero byte replaces the channel
+    const uint8_t *spectrum_flags; // nullptr (none), or [B][nr_blocks * block_len]
+    unsigned long long *replaced;  // nullptr, or [B]: grows by the bytes replaced
+    uint64_t in_spectra, first, out_spectra, first_out;
+    uint32_t C, B, nr_blocks, block_len, fill;
+    uint32_t lanes, tiles;         // filled by the launcher, as bf_rfi_moments_args
+};
+hipError_t bf_launch_rfi_clean(const bf_rfi_clean_args &a, hipStream_t stream);
+hipError_t bf_warm_module_rfi();
+
 // 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
 // [T][C][B], beam fastest; cb = C * B.
 // Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64

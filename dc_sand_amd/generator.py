@@ -8,6 +8,7 @@ torch CUDA tensor's ``data_ptr()``).
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from ctypes import byref, c_float, c_size_t, c_void_p
 
 import numpy as np
@@ -225,6 +226,56 @@ def dm_time_bytes(nr_beams: int, nr_dm: int, out_spectra: int) -> int:
     """Size of the DM-time planes ``uint32 [nr_beams][nr_dm][out_spectra]`` of
     :meth:`SteeringCoefficientGenerator.dedisperse_q8`."""
     return int(nr_beams) * int(nr_dm) * int(out_spectra) * 4
+
+
+def rfi_cell_sums_bytes(params: BeamformerParameters, nr_beams: int, nr_blocks: int) -> int:
+    """Size of the cell sums ``uint32 [nr_beams][nr_blocks][C][2]`` of :meth:`SteeringCoefficientGenerator.rfi_moments`."""
+    return int(nr_beams) * int(nr_blocks) * int(params.NR_CHANNELS) * 8
+
+
+def rfi_zero_dm_bytes(nr_beams: int, nr_spectra: int) -> int:
+    """Size of the zero-DM series ``uint32 [nr_beams][nr_spectra]`` of :meth:`SteeringCoefficientGenerator.rfi_moments`;
+    ``nr_spectra`` is the window, ``nr_blocks * block_len``."""
+    return int(nr_beams) * int(nr_spectra) * 4
+
+
+def rfi_cell_flags_bytes(params: BeamformerParameters, nr_beams: int, nr_blocks: int) -> int:
+    """Size of the cell flags ``uint8 [nr_beams][nr_blocks][C]`` of :meth:`SteeringCoefficientGenerator.rfi_flags`."""
+    return int(nr_beams) * int(nr_blocks) * int(params.NR_CHANNELS)
+
+
+def rfi_channel_mask_bytes(params: BeamformerParameters, nr_beams: int) -> int:
+    """Size of the channel masks ``uint8 [nr_beams][C]`` of :meth:`SteeringCoefficientGenerator.rfi_flags`."""
+    return int(nr_beams) * int(params.NR_CHANNELS)
+
+
+def rfi_spectrum_flags_bytes(nr_beams: int, nr_spectra: int) -> int:
+    """Size of the spectrum flags ``uint8 [nr_beams][nr_spectra]`` of :meth:`SteeringCoefficientGenerator.rfi_flags`."""
+    return int(nr_beams) * int(nr_spectra)
+
+
+def rfi_counts_bytes(nr_beams: int) -> int:
+    """Size of the counts ``uint32 [nr_beams][3]`` of :meth:`SteeringCoefficientGenerator.rfi_flags`."""
+    return int(nr_beams) * 12
+
+
+@dataclasses.dataclass(frozen=True)
+class RfiThresholds:
+    """``dcs_bf_rfi_thresholds`` (include/dcs_rfi.h): an element is an outlier iff its distance from the lower median is
+    above ``max(thr * MAD, floor)``; a channel is masked with more than ``max_bad_blocks`` flagged cells."""
+    mean_thr: float = 6.0
+    mean_floor: float = 0.0
+    var_thr: float = 6.0
+    var_floor: float = 0.0
+    zero_dm_thr: float = 6.0
+    zero_dm_floor: float = 0.0
+    max_bad_blocks: int = 0
+
+
+class _RfiThresholds(ctypes.Structure):  # dcs_bf_rfi_thresholds (include/dcs_rfi.h)
+    _fields_ = [("mean_thr", ctypes.c_double), ("mean_floor", ctypes.c_double), ("var_thr", ctypes.c_double),
+                ("var_floor", ctypes.c_double), ("zero_dm_thr", ctypes.c_double), ("zero_dm_floor", ctypes.c_double),
+                ("max_bad_blocks", ctypes.c_uint32)]
 
 
 def dm_time_sums_bytes(nr_beams: int, nr_dm: int) -> int:
@@ -588,6 +639,57 @@ class SteeringCoefficientGenerator:
                                       int(max_delay), _p_or_null(d_channel_mask), _p(d_dm_time), int(dm_time_bytes),
                                       int(out_spectra), int(first_out), _s(stream)),
               "dcs_bf_dedisperse_q8")
+
+    # -- the RFI flagger between the filterbanks and the dedispersion (include/dcs_rfi.h, companion library libdcs_rfi.so): the
+    #    window of every call is nr_blocks blocks of block_len spectra from first_spectrum on
+    def rfi_moments(self, d_filterbank, filterbank_bytes: int, in_spectra: int, first_spectrum: int, nr_blocks: int,
+                    block_len: int, nr_beams: int, d_cell_sums, cell_sums_bytes: int, d_zero_dm=None, zero_dm_bytes: int = 0,
+                    stream=None) -> None:
+        """Per (beam, block, channel) the exact ``{sum x, sum x^2}`` of the block's ``block_len`` bytes into ``d_cell_sums``
+        (:func:`rfi_cell_sums_bytes`) and, with ``d_zero_dm`` (:func:`rfi_zero_dm_bytes`), per beam and spectrum of the
+        window the sum of the spectrum's bytes over the channels."""
+        rl = _lib.companion("rfi")
+        check(rl.dcs_bf_rfi_moments(c_void_p(self._h), _p(d_filterbank), int(filterbank_bytes), int(in_spectra),
+                                    int(first_spectrum), int(nr_blocks), int(block_len), int(nr_beams), _p(d_cell_sums),
+                                    int(cell_sums_bytes), _p_or_null(d_zero_dm), int(zero_dm_bytes), _s(stream)),
+              "dcs_bf_rfi_moments")
+
+    def rfi_flags(self, d_cell_sums, cell_sums_bytes: int, nr_blocks: int, block_len: int, nr_beams: int, d_cell_flags,
+                  cell_flags_bytes: int, d_channel_mask, channel_mask_bytes: int, d_counts, counts_bytes: int,
+                  thresholds: RfiThresholds = RfiThresholds(), d_zero_dm=None, zero_dm_bytes: int = 0, d_spectrum_flags=None,
+                  spectrum_flags_bytes: int = 0, stream=None) -> None:
+        """The statistics of :meth:`rfi_moments` to flags by a lower median and median absolute deviation across the
+        channels of every (beam, block): bit 0 of a cell's flag (:func:`rfi_cell_flags_bytes`) for its sum, bit 1 for
+        ``n * s2 - s1^2``; a channel's mask byte (:func:`rfi_channel_mask_bytes`) is 0 with more than
+        ``thresholds.max_bad_blocks`` flagged cells, else 1; with ``d_zero_dm`` and ``d_spectrum_flags``
+        (:func:`rfi_spectrum_flags_bytes`) a spectrum's flag is 1 where its zero-DM sum is an outlier of the beam's window.
+        ``d_counts`` (:func:`rfi_counts_bytes`) gets ``{cells flagged, channels masked, spectra flagged}`` per beam."""
+        t = thresholds
+        thr = _RfiThresholds(float(t.mean_thr), float(t.mean_floor), float(t.var_thr), float(t.var_floor), float(t.zero_dm_thr),
+                             float(t.zero_dm_floor), int(t.max_bad_blocks))
+        rl = _lib.companion("rfi")
+        check(rl.dcs_bf_rfi_flags(c_void_p(self._h), _p(d_cell_sums), int(cell_sums_bytes), _p_or_null(d_zero_dm),
+                                  int(zero_dm_bytes), int(nr_blocks), int(block_len), int(nr_beams),
+                                  ctypes.cast(ctypes.pointer(thr), c_void_p), _p(d_cell_flags), int(cell_flags_bytes),
+                                  _p(d_channel_mask), int(channel_mask_bytes), _p_or_null(d_spectrum_flags),
+                                  int(spectrum_flags_bytes), _p(d_counts), int(counts_bytes), _s(stream)),
+              "dcs_bf_rfi_flags")
+
+    def rfi_clean_q8(self, d_filterbank, filterbank_bytes: int, in_spectra: int, first_spectrum: int, nr_blocks: int,
+                     block_len: int, nr_beams: int, fill: int, d_out, out_bytes: int, out_spectra: int, first_out: int = 0,
+                     d_cell_flags=None, d_channel_mask=None, d_spectrum_flags=None, d_replaced=None, stream=None) -> None:
+        """The window into rows ``first_out ..`` of ``d_out`` (``uint8 [nr_beams][out_spectra][C]``; may be the filterbank
+        itself at the same rows) with ``fill`` for every byte whose channel's mask byte is 0, whose cell's flag is not 0 or
+        whose spectrum's flag is not 0 (each ``None``: none); ``d_replaced``: ``None``, or a zeroed device
+        ``uint64 [nr_beams]`` array that grows by the bytes replaced."""
+        if not 0 <= int(fill) <= 255:
+            raise ValueError("fill is a byte")
+        rl = _lib.companion("rfi")
+        check(rl.dcs_bf_rfi_clean_q8(c_void_p(self._h), _p(d_filterbank), int(filterbank_bytes), int(in_spectra),
+                                     int(first_spectrum), int(nr_blocks), int(block_len), int(nr_beams), _p_or_null(d_cell_flags),
+                                     _p_or_null(d_channel_mask), _p_or_null(d_spectrum_flags), int(fill), _p(d_out),
+                                     int(out_bytes), int(out_spectra), int(first_out), _p_or_null(d_replaced), _s(stream)),
+              "dcs_bf_rfi_clean_q8")
 
     # -- the single-pulse search on those planes (include/dcs_single_pulse.h, companion library libdcs_single_pulse.so):
     #    d_widths a device uint32 [nr_widths] array of boxcar widths, d_peaks a device uint32

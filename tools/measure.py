@@ -63,6 +63,11 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         small integers, beside a device-to-device copy of the input's bytes in the same process: the time, the floor of the
         bytes it must move at 8 TB/s and the fraction of it reached; --trace: a few launches only, for a counter run
                                                                                     -> profiles/r18_channeliser.md
+    python tools/measure.py rfi [--rounds 5] [--shapes BEAMSxSPECTRAxCHANNELSxBLOCK_LEN,...] [--nr-dm 512] [--trace]
+        the RFI flagger's statistics pass, flags and cleaning per shape beside stokes_block over the same number of bytes, in
+        turn in one process over two copies of the input: each time, its bytes' floor at 8 TB/s, its ratio to the yardstick, and
+        the whole stage as a share of the dedispersion of the same spectra; --trace: a few launches only, for a counter run
+                                                                                    -> profiles/r19_rfi.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -1201,6 +1206,116 @@ def cmd_channeliser(args):
     g.close()
 
 
+def cmd_rfi(args):
+    """The RFI flagger (include/dcs_rfi.h).  Per shape (beams x spectra x channels x block_len): the statistics pass, the flags
+    and the cleaning (out of place, all three kinds of flags, with the counter) on noise-like bytes, beside stokes_block -- the
+    project's read-bound streaming kernel -- over the same number of input bytes, in turn ``--rounds`` times in one process;
+    then the dedispersion of the same spectra at ``--nr-dm`` DMs (the band of the dedisperse subcommand).  The hot calls and
+    the yardstick rotate over two copies of their input, so that no call finds its bytes in the Infinity Cache.  Floors: the
+    bytes a call must move at 8 TB/s -- B T C read by the statistics, read and written by the cleaning."""
+    from dc_sand_amd.generator import (RfiThresholds, block_stokes_bytes, dm_delays_bytes, dm_time_bytes, filterbank_bytes,
+                                       quantised_beams_bytes, rfi_cell_flags_bytes, rfi_cell_sums_bytes, rfi_channel_mask_bytes,
+                                       rfi_counts_bytes, rfi_spectrum_flags_bytes, rfi_zero_dm_bytes)
+
+    rows = []
+    for text in args.shapes.split(","):
+        B, T, C, n = (int(x) for x in text.lower().split("x"))
+        nb, nr_dm = T // n, args.nr_dm
+        assert nb * n == T and (B * T * C) % 65536 == 0
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+        g = SteeringCoefficientGenerator(bp)
+        band, dms = (1500.0, -300.0 / C, 64e-6), np.linspace(0.0, 500.0, nr_dm)
+        tb, pb = dm_delays_bytes(bp, nr_dm), dm_time_bytes(B, nr_dm, T)
+        d_dms, d_delays, d_plane = device.mem_alloc(dms.nbytes), device.mem_alloc(tb), device.mem_alloc(pb)
+        device.memcpy_htod(d_dms, dms)
+        g.dm_delays(*band, d_dms, nr_dm, d_delays, tb)
+        device.synchronize()
+        table = np.empty((nr_dm, C), np.int32)
+        device.memcpy_dtoh(table, d_delays)
+        max_delay = int(table.max())
+        in_spectra = T + max_delay
+        fb = filterbank_bytes(bp, B, in_spectra)
+        bufs = [device.mem_alloc(fb) for _ in range(2)]
+        for d in bufs:
+            _noise(d, fb)
+        d_clean = device.mem_alloc(fb)
+        sizes = (rfi_cell_sums_bytes(bp, B, nb), rfi_zero_dm_bytes(B, T), rfi_cell_flags_bytes(bp, B, nb), rfi_channel_mask_bytes(bp, B),
+                 rfi_spectrum_flags_bytes(B, T), rfi_counts_bytes(B), 8 * B)
+        d_cs, d_z, d_cf, d_cm, d_sf, d_cnt, d_rep = (device.mem_alloc(s) for s in sizes)
+        device.memset(d_rep, 0, 8 * B)
+        turn = [0]
+
+        def buf():
+            turn[0] ^= 1
+            return bufs[turn[0]]
+        moments = lambda: g.rfi_moments(buf(), fb, in_spectra, 0, nb, n, B, d_cs, sizes[0], d_z, sizes[1])  # noqa: E731
+        moments_only = lambda: g.rfi_moments(buf(), fb, in_spectra, 0, nb, n, B, d_cs, sizes[0])  # noqa: E731
+        flags = lambda: g.rfi_flags(d_cs, sizes[0], nb, n, B, d_cf, sizes[2], d_cm, sizes[3], d_cnt, sizes[5],  # noqa: E731
+                                    thresholds=RfiThresholds(max_bad_blocks=2), d_zero_dm=d_z, zero_dm_bytes=sizes[1],
+                                    d_spectrum_flags=d_sf, spectrum_flags_bytes=sizes[4])
+        clean = lambda: g.rfi_clean_q8(buf(), fb, in_spectra, 0, nb, n, B, 128, d_clean, fb, in_spectra, d_cell_flags=d_cf,  # noqa: E731
+                                       d_channel_mask=d_cm, d_spectrum_flags=d_sf, d_replaced=d_rep)
+        dedisp = lambda: g.dedisperse_q8(bufs[0], fb, in_spectra, 0, T, B, d_delays, nr_dm, max_delay, d_plane, pb, T)  # noqa: E731
+        # the yardstick: 64 beams x 256 samples of two polarisations in Cs channels are B T C bytes
+        Bs, nts, Cs = 64, 256, B * T * C // 65536
+        bps = BeamformerParameters(NR_CHANNELS=Cs, NR_STATIONS=1, NR_BEAMS=Bs, NR_SAMPLES_PER_CHANNEL=nts)
+        gs = SteeringCoefficientGenerator(bps)
+        qb, sb1 = quantised_beams_bytes(bps, nts), block_stokes_bytes(bps, nts, 1)
+        assert 2 * qb == B * T * C
+        sbufs = [device.mem_alloc(2 * qb) for _ in range(2)]
+        for d in sbufs:
+            _noise(d, 2 * qb)
+        d_bs = device.mem_alloc(sb1)
+
+        def stokes():
+            turn[0] ^= 1
+            d = int(sbufs[turn[0]])
+            gs.stokes_block(d, d + qb, qb, d_bs, sb1, nts, nr_stokes=1)
+        for fn in (moments, moments_only, flags, clean, stokes):
+            fn()
+        device.synchronize()
+        if args.trace:
+            for fn in (moments, flags, clean, stokes) * 3:
+                fn()
+            device.synchronize()
+            continue
+        t = {name: [] for name in ("moments", "moments_only", "flags", "clean", "stokes", "dedisperse")}
+        for _ in range(args.rounds):
+            t["moments"].append(per_launch_ms(moments))
+            t["stokes"].append(per_launch_ms(stokes))
+            t["clean"].append(per_launch_ms(clean))
+            t["stokes"].append(per_launch_ms(stokes))
+            t["moments_only"].append(per_launch_ms(moments_only))
+            t["flags"].append(per_launch_ms(flags))
+        dedisp()
+        device.synchronize()
+        for _ in range(min(args.rounds, 3)):
+            t["dedisperse"].append(per_launch_ms(dedisp, settle_ms=100.0, timed_ms=200.0))
+        med = {name: float(np.median(x)) for name, x in t.items()}
+        nbytes = B * T * C
+        floor_us = nbytes / 8e12 * 1e6
+        stage = med["moments"] + med["flags"] + med["clean"]
+        row = {"shape": f"B={B} T={T} C={C} block_len={n}", "bytes_MiB": nbytes >> 20, "max_delay": max_delay, "nr_dm": nr_dm,
+               "moments_us": round(med["moments"] * 1e3, 1), "moments_floor_us": round(floor_us, 1),
+               "moments_share_of_floor": round(floor_us / (med["moments"] * 1e3), 3),
+               "moments_without_zero_dm_us": round(med["moments_only"] * 1e3, 1),
+               "clean_us": round(med["clean"] * 1e3, 1), "clean_floor_us": round(2 * floor_us, 1),
+               "clean_share_of_floor": round(2 * floor_us / (med["clean"] * 1e3), 3),
+               "flags_us": round(med["flags"] * 1e3, 1),
+               "stokes_us": round(med["stokes"] * 1e3, 1), "stokes_spread": round(max(t["stokes"]) / min(t["stokes"]) - 1.0, 4),
+               "moments_over_stokes": round(med["moments"] / med["stokes"], 3), "clean_over_stokes": round(med["clean"] / med["stokes"], 3),
+               "spreads": {k: round(max(v) / min(v) - 1.0, 4) for k, v in t.items()},
+               "rfi_stage_us": round(stage * 1e3, 1), "dedisperse_ms": round(med["dedisperse"], 3),
+               "rfi_stage_over_dedisperse": round(stage / med["dedisperse"], 4)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        g.close()
+        gs.close()
+        for d in bufs + sbufs + [d_clean, d_dms, d_delays, d_plane, d_cs, d_z, d_cf, d_cm, d_sf, d_cnt, d_rep, d_bs]:
+            d.free()
+    print(json.dumps({"rfi": rows}), flush=True)
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1652,6 +1767,11 @@ def main():
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantised call, the float call and the copy per shape")
     p.add_argument("--shapes", default="64x1024x8x8192,64x64x4x131072,64x2048x16x4096", help="INPUTSxNxPxSPECTRA, comma-separated")
     p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
+    p = sub.add_parser("rfi")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the three calls and the Stokes yardstick per shape")
+    p.add_argument("--shapes", default="4x16384x4096x256,4x16384x4100x256", help="BEAMSxSPECTRAxCHANNELSxBLOCK_LEN, comma-separated")
+    p.add_argument("--nr-dm", type=int, default=512, help="DMs of the dedispersion that the stage is compared with")
+    p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1696,7 +1816,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "channeliser": cmd_channeliser, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "channeliser": cmd_channeliser, "rfi": cmd_rfi, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
