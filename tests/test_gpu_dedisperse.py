@@ -8,7 +8,10 @@ from functools import partial
 import numpy as np
 import pytest
 
+from helpers import dedisperse_paths as paths
 from helpers import hip_graph
+from helpers.dedisperse_cases import (ANY_SHAPE, CAPTURE_DM_SETS, CASES, CHAIN_BAND, DM_SETS, MASK_DMS, RAGGED_C, RAGGED_CASES, any_tables,
+                                      capture_mask, some_mask, table_255)
 from helpers.dedisperse_model import (BAND_ASCENDING_100, BAND_DESCENDING_64, DMS_40, INT32_MAX, INT32_MIN, dedisperse, dm_delays,
                                       smooth_table, takes_part)
 from helpers.device_buffers import Context, closed_after
@@ -105,27 +108,6 @@ def test_delays_are_the_model(gpu, case, C):
 
 # ------------------------------------------------------------------------------------- planes with the tables dm_delays makes
 
-DM_SETS = {1: DMS_40[39:], 7: DMS_40[3::6], 40: DMS_40}  # 97.5 alone; 7.5, 22.5 .. 97.5; all
-assert [len(v) for v in DM_SETS.values()] == [1, 7, 40]
-SPECTRA = [1, 3, 4, 5, 63, 64, 65, 257, 1000]
-
-
-def plane_cases():
-    """Every nr_spectra twice, with B, nr_dm, first_spectrum and first_out rotating through their values at different
-    periods, so that every value of each meets both bands and several sizes."""
-    out = []
-    for r in range(2):
-        for i, T in enumerate(SPECTRA):
-            k = i + 4 * r
-            out.append((T, (1, 3)[(k + r) % 2], (1, 7, 40)[k % 3], (0, 1, 6)[(k // 2 + r) % 3], (0, 5)[(k // 3) % 2]))
-    return out
-
-
-CASES = plane_cases()
-assert {c[1] for c in CASES} == {1, 3} and {c[2] for c in CASES} == {1, 7, 40} and {c[3] for c in CASES} == {0, 1, 6}
-assert {c[4] for c in CASES} == {0, 5} and len(set(CASES)) == 18
-
-
 @pytest.fixture(scope="module")
 def band_tables():
     """The two bands' full tables from the model, shared."""
@@ -152,11 +134,11 @@ def test_planes_of_the_device_tables(gpu, case, band_tables, C, band):
     c.check(fb, table, 6, 700, int(table.max()), out_spectra=710, first_out=5, d_delays=d_delays)
 
 
-@pytest.mark.parametrize("C", [1, 3, 17, 257])
+@pytest.mark.parametrize("C", RAGGED_C)
 def test_ragged_columns_with_smooth_tables(gpu, case, C):
     """Chunks that are no whole 32 columns and rows that start at any byte: C odd."""
     c = case(C)
-    for nr_dm, top, T, B, first in ((7, 600, 65, 3, 1), (40, 1330, 257, 1, 6), (1, 90, 1000, 2, 0), (19, 333, 513, 1, 3)):
+    for nr_dm, top, T, B, first in RAGGED_CASES:
         table = smooth_table(C, nr_dm, top, seed=C + nr_dm)
         max_delay = int(table.max())
         fb = seeded_bytes(B, first + T + max_delay, C, seed=C * T)
@@ -168,25 +150,16 @@ def test_ragged_columns_with_smooth_tables(gpu, case, C):
 def test_any_table_and_entries_that_drop(gpu, case):
     """Random entries in [0, 50000]: 6.4 MB of filterbanks that no LDS window holds.  Then the same table with entries
     outside [0, max_delay] sprinkled in, and a DM whose every term drops."""
-    C, B, T, max_delay, nr_dm = 64, 2, 300, 50000, 9
+    C, B, T, max_delay, nr_dm = ANY_SHAPE
     c = case(C)
-    rng = np.random.default_rng(50000)
     fb = seeded_bytes(B, T + max_delay, C, seed=1)
     assert fb.nbytes >= 6_400_000
-    table = rng.integers(0, max_delay + 1, size=(nr_dm, C)).astype(np.int32)
-    table[0, 0], table[1, 1] = 0, max_delay
+    table, bad, smooth = any_tables()
     c.check(fb, table, 0, T, max_delay)
-    bad = table.copy()
-    pos = rng.choice(bad.size, size=40, replace=False)
-    bad.reshape(-1)[pos] = np.resize(np.array([-1, INT32_MIN, max_delay + 1, INT32_MAX], np.int64), 40).astype(np.int32)
-    bad[5] = np.resize(np.array([-1, INT32_MIN, max_delay + 1, INT32_MAX, -77, 2**30], np.int64), C).astype(np.int32)
     assert takes_part(table, max_delay).all() and takes_part(bad, max_delay).sum() < table.size - C - 20
     got = c.check(fb, bad, 0, T, max_delay)
     assert not got[:, 5].any() and got[:, 4].all()
     # the same bad entries in a table that is staged: a smooth one
-    smooth = smooth_table(C, nr_dm, 400, seed=3)
-    smooth.reshape(-1)[pos] = bad.reshape(-1)[pos]
-    smooth[5] = bad[5]
     got = c.check(fb, smooth, 0, T, max_delay)
     assert not got[:, 5].any()
 
@@ -196,14 +169,13 @@ def test_any_table_and_entries_that_drop(gpu, case):
 def test_channel_mask(gpu, case):
     C, B, T = 100, 2, 130
     c = case(C)
-    table = dm_delays(C, *BAND_ASCENDING_100, DMS_40[30:37])
+    table = dm_delays(C, *BAND_ASCENDING_100, MASK_DMS)
     max_delay = int(table.max())
     fb = seeded_bytes(B, T + max_delay, C, seed=2)
     plain = c.check(fb, table, 0, T, max_delay)
     ones = c.check(fb, table, 0, T, max_delay, mask=np.ones(C, np.uint8))
     assert np.array_equal(plain, ones)
-    mask = np.random.default_rng(3).integers(0, 2, size=C).astype(np.uint8) * 0x80  # any non-zero byte keeps the column
-    mask[:34] = 0  # a whole chunk of columns that no DM takes
+    mask = some_mask(C)
     assert 10 < np.count_nonzero(mask) < C - 34
     some = c.check(fb, table, 0, T, max_delay, mask=mask)
     assert not np.array_equal(some, plain)
@@ -218,7 +190,7 @@ def test_every_byte_255(gpu, case, C):
     """258 columns is the smallest count at which a 16-bit lane can wrap: every word is 255 C."""
     T, B = 100, 1
     c = case(C)
-    table = np.stack([np.zeros(C, np.int32), smooth_table(C, 2, 300, seed=C)[1]])
+    table = table_255(C)
     max_delay = int(table.max())
     assert max_delay == 300
     fb = np.full((B, T + max_delay, C), 0xFF, np.uint8)
@@ -235,7 +207,7 @@ def test_both_calls_captured_and_replayed_with_new_contents(gpu, case):
 
     C, B, T, nr_dm, first, first_out, out_spectra = 100, 2, 200, 7, 2, 3, 210
     band = BAND_ASCENDING_100
-    dm_sets = [DMS_40[3::6], DMS_40[20:27], DMS_40[33:]]
+    dm_sets = CAPTURE_DM_SETS
     max_delay = max(int(dm_delays(C, *band, d).max()) for d in dm_sets)
     in_spectra = first + T + max_delay
     c = case(C)
@@ -250,7 +222,7 @@ def test_both_calls_captured_and_replayed_with_new_contents(gpu, case):
     seen = []
     for i, dms in enumerate(dm_sets):
         fb = seeded_bytes(B, in_spectra, C, seed=60 + i)
-        mask = (np.random.default_rng(70 + i).integers(0, 4, size=C) > 0).astype(np.uint8)
+        mask = capture_mask(i, C)
         gpu.memcpy_htod(d_dms, np.ascontiguousarray(dms), stream=s.handle, sync=False)
         gpu.memcpy_htod(d_fb, fb, stream=s.handle, sync=False)
         gpu.memcpy_htod(d_mask, mask, stream=s.handle, sync=False)
@@ -265,6 +237,120 @@ def test_both_calls_captured_and_replayed_with_new_contents(gpu, case):
         assert np.array_equal(got, exp), (i, np.argwhere(got != exp)[:3])
         seen.append(got)
     assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
+    graph.close()
+
+
+# --------------------------------------------------------------------------------- the staged / direct choice at its edges
+#
+# The kernel chooses per chunk, on the device, from the table's contents ("The choice").  The tables
+# below come from helpers/dedisperse_paths.py, whose CPU model says which form every chunk takes; that they sit on the rule's
+# edges -- the conditions a to i -- is asserted on that model in tests/test_dedisperse_paths.py, without a GPU.  Here the
+# bar is the file's own: every word of the plane is the model's, the canary and the prefill are untouched.
+
+KINDS = ("staged", "direct", "none")
+
+
+def check_edge(c, table, mask, T, max_delay, seed, B=2, first=0, first_out=0, tail=0):
+    """One call on B beams of seeded bytes, different per beam; no trivial expectation."""
+    fb = seeded_bytes(B, first + T + max_delay, c.C, seed=seed)
+    assert B < 2 or not np.array_equal(fb[0], fb[1])
+    got = c.check(fb, table, first, T, max_delay, mask=mask, out_spectra=first_out + T + tail, first_out=first_out)
+    assert np.unique(got[:, :, first_out:first_out + T]).size >= min(30, T)
+    return got
+
+
+@pytest.mark.parametrize("C", paths.EDGE_C)
+@pytest.mark.parametrize("part", range(paths.EDGE_PARTS))
+@pytest.mark.parametrize("nt", paths.EDGE_NT)
+def test_chunks_at_the_edges_of_the_choice(gpu, case, nt, part, C):
+    """Conditions a-e, h and i: spread 620 against 621 with the widest window last in LDS at residue 3; for every rounding
+    of the pitch a chunk at rows = 2 pitch + 64 and one a row past it; in tiles of 512, 487 and 1 times; staged by dwords
+    (C = 320) and by bytes with a last chunk of 29 columns (C = 317); a masked and a dead column in a staged edge chunk."""
+    table, mask, T, max_delay = paths.edge_case(nt, part, C)
+    kinds = {p.kind for p in paths.chunk_paths(table, T, max_delay, mask) if p.nt == nt}
+    assert kinds == {"staged", "direct"}
+    k = paths.EDGE_NT.index(nt) + part
+    check_edge(case(C), table, mask, T, max_delay, seed=nt + part + C, first=(0, 3, 6)[k % 3], first_out=(0, 5)[k % 2], tail=k % 2 * 3)
+
+
+@pytest.mark.parametrize("C", paths.ORDER_C)
+def test_every_order_of_staged_direct_and_no_term(gpu, case, C):
+    """Condition f: one workgroup walks chunks whose kinds follow each other in all nine orders; then two DM tiles and two
+    time tiles whose workgroups take different forms at the same chunk."""
+    c = case(C)
+    table, mask, T, max_delay = paths.order_case(C)
+    assert paths.orders(paths.chunk_paths(table, T, max_delay, mask)) == {(a, b) for a in KINDS for b in KINDS}
+    check_edge(c, table, mask, T, max_delay, seed=C)
+    table, mask, T, max_delay = paths.order_case_tiles(C)
+    groups = paths.workgroups(paths.chunk_paths(table, T, max_delay, mask))
+    assert len(groups) == 4 and any({g[i] for g in groups.values()} == set(KINDS) for i in range(10))
+    check_edge(c, table, mask, T, max_delay, seed=C + 1, first=2, first_out=7, tail=2)
+
+
+def test_dm_counts_at_the_waves_boundaries(gpu, case):
+    """Condition g: tiles of 1, 4, 5, 8, 12, 13 and 16 DMs, alone and behind full tiles (nr_dm = 17 and 33 among them)."""
+    c = case(paths.SWEEP_C)
+    seen = set()
+    for nr_dm in paths.SWEEP_NR_DM:
+        table, mask, T, max_delay = paths.sweep_case(nr_dm)
+        seen |= {p.nd for p in paths.chunk_paths(table, T, max_delay, mask)}
+        got = check_edge(c, table, mask, T, max_delay, seed=nr_dm, first=nr_dm % 3, first_out=nr_dm % 2)
+        assert got.shape[1] == nr_dm
+    assert seen == {1, 4, 5, 8, 12, 13, 16}
+
+
+def test_the_launch_is_one_kernel_of_the_tiles_the_model_assumes(gpu, case):
+    """512 times x 16 DMs x one beam per workgroup of 256 threads, from the device side: the captured call is a single
+    kernel node whose grid is ceil(T / 512) ceil(nr_dm / 16) B."""
+    from dc_sand_amd.generator import dm_time_bytes
+
+    C, B, T, nr_dm, max_delay = 64, 2, 1025, 33, 40
+    c = case(C)
+    d_fb = c.upload(seeded_bytes(B, T + max_delay, C, seed=5))
+    d_delays = c.upload(smooth_table(C, nr_dm, max_delay, seed=5))
+    pbytes = dm_time_bytes(B, nr_dm, T)
+    d_out = c.out(pbytes, PREFILL)
+    s = gpu.Stream()
+    others = []
+    nodes = hip_graph.launches(s, lambda: c.g.dedisperse_q8(d_fb, B * (T + max_delay) * C, T + max_delay, 0, T, B, d_delays, nr_dm, max_delay,
+                                                            d_out, pbytes, T, stream=s.handle), others)
+    s.synchronize()
+    assert not others and nodes == [((3 * 3 * 2, 1, 1), (256, 1, 1))], (nodes, others)
+    assert (paths.TILE_T, paths.TILE_D) == (512, 16) and (-(-T // 512), -(-nr_dm // 16)) == (3, 3)
+    assert np.all(c.read(d_out, pbytes, np.uint8, (-1,)) == PREFILL)  # nothing ran
+
+
+def test_a_replay_chooses_again_from_the_table_on_the_device(gpu, case):
+    """Captured with a table whose chunks are staged; replayed after the table on the device was overwritten with one whose
+    same chunks are direct, then with one where they have no term: the choice is made when the work runs."""
+    from dc_sand_amd.generator import dm_time_bytes
+
+    tables, T, max_delay = paths.replay_tables()
+    C, B, nr_dm, first, first_out, out_spectra = paths.REPLAY_C, 2, 16, 1, 2, 520
+    forms = [{p.kind for p in paths.chunk_paths(t, T, max_delay)} for t in tables]
+    assert forms == [{"staged"}, {"direct"}, {"none"}]
+    in_spectra = first + T + max_delay
+    c = case(C)
+    fb = seeded_bytes(B, in_spectra, C, seed=96)
+    pbytes = dm_time_bytes(B, nr_dm, out_spectra)
+    d_fb, d_delays, d_out = c.upload(fb), c.upload(tables[0]), c.out(pbytes, PREFILL)
+    s = gpu.Stream()
+    with hip_graph.capture(s) as graph:
+        c.g.dedisperse_q8(d_fb, fb.nbytes, in_spectra, first, T, B, d_delays, nr_dm, max_delay, d_out, pbytes, out_spectra,
+                          first_out=first_out, stream=s.handle)
+    seen = []
+    for i, table in enumerate(tables):
+        gpu.memcpy_htod(d_delays, np.ascontiguousarray(table), stream=s.handle, sync=False)
+        gpu.memset(d_out, PREFILL, pbytes, stream=s.handle)
+        graph.launch(s)
+        s.synchronize()
+        pre = np.full((B, nr_dm, out_spectra), PREFILL_WORD, np.uint32)
+        exp = dedisperse(fb, table, first, T, max_delay, out=pre, first_out=first_out)
+        got = c.read(d_out, pbytes, np.uint32, (B, nr_dm, out_spectra))
+        assert np.array_equal(got, exp), (i, np.argwhere(got != exp)[:3])
+        seen.append(got[:, :, first_out:first_out + T])
+    assert np.unique(seen[0]).size >= 30 and np.unique(seen[1]).size >= 30 and not np.array_equal(seen[0], seen[1])
+    assert not seen[2].any()
     graph.close()
 
 
@@ -312,7 +398,7 @@ def test_filterbank_q8_descending_into_dedisperse(gpu, case):
     from dc_sand_amd.generator import dm_time_bytes, filterbank_bytes, filterbank_scales_bytes
 
     C, B, nr_dm = 64, 3, 7
-    f0, df, ts = 829.68, 10.64, 306.24e-6
+    f0, df, ts = CHAIN_BAND
     band = (f0 + (C - 1) * df, -df, ts)
     dms = DMS_40[33:]
     table = dm_delays(C, *band, dms)
