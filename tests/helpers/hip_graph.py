@@ -1,5 +1,6 @@
-"""Stream capture into a hipGraph for the GPU tests, through the HIP runtime itself (libamdhip64.so, loaded once).  The
-capture mode is 0 (hipStreamCaptureModeGlobal).  A stream is a ``device.Stream`` or a raw ``hipStream_t``; the caller
+"""Stream capture into a hipGraph for the GPU tests, through the HIP runtime itself: the one the product library is linked
+to, reached through that library's handle ("Which runtime the tests use").  The capture mode is 0
+(hipStreamCaptureModeGlobal).  A stream is a ``device.Stream`` or a raw ``hipStream_t``; the caller
 makes it.
 
 ``with capture(s) as g:`` begins a capture on ``s`` and always ends it, also when the body raises -- the graph is then
@@ -38,19 +39,39 @@ _NODE_TYPE_KERNEL = 0  # hipGraphNodeTypeKernel
 NODE_TYPE_MEMSET = 2   # hipGraphNodeTypeMemset
 
 
+# every HIP entry point this module calls, with its argument types (tests/test_hip_runtime.py looks each of them up)
+ENTRY_POINTS = {
+    "hipStreamBeginCapture": [V, ctypes.c_int],
+    "hipStreamEndCapture": [V, ctypes.POINTER(V)],
+    "hipGraphInstantiate": [ctypes.POINTER(V), V, V, V, ctypes.c_size_t],
+    "hipGraphLaunch": [V, V],
+    "hipGraphExecDestroy": [V],
+    "hipGraphDestroy": [V],
+    "hipGraphGetNodes": [V, ctypes.POINTER(V), ctypes.POINTER(ctypes.c_size_t)],
+    "hipGraphNodeGetType": [V, ctypes.POINTER(ctypes.c_int)],
+    "hipGraphKernelNodeGetParams": [V, ctypes.POINTER(_KernelNodeParams)],
+}
+
+
+class _Entries:
+    pass
+
+
 def _hip():
+    """The entry points above, looked up through the handle of the product library: a lookup on that handle searches the
+    library and what it depends on, so it finds the HIP runtime the library itself calls -- the one that made every stream
+    a test hands in -- whatever else the process has mapped.  No library is opened by name here."""
     global _HIP
     if _HIP is None:
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipStreamBeginCapture.argtypes = [V, ctypes.c_int]
-        hip.hipStreamEndCapture.argtypes = [V, ctypes.POINTER(V)]
-        hip.hipGraphInstantiate.argtypes = [ctypes.POINTER(V), V, V, V, ctypes.c_size_t]
-        hip.hipGraphLaunch.argtypes = [V, V]
-        hip.hipGraphExecDestroy.argtypes = [V]
-        hip.hipGraphDestroy.argtypes = [V]
-        hip.hipGraphGetNodes.argtypes = [V, ctypes.POINTER(V), ctypes.POINTER(ctypes.c_size_t)]
-        hip.hipGraphNodeGetType.argtypes = [V, ctypes.POINTER(ctypes.c_int)]
-        hip.hipGraphKernelNodeGetParams.argtypes = [V, ctypes.POINTER(_KernelNodeParams)]
+        from dc_sand_amd import _lib
+
+        lib = _lib.lib()
+        hip = _Entries()
+        for name, argtypes in ENTRY_POINTS.items():
+            fn = lib[name]  # a function object of its own: nothing is cached on the product library's handle
+            fn.restype = ctypes.c_int
+            fn.argtypes = argtypes
+            setattr(hip, name, fn)
         _HIP = hip
     return _HIP
 

@@ -34,7 +34,7 @@ def test_committed_pmc_traffic_matches_workload():
     assert bench.pmc_traffic(algo // 2) == (None, None)  # another workload: no number is invented
 
 
-def test_gpus_n_without_ranks_is_an_error_not_a_one_gpu_line():
+def test_gpus_n_without_ranks_is_an_error_not_a_one_gpu_line(dcs_lib):
     """bench.py's launch contract, the part that needs no GPU: ``--gpus 2`` without a launcher starts two rank
     processes; here neither finds a HIP device, so the command exits non-zero and prints NO JSON line (round 2's
     bench.py would have measured one GPU and printed ``n_gpus: 1``).  Also: a launcher environment whose WORLD_SIZE
@@ -43,9 +43,10 @@ def test_gpus_n_without_ranks_is_an_error_not_a_one_gpu_line():
     import subprocess
 
     import pytest
-    import torch
 
-    if torch.cuda.device_count() >= 1:
+    from dc_sand_amd import device
+
+    if device.device_count() >= 1:  # the count the `gpu` fixture takes; torch stays out of this process
         pytest.skip("a GPU is present: tests/test_bench_contract.py covers this case there")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], capture_output=True,

@@ -219,3 +219,50 @@ def test_bad_arguments_raise():
         channeliser.channel_of(0, 64, order=2)
     with pytest.raises(ValueError):
         channeliser.channel_of(0.5, 64)
+
+
+# ---- what the GPU tests run of the kernel's instantiations (dc_sand_amd/csrc/bf_channeliser.hip), read from its text
+
+
+def kernel_text():
+    from pathlib import Path
+
+    return (Path(__file__).resolve().parent.parent / "dc_sand_amd" / "csrc" / "bf_channeliser.hip").read_text()
+
+
+def test_the_gpu_parametrisations_run_all_twelve_instantiations():
+    """One kernel per log2 N and per epilogue, and every int8 epilogue has a lane map of its own, made when compiling: the
+    GPU tests that hold an output to this model on seeded data must run each of the twelve."""
+    import re
+
+    from helpers import channeliser_cases as cc
+
+    cases = re.findall(r"case (\d+)u: return q \? launch<(\d+), true>\(a, stream\) : launch<(\d+), false>\(a, stream\);", kernel_text())
+    assert len(cases) == 6 and all(1 << int(L) == int(N) and L == L2 for N, L, L2 in cases)
+    every = {(int(L), q) for _, L, _ in cases for q in (False, True)}
+    assert len(every) == 12 and cc.instantiations() == every, sorted(every - cc.instantiations())
+    # the test's own condition on the model holds for every quantised case: checked there before the GPU is looked at
+
+
+def test_the_large_tensor_test_walks_items_beyond_the_grid():
+    """The launcher caps the grid at kGrid workgroups, which walk the items beyond: tests/test_gpu_channeliser_large.py has
+    262145 items, so that walk is run.  The item count is restated from the launcher's text."""
+    import re
+
+    from helpers import channeliser_large as cl
+
+    text = kernel_text()
+    grid = 1 << int(re.search(r"constexpr uint32_t kGrid = 1u << (\d+);", text).group(1))
+    for line in ("constexpr int total_bits(int L) { return L == 6 ? 12 : L == 11 ? 14 : 13; }",
+                 "constexpr int spectra_bits(int L) { return total_bits(L) - L < 4 ? total_bits(L) - L : 4; }",
+                 "constexpr uint32_t IG = 1u << (LT - L - LS);",
+                 "a.groups = (a.nr_inputs + IG - 1u) / IG;",
+                 "a.items = (uint64_t)(a.nr_spectra / 16u) * a.groups * (16u >> LS);",
+                 "dim3((uint32_t)(a.items < kGrid ? a.items : kGrid))"):
+        assert text.count(line) == 1, line
+    L = cl.N.bit_length() - 1
+    LT = 12 if L == 6 else 14 if L == 11 else 13
+    LS = min(LT - L, 4)
+    IG = 1 << (LT - L - LS)
+    items = (cl.NR_SPECTRA // 16) * ((cl.NI + IG - 1) // IG) * (16 >> LS)
+    assert (grid, items) == (65536, 262145) and items > grid and items % grid != 0

@@ -7,6 +7,7 @@ import pytest
 
 from dc_sand_amd import channeliser
 from helpers import channeliser_model as model
+from helpers.channeliser_cases import QUANTISED_CASES, SIZES
 from helpers import correlator_model, ddc_model, hip_graph
 from helpers.device_buffers import Context
 from helpers.examples import run_example
@@ -15,7 +16,6 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 PREFILL = 0xA5
-SIZES = (64, 128, 256, 512, 1024, 2048)
 
 
 def nan_table(N):
@@ -150,7 +150,7 @@ def test_two_calls_that_fill_a_tensor_are_one_call(case, N):
 # ---- 2. quantised output
 
 
-@pytest.mark.parametrize("N,P,ni,ns", ((64, 4, 3, 32), (256, 5, 2, 16), (2048, 16, 1, 16)))
+@pytest.mark.parametrize("N,P,ni,ns", QUANTISED_CASES)
 def test_the_quantised_output_is_the_model_and_the_float_output_quantised(case, N, P, ni, ns):
     W = channeliser.twiddles(N)
     z = model.seeded_input(ni, (ns + P - 1) * N, seed=N + P)

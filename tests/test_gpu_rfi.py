@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers import rfi_cases as rc
 from helpers import rfi_model as rm
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
 from helpers.device_buffers import Context, closed_after
@@ -75,8 +76,11 @@ class RCase(Context):
                 assert g.dtype == e.dtype and np.array_equal(g, e), (name, thr, np.argwhere(g != e)[:4])
         return got
 
-    def clean(self, fb, first, nb, n, fill, cell=None, mask=None, spec=None, out_spectra=None, first_out=0, count=True, in_place=False):
-        """dcs_bf_rfi_clean_q8 against the model, out of place into a prefilled tensor or in place: (bytes, replaced)."""
+    def clean(self, fb, first, nb, n, fill, cell=None, mask=None, spec=None, out_spectra=None, first_out=0, count=True, in_place=False,
+              offset=None):
+        """dcs_bf_rfi_clean_q8 against the model, out of place into a prefilled tensor or in place: (bytes, replaced).  With
+        ``offset`` every flag tensor lies that many bytes into an allocation of its own, between bytes that would replace
+        what it keeps if they were read as its flags: 0xFF around the cell and the spectrum flags, 0 around the channel mask."""
         B, in_spectra, C = fb.shape
         W = nb * n
         d_fb = self.out(fb.nbytes) if in_place else self.upload(fb)
@@ -87,10 +91,20 @@ class RCase(Context):
             out_spectra = first_out + W if out_spectra is None else out_spectra
             d_out = self.out(B * out_spectra * C, PREFILL)
             pre = np.full((B, out_spectra, C), PREFILL, np.uint8)
-        up = lambda a: None if a is None else self.upload(np.ascontiguousarray(a, dtype=np.uint8))  # noqa: E731
+
+        def up(a, around=0xFF):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            if offset is None:
+                return self.upload(a)
+            host = np.full(offset + a.size + 16, around, np.uint8)
+            host[offset:offset + a.size] = a.ravel()
+            return int(self.upload(host)) + offset
+
         d_rep = self.out(B * 8, 0) if count else None
         self.g.rfi_clean_q8(d_fb, fb.nbytes, in_spectra, first, nb, n, B, fill, d_out, B * out_spectra * C, out_spectra,
-                            first_out=first_out, d_cell_flags=up(cell), d_channel_mask=up(mask), d_spectrum_flags=up(spec),
+                            first_out=first_out, d_cell_flags=up(cell), d_channel_mask=up(mask, 0), d_spectrum_flags=up(spec),
                             d_replaced=d_rep)
         self.gpu.synchronize()
         got = self.read(d_out, B * out_spectra * C, np.uint8, (B, out_spectra, C))
@@ -112,27 +126,8 @@ def seeded_bytes(B, rows, C, seed):
 
 # ------------------------------------------------------------------------------------------------------------------ moments
 
-CHANNELS = [1, 3, 16, 64, 100, 1000, 4100]
-MORE_CHANNELS = [1040, 1030, 20]  # two tiles of channels, the second a part of one: rows in 16-byte units, and in single bytes; two lanes a row
-BLOCK_LENS = [1, 2, 5, 16, 257, 258, 1000]
-LIMIT = 12 << 20
-
-
-def moments_cases():
-    """Every C with every block_len, while nr_blocks, B and first_spectrum rotate at different periods; the largest are cut
-    to one beam and at most two blocks, so that the model stays quick: C -> [(block_len, nr_blocks, B, first)]."""
-    out = {}
-    for ci, C in enumerate(CHANNELS + MORE_CHANNELS):
-        out[C] = []
-        for i, n in enumerate(BLOCK_LENS):
-            nb, B, first = (1, 2, 7)[(i + ci) % 3], (1, 3)[(i + ci // 2) % 2], (0, 5)[(i // 2 + ci) % 2]
-            if B * nb * n * C > LIMIT:
-                nb, B = min(nb, 2), 1
-            out[C].append((n, nb, B, first))
-    return out
-
-
-CASES = moments_cases()
+CHANNELS, MORE_CHANNELS, BLOCK_LENS = rc.CHANNELS, rc.MORE_CHANNELS, rc.BLOCK_LENS  # the tables: helpers/rfi_cases.py
+CASES = rc.moments_cases()
 _ALL = [c for C in CHANNELS for c in CASES[C]]
 assert len(_ALL) == 49 and {c[1] for c in _ALL} == {1, 2, 7} and {c[2] for c in _ALL} == {1, 3} and {c[3] for c in _ALL} == {0, 5}
 assert all({c[0] for c in CASES[C]} == set(BLOCK_LENS) for C in CASES)
@@ -150,6 +145,25 @@ def test_moments_are_the_model(gpu, case, C):
         if i % 2 == 0:  # without the zero-DM series: the same cell sums
             alone, none = c.moments(fb, first, nb, n, zero_dm=False)
             assert none is None and np.array_equal(alone, exp_cs)
+
+
+FORM_CASES = rc.form_cases()
+
+
+@pytest.mark.parametrize("C", rc.FORM_CHANNELS)
+def test_moments_of_every_form_are_the_model(gpu, case, C):
+    """The (U, L) pairs, the partial tiles with whole lanes off and the trip counts of the zero-DM reduction that the tables
+    above leave out (tests/test_rfi_forms.py has the census), every case with and without the zero-DM series."""
+    c = case(C)
+    for i, (n, nb, B, first) in enumerate(FORM_CASES[C]):
+        fb = seeded_bytes(B, first + nb * n + (2 if i % 2 else 0), C, seed=7000 * C + n)
+        exp_cs, exp_z = rm.moments(fb, first, nb, n)
+        d_fb = c.upload(fb)
+        cs, z = c.moments(fb, first, nb, n, d_fb=d_fb)
+        assert np.array_equal(cs, exp_cs), (n, nb, B, first, np.argwhere(cs != exp_cs)[:4])
+        assert np.array_equal(z, exp_z), (n, nb, B, first, np.argwhere(z != exp_z)[:4])
+        alone, none = c.moments(fb, first, nb, n, zero_dm=False, d_fb=d_fb)
+        assert none is None and np.array_equal(alone, exp_cs), (n, nb, B, first)
 
 
 def test_moments_of_the_longest_block_at_full_scale(gpu, case):
@@ -184,7 +198,7 @@ def test_flags_of_the_devices_own_sums(gpu, case, C):
     thresholds 0, 6 and 1e300, and max_bad_blocks 0, 2 and nr_blocks."""
     c = case(C)
     rng = np.random.default_rng(C)
-    for n, nb, B in ((16, 7, 3), (257, 2, 1)) if C < 4100 else ((16, 7, 1), (5, 2, 3)):
+    for n, nb, B in rc.own_sums_shapes(C):
         fb = np.clip(np.rint(rng.normal(128, 16, (B, nb * n, C))), 0, 255).astype(np.uint8)
         fb[0, :, C // 2] = 128
         fb[B - 1, :, C // 3] = np.clip(np.rint(rng.normal(128, 40, nb * n)), 0, 255)
@@ -254,15 +268,16 @@ def test_flags_of_hand_made_sums(gpu, case):
 def test_flags_of_one_and_two_channels(gpu, case, C):
     c = case(C)
     fb = seeded_bytes(2, 40, C, seed=C)
-    cs, z = rm.moments(fb, 0, 4, 10)
+    nb, n = rc.ONE_AND_TWO_CHANNELS
+    cs, z = rm.moments(fb, 0, nb, n)
     for thr in THRESHOLDS:
-        c.check_flags(cs, z, 10, thr)
-    cell = c.check_flags(cs, z, 10, THRESHOLDS[0])[0]
+        c.check_flags(cs, z, n, thr)
+    cell = c.check_flags(cs, z, n, THRESHOLDS[0])[0]
     # one channel is its own median, at distance 0; of two the lower is the median and the other is out at thr = 0
     assert not cell.any() if C == 1 else cell.any() and not np.all(cell != 0)
 
 
-@pytest.mark.parametrize("C,nb,n", [(4096, 4, 4096), (4100, 5, 3277), (4100, 3, 3000), (4097, 1, 16385)])
+@pytest.mark.parametrize("C,nb,n", rc.ON_CHIP_CASES)
 def test_flags_on_both_sides_of_the_on_chip_lines(gpu, case, C, nb, n):
     """Up to 4096 channels and 16384 spectra the values of a bisection stay on chip (LDS, registers); beyond, every pass reads
     them from global memory.  Both lines from both sides, alone and together."""
@@ -279,6 +294,36 @@ def test_flags_on_both_sides_of_the_on_chip_lines(gpu, case, C, nb, n):
     got = c.check_flags(cs, z, n, rm.Thresholds())
     assert got[2][0, 4000:4004].all() and got[2].sum() < 40
     c.check_flags(cs, z, n, rm.Thresholds(2.0, 0.0, 2.0, 0.0, 2.0, 0.0, 1))
+
+
+@pytest.mark.parametrize("nb", rc.UNROLL_NR_BLOCKS)
+def test_flags_across_the_unroll_of_the_bad_block_count(gpu, case, nb):
+    """The beam kernel counts a channel's bad blocks eight at a time, with a tail.  Hand-made sums (helpers/rfi_cases.py;
+    tests/test_rfi_forms.py holds them to their conditions on the model alone) give chosen channels exactly max_bad_blocks and
+    one more bad cell, in the unrolled part only, in the tail only, and in both, for max_bad_blocks 0, 1 and 2."""
+    c = case(rc.UNROLL_C)
+    cs, _ = rm.moments(rc.unroll_filterbank(nb), 0, nb, rc.UNROLL_LEN)
+    bad = rc.unroll_expected_bad(nb)
+    for M in rc.UNROLL_MAX_BAD:
+        cell, mask, _, counts = c.check_flags(cs, None, rc.UNROLL_LEN, rm.Thresholds(max_bad_blocks=M))
+        assert np.array_equal((cell != 0).sum(axis=1), bad)
+        assert np.array_equal(mask, (bad <= M).astype(np.uint8)) and 0 < (mask == 0).sum() < mask.size  # as made, and not trivial
+        assert counts[:, 0].tolist() == bad.sum(axis=1).tolist() and counts[:, 1].tolist() == (bad > M).sum(axis=1).tolist()
+        assert counts[:, :2].all() and not counts[:, 2].any()
+
+
+def test_flags_where_the_top_bits_of_m_and_q_decide(gpu, case):
+    """block_len 65536: m up to 255 * 65536, so that bit 23 and bit 22 each decide a median and a MAD, and q up to
+    65025 * 2^30, the largest there is.  The sums are made from byte counts, so they are sums that bytes can have; that cells
+    are flagged and kept on each side of 2^22 and 2^23, and that the limits lie ON a cell where they are meant to, is held on
+    the model alone (tests/test_rfi_forms.py)."""
+    c = case(rc.TOP_BITS_C)
+    cs = rc.top_bits_sums()
+    seen = [c.check_flags(cs, None, rc.TOP_BITS_LEN, thr) for thr in rc.top_bits_thresholds(cs)]
+    assert all(0 < (s[0] != 0).sum() < s[0].size for s in seen[:6]) and len({s[0].tobytes() for s in seen}) == len(seen)
+    assert (seen[0][0] & 1).any() and (seen[0][0] & 2).any() and 0 < (seen[2][1] == 0).sum() < 70
+    z = np.random.default_rng(23).integers(0, 1 << 32, size=(1, cs.shape[1] * rc.TOP_BITS_LEN), dtype=np.uint32)  # a window past 16384
+    c.check_flags(cs, z, rc.TOP_BITS_LEN, rc.TOP_THRESHOLDS)
 
 
 def test_recipe_gives_the_expected_sets(gpu, case):
@@ -301,11 +346,11 @@ def test_recipe_gives_the_expected_sets(gpu, case):
 
 # -------------------------------------------------------------------------------------------------------------------- clean
 
-@pytest.mark.parametrize("C", [3, 64, 100, 1030, 1040, 4100])
+@pytest.mark.parametrize("C", rc.CLEAN_CHANNELS)
 def test_clean_is_the_model(gpu, case, C):
     c = case(C)
     rng = np.random.default_rng(C)
-    B, nb, n, first, first_out = (3, 7, 5, 2, 4) if C < 4100 else (2, 2, 37, 1, 0)
+    B, nb, n, first, first_out = rc.clean_shape(C)
     W = nb * n
     fb = seeded_bytes(B, first + W + 1, C, seed=C + 1)
     cell = rng.choice(np.array([0, 0, 0, 0, 1, 2, 3, 0x80], np.uint8), size=(B, nb, C))
@@ -328,6 +373,61 @@ def test_clean_is_the_model(gpu, case, C):
     # blocks of one spectrum, and one block of all
     c.clean(fb, first, W, 1, 0, rng.choice(np.array([0, 0, 1], np.uint8), size=(B, W, C)), mask, spec, **kw)
     c.clean(fb, first, 1, W, 255, cell[:, :1], mask, spec, **kw)
+
+
+def flag_tensors(rng, B, nb, W, C):
+    cell = rng.choice(np.array([0, 0, 0, 0, 1, 2, 3, 0x80], np.uint8), size=(B, nb, C))
+    mask = rng.choice(np.array([1, 1, 1, 0x80, 0], np.uint8), size=(B, C))
+    spec = rng.choice(np.array([0, 0, 0, 0, 1, 0xFF], np.uint8), size=(B, W))
+    return cell, mask, spec
+
+
+@pytest.mark.parametrize("C", rc.FORM_CHANNELS)
+def test_clean_of_every_form_is_the_model(gpu, case, C):
+    """The forms test_clean_is_the_model leaves out, as the moments have them: out of place and in place, with and without
+    the flag tensors."""
+    c = case(C)
+    rng = np.random.default_rng(C)
+    for i, (n, nb, B, first) in enumerate(FORM_CASES[C]):
+        W, first_out = nb * n, (0, 2)[i % 2]
+        fb = seeded_bytes(B, first + W + 1, C, seed=C + n)
+        cell, mask, spec = flag_tensors(rng, B, nb, W, C)
+        kw = dict(out_spectra=first_out + W + 1, first_out=first_out)
+        copy, none = c.clean(fb, first, nb, n, 128, **kw)
+        assert not none.any() and np.array_equal(copy[:, first_out:first_out + W], fb[:, first:first + W])
+        both, replaced = c.clean(fb, first, nb, n, 77, cell, mask, spec, **kw)
+        assert np.all(replaced <= W * C) and (C * W < 64 or np.all(replaced > 0))
+        c.clean(fb, first, nb, n, 77, cell=cell, count=False, **kw)
+        c.clean(fb, first, nb, n, 77, mask=mask, spec=spec, **kw)
+        same, _ = c.clean(fb, first, nb, n, 77, cell, mask, spec, in_place=True)
+        assert np.array_equal(same[:, first:first + W], both[:, first_out:first_out + W])
+        assert np.array_equal(same[:, :first], fb[:, :first]) and np.array_equal(same[:, first + W:], fb[:, first + W:])
+
+
+@pytest.mark.parametrize("C,offset", [(C, o) for C, offsets in rc.OFFSET_CASES.items() for o in offsets])
+def test_clean_with_flag_tensors_at_any_byte_offset(gpu, case, C, offset):
+    """include/dcs_rfi.h gives the flag tensors no alignment rule: where one is not aligned to the unit of the row accesses
+    the kernel loads it in single bytes.  Every flag tensor lies `offset` bytes into its allocation, between bytes that would
+    replace what the tensor's own first and last entries keep; no byte of the filterbank equals the fill, so every byte
+    replaced shows.  (A broken byte path fails this; a kernel without one might not, where the hardware serves the
+    unaligned vector load.)"""
+    B, nb, n, first = rc.OFFSET_SHAPE
+    W = nb * n
+    c = case(C)
+    rng = np.random.default_rng(100 * C + offset)
+    fb = seeded_bytes(B, first + W + 1, C, seed=C + offset)
+    fb[fb == 77] = 78
+    cell, mask, spec = flag_tensors(rng, B, nb, W, C)
+    cell[..., 0] = cell[..., -1] = 0     # kept by their own flags, replaced by the bytes around them
+    mask[:, 0] = mask[:, -1] = 1
+    spec[:, 0] = spec[:, -1] = 0
+    aligned, replaced = c.clean(fb, first, nb, n, 77, cell, mask, spec)
+    assert np.all(replaced > 0) and np.all(replaced < W * C)
+    for kw in (dict(cell=cell), dict(mask=mask), dict(spec=spec), dict(cell=cell, mask=mask, spec=spec)):
+        got, _ = c.clean(fb, first, nb, n, 77, offset=offset, **kw)
+        if len(kw) == 3:
+            assert np.array_equal(got, aligned)
+        c.clean(fb, first, nb, n, 77, offset=offset, in_place=True, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------------------- chains

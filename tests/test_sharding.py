@@ -75,7 +75,7 @@ def _worker(rank: int, world: int, port: int, ret):
 
 
 def test_broadcast_and_shard_gloo_world2(oracle):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp  # the workers import torch, each in its own process; this one does not
 
     world = 2
     port = 29500 + (os.getpid() % 2000)
