@@ -19,7 +19,7 @@ SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip
            dc_sand_amd/csrc/bf_candidates.hip dc_sand_amd/csrc/bf_channeliser.hip dc_sand_amd/csrc/bf_rfi.hip \
            dc_sand_amd/csrc/bf_capi.hip \
            dc_sand_amd/csrc/bf_capi_generate.hip \
-           dc_sand_amd/csrc/bf_capi_beamform.hip dc_sand_amd/csrc/bf_capi_detect.hip dc_sand_amd/csrc/bf_capi_stream.hip
+           dc_sand_amd/csrc/bf_capi_beamform.hip dc_sand_amd/csrc/bf_capi_stream.hip
 HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/csrc/bf_device.h dc_sand_amd/csrc/bf_stream_ext.h \
            dc_sand_amd/csrc/bf_ctx_ext.h dc_sand_amd/csrc/bf_arg_checks.h dc_sand_amd/csrc/bf_host.h \
            dc_sand_amd/csrc/bf_beamform_kernel.inc \

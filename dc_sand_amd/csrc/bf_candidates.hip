@@ -21,11 +21,28 @@
 // below max_candidates it counts the window's members and writes its record as two 16-byte stores.
 // Every offset into the planes and the records is 64-bit.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include "bf_arg_checks.h" // the tile's sides and the largest radius: what the workspace figure is made of
 
 #include <hip/hip_runtime.h>
+
+// The candidate sifter (include/dcs_candidates.h): the cells (beam, DM, block)
+// of blocks first_block .. first_block + nr_blocks - 1 at or above threshold that no cell within the two radii beats, as
+// records of eight words in ascending (beam, DM, block).  A segment is a row of a tile: kCandTileBlocks cells of one DM
+struct bf_cand_args {
+    const float *snr;      // [B][nr_dm][nr_widths][peak_blocks]
+    const uint32_t *peaks; // [B][nr_dm][nr_widths][peak_blocks][2], 8-byte aligned
+    uint32_t *cands;       // [max_candidates][8], 8-byte aligned; nullptr where max_candidates == 0
+    uint32_t *count;       // {found, written}
+    uint64_t *marks;       // the workspace: [segments] ballots of the candidates ...
+    uint32_t *places;      // ... and [segments] counts, which the scan makes the segments' first places in the list
+    uint64_t peak_blocks, first_block;
+    uint64_t segments;     // B * nr_dm * k_tiles < 2^32
+    uint32_t B, nr_dm, nr_blocks, nr_widths, dm_radius, block_radius, max_candidates;
+    float threshold;
+    uint32_t dm_tiles, k_tiles; // filled by the launcher: tiles along the DMs and along the blocks
+};
 
 namespace {
 
@@ -251,7 +268,7 @@ hipError_t bf_warm_module_candidates()
 
 // The tile kernel, the scan, and -- where a record can be written -- the scatter; an empty shape launches the scan alone,
 // which zeroes d_count
-hipError_t bf_launch_find_candidates(const bf_cand_args &args, hipStream_t stream)
+static hipError_t bf_launch_find_candidates(const bf_cand_args &args, hipStream_t stream)
 {
     if (args.dm_radius > kCandMaxRadius || args.block_radius > kCandMaxRadius) return hipErrorInvalidValue; // what the LDS tile is sized for
     bf_cand_args a = args;
@@ -273,3 +290,47 @@ hipError_t bf_launch_find_candidates(const bf_cand_args &args, hipStream_t strea
     }
     return hipSuccess;
 }
+
+// The host side of include/dcs_candidates.h, behind the table as in bf_integrate.hip.  Nothing allocated; of the context only
+// its device is used.  The counts and a record's block are 32-bit words: a call with 2^32 cells or more, or with a block past
+// 2^32, is not supported.
+namespace bf_host {
+
+int find_candidates_impl(dcs_bf_context *c, const float *d_snr, size_t snr_bytes, const uint32_t *d_peaks, size_t peaks_bytes,
+                         uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm,
+                         uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
+                         size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes, void *stream)
+{
+    if (int e = find_candidates_args(c, d_snr, d_peaks, peak_blocks, first_block, nr_blocks, nr_beams, threshold, dm_radius,
+                                     block_radius, d_cands, max_candidates, d_count, d_work))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (((unsigned __int128)series * nr_blocks >> 32) || first_block + nr_blocks > (1ull << 32)) return DCS_ERR_UNSUPPORTED;
+    if (!holds(snr_bytes, series, nr_widths, peak_blocks, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cands_bytes, max_candidates, 32u, 1u, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (work_bytes < candidates_workspace_bytes(nr_beams, nr_dm, nr_blocks)) return DCS_ERR_INVALID_ARGUMENT;
+    const uint64_t segments = (uint64_t)candidates_segments(nr_beams, nr_dm, nr_blocks); // no more than the cells
+    bf_cand_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.snr = d_snr;
+    a.peaks = d_peaks;
+    a.cands = static_cast<uint32_t *>(d_cands);
+    a.count = d_count;
+    a.marks = static_cast<uint64_t *>(d_work);
+    a.places = reinterpret_cast<uint32_t *>(a.marks + segments);
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.B = nr_beams;
+    a.nr_dm = nr_dm;
+    a.nr_blocks = nr_blocks;
+    a.nr_widths = nr_widths;
+    a.dm_radius = dm_radius;
+    a.block_radius = block_radius;
+    a.max_candidates = max_candidates;
+    a.threshold = threshold;
+    return (int)bf_launch_find_candidates(a, as_stream(stream));
+}
+
+} // namespace bf_host

@@ -1,7 +1,7 @@
 // bf_capi.hip -- implementation of include/dcs_beamformer.h (the C-ABI): status strings, parameter checks, the
-// verifier's host recipes, the device plumbing, and the context.  The generator, the beamformers, what comes after
-// detection and the streams are in bf_capi_generate.hip, bf_capi_beamform.hip, bf_capi_detect.hip and
-// bf_capi_stream.hip; bf_host.h is what they share.
+// verifier's host recipes, the device plumbing, and the context.  The generator, the beamformers and the streams are in
+// bf_capi_generate.hip, bf_capi_beamform.hip and bf_capi_stream.hip; a stage after detection has its host side at the end
+// of its kernel unit; bf_host.h is what they share.
 // Host code only; the kernels are in bf_kernels.hip.  Nothing here exits,
 // throws across the boundary, prints, or starts threads.
 
@@ -88,7 +88,7 @@ int refuse_if_capturing(hipStream_t stream)
 } // namespace bf_host
 
 namespace {
-// the companions' calls (bf_ctx_ext.h): the beamformers' in bf_capi_beamform.hip, the others in bf_capi_detect.hip
+// the companions' calls (bf_ctx_ext.h): the beamformers' in bf_capi_beamform.hip, the others in their stages' kernel units
 const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_weighted_impl, beamform_accumulated_weighted_impl,
                                     beamform_accumulated_q8_impl, beamform_accumulated_power_impl, integrate_block_power_impl,
                                     incoherent_block_power_impl, integrate_incoherent_power_impl,

@@ -24,9 +24,27 @@
 // low lane bits go to such index bits (lane_map below, made when compiling), so every read and write of steps 2 and 3 is
 // conflict-free; the writes of step 1 (bit-reversed columns) are at most two to a bank.  Offsets into the tensors are size_t.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// The polyphase channeliser (include/dcs_channeliser.h): float [nr_inputs][in_stride][2]
+// -> FIR of P rows of N pairs, N-point butterfly network -> [N][out_blocks][out_inputs][16][2] as floats (out) or quantised
+// (out_q8, with gains and counters); exactly one of out and out_q8 is set
+struct bf_chan_args {
+    const float *in;       // 8-byte aligned
+    const float *taps;     // [P][N]
+    const float *twiddles; // [N / 2][2], 8-byte aligned
+    const float *gains;    // out_q8 only: [nr_inputs][N]
+    float *out;            // 16-byte aligned, or nullptr
+    int8_t *out_q8;        // 16-byte aligned, or nullptr
+    unsigned long long *clip_count; // out_q8 only: [nr_inputs], or nullptr
+    uint64_t in_stride;    // pairs, >= (nr_spectra + P - 1) N
+    uint64_t out_blocks, first_block;
+    uint64_t items;        // filled by the launcher
+    uint32_t N, P, nr_inputs, nr_spectra, order, out_inputs, first_input;
+    uint32_t groups;       // filled by the launcher: the groups of inputs that share an item
+};
 
 namespace {
 
@@ -276,7 +294,7 @@ hipError_t bf_warm_module_channeliser()
     return e;
 }
 
-hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream)
+static hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream)
 {
     if (a.nr_spectra == 0u || a.nr_inputs == 0u) return hipSuccess;
     if (a.nr_spectra % 16u != 0u || a.P < 1u || a.P > (uint32_t)kMaxTaps || a.order > 1u || (a.out != nullptr) == (a.out_q8 != nullptr))
@@ -292,3 +310,61 @@ hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream)
     default: return hipErrorInvalidValue;
     }
 }
+
+// The host side of include/dcs_channeliser.h, behind the table as in bf_integrate.hip.  Of the context these use the device
+// alone: every size is an argument, and the device-free checks are all the checks there are.  Nothing allocated: one launch each.
+namespace bf_host {
+
+static int channelise_launch(dcs_bf_context *c, uint32_t N, uint32_t P, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                             uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order, const float *d_gains,
+                             float *d_out, int8_t *d_out_q8, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs,
+                             uint32_t first_input, unsigned long long *d_clip_count, void *stream)
+{
+    DCS_CHECK_DEVICE(c);
+    if (nr_spectra == 0u || nr_inputs == 0u) return DCS_OK;
+    bf_chan_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_in;
+    a.taps = d_taps;
+    a.twiddles = d_twiddles;
+    a.gains = d_gains;
+    a.out = d_out;
+    a.out_q8 = d_out_q8;
+    a.clip_count = d_clip_count;
+    a.in_stride = in_stride;
+    a.out_blocks = out_blocks;
+    a.first_block = first_block;
+    a.N = N;
+    a.P = P;
+    a.nr_inputs = nr_inputs;
+    a.nr_spectra = nr_spectra;
+    a.order = order;
+    a.out_inputs = out_inputs;
+    a.first_input = first_input;
+    return (int)bf_launch_channelise(a, as_stream(stream));
+}
+
+int channelise_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
+                    size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order, float *d_out,
+                    size_t out_bytes, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs, uint32_t first_input, void *stream)
+{
+    if (int e = channelise_args(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order,
+                                d_out, 4u, out_bytes, out_blocks, first_block, out_inputs, first_input))
+        return e;
+    return channelise_launch(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_stride, d_taps, d_twiddles, order, nullptr, d_out,
+                             nullptr, out_blocks, first_block, out_inputs, first_input, nullptr, stream);
+}
+
+int channelise_q8_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra,
+                       const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
+                       const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
+                       uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count, void *stream)
+{
+    if (int e = channelise_q8_args(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_bytes, in_stride, d_taps, d_twiddles, order,
+                                   d_gains, d_out_q8, out_bytes, out_blocks, first_block, out_inputs, first_input, d_clip_count))
+        return e;
+    return channelise_launch(c, nr_channels, nr_taps, nr_inputs, nr_spectra, d_in, in_stride, d_taps, d_twiddles, order, d_gains, nullptr,
+                             d_out_q8, out_blocks, first_block, out_inputs, first_input, d_clip_count, stream);
+}
+
+} // namespace bf_host

@@ -36,11 +36,28 @@
 // b <= a half; rows and columns past A are not stored (their loads are clamped to antenna A - 1).  Every word is written
 // once, by a plain store.  Byte offsets are 64-bit.  No LDS, no barrier, no scratch (the register report is in DESIGN.md).
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+
+// The correlator (include/dcs_correlator.h): the sample tensor
+// [C][nT16][A][16][2] -> exact visibilities int32 [C][nr_vis][NB][2] of the pairs b <= a, each summed over n blocks
+struct bf_corr_args {
+    const int8_t *ant; // 16-byte aligned
+    int32_t *vis;      // 8-byte aligned
+    uint64_t NB;       // filled by the launcher: A (A + 1) / 2
+    uint64_t items;    // filled by the launcher: C * nr_vis * units
+    uint32_t A;        // 1 .. 256
+    uint32_t C;
+    uint32_t nT16;     // blocks of the tensor, >= nr_vis * n
+    uint32_t n;        // blocks per visibility, 1 .. 4095
+    uint32_t nr_vis;
+    uint32_t tiles;    // filled by the launcher: 16-antenna tiles
+    uint32_t st;       // filled by the launcher: squares of 4 x 4 tiles along the diagonal
+    uint32_t units;    // filled by the launcher: units (the tile pairs a wave takes at once) per (channel, visibility)
+};
 
 namespace {
 
@@ -278,7 +295,7 @@ hipError_t bf_warm_module_correlator()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_correlate_kernel));
 }
 
-hipError_t bf_launch_correlate(const bf_corr_args &args, hipStream_t stream)
+static hipError_t bf_launch_correlate(const bf_corr_args &args, hipStream_t stream)
 {
     if (args.C == 0u || args.nr_vis == 0u) return hipSuccess;
     if (args.A == 0u || args.A > 256u || args.n == 0u) return hipErrorInvalidValue;
@@ -293,3 +310,43 @@ hipError_t bf_launch_correlate(const bf_corr_args &args, hipStream_t stream)
     hipLaunchKernelGGL(bf_correlate_kernel, dim3(grid), dim3(kWaves * 64u), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_correlator.h, behind the table as in bf_integrate.hip.  No coefficients, nothing allocated, and
+// math_mode plays no part.
+namespace bf_host {
+
+int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, uint32_t blocks_per_vis,
+                         int32_t *d_vis, size_t vis_bytes, void *stream)
+{
+    if (int e = correlate_block_args(c, nt, blocks_per_vis, d_vis)) return e;
+    if (nt && !d_antenna) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
+    const uint32_t nr_vis = nt / 16u / blocks_per_vis;
+    if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
+    if (!aligned(d_antenna, 16u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(antenna_bytes, C, nt, A, 2u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(vis_bytes, C, nr_vis, (uint64_t)A * (A + 1u) / 2u, 2u * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_corr_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ant = d_antenna;
+    a.vis = d_vis;
+    a.A = A;
+    a.C = C;
+    a.nT16 = nt / 16u;
+    a.n = blocks_per_vis;
+    a.nr_vis = nr_vis;
+    return (int)bf_launch_correlate(a, as_stream(stream));
+}
+
+// a (channel, visibility) row is 2 NB = A (A + 1) words
+int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis, uint32_t vis_per_integration,
+                                uint32_t accumulate, float *d_out, size_t out_bytes, void *stream)
+{
+    if (int e = integrate_visibilities_args(c, d_vis, nr_vis, vis_per_integration, d_out)) return e;
+    const uint64_t A = (uint32_t)c->p.nr_stations;
+    return integrate_blocks(c, BF_INTEGRATE_I32, d_vis, vis_bytes, A * (A + 1u), nr_vis, vis_per_integration, accumulate, d_out, out_bytes,
+                            stream);
+}
+
+} // namespace bf_host

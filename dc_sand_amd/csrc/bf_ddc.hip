@@ -25,10 +25,35 @@
 // rotation and the gain, each a single fp32 operation (-ffp-contract=off), and ONE dwordx2 store: the 16 lanes of a group write
 // 128 contiguous bytes.  Every word is written once, by a plain store.  Byte offsets are 64-bit.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 #include "bf_math.h"
 
 #include <hip/hip_runtime.h>
+
+// The digital down-converter (include/dcs_ddc.h): real int8 [nr_inputs][in_stride] ->
+// float [band][input][out_stride][{re, im}], nr_out outputs per row, output m from samples 16 m .. 16 m + T - 1
+struct bf_ddc_digits_args {
+    const int32_t *taps; // [band][T][{re, im}]
+    int8_t *digits;      // 16 T bytes, 16-byte aligned
+    uint32_t T;          // 64, 128, 192, 256
+    uint32_t nr_bands;   // 1, 2
+};
+struct bf_ddc_args {
+    const int8_t *x;      // 16-byte aligned
+    const int8_t *digits; // the table of bf_launch_ddc_tap_digits for (T, nr_bands)
+    float *out;           // 8-byte aligned
+    uint64_t in_stride;   // bytes, % 16 == 0, >= 16 (nr_out - 1) + T
+    uint64_t out_stride;  // pairs, >= nr_out
+    uint64_t items;       // filled by the launcher: nr_inputs * spans
+    uint32_t nr_inputs;
+    uint32_t nr_out;
+    uint32_t T;
+    uint32_t nr_bands;
+    uint32_t spans;       // filled by the launcher: the spans of outputs of a row, one workgroup each
+    uint32_t u0[2];       // per band: the phase word of output 0 of the call
+    uint32_t step16[2];   // per band: 16 phase_step, the phase step per output
+    float gain[2];
+};
 
 namespace {
 
@@ -137,14 +162,14 @@ hipError_t bf_warm_module_ddc()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_ddc_kernel));
 }
 
-hipError_t bf_launch_ddc_tap_digits(const bf_ddc_digits_args &a, hipStream_t stream)
+static hipError_t bf_launch_ddc_tap_digits(const bf_ddc_digits_args &a, hipStream_t stream)
 {
     if (a.T % 64u != 0u || a.T < 64u || a.T > 64u * kMaxSteps || a.nr_bands < 1u || a.nr_bands > 2u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bf_ddc_tap_digits_kernel, dim3(a.T / 64u), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 
-hipError_t bf_launch_ddc(const bf_ddc_args &args, hipStream_t stream)
+static hipError_t bf_launch_ddc(const bf_ddc_args &args, hipStream_t stream)
 {
     if (args.nr_out == 0u || args.nr_inputs == 0u) return hipSuccess;
     if (args.T % 64u != 0u || args.T < 64u || args.T > 64u * kMaxSteps || args.nr_bands < 1u || args.nr_bands > 2u)
@@ -155,3 +180,53 @@ hipError_t bf_launch_ddc(const bf_ddc_args &args, hipStream_t stream)
     hipLaunchKernelGGL(bf_ddc_kernel, dim3((uint32_t)(a.items < kGrid ? a.items : kGrid)), dim3(kWaves * 64u), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_ddc.h, behind the table as in bf_integrate.hip.  Of the context these use the device alone:
+// every size is an argument, and the device-free checks are all the checks there are.
+namespace bf_host {
+
+int ddc_tap_digits_impl(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, void *d_digits,
+                        size_t digits_bytes, void *stream)
+{
+    if (int e = ddc_tap_digits_args(c, d_taps, nr_taps, nr_bands, d_digits, digits_bytes)) return e;
+    DCS_CHECK_DEVICE(c);
+    bf_ddc_digits_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.taps = d_taps;
+    a.digits = static_cast<int8_t *>(d_digits);
+    a.T = nr_taps;
+    a.nr_bands = nr_bands;
+    return (int)bf_launch_ddc_tap_digits(a, as_stream(stream));
+}
+
+// the oscillator of output m of the call is phase0 + 16 (first_output + m) phase_step mod 2^32: the part that does not depend on
+// m is made here, in wrapping 32-bit arithmetic
+int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes, uint64_t in_stride,
+             const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands, const dcs_ddc_band *bands,
+             uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream)
+{
+    if (int e = ddc_args(c, nr_inputs, nr_out, d_samples, samples_bytes, in_stride, d_digits, digits_bytes, nr_taps, nr_bands, bands,
+                         d_out, out_bytes, out_stride))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    if (nr_out == 0u || nr_inputs == 0u) return DCS_OK;
+    bf_ddc_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = d_samples;
+    a.digits = static_cast<const int8_t *>(d_digits);
+    a.out = d_out;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.nr_inputs = nr_inputs;
+    a.nr_out = nr_out;
+    a.T = nr_taps;
+    a.nr_bands = nr_bands;
+    for (uint32_t b = 0; b < nr_bands; b++) {
+        a.step16[b] = 16u * bands[b].phase_step;
+        a.u0[b] = bands[b].phase0 + (uint32_t)first_output * a.step16[b];
+        a.gain[b] = bands[b].gain;
+    }
+    return (int)bf_launch_ddc(a, as_stream(stream));
+}
+
+} // namespace bf_host

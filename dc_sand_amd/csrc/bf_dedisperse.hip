@@ -31,9 +31,30 @@
 // Reads stay inside the rows [first, first + T + max_delay) of a beam whatever the table holds: an entry that takes part is
 // at most max_delay, a staged window ends at hi + (the tile's times), and the direct form reads only for times below T.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// Incoherent dedispersion (include/dcs_dedisperse.h).
+// The delay table int32 [nr_dm][C] of a band and DMs, in fp64 rounded once per operation
+struct bf_dmdelay_args {
+    const double *dms; // [nr_dm], 8-byte aligned; read when the work runs
+    int32_t *delays;   // [nr_dm][C]
+    uint64_t total;    // nr_dm * C
+    uint32_t C;
+    double freq_first, freq_step, sample_time;
+};
+// Filterbanks uint8 [B][in_spectra][C] shifted by the table and summed over the columns into out uint32 [B][nr_dm][out_spectra],
+// words first_out .. first_out + T - 1 of every series
+struct bf_dedisp_args {
+    const uint8_t *in;     // 16-byte aligned
+    const int32_t *delays; // [nr_dm][C]; read when the work runs; an entry outside [0, max_delay] drops its term
+    const uint8_t *mask;   // nullptr (every column), or [C]: a zero byte drops the column
+    uint32_t *out;
+    uint64_t in_spectra, first, out_spectra, first_out;
+    uint32_t C, B, T, nr_dm, max_delay;
+    uint32_t t_tiles, dm_tiles; // filled by the launcher: tiles of output times and of DMs
+};
 
 namespace {
 
@@ -298,7 +319,7 @@ hipError_t bf_warm_module_dedisperse()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_dedisperse_kernel));
 }
 
-hipError_t bf_launch_dm_delays(const bf_dmdelay_args &a, hipStream_t stream)
+static hipError_t bf_launch_dm_delays(const bf_dmdelay_args &a, hipStream_t stream)
 {
     if (a.total == 0u) return hipSuccess;
     const uint64_t blocks = (a.total + 255u) / 256u;
@@ -307,7 +328,7 @@ hipError_t bf_launch_dm_delays(const bf_dmdelay_args &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t bf_launch_dedisperse(const bf_dedisp_args &args, hipStream_t stream)
+static hipError_t bf_launch_dedisperse(const bf_dedisp_args &args, hipStream_t stream)
 {
     if (args.T == 0u || args.nr_dm == 0u || args.B == 0u) return hipSuccess;
     bf_dedisp_args a = args;
@@ -318,3 +339,60 @@ hipError_t bf_launch_dedisperse(const bf_dedisp_args &args, hipStream_t stream)
     hipLaunchKernelGGL(bf_dedisperse_kernel, dim3((uint32_t)blocks), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_dedisperse.h, behind the table as in bf_integrate.hip.  No coefficients, nothing allocated, and
+// math_mode plays no part; the band is host memory and travels by value in the kernel's arguments.
+namespace bf_host {
+
+int dm_delays_impl(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
+                   size_t delays_bytes, void *stream)
+{
+    if (int e = dm_delays_args(c, band, d_dms, d_delays)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    const double f_last = band->freq_first_mhz + (double)(C - 1u) * band->freq_step_mhz; // the kernel's own f_(C-1)
+    if (!(f_last > 0.0) || !std::isfinite(f_last)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(delays_bytes, nr_dm, C, sizeof(int32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dmdelay_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.dms = d_dms;
+    a.delays = d_delays;
+    a.total = (uint64_t)nr_dm * C;
+    a.C = C;
+    a.freq_first = band->freq_first_mhz;
+    a.freq_step = band->freq_step_mhz;
+    a.sample_time = band->sample_time_s;
+    return (int)bf_launch_dm_delays(a, as_stream(stream));
+}
+
+int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
+                       uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
+                       uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
+                       uint64_t out_spectra, uint64_t first_out, void *stream)
+{
+    if (int e = dedisperse_q8_args(c, d_filterbank, in_spectra, first_spectrum, nr_spectra, nr_beams, d_delays, max_delay, d_dm_time,
+                                   out_spectra, first_out))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(dm_time_bytes, nr_beams, nr_dm, out_spectra, sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dedisp_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.delays = d_delays;
+    a.mask = d_channel_mask;
+    a.out = d_dm_time;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.out_spectra = out_spectra;
+    a.first_out = first_out;
+    a.C = C;
+    a.B = nr_beams;
+    a.T = nr_spectra;
+    a.nr_dm = nr_dm;
+    a.max_delay = max_delay;
+    return (int)bf_launch_dedisperse(a, as_stream(stream));
+}
+
+} // namespace bf_host

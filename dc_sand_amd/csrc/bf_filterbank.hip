@@ -37,9 +37,40 @@
 // launch geometry.  The scales kernel is one lane per (channel, beam) of fp64 arithmetic; -ffp-contract=off keeps every
 // operation rounded once.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// 8-bit search filterbanks (include/dcs_filterbank.h).  Spectra are float
+// [T][C][B], beam fastest; cb = C * B.
+// Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64
+struct bf_fbsums_args {
+    const float *spectra;
+    double *sums;        // [C][B][2]
+    uint64_t cb;
+    uint32_t T;
+    uint32_t accumulate; // non-zero: the sums start from what sums holds
+};
+// Sums -> scales {mu, k} float [C][B][2], in fp64 rounded once per operation
+struct bf_fbscales_args {
+    const double *sums;
+    float *scales;
+    uint64_t cb;
+    uint64_t count; // spectra behind the sums: 1 .. 2^53 - 1
+    float target_std;
+};
+// Spectra normalised with the scales, quantised and transposed into out uint8 [B][out_spectra][C], rows first .. first + T - 1
+struct bf_fbq8_args {
+    const float *spectra;
+    const float *scales;               // [C][B][2], 8-byte aligned; read when the work runs
+    uint8_t *out;                      // 16-byte aligned
+    unsigned long long *clip_count;    // [B], added to; or nullptr: no counting
+    uint64_t out_spectra, first;
+    uint32_t C, B, T;
+    uint32_t slices;                   // filled by the launcher: time slices a workgroup walks (gridDim.y runs of them)
+    uint32_t descending;               // non-zero: channel c lands in column C - 1 - c
+    float level;
+};
 
 namespace {
 
@@ -224,7 +255,7 @@ hipError_t bf_warm_module_filterbank()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_filterbank_scales_kernel));
 }
 
-hipError_t bf_launch_spectra_sums(const bf_fbsums_args &a, hipStream_t stream)
+static hipError_t bf_launch_spectra_sums(const bf_fbsums_args &a, hipStream_t stream)
 {
     if (a.T == 0u || a.cb == 0u) return hipSuccess;
     const uint64_t blocks = (a.cb + 255u) / 256u;
@@ -233,7 +264,7 @@ hipError_t bf_launch_spectra_sums(const bf_fbsums_args &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t bf_launch_filterbank_scales(const bf_fbscales_args &a, hipStream_t stream)
+static hipError_t bf_launch_filterbank_scales(const bf_fbscales_args &a, hipStream_t stream)
 {
     if (a.cb == 0u) return hipSuccess;
     const uint64_t blocks = (a.cb + 255u) / 256u;
@@ -242,7 +273,7 @@ hipError_t bf_launch_filterbank_scales(const bf_fbscales_args &a, hipStream_t st
     return hipGetLastError();
 }
 
-hipError_t bf_launch_filterbank_q8(const bf_fbq8_args &args, hipStream_t stream)
+static hipError_t bf_launch_filterbank_q8(const bf_fbq8_args &args, hipStream_t stream)
 {
     bf_fbq8_args a = args;
     if (a.T == 0u || a.C == 0u || a.B == 0u) return hipSuccess;
@@ -264,3 +295,72 @@ hipError_t bf_launch_filterbank_q8(const bf_fbq8_args &args, hipStream_t stream)
         hipLaunchKernelGGL(bf_filterbank_q8_kernel<false>, dim3((uint32_t)tiles, runs), dim3(256u), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_filterbank.h, behind the table as in bf_integrate.hip.  No coefficients and nothing allocated;
+// nr_beams is the caller's, so the one set of calls serves detected (the context's beams) and incoherent (1) spectra.
+namespace bf_host {
+
+int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                      uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream)
+{
+    if (int e = spectra_sums_args(c, d_spectra, nr_beams, d_sums)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbsums_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.sums = d_sums;
+    a.cb = (uint64_t)C * nr_beams;
+    a.T = nr_spectra;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_spectra_sums(a, as_stream(stream));
+}
+
+int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
+                           float target_std, float *d_scales, size_t scales_bytes, void *stream)
+{
+    if (int e = filterbank_scales_args(c, d_sums, count, nr_beams, d_scales)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(sums_bytes, C, nr_beams, 2u, sizeof(double))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(scales_bytes, C, nr_beams, 2u, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbscales_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.sums = d_sums;
+    a.scales = d_scales;
+    a.cb = (uint64_t)C * nr_beams;
+    a.count = count;
+    a.target_std = target_std;
+    return (int)bf_launch_filterbank_scales(a, as_stream(stream));
+}
+
+int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
+                       const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
+                       uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream)
+{
+    if (int e = filterbank_q8_args(c, d_spectra, nr_spectra, nr_beams, d_scales, flags, d_filterbank, out_spectra, first_spectrum,
+                                   d_clip_count))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(spectra_bytes, nr_spectra, C, nr_beams, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(filterbank_bytes, nr_beams, out_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_fbq8_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.spectra = d_spectra;
+    a.scales = d_scales;
+    a.out = d_filterbank;
+    a.clip_count = d_clip_count;
+    a.out_spectra = out_spectra;
+    a.first = first_spectrum;
+    a.C = C;
+    a.B = nr_beams;
+    a.T = nr_spectra;
+    a.descending = flags & DCS_FB_DESCENDING;
+    a.level = level;
+    return (int)bf_launch_filterbank_q8(a, as_stream(stream));
+}
+
+} // namespace bf_host

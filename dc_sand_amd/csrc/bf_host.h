@@ -1,6 +1,7 @@
-// bf_host.h -- what the host units of the C-ABI share (bf_capi*.hip): the context, the status macros, and the few
-// functions that cross from one unit to another.  Internal, like bf_ctx_ext.h: never installed, never included by a
-// companion.  What a unit does not find here belongs to another unit alone.
+// bf_host.h -- what the units with host code of the C-ABI share (bf_capi*.hip, and the stage units that carry their own host
+// side behind the table of bf_ctx_ext.h): the context, the status macros, and the few functions that cross from one unit to
+// another.  Internal, like bf_ctx_ext.h: never installed, never included by a companion.  What a unit does not find here
+// belongs to another unit alone.
 #ifndef BF_HOST_H
 #define BF_HOST_H
 
@@ -89,6 +90,9 @@ struct dcs_bf_context {
 #define DCS_PROBE_KNOB(c, f) 0
 #endif
 
+// the words that integrate_blocks sums (bf_integrate.hip, whose launcher takes the same type)
+enum bf_integrate_type { BF_INTEGRATE_F32, BF_INTEGRATE_U32 /* built for bs == 1 */, BF_INTEGRATE_I32 };
+
 namespace bf_host {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
@@ -128,9 +132,13 @@ int stage_dt(dcs_bf_context *c, const dt_source &src, uint32_t off, uint32_t n, 
 // bf_capi_beamform.hip: the terms table and class words (the generator's rows form writes the same table)
 int ensure_terms(dcs_bf_context *c, hipStream_t stream);
 
-// the calls behind bf_ctx_ext_ops, in the table's order: four in bf_capi_beamform.hip, six in bf_capi_detect.hip, the
-// complex product's three in bf_capi_beamform.hip again, and the Stokes detection's two, the dedispersion's two, the
-// single-pulse search's three, the correlator's two and the down-converter's two in bf_capi_detect.hip
+// bf_integrate.hip: the one integration behind the four integrate_* entries, which live with their stages
+int integrate_blocks(dcs_bf_context *c, bf_integrate_type type, const void *d_blocks, size_t blocks_bytes, uint64_t bs,
+                     uint32_t nr_blocks, uint32_t n, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
+
+// the calls behind bf_ctx_ext_ops, in the table's order.  The seven beamformer calls are in bf_capi_beamform.hip, written out
+// as the table writes them; every other one is at the end of its stage's kernel unit and takes its type from the public
+// declaration, as its table entry does: one line per stage, the unit's name behind it
 int generate_and_beamform_weighted_impl(dcs_bf_context *c, const float *dt, uint64_t t0, uint32_t nt, const int8_t *d_antenna,
                                         size_t antenna_bytes, const float *d_weights, float *d_beams, size_t beams_bytes,
                                         void *stream);
@@ -143,20 +151,12 @@ int beamform_accumulated_q8_impl(dcs_bf_context *c, const float *dt_coeff, uint6
 int beamform_accumulated_power_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
                                     size_t antenna_bytes, const float *d_weights, float *d_block_power, size_t power_bytes,
                                     void *stream);
-int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
-                               uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream);
-int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
-                                uint32_t *d_block_power, size_t power_bytes, void *stream);
-int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
-                                    uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
-                                    void *stream);
-int spectra_sums_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
-                      uint32_t accumulate, double *d_sums, size_t sums_bytes, void *stream);
-int filterbank_scales_impl(dcs_bf_context *c, const double *d_sums, size_t sums_bytes, uint64_t count, uint32_t nr_beams,
-                           float target_std, float *d_scales, size_t scales_bytes, void *stream);
-int filterbank_q8_impl(dcs_bf_context *c, const float *d_spectra, size_t spectra_bytes, uint32_t nr_spectra, uint32_t nr_beams,
-                       const float *d_scales, float level, uint32_t flags, uint8_t *d_filterbank, size_t filterbank_bytes,
-                       uint64_t out_spectra, uint64_t first_spectrum, unsigned long long *d_clip_count, void *stream);
+decltype(dcs_bf_integrate_block_power) integrate_block_power_impl;           // bf_integrate.hip
+decltype(dcs_bf_incoherent_block_power) incoherent_block_power_impl;         // bf_incoherent.hip
+decltype(dcs_bf_integrate_incoherent_power) integrate_incoherent_power_impl;
+decltype(dcs_bf_spectra_sums) spectra_sums_impl;                             // bf_filterbank.hip
+decltype(dcs_bf_filterbank_scales) filterbank_scales_impl;
+decltype(dcs_bf_filterbank_q8) filterbank_q8_impl;
 int beamform_accumulated_complex_impl(dcs_bf_context *c, const float *dt_coeff, uint64_t t_coeff, uint32_t nt, const int8_t *d_antenna,
                                       size_t antenna_bytes, const float *d_weights, uint32_t flags, float *d_beams, size_t beams_bytes,
                                       void *stream);
@@ -167,59 +167,27 @@ int beamform_accumulated_complex_q8_impl(dcs_bf_context *c, const float *dt_coef
                                          const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights, uint32_t flags,
                                          const float *d_quant_gains, int8_t *d_beams_q8, size_t beams_bytes,
                                          unsigned long long *d_clip_count, void *stream);
-int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
-                      uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream);
-int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
-                          uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
-                          size_t spectra_bytes, void *stream);
-int dm_delays_impl(dcs_bf_context *c, const dcs_bf_band *band, const double *d_dms, uint32_t nr_dm, int32_t *d_delays,
-                   size_t delays_bytes, void *stream);
-int dedisperse_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra,
-                       uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, const int32_t *d_delays, uint32_t nr_dm,
-                       uint32_t max_delay, const uint8_t *d_channel_mask, uint32_t *d_dm_time, size_t dm_time_bytes,
-                       uint64_t out_spectra, uint64_t first_out, void *stream);
-int dm_time_sums_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
-                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
-                      uint64_t *d_sums, size_t sums_bytes, void *stream);
-int boxcar_peaks_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
-                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths,
-                      uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
-                      uint64_t peak_blocks, uint64_t first_block, void *stream);
-int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes, uint64_t peak_blocks, uint64_t first_block,
-                  uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
-                  uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
-                  uint32_t *d_best, size_t best_bytes, void *stream);
-int correlate_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, uint32_t blocks_per_vis,
-                         int32_t *d_vis, size_t vis_bytes, void *stream);
-int integrate_visibilities_impl(dcs_bf_context *c, const int32_t *d_vis, size_t vis_bytes, uint32_t nr_vis,
-                                uint32_t vis_per_integration, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream);
-int ddc_tap_digits_impl(dcs_bf_context *c, const int32_t *d_taps, uint32_t nr_taps, uint32_t nr_bands, void *d_digits,
-                        size_t digits_bytes, void *stream);
-int ddc_impl(dcs_bf_context *c, uint32_t nr_inputs, uint32_t nr_out, const int8_t *d_samples, size_t samples_bytes, uint64_t in_stride,
-             const void *d_digits, size_t digits_bytes, uint32_t nr_taps, uint32_t nr_bands, const dcs_ddc_band *bands,
-             uint64_t first_output, float *d_out, size_t out_bytes, uint64_t out_stride, void *stream);
+decltype(dcs_bf_stokes_block) stokes_block_impl;                             // bf_stokes.hip
+decltype(dcs_bf_integrate_stokes) integrate_stokes_impl;
+decltype(dcs_bf_dm_delays) dm_delays_impl;                                   // bf_dedisperse.hip
+decltype(dcs_bf_dedisperse_q8) dedisperse_q8_impl;
+decltype(dcs_bf_dm_time_sums) dm_time_sums_impl;                             // bf_single_pulse.hip
+decltype(dcs_bf_boxcar_peaks) boxcar_peaks_impl;
+decltype(dcs_bf_peak_snr) peak_snr_impl;
+decltype(dcs_bf_correlate_block) correlate_block_impl;                       // bf_correlator.hip
+decltype(dcs_bf_integrate_visibilities) integrate_visibilities_impl;
+decltype(dcs_bf_ddc_tap_digits) ddc_tap_digits_impl;                         // bf_ddc.hip
+decltype(dcs_bf_ddc) ddc_impl;
 int find_candidates_impl(dcs_bf_context *c, const float *d_snr, size_t snr_bytes, const uint32_t *d_peaks, size_t peaks_bytes,
                          uint64_t peak_blocks, uint64_t first_block, uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm,
                          uint32_t nr_widths, float threshold, uint32_t dm_radius, uint32_t block_radius, void *d_cands,
-                         size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes, void *stream);
-int channelise_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra, const float *d_in,
-                    size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order, float *d_out,
-                    size_t out_bytes, uint64_t out_blocks, uint64_t first_block, uint32_t out_inputs, uint32_t first_input, void *stream);
-int channelise_q8_impl(dcs_bf_context *c, uint32_t nr_channels, uint32_t nr_taps, uint32_t nr_inputs, uint32_t nr_spectra,
-                       const float *d_in, size_t in_bytes, uint64_t in_stride, const float *d_taps, const float *d_twiddles, uint32_t order,
-                       const float *d_gains, int8_t *d_out_q8, size_t out_bytes, uint64_t out_blocks, uint64_t first_block,
-                       uint32_t out_inputs, uint32_t first_input, unsigned long long *d_clip_count, void *stream);
-int rfi_moments_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
-                     uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, uint32_t *d_cell_sums, size_t cell_sums_bytes,
-                     uint32_t *d_zero_dm, size_t zero_dm_bytes, void *stream);
-int rfi_flags_impl(dcs_bf_context *c, const uint32_t *d_cell_sums, size_t cell_sums_bytes, const uint32_t *d_zero_dm, size_t zero_dm_bytes,
-                   uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr, uint8_t *d_cell_flags,
-                   size_t cell_flags_bytes, uint8_t *d_channel_mask, size_t channel_mask_bytes, uint8_t *d_spectrum_flags,
-                   size_t spectrum_flags_bytes, uint32_t *d_counts, size_t counts_bytes, void *stream);
-int rfi_clean_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
-                      uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_cell_flags, const uint8_t *d_channel_mask,
-                      const uint8_t *d_spectrum_flags, uint8_t fill, uint8_t *d_out, size_t out_bytes, uint64_t out_spectra,
-                      uint64_t first_out, unsigned long long *d_replaced, void *stream);
+                         size_t cands_bytes, uint32_t max_candidates, uint32_t *d_count, void *d_work, size_t work_bytes,
+                         void *stream); // bf_candidates.hip; written out, as the table's entry is
+decltype(dcs_bf_channelise) channelise_impl;                                 // bf_channeliser.hip
+decltype(dcs_bf_channelise_q8) channelise_q8_impl;
+decltype(dcs_bf_rfi_moments) rfi_moments_impl;                               // bf_rfi.hip
+decltype(dcs_bf_rfi_flags) rfi_flags_impl;
+decltype(dcs_bf_rfi_clean_q8) rfi_clean_q8_impl;
 
 } // namespace bf_host
 

@@ -23,9 +23,20 @@
 // packing several rows into one load: correct, and no production shape.
 // Byte offsets are 64-bit.  Nothing here rounds: -ffp-contract and the float flags of the build play no part.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// The incoherent beam (include/dcs_incoherent_beam.h): the sample tensor as
+// rows = C * nT16 rows of A * 32 bytes, each summed to one exact dword of block_power [C][nT16]
+struct bf_incoh_args {
+    const int8_t *ant;     // [rows][A][16][2], 16-byte aligned
+    const float *weights;  // nullptr (every antenna), or [A] flags: antenna a takes part iff weights[a] != 0
+    uint32_t *block_power; // [rows]
+    uint64_t rows;
+    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
+    uint32_t A;            // 1 .. 256
+};
 
 namespace {
 
@@ -126,7 +137,7 @@ hipError_t bf_warm_module_incoherent()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_incoherent_power_kernel<1>));
 }
 
-hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream)
+static hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream)
 {
     if (a.rows == 0u) return hipSuccess;
     if (a.A == 0u || a.A > 256u) return hipErrorInvalidValue;
@@ -142,3 +153,39 @@ hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream
     }
     return hipGetLastError();
 }
+
+// The host side of include/dcs_incoherent_beam.h, behind the table as in bf_integrate.hip.  No coefficients: no delay table,
+// no terms, nothing allocated, and math_mode plays no part.
+namespace bf_host {
+
+int incoherent_block_power_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_antenna, size_t antenna_bytes, const float *d_weights,
+                                uint32_t *d_block_power, size_t power_bytes, void *stream)
+{
+    if (int e = incoherent_block_power_args(c, nt, d_weights, d_block_power)) return e;
+    if (nt && !d_antenna) return DCS_ERR_INVALID_ARGUMENT;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t A = (uint32_t)c->p.nr_stations, C = (uint32_t)c->p.nr_channels;
+    if (A > 256u) return DCS_ERR_UNSUPPORTED; // as the float call
+    if (antenna_bytes < (size_t)A * C * nt * 2u) return DCS_ERR_INVALID_ARGUMENT;
+    if (power_bytes < (size_t)C * (nt / 16u) * sizeof(uint32_t)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!aligned(d_antenna, 16u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_incoh_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ant = d_antenna;
+    a.weights = d_weights;
+    a.block_power = d_block_power;
+    a.rows = (uint64_t)C * (nt / 16u);
+    a.A = A;
+    return (int)bf_launch_incoherent_power(a, as_stream(stream));
+}
+
+int integrate_incoherent_power_impl(dcs_bf_context *c, const uint32_t *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                                    uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes,
+                                    void *stream)
+{
+    if (int e = integrate_incoherent_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
+    return integrate_blocks(c, BF_INTEGRATE_U32, d_block_power, power_bytes, 1u, nr_blocks, blocks_per_spectrum, accumulate, d_spectra,
+                            spectra_bytes, stream);
+}
+
+} // namespace bf_host

@@ -10,11 +10,25 @@
 // integrate in 32 us instead of 193.  A unit of its own, so that an edit here recompiles 20 lines and
 // not the matrix-core beamformer.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+
+// The integrator of every post-detection output: blocks [C][nr_blocks][bs] summed n at a time into
+// out [nr_blocks / n][C][bs].  The element type (bf_integrate_type, bf_host.h) selects the rule: float words are added in
+// order, one rounded add each; 32-bit integer words exactly, in 64 bits, and the sum converted once
+struct bf_integrate_args {
+    const void *blocks;  // words of the type the launch names
+    float *out;
+    uint64_t total;      // (nr_blocks / n) * C * bs
+    uint32_t bs;         // words per (channel, block): B; 1; B * nr_stokes; A (A + 1)
+    uint32_t C;
+    uint32_t nr_blocks;  // a multiple of n
+    uint32_t n;          // blocks per output row, >= 1
+    uint32_t accumulate; // non-zero: float sums start from what out holds, integer sums are added to it once rounded
+};
 
 namespace {
 
@@ -57,7 +71,7 @@ hipError_t bf_warm_module_integrate()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_integrate_kernel<float>));
 }
 
-hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &a, hipStream_t stream)
+static hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &a, hipStream_t stream)
 {
     if (a.total == 0u) return hipSuccess;
     const uint64_t blocks = (a.total + 255u) / 256u;
@@ -74,3 +88,42 @@ hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &
     }
     return hipGetLastError();
 }
+
+// The host side, behind the table at the head of every context (bf_ctx_ext.h).  Of the context these calls use its parameters
+// and its device, nothing else.  Each begins with the device-free checks of its table entry (bf_arg_checks.h), the ones its
+// companion has made already; what follows needs the device or the context's sizes, or is a condition that only this side makes.
+namespace bf_host {
+
+// The one integration behind integrate_block_power, integrate_incoherent_power, integrate_stokes and integrate_visibilities:
+// blocks [C][nr_blocks][bs] of 4-byte words of the named type, n at a time, into out [nr_blocks / n][C][bs].
+// The caller has made its own device-free checks: n >= 1 divides nr_blocks.
+int integrate_blocks(dcs_bf_context *c, bf_integrate_type type, const void *d_blocks, size_t blocks_bytes, uint64_t bs,
+                     uint32_t nr_blocks, uint32_t n, uint32_t accumulate, float *d_out, size_t out_bytes, void *stream)
+{
+    DCS_CHECK_DEVICE(c);
+    const uint64_t C = (uint32_t)c->p.nr_channels, n_out = nr_blocks / n;
+    if (bs > 0xffffffffull) return DCS_ERR_UNSUPPORTED;
+    if (!holds(blocks_bytes, C, nr_blocks, bs, 4u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(out_bytes, n_out, C, bs, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_integrate_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.blocks = d_blocks;
+    a.out = d_out;
+    a.total = n_out * C * bs;
+    a.bs = (uint32_t)bs;
+    a.C = (uint32_t)C;
+    a.nr_blocks = nr_blocks;
+    a.n = n;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_integrate(type, a, as_stream(stream));
+}
+
+int integrate_block_power_impl(dcs_bf_context *c, const float *d_block_power, size_t power_bytes, uint32_t nr_blocks,
+                               uint32_t blocks_per_spectrum, uint32_t accumulate, float *d_spectra, size_t spectra_bytes, void *stream)
+{
+    if (int e = integrate_block_power_args(c, d_block_power, nr_blocks, blocks_per_spectrum, d_spectra)) return e;
+    return integrate_blocks(c, BF_INTEGRATE_F32, d_block_power, power_bytes, (uint32_t)c->p.nr_beams, nr_blocks, blocks_per_spectrum,
+                            accumulate, d_spectra, spectra_bytes, stream);
+}
+
+} // namespace bf_host

@@ -1,6 +1,6 @@
-// bf_kernels.h -- host-callable launchers of the gfx950 kernels in
-// bf_kernels.hip (internal to libdcs_beamformer.so; the public boundary is
-// include/dcs_beamformer.h).
+// bf_kernels.h -- args structs and host-callable launchers of the gfx950 kernels that more than one unit uses: the
+// coefficient generator's and the fused beamformer's (bf_kernels.hip), the matrix-core beamformer's (bf_beamform_mfma.hip)
+// and the streams' gather.  Internal to libdcs_beamformer.so; the public boundary is include/dcs_beamformer.h.
 #ifndef DCS_BF_KERNELS_H
 #define DCS_BF_KERNELS_H
 
@@ -211,268 +211,18 @@ hipError_t bf_launch_beamform_acc(const bf_bacc_args &a, const bf_weights_args *
                                   const bf_complex_args *cx, hipStream_t stream);
 hipError_t bf_warm_module_mfma();
 
-// The incoherent beam (bf_incoherent.hip; include/dcs_incoherent_beam.h): the sample tensor as
-// rows = C * nT16 rows of A * 32 bytes, each summed to one exact dword of block_power [C][nT16]
-struct bf_incoh_args {
-    const int8_t *ant;     // [rows][A][16][2], 16-byte aligned
-    const float *weights;  // nullptr (every antenna), or [A] flags: antenna a takes part iff weights[a] != 0
-    uint32_t *block_power; // [rows]
-    uint64_t rows;
-    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
-    uint32_t A;            // 1 .. 256
-};
-hipError_t bf_launch_incoherent_power(const bf_incoh_args &a, hipStream_t stream);
+// The stages after detection are units of their own, each with its args structs, its launchers and its host side in one file;
+// of them dcs_bf_create (bf_capi.hip) needs only this: the unit's code object loaded, so that a first call only launches
 hipError_t bf_warm_module_incoherent();
-
-// Full-Stokes detection (bf_stokes.hip; include/dcs_stokes.h): two int8 beam tensors as
-// rows = C * nT16 * B rows of 32 bytes each, every row pair reduced to nr_stokes exact dwords of block_stokes [C][nT16][B][nr_stokes]
-struct bf_stokes_args {
-    const int8_t *beams_x; // [rows][16][2], 16-byte aligned; polarisation x
-    const int8_t *beams_y; // the same of polarisation y; may be beams_x
-    int32_t *block_stokes; // [rows][nr_stokes], aligned to 4 * nr_stokes bytes
-    uint64_t rows;
-    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
-    uint32_t nr_stokes;    // 1 (I) or 4 (I, Q, U, V)
-};
-hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream);
 hipError_t bf_warm_module_stokes();
-
-// The integrator of every post-detection output (bf_integrate.hip): blocks [C][nr_blocks][bs] summed
-// n at a time into out [nr_blocks / n][C][bs].  The element type selects the rule: float words are added in order, one rounded
-// add each; 32-bit integer words exactly, in 64 bits, and the sum converted once
-enum bf_integrate_type { BF_INTEGRATE_F32, BF_INTEGRATE_U32 /* built for bs == 1 */, BF_INTEGRATE_I32 };
-struct bf_integrate_args {
-    const void *blocks;  // words of the type the launch names
-    float *out;
-    uint64_t total;      // (nr_blocks / n) * C * bs
-    uint32_t bs;         // words per (channel, block): B; 1; B * nr_stokes; A (A + 1)
-    uint32_t C;
-    uint32_t nr_blocks;  // a multiple of n
-    uint32_t n;          // blocks per output row, >= 1
-    uint32_t accumulate; // non-zero: float sums start from what out holds, integer sums are added to it once rounded
-};
-hipError_t bf_launch_integrate(bf_integrate_type type, const bf_integrate_args &a, hipStream_t stream);
 hipError_t bf_warm_module_integrate();
-
-// Incoherent dedispersion (bf_dedisperse.hip; include/dcs_dedisperse.h).
-// The delay table int32 [nr_dm][C] of a band and DMs, in fp64 rounded once per operation
-struct bf_dmdelay_args {
-    const double *dms; // [nr_dm], 8-byte aligned; read when the work runs
-    int32_t *delays;   // [nr_dm][C]
-    uint64_t total;    // nr_dm * C
-    uint32_t C;
-    double freq_first, freq_step, sample_time;
-};
-hipError_t bf_launch_dm_delays(const bf_dmdelay_args &a, hipStream_t stream);
-// Filterbanks uint8 [B][in_spectra][C] shifted by the table and summed over the columns into out uint32 [B][nr_dm][out_spectra],
-// words first_out .. first_out + T - 1 of every series
-struct bf_dedisp_args {
-    const uint8_t *in;     // 16-byte aligned
-    const int32_t *delays; // [nr_dm][C]; read when the work runs; an entry outside [0, max_delay] drops its term
-    const uint8_t *mask;   // nullptr (every column), or [C]: a zero byte drops the column
-    uint32_t *out;
-    uint64_t in_spectra, first, out_spectra, first_out;
-    uint32_t C, B, T, nr_dm, max_delay;
-    uint32_t t_tiles, dm_tiles; // filled by the launcher: tiles of output times and of DMs
-};
-hipError_t bf_launch_dedisperse(const bf_dedisp_args &a, hipStream_t stream);
 hipError_t bf_warm_module_dedisperse();
-
-// The single-pulse search on the DM-time planes (bf_single_pulse.hip; include/dcs_single_pulse.h).
-// A series is one (beam, DM) pair: series s begins at word s * plane_spectra of the planes.
-// {sum x, sum x^2 mod 2^64} of words first .. first + T - 1 of every series
-struct bf_dtsums_args {
-    const uint32_t *plane; // [series][plane_spectra]
-    uint64_t *sums;        // [series][2]
-    uint64_t plane_spectra, first;
-    uint32_t T;
-    uint32_t accumulate;   // non-zero: added to what sums holds
-};
-hipError_t bf_launch_dm_time_sums(const bf_dtsums_args &a, uint64_t series, hipStream_t stream);
-// Per series, width index i and block k of block_len times: {the largest boxcar sum of width widths[i], its first time} into
-// peaks [series][nr_widths][peak_blocks][2] at block first_block + k; {0, 0xffffffff} for a width outside [1, max_width]
-struct bf_boxcar_args {
-    const uint32_t *plane;  // [series][plane_spectra]; words first .. first + T + max_width - 2 of a series are read
-    const uint32_t *widths; // [nr_widths]; read when the work runs
-    uint32_t *peaks;
-    uint64_t plane_spectra, first, peak_blocks, first_block;
-    uint32_t T, nr_widths, max_width, block_len;
-    uint32_t run;           // filled by the launcher: blocks that a workgroup takes, one after the other
-    uint32_t segments;      // filled by the launcher: such runs per series
-};
-hipError_t bf_launch_boxcar_peaks(const bf_boxcar_args &a, uint64_t series, hipStream_t stream);
-// Peaks and sums -> snr [series][nr_widths][peak_blocks] and best [series][peak_blocks], blocks first_block .. + nr_blocks - 1
-struct bf_peaksnr_args {
-    const uint32_t *peaks;
-    const uint32_t *widths;
-    const uint64_t *sums;
-    float *snr;
-    uint32_t *best;         // nullptr: not wanted
-    uint64_t peak_blocks, first_block, count;
-    uint64_t total;         // series * nr_blocks
-    uint32_t nr_blocks, nr_widths, max_width;
-};
-hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream);
 hipError_t bf_warm_module_single_pulse();
-
-// The correlator (bf_correlator.hip; include/dcs_correlator.h): the sample tensor
-// [C][nT16][A][16][2] -> exact visibilities int32 [C][nr_vis][NB][2] of the pairs b <= a, each summed over n blocks
-struct bf_corr_args {
-    const int8_t *ant; // 16-byte aligned
-    int32_t *vis;      // 8-byte aligned
-    uint64_t NB;       // filled by the launcher: A (A + 1) / 2
-    uint64_t items;    // filled by the launcher: C * nr_vis * units
-    uint32_t A;        // 1 .. 256
-    uint32_t C;
-    uint32_t nT16;     // blocks of the tensor, >= nr_vis * n
-    uint32_t n;        // blocks per visibility, 1 .. 4095
-    uint32_t nr_vis;
-    uint32_t tiles;    // filled by the launcher: 16-antenna tiles
-    uint32_t st;       // filled by the launcher: squares of 4 x 4 tiles along the diagonal
-    uint32_t units;    // filled by the launcher: units (the tile pairs a wave takes at once) per (channel, visibility)
-};
-hipError_t bf_launch_correlate(const bf_corr_args &a, hipStream_t stream);
 hipError_t bf_warm_module_correlator();
-
-// The digital down-converter (bf_ddc.hip; include/dcs_ddc.h): real int8 [nr_inputs][in_stride] ->
-// float [band][input][out_stride][{re, im}], nr_out outputs per row, output m from samples 16 m .. 16 m + T - 1
-struct bf_ddc_digits_args {
-    const int32_t *taps; // [band][T][{re, im}]
-    int8_t *digits;      // 16 T bytes, 16-byte aligned
-    uint32_t T;          // 64, 128, 192, 256
-    uint32_t nr_bands;   // 1, 2
-};
-hipError_t bf_launch_ddc_tap_digits(const bf_ddc_digits_args &a, hipStream_t stream);
-struct bf_ddc_args {
-    const int8_t *x;      // 16-byte aligned
-    const int8_t *digits; // the table of bf_launch_ddc_tap_digits for (T, nr_bands)
-    float *out;           // 8-byte aligned
-    uint64_t in_stride;   // bytes, % 16 == 0, >= 16 (nr_out - 1) + T
-    uint64_t out_stride;  // pairs, >= nr_out
-    uint64_t items;       // filled by the launcher: nr_inputs * spans
-    uint32_t nr_inputs;
-    uint32_t nr_out;
-    uint32_t T;
-    uint32_t nr_bands;
-    uint32_t spans;       // filled by the launcher: the spans of outputs of a row, one workgroup each
-    uint32_t u0[2];       // per band: the phase word of output 0 of the call
-    uint32_t step16[2];   // per band: 16 phase_step, the phase step per output
-    float gain[2];
-};
-hipError_t bf_launch_ddc(const bf_ddc_args &a, hipStream_t stream);
 hipError_t bf_warm_module_ddc();
-
-// The candidate sifter (bf_candidates.hip; include/dcs_candidates.h): the cells (beam, DM, block)
-// of blocks first_block .. first_block + nr_blocks - 1 at or above threshold that no cell within the two radii beats, as
-// records of eight words in ascending (beam, DM, block).  A segment is a row of a tile: kCandTileBlocks cells of one DM
-struct bf_cand_args {
-    const float *snr;      // [B][nr_dm][nr_widths][peak_blocks]
-    const uint32_t *peaks; // [B][nr_dm][nr_widths][peak_blocks][2], 8-byte aligned
-    uint32_t *cands;       // [max_candidates][8], 8-byte aligned; nullptr where max_candidates == 0
-    uint32_t *count;       // {found, written}
-    uint64_t *marks;       // the workspace: [segments] ballots of the candidates ...
-    uint32_t *places;      // ... and [segments] counts, which the scan makes the segments' first places in the list
-    uint64_t peak_blocks, first_block;
-    uint64_t segments;     // B * nr_dm * k_tiles < 2^32
-    uint32_t B, nr_dm, nr_blocks, nr_widths, dm_radius, block_radius, max_candidates;
-    float threshold;
-    uint32_t dm_tiles, k_tiles; // filled by the launcher: tiles along the DMs and along the blocks
-};
-hipError_t bf_launch_find_candidates(const bf_cand_args &a, hipStream_t stream);
 hipError_t bf_warm_module_candidates();
-
-// The polyphase channeliser (bf_channeliser.hip; include/dcs_channeliser.h): float [nr_inputs][in_stride][2]
-// -> FIR of P rows of N pairs, N-point butterfly network -> [N][out_blocks][out_inputs][16][2] as floats (out) or quantised
-// (out_q8, with gains and counters); exactly one of out and out_q8 is set
-struct bf_chan_args {
-    const float *in;       // 8-byte aligned
-    const float *taps;     // [P][N]
-    const float *twiddles; // [N / 2][2], 8-byte aligned
-    const float *gains;    // out_q8 only: [nr_inputs][N]
-    float *out;            // 16-byte aligned, or nullptr
-    int8_t *out_q8;        // 16-byte aligned, or nullptr
-    unsigned long long *clip_count; // out_q8 only: [nr_inputs], or nullptr
-    uint64_t in_stride;    // pairs, >= (nr_spectra + P - 1) N
-    uint64_t out_blocks, first_block;
-    uint64_t items;        // filled by the launcher
-    uint32_t N, P, nr_inputs, nr_spectra, order, out_inputs, first_input;
-    uint32_t groups;       // filled by the launcher: the groups of inputs that share an item
-};
-hipError_t bf_launch_channelise(const bf_chan_args &a, hipStream_t stream);
 hipError_t bf_warm_module_channeliser();
-
-// The RFI flagger (bf_rfi.hip; include/dcs_rfi.h) on the filterbanks uint8 [B][in_spectra][C].  The
-// window is rows first .. first + nr_blocks * block_len - 1 of every beam, nr_blocks blocks of block_len rows.
-// {sum x, sum x^2} per (beam, block, channel), and the sum over the channels of every row of the window
-struct bf_rfi_moments_args {
-    const uint8_t *in;   // 16-byte aligned
-    uint32_t *cell_sums; // [B][nr_blocks][C][2]
-    uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]: zeroed by the launcher, added to by the kernel
-    uint64_t in_spectra, first;
-    uint32_t C, B, nr_blocks, block_len;
-    uint32_t lanes, tiles; // filled by the launcher: lanes of 16 channels per row (a power of two <= 64), channel tiles per row
-};
-hipError_t bf_launch_rfi_moments(const bf_rfi_moments_args &a, hipStream_t stream);
-// cell sums and the zero-DM series -> cell flags, channel masks, spectrum flags, counts; the thresholds by value
-struct bf_rfi_flags_args {
-    const uint32_t *cell_sums; // [B][nr_blocks][C][2]
-    const uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]
-    uint8_t *cell_flags;       // [B][nr_blocks][C]
-    uint8_t *channel_mask;     // [B][C]
-    uint8_t *spectrum_flags;   // nullptr with zero_dm, or [B][nr_blocks * block_len]
-    uint32_t *counts;          // [B][3]
-    double mean_thr, mean_floor, var_thr, var_floor, zero_dm_thr, zero_dm_floor;
-    uint32_t C, B, nr_blocks, block_len, max_bad_blocks;
-};
-hipError_t bf_launch_rfi_flags(const bf_rfi_flags_args &a, hipStream_t stream);
-// the window with every flagged byte replaced by fill, into rows first_out .. of out uint8 [B][out_spectra][C]
-struct bf_rfi_clean_args {
-    const uint8_t *in;             // 16-byte aligned
-    uint8_t *out;                  // 16-byte aligned; may be in where the rows are the same ones
-    const uint8_t *cell_flags;     // nullptr (none), or [B][nr_blocks][C]
-    const uint8_t *channel_mask;   // nullptr (none), or [B][C]: a zero byte replaces the channel
-    const uint8_t *spectrum_flags; // nullptr (none), or [B][nr_blocks * block_len]
-    unsigned long long *replaced;  // nullptr, or [B]: grows by the bytes replaced
-    uint64_t in_spectra, first, out_spectra, first_out;
-    uint32_t C, B, nr_blocks, block_len, fill;
-    uint32_t lanes, tiles;         // filled by the launcher, as bf_rfi_moments_args
-};
-hipError_t bf_launch_rfi_clean(const bf_rfi_clean_args &a, hipStream_t stream);
 hipError_t bf_warm_module_rfi();
-
-// 8-bit search filterbanks (bf_filterbank.hip; include/dcs_filterbank.h).  Spectra are float
-// [T][C][B], beam fastest; cb = C * B.
-// Running sums {s1, s2} per (channel, beam) over the T spectra, in order, in fp64
-struct bf_fbsums_args {
-    const float *spectra;
-    double *sums;        // [C][B][2]
-    uint64_t cb;
-    uint32_t T;
-    uint32_t accumulate; // non-zero: the sums start from what sums holds
-};
-hipError_t bf_launch_spectra_sums(const bf_fbsums_args &a, hipStream_t stream);
-// Sums -> scales {mu, k} float [C][B][2], in fp64 rounded once per operation
-struct bf_fbscales_args {
-    const double *sums;
-    float *scales;
-    uint64_t cb;
-    uint64_t count; // spectra behind the sums: 1 .. 2^53 - 1
-    float target_std;
-};
-hipError_t bf_launch_filterbank_scales(const bf_fbscales_args &a, hipStream_t stream);
-// Spectra normalised with the scales, quantised and transposed into out uint8 [B][out_spectra][C], rows first .. first + T - 1
-struct bf_fbq8_args {
-    const float *spectra;
-    const float *scales;               // [C][B][2], 8-byte aligned; read when the work runs
-    uint8_t *out;                      // 16-byte aligned
-    unsigned long long *clip_count;    // [B], added to; or nullptr: no counting
-    uint64_t out_spectra, first;
-    uint32_t C, B, T;
-    uint32_t slices;                   // filled by the launcher: time slices a workgroup walks (gridDim.y runs of them)
-    uint32_t descending;               // non-zero: channel c lands in column C - 1 - c
-    float level;
-};
-hipError_t bf_launch_filterbank_q8(const bf_fbq8_args &a, hipStream_t stream);
 hipError_t bf_warm_module_filterbank();
 
 // One coefficient per lane, one time step (reference kernel a1's shape).

@@ -28,9 +28,44 @@
 // series of the whole window.  Both keep the values of a pass on chip where they fit (4096 channels in LDS, 16384 spectra in
 // registers) and read them from global memory in every pass where they do not: the same counts either way.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// The RFI flagger (include/dcs_rfi.h) on the filterbanks uint8 [B][in_spectra][C].  The
+// window is rows first .. first + nr_blocks * block_len - 1 of every beam, nr_blocks blocks of block_len rows.
+// {sum x, sum x^2} per (beam, block, channel), and the sum over the channels of every row of the window
+struct bf_rfi_moments_args {
+    const uint8_t *in;   // 16-byte aligned
+    uint32_t *cell_sums; // [B][nr_blocks][C][2]
+    uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]: zeroed by the launcher, added to by the kernel
+    uint64_t in_spectra, first;
+    uint32_t C, B, nr_blocks, block_len;
+    uint32_t lanes, tiles; // filled by the launcher: lanes of 16 channels per row (a power of two <= 64), channel tiles per row
+};
+// cell sums and the zero-DM series -> cell flags, channel masks, spectrum flags, counts; the thresholds by value
+struct bf_rfi_flags_args {
+    const uint32_t *cell_sums; // [B][nr_blocks][C][2]
+    const uint32_t *zero_dm;   // nullptr, or [B][nr_blocks * block_len]
+    uint8_t *cell_flags;       // [B][nr_blocks][C]
+    uint8_t *channel_mask;     // [B][C]
+    uint8_t *spectrum_flags;   // nullptr with zero_dm, or [B][nr_blocks * block_len]
+    uint32_t *counts;          // [B][3]
+    double mean_thr, mean_floor, var_thr, var_floor, zero_dm_thr, zero_dm_floor;
+    uint32_t C, B, nr_blocks, block_len, max_bad_blocks;
+};
+// the window with every flagged byte replaced by fill, into rows first_out .. of out uint8 [B][out_spectra][C]
+struct bf_rfi_clean_args {
+    const uint8_t *in;             // 16-byte aligned
+    uint8_t *out;                  // 16-byte aligned; may be in where the rows are the same ones
+    const uint8_t *cell_flags;     // nullptr (none), or [B][nr_blocks][C]
+    const uint8_t *channel_mask;   // nullptr (none), or [B][C]: a zero byte replaces the channel
+    const uint8_t *spectrum_flags; // nullptr (none), or [B][nr_blocks * block_len]
+    unsigned long long *replaced;  // nullptr, or [B]: grows by the bytes replaced
+    uint64_t in_spectra, first, out_spectra, first_out;
+    uint32_t C, B, nr_blocks, block_len, fill;
+    uint32_t lanes, tiles;         // filled by the launcher, as bf_rfi_moments_args
+};
 
 namespace {
 
@@ -546,7 +581,7 @@ hipError_t bf_warm_module_rfi()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_rfi_beam_kernel));
 }
 
-hipError_t bf_launch_rfi_moments(const bf_rfi_moments_args &args, hipStream_t stream)
+static hipError_t bf_launch_rfi_moments(const bf_rfi_moments_args &args, hipStream_t stream)
 {
     if (args.nr_blocks == 0u || args.B == 0u || args.C == 0u) return hipSuccess;
     bf_rfi_moments_args a = args;
@@ -565,7 +600,7 @@ hipError_t bf_launch_rfi_moments(const bf_rfi_moments_args &args, hipStream_t st
     return hipGetLastError();
 }
 
-hipError_t bf_launch_rfi_flags(const bf_rfi_flags_args &a, hipStream_t stream)
+static hipError_t bf_launch_rfi_flags(const bf_rfi_flags_args &a, hipStream_t stream)
 {
     if (a.B == 0u || a.C == 0u) return hipSuccess;
     const uint64_t cells = (uint64_t)a.B * a.nr_blocks;
@@ -575,7 +610,7 @@ hipError_t bf_launch_rfi_flags(const bf_rfi_flags_args &a, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t bf_launch_rfi_clean(const bf_rfi_clean_args &args, hipStream_t stream)
+static hipError_t bf_launch_rfi_clean(const bf_rfi_clean_args &args, hipStream_t stream)
 {
     if (args.nr_blocks == 0u || args.B == 0u || args.C == 0u) return hipSuccess;
     bf_rfi_clean_args a = args;
@@ -589,3 +624,102 @@ hipError_t bf_launch_rfi_clean(const bf_rfi_clean_args &args, hipStream_t stream
         hipLaunchKernelGGL(bf_rfi_clean_kernel<1u>, dim3(blocks), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_rfi.h, behind the table as in bf_integrate.hip.  Nothing allocated; of the context the channel
+// count and the device are used.  The sizes that need C are checked here; the thresholds are host memory and travel by value
+// in the kernels' arguments.
+namespace bf_host {
+
+int rfi_moments_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                     uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, uint32_t *d_cell_sums, size_t cell_sums_bytes,
+                     uint32_t *d_zero_dm, size_t zero_dm_bytes, void *stream)
+{
+    if (int e = rfi_moments_args(c, d_filterbank, in_spectra, first_spectrum, nr_blocks, block_len, nr_beams, d_cell_sums, d_zero_dm,
+                                 zero_dm_bytes))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cell_sums_bytes, nr_beams, nr_blocks, C, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_moments_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.cell_sums = d_cell_sums;
+    a.zero_dm = d_zero_dm;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    return (int)bf_launch_rfi_moments(a, as_stream(stream));
+}
+
+int rfi_flags_impl(dcs_bf_context *c, const uint32_t *d_cell_sums, size_t cell_sums_bytes, const uint32_t *d_zero_dm, size_t zero_dm_bytes,
+                   uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const dcs_bf_rfi_thresholds *thr, uint8_t *d_cell_flags,
+                   size_t cell_flags_bytes, uint8_t *d_channel_mask, size_t channel_mask_bytes, uint8_t *d_spectrum_flags,
+                   size_t spectrum_flags_bytes, uint32_t *d_counts, size_t counts_bytes, void *stream)
+{
+    if (int e = rfi_flags_args(c, d_cell_sums, d_zero_dm, zero_dm_bytes, nr_blocks, block_len, nr_beams, thr, d_cell_flags, d_channel_mask,
+                               d_spectrum_flags, spectrum_flags_bytes, d_counts, counts_bytes))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(cell_sums_bytes, nr_beams, nr_blocks, C, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(cell_flags_bytes, nr_beams, nr_blocks, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(channel_mask_bytes, nr_beams, C, 1u, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_flags_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.cell_sums = d_cell_sums;
+    a.zero_dm = d_zero_dm;
+    a.cell_flags = d_cell_flags;
+    a.channel_mask = d_channel_mask;
+    a.spectrum_flags = d_spectrum_flags;
+    a.counts = d_counts;
+    a.mean_thr = thr->mean_thr;
+    a.mean_floor = thr->mean_floor;
+    a.var_thr = thr->var_thr;
+    a.var_floor = thr->var_floor;
+    a.zero_dm_thr = thr->zero_dm_thr;
+    a.zero_dm_floor = thr->zero_dm_floor;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    a.max_bad_blocks = thr->max_bad_blocks;
+    return (int)bf_launch_rfi_flags(a, as_stream(stream));
+}
+
+int rfi_clean_q8_impl(dcs_bf_context *c, const uint8_t *d_filterbank, size_t filterbank_bytes, uint64_t in_spectra, uint64_t first_spectrum,
+                      uint32_t nr_blocks, uint32_t block_len, uint32_t nr_beams, const uint8_t *d_cell_flags, const uint8_t *d_channel_mask,
+                      const uint8_t *d_spectrum_flags, uint8_t fill, uint8_t *d_out, size_t out_bytes, uint64_t out_spectra,
+                      uint64_t first_out, unsigned long long *d_replaced, void *stream)
+{
+    if (int e = rfi_clean_q8_args(c, d_filterbank, in_spectra, first_spectrum, nr_blocks, block_len, nr_beams, d_out, out_spectra, first_out,
+                                  d_replaced))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t C = (uint32_t)c->p.nr_channels;
+    if (!holds(filterbank_bytes, nr_beams, in_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(out_bytes, nr_beams, out_spectra, C, 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_rfi_clean_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = d_filterbank;
+    a.out = d_out;
+    a.cell_flags = d_cell_flags;
+    a.channel_mask = d_channel_mask;
+    a.spectrum_flags = d_spectrum_flags;
+    a.replaced = d_replaced;
+    a.in_spectra = in_spectra;
+    a.first = first_spectrum;
+    a.out_spectra = out_spectra;
+    a.first_out = first_out;
+    a.C = C;
+    a.B = nr_beams;
+    a.nr_blocks = nr_blocks;
+    a.block_len = block_len;
+    a.fill = fill;
+    return (int)bf_launch_rfi_clean(a, as_stream(stream));
+}
+
+} // namespace bf_host

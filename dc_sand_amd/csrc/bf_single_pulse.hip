@@ -29,9 +29,42 @@
 // bf_peak_snr_kernel: one lane per (series, block), looping over the widths; fp64 rounded once per operation (the build has
 // -ffp-contract=off; the divides and the square root are the correctly rounded ones, as bf_filterbank.hip's scales rely on).
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// The single-pulse search on the DM-time planes (include/dcs_single_pulse.h).
+// A series is one (beam, DM) pair: series s begins at word s * plane_spectra of the planes.
+// {sum x, sum x^2 mod 2^64} of words first .. first + T - 1 of every series
+struct bf_dtsums_args {
+    const uint32_t *plane; // [series][plane_spectra]
+    uint64_t *sums;        // [series][2]
+    uint64_t plane_spectra, first;
+    uint32_t T;
+    uint32_t accumulate;   // non-zero: added to what sums holds
+};
+// Per series, width index i and block k of block_len times: {the largest boxcar sum of width widths[i], its first time} into
+// peaks [series][nr_widths][peak_blocks][2] at block first_block + k; {0, 0xffffffff} for a width outside [1, max_width]
+struct bf_boxcar_args {
+    const uint32_t *plane;  // [series][plane_spectra]; words first .. first + T + max_width - 2 of a series are read
+    const uint32_t *widths; // [nr_widths]; read when the work runs
+    uint32_t *peaks;
+    uint64_t plane_spectra, first, peak_blocks, first_block;
+    uint32_t T, nr_widths, max_width, block_len;
+    uint32_t run;           // filled by the launcher: blocks that a workgroup takes, one after the other
+    uint32_t segments;      // filled by the launcher: such runs per series
+};
+// Peaks and sums -> snr [series][nr_widths][peak_blocks] and best [series][peak_blocks], blocks first_block .. + nr_blocks - 1
+struct bf_peaksnr_args {
+    const uint32_t *peaks;
+    const uint32_t *widths;
+    const uint64_t *sums;
+    float *snr;
+    uint32_t *best;         // nullptr: not wanted
+    uint64_t peak_blocks, first_block, count;
+    uint64_t total;         // series * nr_blocks
+    uint32_t nr_blocks, nr_widths, max_width;
+};
 
 namespace {
 
@@ -308,7 +341,7 @@ hipError_t bf_warm_module_single_pulse()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_boxcar_peaks_kernel));
 }
 
-hipError_t bf_launch_dm_time_sums(const bf_dtsums_args &a, uint64_t series, hipStream_t stream)
+static hipError_t bf_launch_dm_time_sums(const bf_dtsums_args &a, uint64_t series, hipStream_t stream)
 {
     if (series == 0u) return hipSuccess;
     if (series > 0x7fffffffull) return hipErrorInvalidValue;
@@ -316,7 +349,7 @@ hipError_t bf_launch_dm_time_sums(const bf_dtsums_args &a, uint64_t series, hipS
     return hipGetLastError();
 }
 
-hipError_t bf_launch_boxcar_peaks(const bf_boxcar_args &args, uint64_t series, hipStream_t stream)
+static hipError_t bf_launch_boxcar_peaks(const bf_boxcar_args &args, uint64_t series, hipStream_t stream)
 {
     if (series == 0u || args.T == 0u || args.nr_widths == 0u) return hipSuccess;
     if (args.max_width < 1u || args.max_width > kMaxWidth || args.block_len < 64u || args.block_len > kSegment || args.block_len % 64u)
@@ -331,7 +364,7 @@ hipError_t bf_launch_boxcar_peaks(const bf_boxcar_args &args, uint64_t series, h
     return hipGetLastError();
 }
 
-hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream)
+static hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream)
 {
     if (a.total == 0u) return hipSuccess;
     const uint64_t blocks = (a.total + 255u) / 256u;
@@ -339,3 +372,90 @@ hipError_t bf_launch_peak_snr(const bf_peaksnr_args &a, hipStream_t stream)
     hipLaunchKernelGGL(bf_peak_snr_kernel, dim3((uint32_t)blocks), dim3(256u), 0, stream, a);
     return hipGetLastError();
 }
+
+// The host side of include/dcs_single_pulse.h, behind the table as in bf_integrate.hip.  Nothing allocated; of the context only
+// its device is used.  A series is one (beam, DM) pair; nr_beams * nr_dm of them fit 64 bits.
+namespace bf_host {
+
+int dm_time_sums_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, uint32_t accumulate,
+                      uint64_t *d_sums, size_t sums_bytes, void *stream)
+{
+    if (int e = dm_time_sums_args(c, d_dm_time, plane_spectra, first_spectrum, nr_spectra, nr_beams, d_sums)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, series, 2u, sizeof(uint64_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    bf_dtsums_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.plane = d_dm_time;
+    a.sums = d_sums;
+    a.plane_spectra = plane_spectra;
+    a.first = first_spectrum;
+    a.T = nr_spectra;
+    a.accumulate = accumulate ? 1u : 0u;
+    return (int)bf_launch_dm_time_sums(a, series, as_stream(stream));
+}
+
+int boxcar_peaks_impl(dcs_bf_context *c, const uint32_t *d_dm_time, size_t dm_time_bytes, uint64_t plane_spectra,
+                      uint64_t first_spectrum, uint32_t nr_spectra, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths,
+                      uint32_t nr_widths, uint32_t max_width, uint32_t block_len, uint32_t *d_peaks, size_t peaks_bytes,
+                      uint64_t peak_blocks, uint64_t first_block, void *stream)
+{
+    if (int e = boxcar_peaks_args(c, d_dm_time, plane_spectra, first_spectrum, nr_spectra, nr_beams, d_widths, max_width, block_len,
+                                  d_peaks, peak_blocks, first_block))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(dm_time_bytes, series, plane_spectra, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_boxcar_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.plane = d_dm_time;
+    a.widths = d_widths;
+    a.peaks = d_peaks;
+    a.plane_spectra = plane_spectra;
+    a.first = first_spectrum;
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.T = nr_spectra;
+    a.nr_widths = nr_widths;
+    a.max_width = max_width;
+    a.block_len = block_len;
+    return (int)bf_launch_boxcar_peaks(a, series, as_stream(stream));
+}
+
+int peak_snr_impl(dcs_bf_context *c, const uint32_t *d_peaks, size_t peaks_bytes, uint64_t peak_blocks, uint64_t first_block,
+                  uint32_t nr_blocks, uint32_t nr_beams, uint32_t nr_dm, const uint32_t *d_widths, uint32_t nr_widths,
+                  uint32_t max_width, const uint64_t *d_sums, size_t sums_bytes, uint64_t count, float *d_snr, size_t snr_bytes,
+                  uint32_t *d_best, size_t best_bytes, void *stream)
+{
+    if (int e = peak_snr_args(c, d_peaks, peak_blocks, first_block, nr_blocks, nr_beams, d_widths, max_width, d_sums, count, d_snr,
+                              d_best))
+        return e;
+    DCS_CHECK_DEVICE(c);
+    const uint64_t series = (uint64_t)nr_beams * nr_dm;
+    if (!holds(peaks_bytes, series, nr_widths, peak_blocks, 2u * sizeof(uint32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(sums_bytes, series, 2u, sizeof(uint64_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(snr_bytes, series, nr_widths, peak_blocks, sizeof(float))) return DCS_ERR_INVALID_ARGUMENT;
+    if (d_best && !holds(best_bytes, series, peak_blocks, sizeof(uint32_t), 1u)) return DCS_ERR_INVALID_ARGUMENT;
+    const unsigned __int128 total = (unsigned __int128)series * nr_blocks;
+    if (total >> 64) return DCS_ERR_INVALID_ARGUMENT;
+    bf_peaksnr_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.peaks = d_peaks;
+    a.widths = d_widths;
+    a.sums = d_sums;
+    a.snr = d_snr;
+    a.best = d_best;
+    a.peak_blocks = peak_blocks;
+    a.first_block = first_block;
+    a.count = count;
+    a.total = (uint64_t)total;
+    a.nr_blocks = nr_blocks;
+    a.nr_widths = nr_widths;
+    a.max_width = max_width;
+    return (int)bf_launch_peak_snr(a, as_stream(stream));
+}
+
+} // namespace bf_host

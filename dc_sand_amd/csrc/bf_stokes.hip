@@ -23,9 +23,20 @@
 // does not store it.  Byte offsets are 64-bit.  Nothing here rounds: -ffp-contract and the float flags of the build play
 // no part.
 
-#include "bf_kernels.h"
+#include "bf_host.h"
 
 #include <hip/hip_runtime.h>
+
+// Full-Stokes detection (include/dcs_stokes.h): two int8 beam tensors as
+// rows = C * nT16 * B rows of 32 bytes each, every row pair reduced to nr_stokes exact dwords of block_stokes [C][nT16][B][nr_stokes]
+struct bf_stokes_args {
+    const int8_t *beams_x; // [rows][16][2], 16-byte aligned; polarisation x
+    const int8_t *beams_y; // the same of polarisation y; may be beams_x
+    int32_t *block_stokes; // [rows][nr_stokes], aligned to 4 * nr_stokes bytes
+    uint64_t rows;
+    uint64_t n_groups;     // filled by the launcher: groups of rows that a wave carries at once
+    uint32_t nr_stokes;    // 1 (I) or 4 (I, Q, U, V)
+};
 
 namespace {
 
@@ -128,7 +139,7 @@ hipError_t bf_warm_module_stokes()
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&bf_stokes_block_kernel<4>));
 }
 
-hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream)
+static hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream)
 {
     if (a.rows == 0u) return hipSuccess;
     switch (a.nr_stokes) {
@@ -138,3 +149,36 @@ hipError_t bf_launch_stokes_block(const bf_stokes_args &a, hipStream_t stream)
     }
     return hipGetLastError();
 }
+
+// The host side of include/dcs_stokes.h, behind the table as in bf_integrate.hip.  No coefficients, nothing allocated, and
+// math_mode plays no part.
+namespace bf_host {
+
+int stokes_block_impl(dcs_bf_context *c, uint32_t nt, const int8_t *d_beams_x, const int8_t *d_beams_y, size_t beams_bytes,
+                      uint32_t nr_stokes, int32_t *d_block_stokes, size_t stokes_bytes, void *stream)
+{
+    if (int e = stokes_block_args(c, nt, d_beams_x, d_beams_y, nr_stokes, d_block_stokes)) return e;
+    DCS_CHECK_DEVICE(c);
+    const uint32_t B = (uint32_t)c->p.nr_beams, C = (uint32_t)c->p.nr_channels;
+    if (!holds(beams_bytes, C, nt, B, 2u)) return DCS_ERR_INVALID_ARGUMENT;
+    if (!holds(stokes_bytes, C, nt / 16u, B, (uint64_t)nr_stokes * sizeof(int32_t))) return DCS_ERR_INVALID_ARGUMENT;
+    bf_stokes_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.beams_x = d_beams_x;
+    a.beams_y = d_beams_y;
+    a.block_stokes = d_block_stokes;
+    a.rows = (uint64_t)C * (nt / 16u) * B;
+    a.nr_stokes = nr_stokes;
+    return (int)bf_launch_stokes_block(a, as_stream(stream));
+}
+
+int integrate_stokes_impl(dcs_bf_context *c, const int32_t *d_block_stokes, size_t stokes_bytes, uint32_t nr_blocks,
+                          uint32_t blocks_per_spectrum, uint32_t nr_stokes, uint32_t accumulate, float *d_spectra,
+                          size_t spectra_bytes, void *stream)
+{
+    if (int e = integrate_stokes_args(c, d_block_stokes, nr_blocks, blocks_per_spectrum, nr_stokes, d_spectra)) return e;
+    return integrate_blocks(c, BF_INTEGRATE_I32, d_block_stokes, stokes_bytes, (uint64_t)(uint32_t)c->p.nr_beams * nr_stokes, nr_blocks,
+                            blocks_per_spectrum, accumulate, d_spectra, spectra_bytes, stream);
+}
+
+} // namespace bf_host
