@@ -1,19 +1,22 @@
-"""What the GPU tests of the beamformers share (tests/test_gpu_beam_weights.py, test_gpu_beamformer_exact.py,
-test_gpu_beam_quant.py, test_gpu_beam_power.py): the shapes, one context with its samples and output buffer, and
-seeded random weights."""
+"""What the GPU tests of the beamformers share (tests/test_gpu_parity.py, test_gpu_parity_fused.py,
+test_gpu_beam_weights.py, test_gpu_beamformer_exact.py, test_gpu_beam_quant.py, test_gpu_beam_power.py): the shapes, one
+context with its samples and output buffer, and seeded random weights."""
 import numpy as np
 
 from conftest import rand_table
 from helpers.device_buffers import Context
 
-# test_beamform_accumulated_on_the_matrix_cores's shapes: staged and kChain, ragged antennas / beams, several beam groups
-# and several workgroups per channel
+# The shapes of test_beamform_accumulated_on_the_matrix_cores (tests/test_gpu_parity.py) and of the tests that hold
+# the same launches bit for bit: staged and kChain, ragged antennas / beams, several beam groups and several workgroups per
+# channel
 ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 48), (8, 4, 5, 16), (37, 21, 9, 48),
               (130, 3, 4, 16), (4, 40, 7, 32), (9, 5, 3, 16), (129, 33, 2, 32), (256, 17, 2, 16), (1, 1, 1, 16),
               (66, 70, 2, 80), (128, 16, 3, 64), (192, 48, 2, 32), (200, 20, 2, 32), (64, 1024, 1, 32),
               (64, 32, 3, 112), (64, 24, 2, 272), (64, 16, 2, 592), (48, 16, 3, 48), (64, 64, 2, 272),
               (256, 64, 2, 272), (100, 20, 3, 112), (256, 16, 1, 1600), (65, 16, 2, 48),
+              # enough workgroups for the XCD-grouped numbering to leave its identity tail (> 8 x the sharers):
               (64, 1024, 9, 32), (130, 20, 9, 32), (256, 64, 9, 16), (192, 48, 11, 48),
+              # more than 64 beams at <= 64 antennas (several beam groups per channel, ragged last group)
               (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
 FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
                 (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
@@ -72,14 +75,18 @@ def passes_of_fused_launch(A, B, C, nt16, grid_x, shared_bytes):
 
 class Case(Context):
     """One context, its samples and output buffer (0xFF with a 0xFF canary: unwritten floats read as NaN), and both
-    beamformers with and without weights."""
+    beamformers with and without weights.  ``table`` and ``ant`` replace the seeded table [b*A + a] and samples;
+    ``parameters`` are further fields of the context's BeamformerParameters."""
 
-    def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None):
-        super().__init__(gpu, C, A, B, NR_SAMPLES_PER_CHANNEL=nt)
+    def __init__(self, gpu, oracle, A, B, C, nt, seed=0, table=None, ant=None, **parameters):
+        super().__init__(gpu, C, A, B, **{"NR_SAMPLES_PER_CHANNEL": nt, **parameters})
         self.oracle, self.nt = oracle, nt
         self.op = oracle.params_from(self.bp)
         self.table = rand_table(self.bp.n_pairs, seed=A + B + seed) if table is None else table  # [b*A + a]
-        self.ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+        if ant is None:
+            ant = np.random.default_rng(A + seed).integers(-128, 128, size=(C, nt // 16, A, 16, 2), dtype=np.int8)
+        assert ant.shape == (C, nt // 16, A, 16, 2) and ant.dtype == np.int8
+        self.ant = ant
         self.g.upload_delays(self.table)
         self.d_ant = self.upload(self.ant)
         self.shape = (C, nt // 16, B, 16, 2)

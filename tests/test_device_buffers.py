@@ -1,62 +1,16 @@
 """helpers/device_buffers.py on the CPU: DeviceBuffers driven with a host stand-in for dc_sand_amd.device, so that what the
 GPU tests rely on -- a byte written behind a tensor is caught, the memory is freed whatever the test's end -- is itself
 tested, without a device."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from helpers.device_buffers import CANARY, DeviceBuffers
-
-
-class _HostAllocation:
-    def __init__(self, device, nbytes):
-        assert nbytes >= 1
-        self.device, self.nbytes, self.buf = device, nbytes, (ctypes.c_uint8 * nbytes)()
-
-    def __int__(self):
-        return ctypes.addressof(self.buf)
-
-    def free(self):
-        self.device.freed.append(int(self))
-        del self.device.live[int(self)]
-
-
-class _HostDevice:
-    """mem_alloc, memset, memcpy_htod, memcpy_dtoh and synchronize over ctypes buffers; every access is checked to lie inside
-    one live allocation, and free() is counted."""
-
-    def __init__(self):
-        self.live, self.freed, self.synchronized = {}, [], 0
-
-    def mem_alloc(self, nbytes):
-        a = _HostAllocation(self, nbytes)
-        self.live[int(a)] = a
-        return a
-
-    def _bytes(self, address, nbytes):
-        address = int(address)
-        for base, a in self.live.items():
-            if base <= address and address + nbytes <= base + a.nbytes:
-                return np.frombuffer(a.buf, np.uint8)[address - base:address - base + nbytes]
-        raise AssertionError(f"{nbytes} bytes at {address:#x} lie in no live allocation")
-
-    def memset(self, dst, value, nbytes, stream=None):
-        self._bytes(dst, nbytes)[:] = value
-
-    def memcpy_htod(self, dst, src):
-        self._bytes(dst, src.nbytes)[:] = src.view(np.uint8).ravel()
-
-    def memcpy_dtoh(self, dst, src):
-        dst.view(np.uint8).ravel()[:] = self._bytes(src, dst.nbytes)
-
-    def synchronize(self):
-        self.synchronized += 1
+from helpers.host_device import HostDevice
 
 
 @pytest.fixture
 def dev():
-    return _HostDevice()
+    return HostDevice()
 
 
 def test_read_returns_the_body_as_a_copy(dev):

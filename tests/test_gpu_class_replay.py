@@ -7,8 +7,9 @@ Here a table has ONE pair of a higher class -- full degree (fPhase_rad 20000), s
 (fDelayRate_sps inf, beam 2) -- each in a beam of its own, and captured calls are replayed on new samples, weights and gains
 among other graphs and plain calls of the same context.  Every output is held twice:
 
- (a) against the CPU oracle, at the bound of the plain-call tests of tests/test_gpu_parity.py (4e-5 A + 1e-6 for the
-     matrix-core call, 2e-5 A + 1e-6 for the per-sample fused call, times s_b with weights), NaN exactly where the
+ (a) against the CPU oracle, at the bound of the plain-call tests (4e-5 A + 1e-6 for the matrix-core call,
+     tests/test_gpu_parity.py; 2e-5 A + 1e-6 for the per-sample fused call, tests/test_gpu_parity_fused.py;
+     times s_b with weights), NaN exactly where the
      oracle has NaN.  The quantised and the detected outputs are the numpy models (helpers/beam_quant_model.py,
      helpers/beam_power_model.py) of the float output, byte for byte and bit for bit;
  (b) bit for bit against the same call made plainly on a FRESH context with the same table, samples, weights and gains:

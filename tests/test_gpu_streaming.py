@@ -1,39 +1,69 @@
-"""GPU parity of the streaming path (BASELINE configs[4]) beyond the single-node graph: the TWO-NODE graph (terms
+"""GPU parity of the streaming path (BASELINE configs[4]): the hipGraph replayed per tick, one node and TWO nodes (terms
 pre-pass + generator, what slabs of >= 2 GiB and ``form = 3`` build -- the path ``bench.py``'s full-tensor
-``streaming_cfg5`` figure runs on) and the ticks that take their new delay table from DEVICE memory
-(``dcs_bf_stream_tick_*_from_global``: a gather node in the replayed graph; configs[3] + configs[4] composed).
+``streaming_cfg5`` figure runs on), ticks by time index, by fDeltaTime and by (current, reference), a new delay table
+landing between ticks from the host or from DEVICE memory (``dcs_bf_stream_tick_*_from_global``: a gather node in the
+replayed graph; configs[3] + configs[4] composed).
 
 Everything is compared with the CPU oracle evaluated at the tick's own fDeltaTime and table -- never with another GPU
-launch.  Bar as in test_gpu_parity.py: fp32 within 1 ULP, binary16 within one binary16 ulp of RN-even(oracle).
+launch.  Bar as in test_gpu_parity.py: fp32 within 1 ULP, binary16 within one binary16 ulp of RN-even(oracle).  Contexts,
+streams and buffers belong to a StreamCase that the fixture closes; every slab has a guard behind it.
 """
+from functools import partial
+
 import numpy as np
 import pytest
 
 from conftest import rand_table
+from helpers.device_buffers import closed_after
+from helpers.parity_case import GeneratorCase, check_1ulp, ordered_distance
 
 pytestmark = pytest.mark.gpu
 
 
-def _ordered16(u):
-    return np.where(u & 0x8000, -(u & 0x7FFF), u & 0x7FFF)
+class StreamCase(GeneratorCase):
+    """A generator, the stream its ticks run on and the CoefficientStreams begun on it: close() ends them before the
+    generator and the buffers go."""
+
+    def __init__(self, gpu, bp, table=None, tuning=None):
+        super().__init__(gpu, bp, table, tuning)
+        self.stream, self.begun = gpu.Stream(), []
+
+    def begin(self, out, c0, nc, bitwidth=1):
+        """stream_begin into the Tensor ``out``, whose fill (made on the null stream) is complete first."""
+        self.gpu.synchronize()
+        self.begun.append(self.g.stream_begin(out.ptr, out.nbytes, c0, nc, self.stream, bitwidth=bitwidth))
+        return self.begun[-1]
+
+    def close(self):
+        try:
+            self.stream.synchronize()
+            for st in self.begun:
+                st.end()
+        finally:
+            super().close()
 
 
-def _check_slab(oracle, gpu, buf, exp, bitwidth, tag):
-    """exp: the oracle's fp32 slab; NaN exactly where the verifier has NaN, the rest within the bar."""
+@pytest.fixture
+def streaming(gpu):
+    yield from closed_after(partial(StreamCase, gpu))
+
+
+def _check_slab(oracle, got, exp, tag):
+    """got: floats or halves off the device; exp: the oracle's fp32 slab; NaN exactly where the verifier has NaN, the rest
+    within the bar."""
     fin = ~np.isnan(exp)
-    if bitwidth == 1:
-        got = np.empty(exp.shape, dtype=np.float32)
-        gpu.memcpy_dtoh(got, buf)
-        assert np.array_equal(np.isnan(got), ~fin), tag
-        mx, n_over, first = oracle.max_ulp(np.where(fin, got, 0).astype(np.float32), np.where(fin, exp, 0).astype(np.float32), 1)
-        assert n_over == 0, (tag, mx, n_over, first)
+    assert np.array_equal(np.isnan(got), ~fin), tag
+    if got.dtype == np.float32:
+        check_1ulp(oracle, np.where(fin, got, 0).astype(np.float32), np.where(fin, exp, 0).astype(np.float32), tol=None, tag=tag)
     else:
-        h16 = np.empty(exp.shape, dtype=np.float16)
-        gpu.memcpy_dtoh(h16, buf)
-        assert np.array_equal(np.isnan(h16), ~fin), tag
-        have = np.where(fin, h16, 0).astype(np.float16).view(np.uint16).astype(np.int32)
-        want = np.where(fin, exp, 0).astype(np.float16).view(np.uint16).astype(np.int32)
-        assert np.abs(_ordered16(have) - _ordered16(want)).max() <= 1, tag
+        assert ordered_distance(np.where(fin, got, 0).astype(np.float16), np.where(fin, exp, 0).astype(np.float16)) <= 1, tag
+
+
+def _rows(gpu, out, first, shape):
+    """Rows of a slab too large to come back whole: ``shape`` floats from row ``first`` of the Tensor ``out``."""
+    host = np.empty(shape, dtype=np.float32)
+    gpu.memcpy_dtoh(host, out.ptr + first * int(np.prod(out.shape[2:])) * 4)
+    return host
 
 
 def _tables(n_pairs, seeds, slow_in=()):
@@ -52,30 +82,23 @@ def _tables(n_pairs, seeds, slow_in=()):
 
 
 @pytest.mark.parametrize("bitwidth,math_mode", [(1, 0), (0, 0), (0, 4)])
-def test_two_node_streaming_graph_every_tick_against_the_oracle(gpu, oracle, bitwidth, math_mode):
+def test_two_node_streaming_graph_every_tick_against_the_oracle(streaming, oracle, bitwidth, math_mode):
     """``form = 3`` before ``stream_begin`` builds the two-node graph (bf_terms_kernel -> tiled generator reading the
     terms table) at a small shape.  Ticks by time index, by fDeltaTime and by (current, reference); a new HOST table
     on some ticks (one of them with slow-class pairs, so the pre-pass node's own stores into d_out happen inside the
     graph) and a new DEVICE table on others; the whole slab after every tick against the oracle."""
     from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator, delta_times
+    from dc_sand_amd.generator import delta_times
 
     bp = BeamformerParameters(NR_CHANNELS=96, NR_STATIONS=8, NR_BEAMS=40)
     op = oracle.params_from(bp)
     c0, nc = 16, 64
     tables = _tables(bp.n_pairs, (131, 132, 133, 134), slow_in=(1, 3))
-    d_tables = []
-    for t in tables:
-        d = gpu.mem_alloc(t.nbytes)
-        gpu.memcpy_htod(d, t)
-        d_tables.append(d)
-    g = SteeringCoefficientGenerator(bp)
-    g.set_tuning(form=3, math_mode=math_mode)
-    stream = gpu.Stream()
-    g.upload_delays(tables[0], stream=stream)
-    nbytes = nc * bp.n_pairs * (8 if bitwidth == 1 else 4)
-    buf = gpu.mem_alloc(nbytes)
-    st = g.stream_begin(buf, nbytes, c0, nc, stream, bitwidth=bitwidth)
+    c = streaming(bp, tuning=dict(form=3, math_mode=math_mode))
+    d_tables = [c.upload(t) for t in tables]
+    c.g.upload_delays(tables[0], stream=c.stream)
+    out = c.tensor(1, nc, bitwidth)
+    st = c.begin(out, c0, nc, bitwidth)
     cur = 0
     ref = (41, 999_800_000)
     #        kind  time                      table source
@@ -88,6 +111,7 @@ def test_two_node_streaming_graph_every_tick_against_the_oracle(gpu, oracle, bit
             cur = src[1]
             host_tbl = tables[cur] if src[0] == "host" else None
         dev = src is not None and src[0] == "dev"
+        out.refill(stream=c.stream)
         if kind == "t":
             dt = delta_times(bp, when, 1)[0]
             st.tick_from_global(when, d_tables[cur]) if dev else st.tick(when, host_tbl)
@@ -97,109 +121,78 @@ def test_two_node_streaming_graph_every_tick_against_the_oracle(gpu, oracle, bit
         else:
             dt = oracle.ts_diff(ref, when)
             st.tick_at_from_global(when, ref, d_tables[cur]) if dev else st.tick_at(when, ref, host_tbl)
-        stream.synchronize()
-        exp = oracle.generate_dt(op, tables[cur], [dt], c0, nc)
-        _check_slab(oracle, gpu, buf, exp, bitwidth, (tick, kind, when, src))
-    st.end()
-    g.close()
-    buf.free()
-    for d in d_tables:
-        d.free()
+        c.stream.synchronize()
+        _check_slab(oracle, out.read(), oracle.generate_dt(op, tables[cur], [dt], c0, nc), (tick, kind, when, src))
 
 
-def test_streaming_from_a_global_device_table_changing_every_tick(gpu, oracle):
+def test_streaming_from_a_global_device_table_changing_every_tick(streaming, oracle):
     """configs[3] + configs[4] composed: the context owns beams [off, off + B_loc) of a GLOBAL [A][B_total] table that
     sits in device memory (where an RCCL broadcast lands it) and CHANGES ON EVERY TICK; the tick gathers its slice
     inside the replayed graph.  Both graph shapes (one node / two nodes behind the gather), both widths; each tick's
     slab against the oracle on that tick's slice.  Ticks are queued back to back in bursts (no host
     synchronisation between them) into separate output slabs, so the double-buffered table is exercised while
     earlier replays are still in flight."""
-    from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator
+    from dc_sand_amd import BeamformerParameters, _lib
 
     A, B_total, C = 6, 50, 40
     rng = np.random.default_rng(77)
     n_ticks = 9
     globs = [rand_table(A * B_total, seed=900 + k) for k in range(n_ticks)]
     globs[4]["fDelayRate_sps"][3 * B_total + 20] = 2e-2  # a slow-class pair inside the second shard below
-    d_globs = []
-    for t in globs:
-        d = gpu.mem_alloc(t.nbytes)
-        gpu.memcpy_htod(d, t)
-        d_globs.append(d)
     for (off, bl), form, bw in (((0, 16), 0, 1), ((16, 34), 3, 1), ((7, 9), 3, 0), ((49, 1), 0, 0)):
         bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=bl)
         op = oracle.params_from(bp)
-        g = SteeringCoefficientGenerator(bp)
-        if form:
-            g.set_tuning(form=form)
-        stream = gpu.Stream()
-        g.set_delays_from_global(d_globs[0], B_total, off, stream=stream)
+        c = streaming(bp, tuning=dict(form=form) if form else None)
+        d_globs = [c.upload(t) for t in globs]
+        c.g.set_delays_from_global(d_globs[0], B_total, off, stream=c.stream)
         c0, nc = 3, 30
-        slab = nc * bp.n_pairs * (8 if bw == 1 else 4)
-        slab_pad = (slab + 255) & ~255
-        buf = gpu.mem_alloc(slab_pad * n_ticks)
-        streams = [g.stream_begin(int(buf) + k * slab_pad, slab, c0, nc, stream, bitwidth=bw) for k in range(n_ticks)]
+        outs = [c.tensor(1, nc, bw) for k in range(n_ticks)]
+        streams = [c.begin(outs[k], c0, nc, bw) for k in range(n_ticks)]
         dts = [np.float32(k * 200e-6 + rng.uniform(0, 1e-5)) for k in range(n_ticks)]
         for k in range(n_ticks):  # one burst: nine graph launches, nine different tables, no synchronisation
             streams[k].tick_dt_from_global(float(dts[k]), d_globs[k], B_total, off)
-        stream.synchronize()
+        c.stream.synchronize()
         for k in range(n_ticks):
             local = np.ascontiguousarray(globs[k].reshape(A, B_total)[:, off:off + bl]).ravel()
-            exp = oracle.generate_dt(op, local, [dts[k]], c0, nc)
-            _check_slab(oracle, gpu, int(buf) + k * slab_pad, exp, bw, (off, bl, form, bw, k))
+            _check_slab(oracle, outs[k].read(), oracle.generate_dt(op, local, [dts[k]], c0, nc), (off, bl, form, bw, k))
         # the argument checks of the device-table ticks
-        from dc_sand_amd import _lib
-
         with pytest.raises(_lib.DcsError) as e:
             streams[0].tick_dt_from_global(0.0, d_globs[0], B_total, B_total - bl + 1)  # slice runs past the table
         assert e.value.status == _lib.DCS_ERR_OUT_OF_RANGE
         with pytest.raises(_lib.DcsError) as e:
             streams[0].tick_dt_from_global(0.0, int(d_globs[0]) + 4, B_total, off)  # not 16-byte aligned
         assert e.value.status == _lib.DCS_ERR_INVALID_ARGUMENT
-        for s_ in streams:
-            s_.end()
-        g.close()
-        buf.free()
-    for d in d_globs:
-        d.free()
 
 
-def test_host_table_on_every_tick_never_reuses_a_staging_buffer_in_flight(gpu, oracle):
+def test_host_table_on_every_tick_never_reuses_a_staging_buffer_in_flight(gpu, streaming, oracle):
     """A new HOST table with every tick, twelve ticks queued back to back (more than the ring of four pinned staging
     buffers): the caller's array may be overwritten as soon as the tick call returns, and every slab still shows
     its own tick's table."""
     from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator
 
     bp = BeamformerParameters(NR_CHANNELS=48, NR_STATIONS=4, NR_BEAMS=96)
     op = oracle.params_from(bp)
     n_ticks = 12
     tables = [rand_table(bp.n_pairs, seed=500 + k) for k in range(n_ticks)]
-    g = SteeringCoefficientGenerator(bp)
-    stream = gpu.Stream()
-    g.upload_delays(tables[0], stream=stream)
-    slab = bp.NR_CHANNELS * bp.n_pairs * 8
-    buf = gpu.mem_alloc(slab)
-    keep = gpu.mem_alloc(slab * n_ticks)  # every tick's slab is copied aside on the same stream
-    st = g.stream_begin(buf, slab, 0, bp.NR_CHANNELS, stream)
+    c = streaming(bp)
+    c.g.upload_delays(tables[0], stream=c.stream)
+    out, keep = c.tensor(1), c.tensor(n_ticks)  # every tick's slab is copied aside on the same stream
+    st = c.begin(out, 0, bp.NR_CHANNELS)
     scratch = np.empty_like(tables[0])
     for k in range(n_ticks):
         scratch[:] = tables[k]
+        out.refill(stream=c.stream)
         st.tick_dt(k * 200e-6, scratch)
         scratch["fDelay_s"][:] = np.nan  # the call has copied it: the caller's buffer is free again
-        gpu.memcpy_dtod(int(keep) + k * slab, buf, slab, stream)
-    stream.synchronize()
+        gpu.memcpy_dtod(keep.ptr + k * out.nbytes, out.ptr, out.nbytes, c.stream)
+    c.stream.synchronize()
+    out.guard_untouched()
+    kept = keep.read()
     for k in range(n_ticks):
-        exp = oracle.generate_dt(op, tables[k], [np.float32(k * 200e-6)])
-        _check_slab(oracle, gpu, int(keep) + k * slab, exp, 1, k)
-    st.end()
-    g.close()
-    buf.free()
-    keep.free()
+        _check_slab(oracle, kept[k:k + 1], oracle.generate_dt(op, tables[k], [np.float32(k * 200e-6)]), k)
 
 
-def test_config5_full_tensor_two_node_graph_every_element(gpu, oracle, record_property):
+def test_config5_full_tensor_two_node_graph_every_element(gpu, streaming, oracle, record_property):
     """BASELINE configs[4] at FULL size: ``stream_begin`` over the whole 64 x 1024 x 32768 tensor (16 GiB >= 2 GiB: the
     two-node graph, the code ``bench.py``'s ``streaming_cfg5.full_tensor_period_us`` times), three ticks at a 200 us
     model cadence -- the second with a new host table, the third with a new DEVICE table --, then EVERY one of the 2^32
@@ -207,38 +200,34 @@ def test_config5_full_tensor_two_node_graph_every_element(gpu, oracle, record_pr
     import time
 
     from dc_sand_amd import BeamformerParameters
-    from dc_sand_amd.generator import SteeringCoefficientGenerator
     from helpers.every_element import compare_every_element
 
     bp = BeamformerParameters(NR_CHANNELS=32768, NR_STATIONS=64, NR_BEAMS=1024)
     op = oracle.params_from(bp)
     tables = [rand_table(bp.n_pairs, seed=s) for s in (71, 72, 73)]
-    d_tab = gpu.mem_alloc(tables[2].nbytes)
-    gpu.memcpy_htod(d_tab, tables[2])
-    g = SteeringCoefficientGenerator(bp)
-    stream = gpu.Stream()
-    g.upload_delays(tables[0], stream=stream)
-    nbytes = g.output_bytes(1, 1)
-    assert nbytes == 16 * 2 ** 30
-    buf = gpu.mem_alloc(nbytes)
-    st = g.stream_begin(buf, nbytes, 0, bp.NR_CHANNELS, stream)
-    row = bp.n_pairs * 8
-    host = np.empty((bp.NR_STATIONS, bp.NR_BEAMS, 2), dtype=np.float32)
+    c = streaming(bp)
+    d_tab = c.upload(tables[2])
+    c.g.upload_delays(tables[0], stream=c.stream)
+    out = c.tensor(1)
+    assert out.nbytes == c.g.output_bytes(1, 1) == 16 * 2 ** 30
+    st = c.begin(out, 0, bp.NR_CHANNELS)
+    row = (1, 1) + out.shape[2:]
     dts = [np.float32(k * 200e-6) for k in (1, 2, 3)]
     st.tick_dt(float(dts[0]))
-    stream.synchronize()
-    for c in (0, 12345, 32767):  # sampled rows of the earlier ticks, everything of the last
-        gpu.memcpy_dtoh(host, int(buf) + c * row)
-        assert oracle.max_ulp(host, oracle.generate_dt(op, tables[0], [dts[0]], c, 1), 1)[1] == 0, c
+    c.stream.synchronize()
+    for ch in (0, 12345, 32767):  # sampled rows of the earlier ticks, everything of the last
+        _check_slab(oracle, _rows(gpu, out, ch, row), oracle.generate_dt(op, tables[0], [dts[0]], ch, 1), ch)
+    out.refill(stream=c.stream)
     st.tick_dt(float(dts[1]), tables[1])
-    stream.synchronize()
-    for c in (1, 20000, 32766):
-        gpu.memcpy_dtoh(host, int(buf) + c * row)
-        assert oracle.max_ulp(host, oracle.generate_dt(op, tables[1], [dts[1]], c, 1), 1)[1] == 0, c
+    c.stream.synchronize()
+    for ch in (1, 20000, 32766):
+        _check_slab(oracle, _rows(gpu, out, ch, row), oracle.generate_dt(op, tables[1], [dts[1]], ch, 1), ch)
+    out.refill(stream=c.stream)
     st.tick_dt_from_global(float(dts[2]), d_tab)
-    stream.synchronize()
+    c.stream.synchronize()
+    out.guard_untouched()
     t0 = time.perf_counter()
-    res = compare_every_element(gpu, oracle, buf, op, tables[2], dts[2], bp.NR_CHANNELS, bp.n_pairs)
+    res = compare_every_element(gpu, oracle, out.ptr, op, tables[2], dts[2], bp.NR_CHANNELS, bp.n_pairs)
     wall = time.perf_counter() - t0
     n = bp.NR_CHANNELS * bp.n_pairs * 2
     for r in (0, 1):
@@ -249,7 +238,114 @@ def test_config5_full_tensor_two_node_graph_every_element(gpu, oracle, record_pr
                f"{res[0]['hist'][1]} at 1 ULP, 0 beyond (float-libm reading: {res[1]['hist'][1]}, 0 beyond); {wall:.1f} s wall")
     print(summary)
     record_property("config5_full_compare", summary)
-    st.end()
-    g.close()
-    buf.free()
-    d_tab.free()
+
+
+def test_streaming_graph_ticks_with_table_updates(streaming, oracle):
+    """BASELINE configs[4] plumbing: hipGraph-captured launch replayed per tick
+    with a new time index, and a new delay table landing between ticks
+    (double-buffered); every tick's slab equals the oracle's."""
+    from dc_sand_amd import BeamformerParameters
+
+    bp = BeamformerParameters(NR_CHANNELS=96, NR_STATIONS=8, NR_BEAMS=40)
+    op = oracle.params_from(bp)
+    c0, nc = 16, 64
+    tables = [rand_table(bp.n_pairs, seed=s) for s in (31, 32, 33)]
+    c = streaming(bp, tables[0])
+    out = c.tensor(1, nc)
+    st = c.begin(out, c0, nc)
+    cur = 0
+    for tick, t in enumerate([0, 1, 5, 7, 9, 18, 255, 256, 1000]):
+        new = None
+        if tick in (3, 4, 7):
+            cur = (cur + 1) % 3
+            new = tables[cur]
+        out.refill(stream=c.stream)
+        st.tick(t, new)
+        c.stream.synchronize()
+        _check_slab(oracle, out.read(), oracle.generate(op, tables[cur], t, 1, c0, nc), (tick, t))
+
+
+def test_config5_streaming_at_the_200us_slab(gpu, streaming, oracle):
+    """BASELINE configs[4] at size: 64 x 1024 pairs x the 2560-channel slab that sustains the 200 us cadence
+    (1.34 GB per tick), hipGraph replay, MODEL time advancing 200 us per tick (dcs_bf_stream_tick_dt, and
+    dcs_bf_stream_tick_at across a seconds boundary), a new delay table landing between ticks; sampled rows of
+    every tick against the oracle evaluated at the same fDeltaTime."""
+    from dc_sand_amd import BeamformerParameters
+
+    bp = BeamformerParameters(NR_CHANNELS=32768, NR_STATIONS=64, NR_BEAMS=1024)
+    op = oracle.params_from(bp)
+    c0, nc = 4096, 2560
+    tables = [rand_table(bp.n_pairs, seed=s) for s in (61, 62)]
+    c = streaming(bp, tables[0])
+    out = c.tensor(1, nc)
+    st = c.begin(out, c0, nc)
+    row = (1, 1) + out.shape[2:]
+    cur = 0
+    ref = (777, 999_500_000)  # 0.5 ms before a seconds boundary: ticks 3.. lie beyond it
+    for tick in range(1, 7):
+        new = None
+        if tick == 3:
+            cur, new = 1, tables[1]
+        out.refill(stream=c.stream)
+        if tick % 2:
+            dt = np.float32(tick * 200e-6)
+            st.tick_dt(dt, new)
+        else:
+            ns = ref[1] + tick * 200_000
+            now = (ref[0] + ns // 10 ** 9, ns % 10 ** 9)  # a normalised wall-clock reading
+            dt = oracle.ts_diff(ref, now)
+            assert abs(float(dt) - tick * 200e-6) < 1e-7
+            st.tick_at(now, ref, new)
+        c.stream.synchronize()
+        out.guard_untouched()
+        for cl in (0, 1279, nc - 1):
+            _check_slab(oracle, _rows(gpu, out, cl, row), oracle.generate_dt(op, tables[cur], [dt], c0 + cl, 1), (tick, cl))
+    out.refill(stream=c.stream)
+    st.tick(300)  # the time-index form still works on the same stream object
+    c.stream.synchronize()
+    out.guard_untouched()
+    _check_slab(oracle, _rows(gpu, out, 0, row), oracle.generate(op, tables[cur], 300, 1, c0, 1), 300)
+
+
+def test_streaming_seeded_fuzz_of_tick_kinds_slabs_and_table_updates(streaming, oracle):
+    """12 seeded streams (hipGraph replay, BASELINE configs[4]'s plumbing) x 8 ticks each: a random channel slab and
+    output width per stream, every tick by time index, by fDeltaTime or by a (current, reference) pair, a new delay table
+    landing with some of the ticks (double-buffered), the slab read back after every tick: fp32 within 1 ULP of the
+    verifier at that tick's time and table, fp16 within one binary16 ulp of its RN-even image."""
+    from dc_sand_amd import BeamformerParameters
+    from dc_sand_amd.generator import delta_times
+
+    rng = np.random.default_rng(20261009)
+    for n in range(12):
+        A, B, C = int(rng.integers(1, 7)), int(rng.integers(1, 40)), int(rng.integers(2, 60))
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=A, NR_BEAMS=B)
+        op = oracle.params_from(bp)
+        table = rand_table(bp.n_pairs, seed=11000 + n)
+        c0 = int(rng.integers(0, C))
+        nc = int(rng.integers(1, C - c0 + 1))
+        bw = int(rng.integers(0, 2))
+        c = streaming(bp)
+        c.g.upload_delays(table, stream=c.stream)
+        out = c.tensor(1, nc, bw)
+        s_ = c.begin(out, c0, nc, bw)
+        for tick in range(8):
+            new = None
+            if rng.integers(0, 3) == 0:
+                table = rand_table(bp.n_pairs, seed=12000 + 10 * n + tick)
+                new = table
+            kind = int(rng.integers(0, 3))
+            out.refill(stream=c.stream)
+            if kind == 0:
+                t = int(rng.integers(0, 5000))
+                s_.tick(t, new_table=new)
+                dt = delta_times(bp, t, 1)[0]
+            elif kind == 1:
+                dt = np.float32(rng.uniform(-2.0, 2.0))
+                s_.tick_dt(float(dt), new_table=new)
+            else:
+                ref = (int(rng.integers(0, 10 ** 6)), int(rng.integers(0, 10 ** 9)))
+                cur = (ref[0] + int(rng.integers(0, 3)), int(rng.integers(0, 10 ** 9)))
+                s_.tick_at(cur, ref, new_table=new)
+                dt = oracle.ts_diff(ref, cur)
+            c.stream.synchronize()
+            _check_slab(oracle, out.read(), oracle.generate_dt(op, table, [dt], c0, nc), (n, tick, kind, A, B, C, c0, nc, bw, float(dt)))
