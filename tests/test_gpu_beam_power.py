@@ -13,6 +13,7 @@ from helpers.bacc_case import DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beam_quant_model import SHAPES, seeded_weights
 from helpers.device_buffers import closed_after
+from helpers.integrate_cases import FORM_N, FORM_NBLK
 
 pytestmark = pytest.mark.gpu
 
@@ -284,6 +285,34 @@ def test_integration_is_the_ordered_sum(gpu, oracle, case, A, B, C, nt):
     c.call_integrate(2, stream=s.handle)
     s.synchronize()
     assert same_bits(c.read_spectra(2), integrate(P2, 2)) is None
+
+
+def test_integration_takes_every_unrolled_trip_and_tail_in_order(gpu, oracle, case):
+    """The float integrator adds a lane's blocks in order, four to an unrolled trip: n = 1 .. 5, 8, 9, 16 and 17 give no trip,
+    one and two whole trips, each with and without a tail, plain (the loop starts at the second block) and accumulating (at
+    the first): helpers/launch_forms.integrate_trips; tests/test_launch_forms.py.  The block powers are given, not detected:
+    magnitudes spread over nine decades, so that the sum depends on its order -- the ordered sum differs from the sum of the
+    same blocks taken backwards, and from the exact sum rounded once."""
+    B, C = 3, 2
+    c = case(4, B, C, FORM_NBLK * 16)
+    rng = np.random.default_rng(4)
+    P = (rng.uniform(1.0, 2.0, size=c.pshape) * 10.0 ** rng.uniform(-3, 6, size=c.pshape)).astype(np.float32)
+    gpu.memcpy_htod(c.d_p, P)
+    for n in FORM_N:
+        exp = integrate(P, n)
+        assert exp.shape == (FORM_NBLK // n, C, B) and np.all(np.isfinite(exp)) and np.unique(exp).size >= 100
+        if n > 2:
+            groups = P.reshape(C, FORM_NBLK // n, n, B)
+            backwards = integrate(groups[:, :, ::-1].reshape(P.shape), n)
+            once = groups.astype(np.float64).sum(axis=2).transpose(1, 0, 2).astype(np.float32)
+            assert same_bits(exp, backwards) is not None and same_bits(exp, once) is not None, n
+        got = c.spectra(n)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        prior = (rng.uniform(1.0, 2.0, size=exp.shape) * 10.0 ** rng.uniform(-3, 6, size=exp.shape)).astype(np.float32)
+        want = integrate(P, n, prior=prior)
+        got = c.spectra(n, accumulate=True, prior=prior)
+        assert same_bits(got, want) is None, (n, "accumulate", same_bits(got, want))
+    assert same_bits(c.read_power(), P) is None  # the blocks are as they were given
 
 
 @pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])

@@ -7,6 +7,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
+from helpers import candidates_cases as cc
 from helpers import hip_graph
 from helpers.candidates_model import CANDIDATE, collapse, expected_buffer, find_candidates, same_bits, seeded_planes
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
@@ -70,7 +71,7 @@ def case(gpu):
 
 @lru_cache(maxsize=None)
 def ragged_planes(special=0.0):
-    return seeded_planes(2, 37, 3, 200, seed=21, special=special, step=1024)  # few ties: candidates in every tile, at every radius
+    return seeded_planes(*cc.RAGGED, seed=21, special=special, step=1024)  # few ties: candidates in every tile, at every radius
 
 
 def tiles_of(B, nr_dm, nr_blocks):
@@ -114,9 +115,9 @@ def test_equal_maxima_across_tile_borders_and_halo_corners(case):
     # a plateau over the corner of four tiles, and maxima eight cells apart on both axes: the far corner of the halo
     s[2 * TD - 2:2 * TD + 2, TK - 20:TK - 16] = 9.0
     s[TD - 1, TK + 20], s[TD + 7, TK + 28], s[TD + 7, TK + 12] = 15.0, 15.0, 15.0
-    snr = np.full((1, nr_dm, 2, first_block + nr_blocks + 1), -np.inf, np.float32)
+    snr = np.full((1, nr_dm, cc.BORDER_WIDTHS, first_block + nr_blocks + 1), -np.inf, np.float32)
     snr[0, :, 1, first_block:first_block + nr_blocks] = s
-    peaks = seeded_planes(1, nr_dm, 2, snr.shape[3], seed=5)[1]
+    peaks = seeded_planes(1, nr_dm, cc.BORDER_WIDTHS, snr.shape[3], seed=5)[1]
     d_planes = (case.upload(snr), case.upload(peaks))
     for radii in ((1, 1), (8, 8), (0, 1), (1, 0), (0, 0), (8, 7), (7, 8)):
         rec, _ = case.find(snr, peaks, first_block, nr_blocks, 5.0, radii, d_planes=d_planes)
@@ -135,12 +136,12 @@ def test_equal_maxima_across_tile_borders_and_halo_corners(case):
 def test_more_segments_than_two_rounds_of_the_scan(case):
     from dc_sand_amd.generator import CANDIDATES_SCAN_SPAN
 
-    B, nr_dm, nr_blocks = 2, 600, 1100
+    B, nr_dm, nw, nr_blocks = cc.SCAN
     _, dm_tiles, k_tiles = tiles_of(B, nr_dm, nr_blocks)
     tiles, segments = B * dm_tiles * k_tiles, B * nr_dm * k_tiles
     assert (dm_tiles, k_tiles) == (38, 18) and tiles == 1368 > 1024  # more tiles than the scan workgroup has lanes
     assert segments > 2 * CANDIDATES_SCAN_SPAN and segments % CANDIDATES_SCAN_SPAN  # three rounds and more, the last one short
-    snr, peaks = seeded_planes(B, nr_dm, 2, nr_blocks, seed=33)
+    snr, peaks = seeded_planes(B, nr_dm, nw, nr_blocks, seed=33)
     rec, count = case.find(snr, peaks, 0, nr_blocks, 7.0, (1, 1))
     assert count[0] > 3 * CANDIDATES_SCAN_SPAN  # candidates in every round's segments
     per_round = np.bincount(((rec["beam"].astype(np.int64) * nr_dm + rec["dm"]) * k_tiles + rec["block"] // 64) // CANDIDATES_SCAN_SPAN)
@@ -198,12 +199,33 @@ def test_non_finite_planes(case):
     assert count.tolist() == [0, 0]
 
 
+# ------------------------------------------------------------------------------------------- every unrolled chain of widths
+
+@pytest.mark.parametrize("nw", cc.FORM_NR_WIDTHS)
+def test_every_width_of_every_unrolled_chain(case, nw):
+    """Eight widths and more: the collapse takes them eight at a time, then four, then one by one (helpers/launch_forms.py,
+    candidate_width_chain).  In every plane each width index is the winning one of some candidate, at both radii, and the
+    hand-made cells hold equal maxima at two indices (the lower one wins), a NaN at one of such a pair, and -infinity in all
+    widths but the last: helpers/candidates_cases.py, whose conditions tests/test_launch_forms.py asserts on the model; here
+    they are asserted on the model's records before the device is called."""
+    _, _, blocks = cc.FORM_SHAPE
+    snr, peaks = cc.form_planes(nw)
+    d_planes = (case.upload(snr), case.upload(peaks))
+    for radii in cc.FORM_RADII:
+        rec, _ = find_candidates(snr, peaks, 0, blocks, cc.FORM_THRESHOLD, *radii, 0)
+        assert set(rec["width_index"].tolist()) == set(range(nw)), radii
+        won = {(int(r["dm"]), int(r["block"])): int(r["width_index"]) for r in rec}
+        assert all(won[cell] == winner for cell, (_, winner) in cc.hand_cells(nw).items()), radii
+        got, count = case.find(snr, peaks, 0, blocks, cc.FORM_THRESHOLD, radii, d_planes=d_planes)
+        assert count[0] == len(rec) >= nw + len(cc.hand_cells(nw))
+
+
 # ------------------------------------------------------------------------------------------- width_index is peak_snr's d_best
 
 def test_width_index_is_the_best_width_of_peak_snr(case, gpu):
     from dc_sand_amd.generator import best_width_bytes, peak_snr_bytes
 
-    T, widths, max_width = 1500, np.array([4, 1, 33, 16, 0, 4, 32], np.uint32), 32
+    T, widths, max_width = 1500, np.array(cc.BEST_WIDTHS, np.uint32), 32
     plane = np.random.default_rng(44).integers(0, 1 << 20, size=(2, 19, T + max_width - 1), dtype=np.uint32)
     plane[1, 3] = 777  # a constant series: every width gives 0, the lowest index is the best
     pk, sm = model_peaks(plane, 0, T, widths, max_width, 64), model_sums(plane, 0, T)
@@ -228,7 +250,7 @@ def test_short_buffers_are_refused_and_nothing_is_enqueued(case, gpu):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DCS_ERR_UNSUPPORTED, DcsError
     from dc_sand_amd.generator import candidates_bytes, candidates_workspace_bytes
 
-    B, nr_dm, nw, pb, first_block, nr_blocks, cap = 2, 20, 3, 80, 2, 70, 6
+    (B, nr_dm, nw, pb), first_block, nr_blocks, cap = cc.SHORT, 2, 70, 6
     snr, peaks = seeded_planes(B, nr_dm, nw, pb, seed=50)
     sbytes, kbytes, cbytes, wbytes = snr.nbytes, peaks.nbytes, candidates_bytes(cap), candidates_workspace_bytes(B, nr_dm, nr_blocks)
     d_snr, d_peaks = case.upload(snr), case.upload(peaks)
@@ -274,7 +296,7 @@ def test_captured_on_first_use_and_replayed_with_new_contents(case, gpu):
     both counts follow the new contents, a different number of candidates each time, one of them more than fit."""
     from dc_sand_amd.generator import candidates_bytes, candidates_workspace_bytes
 
-    B, nr_dm, nw, pb, first_block, nr_blocks, cap = 2, 37, 3, 140, 3, 131, 1000
+    (B, nr_dm, nw, pb), first_block, nr_blocks, cap = cc.CAPTURE, 3, 131, 1000
     c = case
     snr0, peaks0 = seeded_planes(B, nr_dm, nw, pb, seed=60)
     sbytes, kbytes, cbytes, wbytes = snr0.nbytes, peaks0.nbytes, candidates_bytes(cap), candidates_workspace_bytes(B, nr_dm, nr_blocks)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers.correlator_cases import BLOCKS, FORM_STATIONS, NR_VIS, STATIONS, WALK, shape_of
 from helpers.correlator_model import MAX_BLOCKS, baseline, integrate, nr_baselines, same_bits, visibilities
 from helpers.device_buffers import Context, closed_after
 from helpers.examples import run_example
@@ -54,18 +55,15 @@ def case(gpu):
     yield from closed_after(partial(CCase, gpu))
 
 
-# one antenna; a few; one tile; a tile and one row; one unit of four tiles; ragged tiles in a second unit; every unit of the
-# tile-group split.  n: one block (three zero operands), a pair, three (a ragged K group), one group and a block, two groups
-STATIONS = (1, 3, 16, 17, 64, 100, 256)
-BLOCKS = (1, 2, 3, 5, 8)
-
-
-@pytest.mark.parametrize("A", STATIONS)
+@pytest.mark.parametrize("A", STATIONS + FORM_STATIONS)
 def test_visibilities_are_the_model(gpu, case, A):
-    C = 3
-    c = case(A, C, max(BLOCKS) * 3)
-    for n in BLOCKS:
-        for nr_vis in (1, 3):
+    """STATIONS with C = 3 and every n of BLOCKS; FORM_STATIONS -- one A and more per tile count 1 .. 16, so that every unit form
+    (diagonal or not, the a tiles that exist) is run: helpers/launch_forms.py, tests/test_launch_forms.py -- with C = 2 and
+    n = 3, 4, 5: a masked last step, a whole one, two steps."""
+    C, blocks = shape_of(A)
+    c = case(A, C, max(blocks) * max(NR_VIS))
+    for n in blocks:
+        for nr_vis in NR_VIS:
             ant = seeded_samples(A, C, n * nr_vis)
             exp = visibilities(ant, n)
             got = c.correlate(ant, n)
@@ -73,6 +71,37 @@ def test_visibilities_are_the_model(gpu, case, A):
             assert np.unique(exp).size >= min(100, exp.size // 3), (A, n, nr_vis)  # no trivial expectation
             for a in range(A):
                 assert not got[:, :, baseline(a, a), 1].any()
+
+
+def test_waves_walk_items_beyond_the_grid(gpu, case, record_property):
+    """A = 2, n = 1 and C * nr_vis a little above 4 * 2^20: one unit per (channel, visibility), so more items than the 2^20
+    workgroups of four waves hold, and the waves of the first workgroups take a second item.  The grid is read from the
+    captured launch (nothing allocates, so the capture may come first), and every visibility is compared.  The walk with
+    several units per (channel, visibility) -- A > 64 -- would need tensors of several GiB and stays untested."""
+    A, C, nr_vis, n = WALK["A"], WALK["C"], WALK["nr_vis"], WALK["n"]
+    c = case(A, C, nr_vis * n)
+    ant = seeded_samples(A, C, nr_vis * n)
+    nt, vbytes = 16 * nr_vis * n, C * nr_vis * c.NB * 8
+    d_ant = c.upload(ant)
+    s = gpu.Stream()
+    nodes = hip_graph.launches(s, lambda: c.g.correlate_block(d_ant, ant.nbytes, c.d_vis, vbytes, nt, n, stream=s.handle))
+    s.synchronize()
+    assert len(nodes) == 1, nodes
+    grid, block = nodes[0]
+    assert grid[1] == grid[2] == 1 and block == (256, 1, 1), nodes
+    items = C * nr_vis
+    record_property("gridDim.x, items", (grid[0], items))
+    print(f"correlator walk: gridDim.x {grid[0]}, items {items}")
+    assert grid[0] * 4 < items, f"{grid[0]} workgroups of four waves hold {items} items: raise the channel count"
+    c.refill(c.d_vis)
+    c.g.correlate_block(d_ant, ant.nbytes, c.d_vis, vbytes, nt, n)
+    gpu.synchronize()
+    got = c.read(c.d_vis, vbytes, np.int32, (C, nr_vis, c.NB, 2))
+    step = 64  # the model a slice of channels at a time: it works in int64
+    for c0 in range(0, C, step):
+        exp = visibilities(ant[c0:c0 + step], n)
+        assert np.array_equal(got[c0:c0 + step], exp), (c0, np.argwhere(got[c0:c0 + step] != exp)[:4])
+    assert np.unique(got[-1]).size >= 100  # no trivial expectation, also among the items of the second trip
 
 
 def test_one_hot_every_byte_of_a_row_reaches_its_baselines_with_its_sign(gpu, case):

@@ -9,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from helpers import ddc_cases as dc
 from helpers import ddc_model as model
 from helpers import hip_graph
 from helpers.device_buffers import Context
@@ -100,13 +101,13 @@ def check(case, x, taps, bands, nr_out, **kw):
 
 # one output; a tile less one; a tile; a tile and one (the second tile of a pair holds one output); two tiles and one (a second
 # pair).  T: every number of K steps.  One input and several; one band and two
-@pytest.mark.parametrize("nb", (1, 2))
-@pytest.mark.parametrize("ni", (1, 3))
-@pytest.mark.parametrize("T", (64, 128, 192, 256))
+@pytest.mark.parametrize("nb", dc.NR_BANDS)
+@pytest.mark.parametrize("ni", dc.NR_INPUTS)
+@pytest.mark.parametrize("T", dc.NR_TAPS)
 def test_outputs_are_the_model_bit_for_bit(case, T, ni, nb):
     taps = seeded_taps(nb, T, seed=T + nb)
     assert np.abs(taps).max() > 127 * 257  # past two digits: all three digit planes
-    for nr_out in (1, 15, 16, 17, 33):
+    for nr_out in dc.NR_OUT:
         x = seeded((ni, row_bytes(nr_out, T)), seed=1000 * T + 10 * nr_out + ni)
         got = check(case, x, taps, BANDS2[:nb], nr_out)
         assert np.unique(got).size >= min(60, got.size // 2)  # no trivial expectation
@@ -115,8 +116,51 @@ def test_outputs_are_the_model_bit_for_bit(case, T, ni, nb):
 def test_several_spans_and_every_wave_of_a_workgroup(case):
     """A workgroup takes 512 outputs, a wave 128 of them: 511, 512, 513 and 1100 outputs (a third span, a wave's ragged run)."""
     taps = seeded_taps(2, 256, seed=9)
-    for nr_out in (511, 512, 513, 1100):
-        check(case, seeded((2, row_bytes(nr_out, 256)), seed=nr_out), taps, BANDS2, nr_out)
+    for nr_out in dc.SPANS_NR_OUT:
+        check(case, seeded((dc.SPANS_NR_INPUTS, row_bytes(nr_out, 256)), seed=nr_out), taps, BANDS2, nr_out)
+
+
+def test_workgroups_walk_items_beyond_the_grid(case, gpu, record_property):
+    """2^20 + 37 rows of three outputs, T = 64, one band, rows packed (in_stride 96): one item per row and 2^20 workgroups at
+    the most, so 37 workgroups take a second row and stage its span over the first one's behind a barrier.  The grid is
+    read from the captured launch.  No two consecutive rows are equal, and row r + 2^20 is not row r.  The model over a
+    million rows takes minutes, so these rows are compared bit for bit: rows 0 .. 63, the 64 rows below 2^20, every row
+    from 2^20 on, rows 0 .. 36 (they share workgroups with those), and 4096 seeded rows; the padding of every output row
+    and the canary must hold their prefill."""
+    from dc_sand_amd.generator import ddc_out_bytes
+
+    T, nr_out, in_stride, ni = dc.WALK["T"], dc.WALK["nr_out"], dc.WALK["in_stride"], dc.WALK["nr_inputs"]
+    assert in_stride == row_bytes(nr_out, T)
+    x = seeded((ni, in_stride), seed=20)
+    assert (x[1:] != x[:-1]).any(axis=1).all() and (x[1 << 20:] != x[:ni - (1 << 20)]).any(axis=1).all()
+    taps = seeded_taps(1, T, seed=21)
+    band = BANDS2[:1]
+    out_stride = nr_out + 1
+    obytes = ddc_out_bytes(ni, out_stride, 1)
+    d_x, d_out, d_digits = case.upload(x), case.out(obytes), case.digits(taps)
+    s = gpu.Stream()
+    nodes = hip_graph.launches(s, lambda: case.g.ddc(d_x, x.nbytes, in_stride, ni, nr_out, d_digits, 16 * T, T, band, d_out, obytes,
+                                                     out_stride, stream=s.handle))
+    s.synchronize()
+    assert len(nodes) == 1, nodes
+    grid, block = nodes[0]
+    assert grid[1] == grid[2] == 1 and block == (256, 1, 1), nodes
+    record_property("gridDim.x, items", (grid[0], ni))
+    print(f"ddc walk: gridDim.x {grid[0]}, items {ni}")
+    assert grid[0] < ni, f"{grid[0]} workgroups take {ni} items one each: raise the row count"
+    case.g.ddc(d_x, x.nbytes, in_stride, ni, nr_out, d_digits, 16 * T, T, band, d_out, obytes, out_stride)
+    gpu.synchronize()
+    out = case.read(d_out, obytes, np.float32, (1, ni, out_stride, 2))
+    assert np.all(out[:, :, nr_out:].view(np.uint8) == PREFILL), "written into the padding of a row"
+    line = 1 << 20
+    rows = np.unique(np.concatenate([np.arange(64), np.arange(line - 64, ni), np.random.default_rng(22).integers(0, ni, size=4096)]))
+    assert rows.size > 4096 and set(range(37)) <= set(rows.tolist())
+    exp = model.ddc(x[rows], taps, band, nr_out)
+    got = out[:, rows, :nr_out]
+    assert model.same_bits(got, exp) is None, model.same_bits(got, exp)
+    assert np.unique(got).size >= got.size // 2  # no trivial expectation
+    # the rows of the second trip are their own, not those of the workgroups' first rows
+    assert model.same_bits(out[:, line:, :nr_out], out[:, :ni - line, :nr_out]) is not None
 
 
 def test_int32_extremes_at_the_bound(case):

@@ -10,6 +10,8 @@ import pytest
 from helpers import hip_graph
 from helpers import stokes_model
 from helpers.device_buffers import Context, closed_after
+from helpers.incoherent_cases import FORM_LOOPING_SHAPES, FORM_SHAPES, LOOPING_SHAPES, SHAPES
+from helpers.integrate_cases import FORM_N, FORM_NBLK
 from helpers.incoherent_model import block_power, full_range_words, integrate, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -99,13 +101,7 @@ def case(gpu):
     yield from closed_after(partial(ICase, gpu))
 
 
-# a single row; rows that could share a wave's load; both sides of a wave-load boundary (32 antennas); a last partial
-# load; every loads-per-row count's neighbourhood; row counts odd and no multiple of any rows-per-wave choice
-SHAPES = [(1, 1, 16), (3, 5, 48), (8, 4, 32), (31, 3, 48), (32, 3, 48), (33, 3, 48), (64, 7, 64), (65, 2, 48), (130, 4, 16),
-          (255, 2, 32), (256, 3, 80), (64, 1, 1600)]
-
-
-@pytest.mark.parametrize("A,C,nt", SHAPES)
+@pytest.mark.parametrize("A,C,nt", SHAPES + FORM_SHAPES)
 def test_block_power_is_the_model(gpu, case, A, C, nt):
     c = case(A, C, nt)
     exp = block_power(c.ant)
@@ -117,14 +113,7 @@ def test_block_power_is_the_model(gpu, case, A, C, nt):
     assert np.array_equal(got, block_power(c.ant, w)), np.argwhere(got != block_power(c.ant, w))[:4]
 
 
-# SHAPES have 25 groups of rows at the most, and the kernel's grid holds 2048 workgroups x 4 waves: no wave takes a second
-# trip of its loop over the row groups.  These have 1.25 to 1.35 times 8192 groups, and an odd row count that is no multiple of the rows a
-# wave carries per trip (A, C, nt, those rows: 8 / loads per row, a load being 32 antennas): (1 load, 8 rows), (3 loads, 2
-# rows, ragged), (8 loads, 1 row, ragged)
-LOOPING_SHAPES = [(32, 1283, 1040, 8), (65, 1283, 272, 2), (255, 643, 256, 1)]
-
-
-@pytest.mark.parametrize("A,C,nt,rows_per_trip", LOOPING_SHAPES)
+@pytest.mark.parametrize("A,C,nt,rows_per_trip", LOOPING_SHAPES + FORM_LOOPING_SHAPES)
 def test_block_power_when_a_wave_takes_a_second_trip(gpu, case, record_property, A, C, nt, rows_per_trip):
     """The launch geometry, read from a captured graph (nothing allocates, so the capture may come first), must prove the
     second trip: its waves, each carrying `rows_per_trip` rows per trip, cannot hold the rows in one."""
@@ -165,6 +154,26 @@ def test_integration_over_several_workgroups(gpu, case):
         prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
         got = c.spectra(n, accumulate=True, prior=prior)
         assert same_bits(got, integrate(P, n, prior=prior)) is None, (n, "accumulate", same_bits(got, integrate(P, n, prior=prior)))
+
+
+def test_integration_takes_every_unrolled_trip_and_tail(gpu, case):
+    """The unit-stride uint32 integrator takes a lane's n words eight to a trip: n = 1 .. 5 (a tail alone), 8 and 16 (one and
+    two whole trips), 9 and 17 (a tail behind them), plain and accumulating, over full-range words whose exact sums need
+    all 64 bits of the running sum (helpers/launch_forms.integrate_trips; tests/test_launch_forms.py)."""
+    C = 2
+    c = case(1, C, FORM_NBLK * 16)
+    P = np.random.default_rng(8).integers(0, 1 << 32, size=(C, FORM_NBLK), dtype=np.uint64).astype(np.uint32)
+    P[0, :17] = 0xFFFFFFFF
+    c.set_power(P)
+    for n in FORM_N:
+        exp = integrate(P, n)
+        assert exp.shape == (FORM_NBLK // n, C) and np.unique(exp).size >= 100
+        got = c.spectra(n)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        prior = np.random.default_rng(n).uniform(0.0, float(exp.max()), size=exp.shape).astype(np.float32)
+        want = integrate(P, n, prior=prior)
+        got = c.spectra(n, accumulate=True, prior=prior)
+        assert same_bits(got, want) is None, (n, "accumulate", same_bits(got, want))
 
 
 @pytest.mark.parametrize("A,C,nt", [(37, 2, 32), (130, 2, 32)])

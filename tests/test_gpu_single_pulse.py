@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers import single_pulse_cases as sc
 from helpers.dedisperse_model import BAND_DESCENDING_64, DMS_40, dedisperse, dm_delays
 from helpers.device_buffers import Context
 from helpers.examples import run_example
@@ -99,12 +100,12 @@ def case(gpu):
 
 # ------------------------------------------------------------------------------------------------------- block and window edges
 
-WIDTHS_5 = [3, 7, 1, 100, 7]
+WIDTHS_5 = sc.WIDTHS_5
 
 
 def test_block_and_window_edges(case):
     """B = 2 and nr_dm = 5 with an odd plane_spectra and first_spectrum = 3: the ten series begin at every alignment."""
-    for T in (1, 63, 64, 65, 1000):
+    for T in sc.EDGE_T:
         plane = seeded_plane(2, 5, (3 + T + 99) | 1, seed=T)
         got = case.peaks(plane, 3, T, WIDTHS_5, 100, 64, peak_blocks=nr_blocks_of(T, 64) + 3, first_block=2)
         assert np.array_equal(got[:, :, 1], got[:, :, 4])
@@ -116,12 +117,12 @@ def test_block_and_window_edges(case):
     case.peaks(plane, 333, 300, WIDTHS_5, 100, 128, peak_blocks=4, first_block=1)
 
 
-@pytest.mark.parametrize("T,block_len,max_width", [(5000, 64, 33), (5000, 4096, 4096), (9000, 192, 2000), (4097, 1024, 1)])
+@pytest.mark.parametrize("T,block_len,max_width", sc.RUNS)
 def test_several_runs_of_blocks_per_series(case, T, block_len, max_width):
     """More than 4096 times per series: several workgroups each, whose runs of blocks meet at any alignment; 192 does not
     divide 4096."""
     plane = seeded_plane(1, 3, 1 + T + max_width - 1, seed=T + block_len)
-    widths = sorted({1, 2, max_width // 3 + 1, max_width})
+    widths = sc.run_widths(max_width)
     got = case.peaks(plane, 1, T, widths, max_width, block_len)
     assert np.unique(got[..., 1] % 64).size > 4  # no trivial expectation
 
@@ -132,19 +133,43 @@ def test_width_lists(case):
     plane = seeded_plane(1, 2, 130, seed=6)
     case.peaks(plane, 0, 130, [1], 1, 64)
     # the halo is 64 times the block
-    powers = [1 << k for k in range(13)]
+    powers = sc.POWERS
     plane = seeded_plane(1, 2, 130 + 4095, seed=7)
     got = case.peaks(plane, 0, 130, powers, 4096, 64)
     assert np.all(np.diff(got[..., 0].astype(np.int64), axis=2) > 0)  # a wider boxcar of positive words sums to more
     # widths that take no part: 0, max_width + 1 and 0xFFFFFFFF read {0, 0xFFFFFFFF}; the others are as without them
     plane = seeded_plane(2, 3, 2 + 300 + 99, seed=8)
     plain = case.peaks(plane, 2, 300, WIDTHS_5, 100, 64)
-    mixed = case.peaks(plane, 2, 300, [0, 3, 7, 101, 1, NO_TIME, 100, 7, 4096], 100, 64)
+    mixed = case.peaks(plane, 2, 300, sc.MIXED, 100, 64)
     assert np.array_equal(mixed[:, :, [1, 2, 4, 6, 7]], plain)
     assert np.all(mixed[:, :, [0, 3, 5, 8], :, 0] == 0) and np.all(mixed[:, :, [0, 3, 5, 8], :, 1] == NO_TIME)
     # no width takes part
-    none = case.peaks(plane, 2, 300, [0, 101], 100, 64)
+    none = case.peaks(plane, 2, 300, sc.NONE, 100, 64)
     assert np.all(none[..., 0] == 0) and np.all(none[..., 1] == NO_TIME)
+
+
+# ------------------------------------------------------------------------------------ batches and blocks in every order
+
+@pytest.mark.parametrize("nw", sc.WALK_NR_WIDTHS)
+def test_batches_and_blocks_in_every_order(case, nw):
+    """One to eight batches of eight widths against runs of 1, 2, 3, 4, 5 and 7 blocks (and, for two of the lists, a run of 64
+    and a second workgroup with two): the four waves of a workgroup take the (batch, block) pairs in turn, so with fewer
+    blocks than waves a wave skips batches, several per round where the run is one or two blocks
+    (helpers/launch_forms.boxcar_walk; tests/test_launch_forms.py holds that in these shapes the waves take several pairs
+    each and batches four apart).  Widths that take no part sit in the second and in the last batch.  Every word of the
+    prefilled peak plane is compared."""
+    widths = sc.walk_widths(nw)
+    for nb in sc.WALK_NB:
+        T = sc.walk_T(nb)
+        plane = seeded_plane(1, 2, T + sc.WALK_MAX_WIDTH - 1, seed=100 * nw + nb)
+        got = case.peaks(plane, 0, T, widths, sc.WALK_MAX_WIDTH, sc.WALK_BLOCK_LEN)
+        on = [i for i, w in enumerate(widths) if 1 <= w <= sc.WALK_MAX_WIDTH]
+        assert np.unique(got[:, :, on, :, 0]).size >= min(100, got[:, :, on, :, 0].size // 2)  # no trivial expectation
+    if nw in sc.WALK_LONG_NR_WIDTHS:
+        T = sc.WALK_LONG_T
+        plane = seeded_plane(1, 2, T + sc.WALK_MAX_WIDTH - 1, seed=nw)
+        got = case.peaks(plane, 0, T, widths, sc.WALK_MAX_WIDTH, sc.WALK_BLOCK_LEN)
+        assert got.shape[3] == 66
 
 
 # -------------------------------------------------------------------------------------------------------------------------- ties

@@ -12,6 +12,7 @@ from conftest import rand_table
 from helpers import filterbank_model, hip_graph
 from helpers.device_buffers import Context, closed_after
 from helpers.filterbank_model import same_bits  # bit for bit; two NaNs agree (their payload is the implementation's)
+from helpers.integrate_cases import FORM_N, FORM_NBLK
 from helpers.stokes_model import block_stokes, integrate
 
 pytestmark = pytest.mark.gpu
@@ -265,6 +266,25 @@ def test_integration_is_the_exact_sum_rounded_once(gpu, case, ns):
     prior = np.full((1, C, B, ns), -0.0, dtype=np.float32)
     got = c.spectra(c.nblk, ns, prior=prior)
     assert same_bits(got, integrate(zeros, c.nblk, prior=prior)) is None and not np.signbit(got).any()
+
+
+def test_integration_takes_every_unrolled_trip_and_tail(gpu, case):
+    """The int32 integrator takes a lane's n words eight to a trip: n = 1 .. 5 (a tail alone), 8 and 16 (one and two whole
+    trips), 9 and 17 (a tail behind them), plain and accumulating, over full-range words of both signs
+    (helpers/launch_forms.integrate_trips; tests/test_launch_forms.py)."""
+    B, C, ns = 3, 2, 4
+    c = case(B, C, FORM_NBLK * 16)
+    block = np.random.default_rng(6).integers(-(1 << 31), 1 << 31, size=(C, FORM_NBLK, B, ns), dtype=np.int64).astype(np.int32)
+    c.set_block(block)
+    for n in FORM_N:
+        exp = integrate(block, n)
+        assert exp.shape == (FORM_NBLK // n, C, B, ns) and np.unique(exp).size >= 100
+        got = c.spectra(n, ns)
+        assert same_bits(got, exp) is None, (n, same_bits(got, exp))
+        prior = np.random.default_rng(n).uniform(-3e9, 3e9, size=exp.shape).astype(np.float32)
+        want = integrate(block, n, prior=prior)
+        got = c.spectra(n, ns, prior=prior)
+        assert same_bits(got, want) is None, (n, "accumulate", same_bits(got, want))
 
 
 def test_refusals_enqueue_nothing_and_empty_calls_succeed(gpu, case):
