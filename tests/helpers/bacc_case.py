@@ -1,40 +1,15 @@
 """What the GPU tests of the beamformers share (tests/test_gpu_parity.py, test_gpu_parity_fused.py,
-test_gpu_beam_weights.py, test_gpu_beamformer_exact.py, test_gpu_beam_quant.py, test_gpu_beam_power.py): the shapes, one
-context with its samples and output buffer, and seeded random weights."""
+test_gpu_beam_weights.py, test_gpu_beamformer_exact.py, test_gpu_beam_quant.py, test_gpu_beam_power.py): one context with its
+samples and output buffer, the proof of a launch's depth, and seeded random weights.  The shapes: helpers/bacc_cases.py."""
 import numpy as np
 
 from conftest import rand_table
+from helpers.bacc_cases import ACC_SHAPES, DEEP_SHAPES, DEEPEST_SHAPES, MIN_DEPTH  # noqa: F401  (the tests take them from here)
 from helpers.device_buffers import Context
 
-# The shapes of test_beamform_accumulated_on_the_matrix_cores (tests/test_gpu_parity.py) and of the tests that hold
-# the same launches bit for bit: staged and kChain, ragged antennas / beams, several beam groups and several workgroups per
-# channel
-ACC_SHAPES = [(64, 16, 64, 256), (64, 16, 5, 32), (64, 64, 7, 64), (64, 40, 3, 48), (8, 4, 5, 16), (37, 21, 9, 48),
-              (130, 3, 4, 16), (4, 40, 7, 32), (9, 5, 3, 16), (129, 33, 2, 32), (256, 17, 2, 16), (1, 1, 1, 16),
-              (66, 70, 2, 80), (128, 16, 3, 64), (192, 48, 2, 32), (200, 20, 2, 32), (64, 1024, 1, 32),
-              (64, 32, 3, 112), (64, 24, 2, 272), (64, 16, 2, 592), (48, 16, 3, 48), (64, 64, 2, 272),
-              (256, 64, 2, 272), (100, 20, 3, 112), (256, 16, 1, 1600), (65, 16, 2, 48),
-              # enough workgroups for the XCD-grouped numbering to leave its identity tail (> 8 x the sharers):
-              (64, 1024, 9, 32), (130, 20, 9, 32), (256, 64, 9, 16), (192, 48, 11, 48),
-              # more than 64 beams at <= 64 antennas (several beam groups per channel, ragged last group)
-              (64, 128, 3, 64), (48, 200, 2, 48), (64, 72, 2, 32), (33, 129, 2, 16), (64, 256, 2, 272)]
+# (the matrix-core beamformer's tables: helpers/bacc_cases.py, with the declared list of what each is run with)
 FUSED_SHAPES = [(64, 16, 64, 256), (8, 4, 5, 16), (37, 21, 9, 48), (130, 3, 4, 16), (4, 40, 7, 32), (129, 2, 2, 16),
                 (258, 2, 5, 16), (1, 1, 1, 16), (3, 17, 2, 32)]
-# The shapes above launch fewer workgroups than the chip holds (1280 four-wave ones of the matrix-core beamformer), and the
-# launcher then halves a workgroup's share of the sample blocks until every wave has ONE: the second block of a pair, the
-# later pairs and every later trip of the kernels' loops never run at them.  These launch 1280 to 1296 workgroups, so the
-# launcher leaves a wave several blocks: (A, B, C, nt, the number of blocks that blocks_on_some_wave must prove).
-# staged: 1 tile per workgroup and waves of 3 / 2, 1, 1, 1 blocks (whole and ragged antennas and beams); 2 tiles (shared
-# coefficient making); 4 tiles with one beam group (the 8-block cap: 5 / 4 blocks) and with two, ragged; the XCD-grouped
-# numbering.  kChain: 2 chunks with a partial one, 2 whole chunks, 3 chunks (a wave without one), 4 whole chunks with a
-# ragged last beam group.  Last, the deep ones: 4 blocks per wave (two whole pairs), 16 (eight pairs), and kChain's 4.
-MIN_DEPTH = 3  # a third block is a live second pair
-DEEP_SHAPES = [(64, 16, 640, 272, MIN_DEPTH), (37, 9, 640, 272, MIN_DEPTH), (64, 24, 640, 144, MIN_DEPTH),
-               (64, 40, 640, 144, MIN_DEPTH), (48, 72, 320, 144, MIN_DEPTH), (64, 1024, 40, 80, MIN_DEPTH),
-               (100, 20, 320, 272, MIN_DEPTH), (128, 16, 640, 272, MIN_DEPTH), (130, 20, 320, 272, MIN_DEPTH),
-               (256, 33, 216, 272, MIN_DEPTH),
-               (64, 16, 1280, 256, 4), (48, 72, 640, 256, 10), (130, 20, 640, 256, 4)]
-DEEPEST_SHAPES = DEEP_SHAPES[-3:]
 T_COEFF = 9
 
 
@@ -48,6 +23,16 @@ def blocks_on_some_wave(B, C, nt, grid, block):
     waves = grid[0] * (block[0] // 64)
     units = C * -(-B // 16) * (nt // 16)
     return -(-units // waves)
+
+
+def plan_of(shape, kind):
+    """helpers/launch_forms.py: bacc_plan of (A, B, C, nt) for a call (output kind, weighted, math_mode) of helpers/bacc_cases.py."""
+    from helpers import launch_forms as lf
+    from helpers.bacc_cases import KINDS
+
+    name, weighted, math_mode = kind
+    quant, power, complex_ = KINDS[name]
+    return lf.bacc_plan(*shape, fp32_chain=bool(math_mode & 8), weighted=weighted, quant=quant, power=power, complex_=complex_)
 
 
 def passes_of_fused_launch(A, B, C, nt16, grid_x, shared_bytes):
@@ -142,18 +127,26 @@ class Case(Context):
         else:
             self.g.beamform_accumulated(self.d_ant, self.ant.nbytes, self.d_beams, self.nbytes, self.nt, t_coeff=T_COEFF, stream=stream)
 
-    def prove_depth(self, depth, call):
+    def prove_depth(self, depth, call, kind=None):
         """Asserts that the beamformer launch of ``call(stream)`` gives some wave at least ``depth`` sample blocks
         (blocks_on_some_wave); ``call`` must have been made once already, since a first call allocates.  Nothing runs.
-        Returns (gridDim.x, blockDim.x, proven blocks)."""
+        With ``kind`` = (output kind of helpers/bacc_cases.py, weighted, math_mode) the captured (gridDim.x, blockDim.x,
+        dynamic LDS bytes) must also be what helpers/launch_forms.py: bacc_plan restates for this shape and kind -- the link
+        between the CPU census and what the library launches.  Returns (gridDim.x, blockDim.x, proven blocks)."""
         from helpers import hip_graph
 
         s = self.gpu.Stream()
-        grid, block = hip_graph.largest_launch(hip_graph.launches(s, lambda: call(s.handle)))
+        grid, block, shared = hip_graph.largest_launch(hip_graph.launches(s, lambda: call(s.handle), shared=True))
         s.synchronize()
         proven = blocks_on_some_wave(self.B, self.C, self.nt, grid, block)
         assert proven >= depth, (f"(A, B, C, nt) = {(self.A, self.B, self.C, self.nt)} launches {grid[0]} workgroups of {block[0]} lanes: "
                                  f"only {proven} block(s) proven on some wave, {depth} wanted -- raise the shape's channel count")
+        if kind is not None:
+            plan = plan_of((self.A, self.B, self.C, self.nt), kind)
+            assert (grid[0], block[0], shared) == (plan["grid"], plan["block"], plan["lds"]), \
+                (f"(A, B, C, nt) = {(self.A, self.B, self.C, self.nt)}, {kind}: the launch is (grid, block, LDS bytes) = "
+                 f"{(grid[0], block[0], shared)}, the plan {(plan['grid'], plan['block'], plan['lds'])}")
+            assert proven <= max(plan["blocks_full"][-1], plan["blocks_last"][-1])
         return grid[0], block[0], proven
 
     def enqueue_fused(self, weighted, stream, dts=None):

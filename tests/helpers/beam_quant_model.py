@@ -4,6 +4,8 @@ y = RN(v * k_b) in fp32; NaN -> -128; otherwise clamp(rint(y), -127, 127) with t
 applies it to the float call's output and compares the quantised kernels with it byte for byte."""
 import numpy as np
 
+from helpers.bacc_cases import QUANT_SHAPES as SHAPES  # noqa: F401  (the table stands with the beamformer's others)
+
 
 def quantise(v, gains, beam_axis=2):
     """v: fp32 array with the beams on ``beam_axis`` (default: the beam tensor [C][nt/16][B][16][2]); gains: [B] fp32.
@@ -24,9 +26,6 @@ def quantise(v, gains, beam_axis=2):
 
 # ---- the gain sets of tests/test_gpu_beam_quant.py, derived from the float output alone
 
-# (A, B, C, nt): kStaged and kChain, FULL and ragged antennas, ragged beam tiles, odd numbers of sample blocks
-SHAPES = [(4, 2, 8, 16), (64, 16, 64, 256), (64, 256, 4, 64), (130, 3, 4, 16), (129, 33, 2, 32), (200, 20, 2, 32),
-          (65, 16, 2, 48), (100, 20, 3, 112), (256, 64, 8, 256)]
 # The clipping gain set puts 127 at this per-beam quantile of |v_b|: about 3 % of a beam's components lie above it, so a beam
 # of 128 components (the smallest here) still expects ~4 clipped ones -- inside the 0.5 % .. 20 % window with room on both
 # sides whatever the distribution's tail is

@@ -1,5 +1,5 @@
-"""Which compiled form a call of five kernels takes ("The forms" of sections 5.11, 5.17, 5.18, 5.19, 5.20 and 5.22),
-restated on the CPU: the correlator's units (bf_correlator.hip), the incoherent beam's loads per row (bf_incoherent.hip), the
+"""Which compiled form a call of six kernels takes ("The forms" of sections 5.4, 5.11, 5.17, 5.18, 5.19, 5.20 and
+5.22), restated on the CPU: the matrix-core beamformer's instantiation and geometry (bf_beamform_mfma.hip), the correlator's units (bf_correlator.hip), the incoherent beam's loads per row (bf_incoherent.hip), the
 sifter's collapse of the width axis (bf_candidates.hip), the walk of the boxcar kernel's waves over (batch, block) pairs
 (bf_single_pulse.hip), the grids of the two kernels whose workgroups walk their items (the correlator, bf_ddc.hip) and the
 unrolled trips of the integrator (bf_integrate.hip).  Each launcher picks its form from the arguments alone, so a shape names
@@ -149,3 +149,100 @@ def integrate_trips(kind, n, accumulate):
     count = n - (0 if accumulate or kind != "f32" else 1)
     unroll = INTEGRATE_UNROLL[kind]
     return min(count // unroll, 2), count % unroll
+
+
+# ------------------------------------------------------------------------------------------------- matrix-core beamformer
+
+BACC_WAVES = 4              # waves per workgroup of the product build
+BACC_CHUNK = 64             # kKC: antennas per chunk
+BACC_FP32_LDS_CAP = 26 * 1024
+BACC_ENOUGH_INT8 = 5120     # waves that fill the chip once: 1280 four-wave workgroups
+BACC_ENOUGH_FP32 = 4096     # workgroups
+BACC_FLAGS = [(w, q, p, c) for w in (False, True) for q in (False, True) for p in (False, True) for c in (False, True) if not (q and p)]
+
+
+def bacc_lds_bytes(nbt, A):
+    """bacc_lds_bytes: the fp32 form's two coefficient planes, rows padded where tiles share them."""
+    a_pad = (A + 3) & ~3
+    ws = 16 * nbt + (16 if nbt > 1 else 0)
+    return a_pad * ws * 2 * 4
+
+
+def _wave_blocks(width, nbt, tpr):
+    """The kernels' n_blocks of the four waves of a workgroup that owns ``width`` sample blocks, sorted."""
+    out = []
+    for wave in range(BACC_WAVES):
+        slot = wave // nbt
+        out.append((width - slot + tpr - 1) // tpr if width > slot else 0)
+    return sorted(out)
+
+
+def bacc_plan(A, B, C, nt, fp32_chain=False, weighted=False, quant=False, power=False, complex_=False):
+    """bf_launch_beamform_acc for the product build (every probe knob 0), as a dict; None where it launches nothing (an empty
+    tensor).  A refused call is an AssertionError.  ``fp32_chain`` is the launcher's `chain` (math_mode bit 3), and has
+    nothing to do with the int8 form kChain, which is called "chain" here as in the kernel's FORM."""
+    assert nt % 16 == 0
+    nT16 = nt // 16
+    if A == 0 or B == 0 or C == 0 or nT16 == 0:
+        return None
+    assert A <= 256, "not built"
+    assert not (fp32_chain and (weighted or quant or power or complex_)) and not (quant and power), "refused"
+    wide = not fp32_chain and A > 64
+    staged = not fp32_chain and A <= 64
+    nbt = 1 if wide else (4 if B > 32 else (2 if B > 16 else 1))
+    nw = BACC_WAVES
+    lds_of_four = bacc_lds_bytes(4, A)
+    while fp32_chain and nbt > 1 and bacc_lds_bytes(nbt, A) > BACC_FP32_LDS_CAP:
+        nbt >>= 1
+    n_bgroups = (B + 16 * nbt - 1) // (16 * nbt)
+    tpr = nw // nbt
+    blocks_cap = 8 if staged and nbt == 4 and n_bgroups == 1 else 16
+    max_rounds = 16 if fp32_chain else blocks_cap // tpr
+    tiles = (nT16 + tpr - 1) // tpr * tpr
+    if tiles > max_rounds * tpr:  # equal shares
+        parts = (nT16 + max_rounds * tpr - 1) // (max_rounds * tpr)
+        tiles = ((nT16 + parts - 1) // parts + tpr - 1) // tpr * tpr
+    enough = BACC_ENOUGH_FP32 if fp32_chain else BACC_ENOUGH_INT8 // nw
+    while tiles > tpr and C * n_bgroups * ((nT16 + tiles - 1) // tiles) < enough:
+        tiles = ((tiles // tpr + 1) // 2) * tpr
+    n_tgroups = (nT16 + tiles - 1) // tiles
+    xcd_group = n_bgroups if wide else (n_bgroups if not fp32_chain and n_bgroups >= 16 else 1)
+    grid = C * n_bgroups * n_tgroups
+    assert grid <= 0x7fffffff
+    assert not (quant and tiles // tpr > 126)  # (cannot be reached: rounds are 16 at the most)
+    nop = 9 if complex_ else 6
+    if fp32_chain:
+        form, lds = "fp32", bacc_lds_bytes(nbt, A)
+    elif staged:
+        form, lds = "staged", (tiles * A * 32 + 1023) // 1024 * 1024
+        if tpr > 1:
+            lds += nbt * 4 * nop * 64 * 4
+    else:
+        form, lds = "chain", 4 * nop * 64 * 16 + 8 * 4 + (32 if quant else (16 if weighted else 0)) * 4
+    last = nT16 - (n_tgroups - 1) * tiles
+    return {"form": form, "full": A % 64 == 0, "nbt": nbt, "lds_of_four_tiles": lds_of_four, "tpr": tpr, "blocks_cap": blocks_cap,
+            "tiles_per_wg": tiles, "n_tgroups": n_tgroups, "n_bgroups": n_bgroups, "xcd_group": xcd_group,
+            "grid": grid, "block": 64 * nw, "lds": lds,
+            "chunks": (A + BACC_CHUNK - 1) // BACC_CHUNK, "partial_chunk": A % BACC_CHUNK != 0,
+            "blocks_full": _wave_blocks(min(tiles, nT16), nbt, tpr), "blocks_last": _wave_blocks(last, nbt, tpr)}
+
+
+def bacc_instantiation(A, weighted=False, quant=False, power=False, complex_=False):
+    """(FORM, FULL, W, Q, P, C): the instantiation of bf_beamform_i8_kernel that launch_i8 picks.  (The fp32 form's three
+    instantiations are named by their plan's nbt.)"""
+    assert not (quant and power) and 1 <= A <= 256
+    return ("staged" if A <= 64 else "chain", A % 64 == 0, bool(weighted), bool(quant), bool(power), bool(complex_))
+
+
+def bacc_instantiations_that_exist():
+    return {(form, full) + flags for form in ("staged", "chain") for full in (False, True) for flags in BACC_FLAGS}
+
+
+def bacc_depth(plan):
+    """The most sample blocks the plan gives a wave."""
+    return max(plan["blocks_full"][-1], plan["blocks_last"][-1])
+
+
+def bacc_is_deep(plan):
+    """A third block is a live second pair; the fp32 form has no pairs, its second block is its second trip."""
+    return bacc_depth(plan) >= (2 if plan["form"] == "fp32" else 3)

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import DEEP_SHAPES, T_COEFF, Case, random_weights
+from helpers import bacc_cases as bc
+from helpers.bacc_case import T_COEFF, Case, random_weights
 from helpers.beam_complex_model import complex_model
 from helpers.beam_power_model import block_power, integrate, same_bits
 from helpers.beamformer_model import first_difference, normalise, weighted_coefficients
@@ -23,11 +24,7 @@ from test_gpu_class_replay import class_table
 
 pytestmark = pytest.mark.gpu
 
-STAGED = [(8, 4, 5, 16), (64, 16, 2, 32), (37, 21, 3, 48), (64, 40, 3, 48), (64, 72, 2, 32)]
-CHAIN = [(65, 16, 2, 48), (130, 3, 4, 16), (200, 20, 2, 32), (256, 17, 2, 16)]
-SMALL = STAGED + CHAIN
-DEEP = [(64, 16, 640, 272, 3), (48, 72, 320, 144, 3), (130, 20, 320, 272, 3)]  # one per code path: kStaged 1 and 4 tiles, kChain
-assert all(s in DEEP_SHAPES for s in DEEP)
+DEEP = bc.COMPLEX_DEEP  # (the tables: helpers/bacc_cases.py)
 
 
 class Complex:
@@ -107,7 +104,7 @@ def check_model(x, coef, conj, w=None, dt=None, what=""):
 
 
 # ---- bit for bit: plain and conjugated, the index entry point and the _dt one
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_complex_product_is_the_model_bit_for_bit"))
 def test_complex_product_is_the_model_bit_for_bit(gpu, oracle, exact, A, B, C, nt):
     x = Complex(exact(A, B, C, nt))
     plain = x.c.floats()
@@ -122,7 +119,7 @@ def test_complex_product_is_the_model_bit_for_bit(gpu, oracle, exact, A, B, C, n
 
 
 # ---- cross-checks against the existing call: no model involved
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_call"))
 def test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_call(gpu, oracle, case, A, B, C, nt):
     """x_im = 0: re = sum w_re x_re, the plain call's re plane.  x_re = 0, conjugated: re = sum w_im x_im, the plain call's
     im plane (the operand is fixed(-sigma w_im) = fixed(w_im): the same digits).  Bit for bit, both entry points."""
@@ -151,7 +148,7 @@ def test_one_sample_component_at_a_time_gives_the_planes_of_the_element_wise_cal
 
 
 # ---- weights
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_weights"))
 def test_weights(gpu, oracle, exact, A, B, C, nt):
     x = Complex(exact(A, B, C, nt))
     dt_arg, dt = dt_of(x.c, True)
@@ -204,7 +201,7 @@ def within_fp64_bound(got, coef, ant, conj, nan_beams, what):
     print(f"{what}: max |got - fp64| / sum|x| = {np.nanmax(np.abs(got - exp) / mag[:, :, None, :, None]):.3e}")
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(37, 21, 3, 48), (200, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_slow_class_and_nan_delays_against_the_fp64_sum"))
 def test_slow_class_and_nan_delays_against_the_fp64_sum(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.generator import delta_times
 
@@ -235,23 +232,32 @@ def test_slow_class_and_nan_delays_against_the_fp64_sum(gpu, oracle, case, A, B,
 
 
 # ---- where a wave takes several sample blocks
-@pytest.mark.parametrize("A,B,C,nt,depth", DEEP)
+@pytest.mark.parametrize("A,B,C,nt,depth", bc.shapes_of(bc.COMPLEX + "test_several_blocks_per_wave_bit_for_bit", raw=True))
 def test_several_blocks_per_wave_bit_for_bit(gpu, oracle, exact, record_property, A, B, C, nt, depth):
+    """The float call plain and conjugated, and conjugated with weights, against the model; the detecting call without and
+    with weights against block_power of those floats.  Every launch, read from a captured graph, must prove `depth` blocks
+    on some wave and be the one helpers/launch_forms.py plans (nine coefficient operands: other LDS bytes than the
+    element-wise call's)."""
     x = Complex(exact(A, B, C, nt))
     dt_arg, dt = dt_of(x.c, DEEP.index((A, B, C, nt, depth)) % 2 == 0)
     coef = x.c.coefficient_bits(dt)[0]
     check_model(x, coef, False, dt=dt_arg, what="deep")
     v = check_model(x, coef, True, dt=dt_arg, what="deep")
     record_property("gridDim.x, blockDim.x, blocks proven on some wave",
-                    x.c.prove_depth(depth, lambda s: x.enqueue(True, dt=dt_arg, stream=s)))
-    if A == 130:  # the detected form at one deep shape, and its launch
-        p = x.power(True, dt=dt_arg)
-        assert same_bits(p, block_power(v)) is None, same_bits(p, block_power(v))
-        x.c.prove_depth(depth, lambda s: x.enqueue_power(True, dt=dt_arg, stream=s))
+                    x.c.prove_depth(depth, lambda s: x.enqueue(True, dt=dt_arg, stream=s), kind=bc.CX))
+    p = x.power(True, dt=dt_arg)  # the detected form, and its launch
+    assert same_bits(p, block_power(v)) is None, same_bits(p, block_power(v))
+    x.c.prove_depth(depth, lambda s: x.enqueue_power(True, dt=dt_arg, stream=s), kind=bc.CXP)
+    w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=False)
+    vw = check_model(x, coef, True, w=w, dt=dt_arg, what="deep, weighted")
+    x.c.prove_depth(depth, lambda s: x.enqueue(True, weighted=True, dt=dt_arg, stream=s), kind=bc.CXW)
+    p = x.power(True, w, dt=dt_arg)
+    assert np.all(np.isfinite(p)) and same_bits(p, block_power(vw)) is None, same_bits(p, block_power(vw))
+    x.c.prove_depth(depth, lambda s: x.enqueue_power(True, weighted=True, dt=dt_arg, stream=s), kind=bc.CXPW)
 
 
 # ---- the detected form
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_block_power_is_the_model_of_the_complex_float_output"))
 def test_block_power_is_the_model_of_the_complex_float_output(gpu, oracle, case, A, B, C, nt):
     x = Complex(case(A, B, C, nt))
     w = random_weights(np.random.default_rng(3 * A + B), B, A, zero_beam=False)
@@ -323,7 +329,7 @@ def test_fp32_chain_form_is_refused_and_writes_nothing(gpu, oracle, case):
 
 
 # ---- graph replay (tests/test_gpu_class_replay.py's scheme): a table with one full-degree pair
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 2, 32), (130, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_captured_complex_call_replayed_after_a_younger_plain_call"))
 def test_captured_complex_call_replayed_after_a_younger_plain_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_UNSUPPORTED, DcsError
     from dc_sand_amd.generator import SteeringCoefficientGenerator
@@ -372,7 +378,7 @@ def test_captured_complex_call_replayed_after_a_younger_plain_call(gpu, oracle, 
 
 
 # ---- physics: a beam steered at the source it was made for
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 2, 32), (130, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.COMPLEX + "test_a_conjugate_beam_on_its_own_source_adds_coherently"))
 def test_a_conjugate_beam_on_its_own_source_adds_coherently(gpu, oracle, case, A, B, C, nt):
     """x_a(t) = rint(100 * w_{a, b0}) per component: conj(w) x = 100 |w|^2 = 100 per antenna up to the rounding of the
     sample, at most 0.5 per component -- magnitude sqrt(0.5) after the unit-modulus rotation -- so beam b0 is within

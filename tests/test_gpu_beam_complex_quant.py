@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import DEEP_SHAPES, T_COEFF
+from helpers import bacc_cases as bc
+from helpers.bacc_case import T_COEFF
 from helpers.beam_complex_model import complex_model
 from helpers.beam_quant_model import (expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
@@ -23,11 +24,7 @@ from test_gpu_beamformer_exact import DT_COEFF, Exact
 
 pytestmark = pytest.mark.gpu
 
-STAGED = [(8, 4, 5, 16), (64, 16, 2, 32), (37, 21, 3, 48), (64, 40, 3, 48), (64, 72, 2, 32)]
-CHAIN = [(65, 16, 2, 48), (130, 3, 4, 16), (200, 20, 2, 32), (256, 17, 2, 16)]
-SMALL = STAGED + CHAIN
-DEEP = [(64, 16, 640, 272, 3), (48, 72, 320, 144, 3), (130, 20, 320, 272, 3)]  # kStaged 1 and 4 tiles, kChain
-assert all(s in DEEP_SHAPES for s in DEEP)
+SMALL, DEEP = bc.COMPLEX_SMALL, bc.COMPLEX_DEEP  # (the tables: helpers/bacc_cases.py)
 
 
 class ExactQ(QCase, Exact):
@@ -88,8 +85,8 @@ def exact(gpu, oracle):
 
 
 # ---- 1. the bytes are the quantised floats of the complex float call: plain and conjugated, both entry points
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.CQUANT + "test_bytes_and_counters_are_the_quantised_complex_float_output"))
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_bytes_and_counters_are_the_quantised_complex_float_output"))
 def test_bytes_and_counters_are_the_quantised_complex_float_output(gpu, oracle, case, A, B, C, nt, weighted):
     x = CQ(case(A, B, C, nt))
     w = seeded_weights(B, A) if weighted else None
@@ -99,7 +96,7 @@ def test_bytes_and_counters_are_the_quantised_complex_float_output(gpu, oracle, 
 
 
 # ---- 2. ... and of the model on the generator's coefficient bits: the float kernels are not involved
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_bytes_are_the_quantised_model_on_the_coefficient_bits"))
 def test_bytes_are_the_quantised_model_on_the_coefficient_bits(gpu, oracle, exactq, A, B, C, nt):
     x = CQ(exactq(A, B, C, nt))
     c = x.c
@@ -121,7 +118,7 @@ def test_bytes_are_the_quantised_model_on_the_coefficient_bits(gpu, oracle, exac
 
 
 # ---- 3. not the element-wise form
-@pytest.mark.parametrize("A,B,C,nt", SMALL)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im"))
 def test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im(gpu, oracle, case, A, B, C, nt):
     x = CQ(case(A, B, C, nt))
     c = x.c
@@ -143,19 +140,19 @@ def test_not_the_element_wise_quantised_call_but_its_re_plane_without_x_im(gpu, 
 
 
 # ---- 4. where a wave takes several sample blocks
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt,depth", DEEP)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.CQUANT + "test_several_blocks_per_wave"))
+@pytest.mark.parametrize("A,B,C,nt,depth", bc.shapes_of(bc.CQUANT + "test_several_blocks_per_wave", raw=True))
 def test_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
     x = CQ(case(A, B, C, nt))
     w = seeded_weights(B, A) if weighted else None
     dt = float(DT_COEFF) if DEEP.index((A, B, C, nt, depth)) % 2 else None
     x.check(True, w, dt, f"deep, weighted {weighted}, (A, B, C, nt) = {(A, B, C, nt)}")
     record_property("gridDim.x, blockDim.x, blocks proven on some wave",
-                    x.c.prove_depth(depth, lambda s: x.enqueue_q8(True, weighted, dt=dt, stream=s)))
+                    x.c.prove_depth(depth, lambda s: x.enqueue_q8(True, weighted, dt=dt, stream=s), kind=bc.CXQW if weighted else bc.CXQ))
 
 
 # ---- 5. special gains and a NaN delay value touch their beam only
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_special_gains_and_a_nan_delay_touch_their_beam_only"))
 def test_special_gains_and_a_nan_delay_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
     x = CQ(case(A, B, C, nt))
     c = x.c
@@ -207,7 +204,7 @@ def test_special_gains_and_a_nan_delay_touch_their_beam_only(gpu, oracle, case, 
     assert np.array_equal(got[:, :, others], base[:, :, others]) and np.array_equal(n[others], n_base[others])
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_null_weights_equal_all_ones_weights"))
 def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
     x = CQ(case(A, B, C, nt))
     k = gains_with_clipping(x.floats(True))
@@ -217,7 +214,7 @@ def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
 
 
 # ---- 6. the output's alignment rule is the float call's
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_int8_beams_at_an_address_that_is_8_byte_aligned_only"))
 def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
@@ -241,7 +238,7 @@ def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case,
 
 
 # ---- 7. gains are read when the work runs
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_captured_call_picks_up_new_gains_on_replay"))
 def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, case, A, B, C, nt):
     x = CQ(case(A, B, C, nt))
     c = x.c
@@ -265,7 +262,7 @@ def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, case, A, B, C, 
 
 
 # ---- 8. a context per beam slice, gains and counters offset
-@pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.CQUANT + "test_beam_slices_reproduce_the_full_call"))
 def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.beam_quant import BeamQuantGains
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table

@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers import bacc_cases as bc
 from helpers.bacc_case import DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
 from helpers.beam_power_model import block_power, integrate, same_bits
-from helpers.beam_quant_model import SHAPES, seeded_weights
+from helpers.beam_quant_model import seeded_weights
 from helpers.device_buffers import closed_after
 from helpers.integrate_cases import FORM_N, FORM_NBLK
 
@@ -78,8 +79,8 @@ def case(gpu, oracle):
     yield from closed_after(partial(PCase, gpu, oracle))
 
 
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt", SHAPES)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.POWER + "test_block_power_is_the_model_of_the_float_output"))
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_block_power_is_the_model_of_the_float_output"))
 def test_block_power_is_the_model_of_the_float_output(gpu, oracle, case, A, B, C, nt, weighted):
     c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
@@ -95,13 +96,13 @@ def test_block_power_is_the_model_of_the_float_output(gpu, oracle, case, A, B, C
         assert same_bits(got, exp) is None, (dt, same_bits(got, exp))
 
 
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.POWER + "test_block_power_with_several_blocks_per_wave"))
+@pytest.mark.parametrize("A,B,C,nt,depth", bc.shapes_of(bc.POWER + "test_block_power_with_several_blocks_per_wave", raw=True))
 def test_block_power_with_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
-    """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
+    """The shapes above give every wave one sample block (helpers/bacc_cases.py says why); here a wave has a live second block
     in its pairs and several pairs.  One time form per shape, in turn; then the integrator over many workgroups, every block
     its own spectrum and all blocks in one.  The launch itself, read from a captured graph, must prove `depth` blocks on
-    some wave."""
+    some wave and be the one helpers/launch_forms.py plans."""
     c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
@@ -115,7 +116,7 @@ def test_block_power_with_several_blocks_per_wave(gpu, oracle, case, record_prop
         sp = c.spectra(n)
         assert same_bits(sp, integrate(got, n)) is None, (n, same_bits(sp, integrate(got, n)))
     record_property("gridDim.x, blockDim.x, blocks proven on some wave",
-                    c.prove_depth(depth, lambda s: c.call_power(weighted=weighted, dt=dt, stream=s)))
+                    c.prove_depth(depth, lambda s: c.call_power(weighted=weighted, dt=dt, stream=s), kind=bc.PW if weighted else bc.P))
     if (A, B, C, nt, depth) in DEEPEST_SHAPES and not weighted:
         # a NaN pair (the whole table in the slow class): its beam NaN in every pair of blocks, the others the model's
         nb = B // 2
@@ -129,7 +130,7 @@ def test_block_power_with_several_blocks_per_wave(gpu, oracle, case, record_prop
         assert np.all(np.isnan(got[:, :, nb]))
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_special_weights_and_delay_values_touch_their_beam_only"))
 def test_special_weights_and_delay_values_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     w1 = seeded_weights(B, A)
@@ -181,7 +182,7 @@ def test_special_weights_and_delay_values_touch_their_beam_only(gpu, oracle, cas
     assert same_bits(got[:, :, others], base[:, :, others]) is None
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_null_weights_equal_all_ones_weights"))
 def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     plain = c.power()
@@ -190,7 +191,7 @@ def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
     assert same_bits(plain, block_power(c.floats())) is None
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (37, 21, 4, 32), (192, 17, 2, 32), (130, 20, 3, 48)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_subnormal_squares_are_not_flushed"))
 def test_subnormal_squares_are_not_flushed(gpu, oracle, case, A, B, C, nt):
     """Per-beam scales that put |v|^2 of some beams below the smallest normal number: the block powers of those beams are
     sums of subnormal numbers and still the model's."""
@@ -210,7 +211,7 @@ def test_subnormal_squares_are_not_flushed(gpu, oracle, case, A, B, C, nt):
     assert same_bits(got, exp) is None, same_bits(got, exp)
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_block_power_at_an_address_that_is_4_byte_aligned_only"))
 def test_block_power_at_an_address_that_is_4_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
@@ -245,7 +246,7 @@ def test_block_power_at_an_address_that_is_4_byte_aligned_only(gpu, oracle, case
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 96), (64, 16, 5, 256), (256, 33, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_integration_is_the_ordered_sum"))
 def test_integration_is_the_ordered_sum(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
 
@@ -315,7 +316,7 @@ def test_integration_takes_every_unrolled_trip_and_tail_in_order(gpu, oracle, ca
     assert same_bits(c.read_power(), P) is None  # the blocks are as they were given
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_captured_calls_pick_up_new_samples_on_replay"))
 def test_captured_calls_pick_up_new_samples_on_replay(gpu, oracle, case, A, B, C, nt):
     """Both calls in one hipGraph (the process's default queue count is left as it is), replayed with new samples in the
     same buffer."""
@@ -367,7 +368,7 @@ def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle, cas
     assert same_bits(c.read_power(), ref) is None
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.POWER + "test_beam_slices_reproduce_the_full_call"))
 def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table
 

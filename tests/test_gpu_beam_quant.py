@@ -9,8 +9,9 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
+from helpers import bacc_cases as bc
 from helpers.bacc_case import DEEP_SHAPES, DEEPEST_SHAPES, T_COEFF, Case
-from helpers.beam_quant_model import (SHAPES, expected_with_clipping, expected_without_clipping, gains_with_clipping,
+from helpers.beam_quant_model import (expected_with_clipping, expected_without_clipping, gains_with_clipping,
                                       gains_without_clipping, quantise, seeded_weights)
 from helpers.device_buffers import closed_after
 
@@ -71,8 +72,8 @@ def same(got, exp):
     return f"{bad.size} of {got.size} bytes differ; first at {np.unravel_index(i, got.shape)}: got {got.ravel()[i]}, expected {exp.ravel()[i]}"
 
 
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt", SHAPES)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.QUANT + "test_quantised_output_is_the_model_of_the_float_output"))
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_quantised_output_is_the_model_of_the_float_output"))
 def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, case, A, B, C, nt, weighted):
     c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
@@ -88,12 +89,12 @@ def test_quantised_output_is_the_model_of_the_float_output(gpu, oracle, case, A,
             assert same(got0, exp) is None, (expected.__name__, dt, "no counters", same(got0, exp))
 
 
-@pytest.mark.parametrize("weighted", [False, True])
-@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+@pytest.mark.parametrize("weighted", bc.weighted_of(bc.QUANT + "test_quantised_output_with_several_blocks_per_wave"))
+@pytest.mark.parametrize("A,B,C,nt,depth", bc.shapes_of(bc.QUANT + "test_quantised_output_with_several_blocks_per_wave", raw=True))
 def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, case, record_property, A, B, C, nt, depth, weighted):
-    """SHAPES above give every wave one sample block (helpers/bacc_case.py says why); here a wave has a live second block
+    """The shapes above give every wave one sample block (helpers/bacc_cases.py says why); here a wave has a live second block
     in its pairs and several pairs, and its byte counters run across them.  One time form per shape, in turn.  The launch
-    itself, read from a captured graph, must prove `depth` blocks on some wave."""
+    itself, read from a captured graph, must prove `depth` blocks on some wave and be the one helpers/launch_forms.py plans."""
     c = case(A, B, C, nt)
     w = seeded_weights(B, A) if weighted else None
     dt = DT_COEFF if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 else None
@@ -107,7 +108,7 @@ def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, case, record
     got0, _ = c.q8(k, w, count=False, dt=dt)  # no counters: the same bytes
     assert same(got0, exp) is None, ("no counters", dt, same(got0, exp))
     record_property("gridDim.x, blockDim.x, blocks proven on some wave",
-                    c.prove_depth(depth, lambda s: c.call_q8(weighted=weighted, dt=dt, stream=s)))
+                    c.prove_depth(depth, lambda s: c.call_q8(weighted=weighted, dt=dt, stream=s), kind=bc.QW if weighted else bc.Q))
     if (A, B, C, nt, depth) in DEEPEST_SHAPES and not weighted:
         # a gain that clips every component: a lane's byte counters go as high as the geometry lets them (4 per pair of
         # blocks and register).  No component is 0 (asserted: the inputs are seeded), so every product is beyond 127
@@ -130,7 +131,7 @@ def test_quantised_output_with_several_blocks_per_wave(gpu, oracle, case, record
         assert np.array_equal(n, n_exp) and n[nb] == C * nt * 2 and np.all(got[:, :, nb] == -128), (n, n_exp)
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 5, 80), (64, 40, 3, 48), (130, 20, 3, 48), (256, 33, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_counters_add_up_and_stay_zero_without_clipping"))
 def test_counters_add_up_and_stay_zero_without_clipping(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     v = c.floats()
@@ -151,7 +152,7 @@ def test_counters_add_up_and_stay_zero_without_clipping(gpu, oracle, case, A, B,
     assert np.array_equal(n, start + n_exp)
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (48, 37, 2, 48), (130, 20, 2, 32), (256, 16, 2, 48)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_special_gains_weights_and_delay_values_touch_their_beam_only"))
 def test_special_gains_weights_and_delay_values_touch_their_beam_only(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     w1 = seeded_weights(B, A)
@@ -215,7 +216,7 @@ def test_special_gains_weights_and_delay_values_touch_their_beam_only(gpu, oracl
         assert np.array_equal(got[:, :, others], base[:, :, others]) and np.array_equal(n[others], n_base[others])
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 24, 3, 48), (200, 20, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_null_weights_equal_all_ones_weights"))
 def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     k = gains_with_clipping(c.floats())
@@ -224,7 +225,7 @@ def test_null_weights_equal_all_ones_weights(gpu, oracle, case, A, B, C, nt):
     assert np.array_equal(plain, ones) and np.array_equal(n_plain, n_ones) and n_plain.sum() > 0
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 48), (192, 17, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_int8_beams_at_an_address_that_is_8_byte_aligned_only"))
 def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case, A, B, C, nt):
     """d_beams_q8 has the float call's rule: 8-byte alignment is enough, 4 is refused."""
     from dc_sand_amd._lib import DCS_ERR_INVALID_ARGUMENT, DcsError
@@ -247,7 +248,7 @@ def test_int8_beams_at_an_address_that_is_8_byte_aligned_only(gpu, oracle, case,
     assert e.value.status == DCS_ERR_INVALID_ARGUMENT
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 40, 3, 64), (130, 20, 3, 64)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_captured_call_picks_up_new_gains_on_replay"))
 def test_captured_call_picks_up_new_gains_on_replay(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     w = seeded_weights(B, A)
@@ -293,7 +294,7 @@ def test_fp32_chain_form_is_refused_and_the_stream_stays_usable(gpu, oracle, cas
     assert np.array_equal(c.read_q8(), ref) and np.array_equal(c.counts(), n_ref)
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(65, 37, 3, 48), (64, 50, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.QUANT + "test_beam_slices_reproduce_the_full_call"))
 def test_beam_slices_reproduce_the_full_call(gpu, oracle, case, A, B, C, nt):
     from dc_sand_amd.beam_quant import BeamQuantGains
     from dc_sand_amd.sharding import beam_range, local_parameters, slice_table

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from helpers import hip_graph
-from helpers.bacc_case import ACC_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
+from helpers import bacc_cases as bc
+from helpers.bacc_case import FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import fused_model, normalise
 from helpers.device_buffers import closed_after
 
@@ -50,7 +51,7 @@ def fused_expected(case, w):
     return fused_model(case.coefficients(delta_times(case.bp, 0, case.nt)), case.ant, ghat=gh, scale=s)
 
 
-@pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.WEIGHTS + "test_unit_and_power_of_two_weights_on_the_matrix_cores"))
 def test_unit_and_power_of_two_weights_on_the_matrix_cores(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     base = c.run("acc")
@@ -77,7 +78,7 @@ def test_unit_and_power_of_two_weights_in_the_fused_kernel(gpu, oracle, case, A,
 
 
 @pytest.mark.parametrize("kind", ["acc", "fused"])
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 3, 64), (37, 21, 4, 48), (130, 20, 2, 32), (256, 17, 2, 16), (4, 40, 3, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.WEIGHTS + "test_flagged_antennas_contribute_nothing"))
 def test_flagged_antennas_contribute_nothing(gpu, oracle, case, kind, A, B, C, nt):
     rng = np.random.default_rng(A * B)
     c = case(A, B, C, nt)
@@ -132,8 +133,7 @@ def test_a_non_finite_weight_poisons_its_beam_only(gpu, oracle, case, kind):
         assert np.array_equal(bits(got[:, :, others]), bits(ref[:, :, others]))
 
 
-@pytest.mark.parametrize("A,B,C,nt", [(64, 16, 4, 64), (37, 21, 3, 48), (129, 33, 2, 32), (256, 64, 2, 32), (1, 1, 1, 16),
-                                      (64, 128, 2, 48), (192, 48, 2, 32)])
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.WEIGHTS + "test_random_weights_on_the_matrix_cores_within_the_bound"))
 def test_random_weights_on_the_matrix_cores_within_the_bound(gpu, oracle, case, A, B, C, nt):
     c = case(A, B, C, nt)
     w = random_weights(np.random.default_rng(A + 7 * B), B, A, zero_beam=B > 1)

@@ -20,7 +20,8 @@ import numpy as np
 import pytest
 
 from conftest import rand_table
-from helpers.bacc_case import ACC_SHAPES, DEEP_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
+from helpers import bacc_cases as bc
+from helpers.bacc_case import DEEP_SHAPES, FUSED_SHAPES, T_COEFF, Case, random_weights
 from helpers.beamformer_model import (acc_model, all_pairs_fast, first_difference, fused_model, normalise, weighted_coefficients)
 
 pytestmark = pytest.mark.gpu
@@ -166,7 +167,7 @@ def weights_for(A, B, seed):
 # several workgroups per (channel, beam group), the shapes that leave the XCD-grouped numbering's identity tail,
 # (64, 1024, 1, 32).  At these channel counts (64 at the most) the launcher splits the sample blocks until every wave has
 # ONE: no wave sees a second block, a second pair or a second round.  DEEP_SHAPES, below, are the shapes that do.
-@pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.EXACT + "test_matrix_core_form_is_the_fixed_point_model_bit_for_bit"))
 def test_matrix_core_form_is_the_fixed_point_model_bit_for_bit(gpu, oracle, A, B, C, nt):
     """By time index (unweighted and weighted) and by fDeltaTime value (unweighted and weighted)."""
     c = Exact(gpu, oracle, A, B, C, nt)
@@ -176,13 +177,14 @@ def test_matrix_core_form_is_the_fixed_point_model_bit_for_bit(gpu, oracle, A, B
     c.close()
 
 
-# ---- a'. the same form where a wave takes several sample blocks (helpers/bacc_case.py: DEEP_SHAPES): the live second block
+# ---- a'. the same form where a wave takes several sample blocks (helpers/bacc_cases.py: DEEP_SHAPES): the live second block
 # of a pair, the later pairs (kStaged's LDS offsets of later blocks, kChain's stepping of its two sample buffers and the
 # re-zeroed accumulators), waves of one workgroup with different block counts, the equal-shares split with several rounds
-@pytest.mark.parametrize("A,B,C,nt,depth", DEEP_SHAPES)
+@pytest.mark.parametrize("A,B,C,nt,depth", bc.shapes_of(bc.EXACT + "test_matrix_core_form_with_several_blocks_per_wave_bit_for_bit", raw=True))
 def test_matrix_core_form_with_several_blocks_per_wave_bit_for_bit(gpu, oracle, record_property, A, B, C, nt, depth):
     """Unweighted and weighted at one time form per shape (by index and by value in turn).  The launch itself, read from
-    a captured graph, must prove `depth` blocks on some wave: 3 is a live second pair."""
+    a captured graph, must prove `depth` blocks on some wave: 3 is a live second pair; and its grid, block and dynamic LDS
+    bytes must be those of helpers/launch_forms.py: bacc_plan, whose census tests/test_launch_forms.py takes."""
     c = Exact(gpu, oracle, A, B, C, nt)
     w = weights_for(A, B, A + 7 * B)
     if DEEP_SHAPES.index((A, B, C, nt, depth)) % 2 == 0:
@@ -191,7 +193,7 @@ def test_matrix_core_form_with_several_blocks_per_wave_bit_for_bit(gpu, oracle, 
         c.check_acc(weights=(None, w), dt_coeff=DT_COEFF)
     for weighted in (False, True):
         record_property(f"{'weighted' if weighted else 'unweighted'}: gridDim.x, blockDim.x, blocks proven on some wave",
-                        c.prove_depth(depth, lambda s: c.enqueue_floats(weighted, s)))
+                        c.prove_depth(depth, lambda s: c.enqueue_floats(weighted, s), kind=bc.FW if weighted else bc.F))
     c.close()
 
 
@@ -289,8 +291,7 @@ def full_scale_samples(pattern, C, nt, A):
     return x
 
 
-@pytest.mark.parametrize("kind,A,B,C,nt", [("acc", 64, 16, 2, 32), ("acc", 256, 17, 2, 32), ("acc", 200, 20, 2, 48),
-                                           ("fused", 48, 5, 2, 16), ("fused", 200, 3, 2, 16)])
+@pytest.mark.parametrize("kind,A,B,C,nt", bc.shapes_of(bc.EXACT + "test_full_scale_samples_against_unit_coefficients", raw=True))
 def test_full_scale_samples_against_unit_coefficients(gpu, oracle, kind, A, B, C, nt):
     """Samples all -128, all 127 and alternating by antenna, against the coefficients of a zero table (cos = 1, sin = 0)
     and of fPhase_rad = fp32(pi) and fp32(pi / 2) (cos = -1, sin = 1: digits +-127, 127, 127): the largest integer sums the
@@ -326,8 +327,7 @@ def one_hot_samples(C, A, value):
     return x
 
 
-@pytest.mark.parametrize("kind,A,B,C", [("acc", 37, 21, 2), ("acc", 130, 20, 1), ("acc", 256, 16, 1),
-                                        ("fused", 37, 5, 2), ("fused", 130, 3, 1)])
+@pytest.mark.parametrize("kind,A,B,C", bc.shapes_of(bc.EXACT + "test_one_antenna_at_a_time", raw=True))
 def test_one_antenna_at_a_time(gpu, oracle, kind, A, B, C):
     """One-hot samples: every output column is one antenna's (quantised) coefficient, times 1 and times -128 -- a wrong
     digit of a single antenna, or a permutation error of the contraction index, shows in the column of that antenna:

@@ -21,7 +21,9 @@ import pytest
 
 from conftest import rand_table
 from helpers import hip_graph
-from helpers.bacc_case import ACC_SHAPES, T_COEFF, Case
+from helpers import bacc_cases as bc
+from helpers import launch_forms as lf
+from helpers.bacc_case import T_COEFF, Case, plan_of
 from helpers.device_buffers import DeviceBuffers, closed_after
 from helpers.every_element import compare_every_element
 from helpers.parity_case import (GeneratorCase, Tensor, accumulated_bound, check_1ulp, check_exact_sum, check_float_reading, fused_bound,
@@ -943,8 +945,8 @@ def test_autotune_measures_a_large_shape_once(gpu, generator, oracle):
 
 # ---- beamformer with coefficient reuse on the matrix cores ("general version"): the verifier's beamformer with
 # ---- the coefficient of ONE time held (BeamformerCoefficientTest.cu:363-414); bounds: accumulated_bound, check_exact_sum
-@pytest.mark.parametrize("math_mode", [0, 8])
-@pytest.mark.parametrize("A,B,C,nt", ACC_SHAPES)
+@pytest.mark.parametrize("math_mode", bc.math_modes_of(bc.PARITY + "test_beamform_accumulated_on_the_matrix_cores"))
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.PARITY + "test_beamform_accumulated_on_the_matrix_cores"))
 def test_beamform_accumulated_on_the_matrix_cores(case, oracle, A, B, C, nt, math_mode):
     """dcs_bf_beamform_accumulated: the coefficients of ONE time applied to nt samples as two real contractions over the
     antennas on the matrix cores, against the verifier's beamformer with the coefficient held.  Both forms: the default
@@ -954,7 +956,8 @@ def test_beamform_accumulated_on_the_matrix_cores(case, oracle, A, B, C, nt, mat
     ACC_SHAPES cover every beam-tile count (1, 2, 4 per workgroup: coefficients shared by 4, 2, 1 waves), ragged antennas /
     beams / sample blocks, odd block counts and several workgroups per (channel, beam group) -- at these channel counts the
     launcher splits the blocks until every wave has ONE, whatever their number: what a wave does with several is held, bit
-    for bit, at the DEEP_SHAPES of helpers/bacc_case.py (tests/test_gpu_beamformer_exact.py, _beam_quant.py, _beam_power.py) --, 1-4
+    for bit, at the DEEP_SHAPES of helpers/bacc_cases.py (tests/test_gpu_beamformer_exact.py, _beam_quant.py, _beam_power.py), and for
+    the fp32 form by test_fp32_chain_form_with_several_blocks_per_wave below --, 1-4
     64-antenna chunks (whole and partial) and the 256-antenna limit -- above 64 antennas the kChain form (round 3: the
     coefficients in LDS, the integer sums chained through the chunks by the matrix instruction's accumulator), with fewer
     sample blocks than waves (waves that only make their chunk's coefficients), odd pair counts and several workgroups
@@ -1018,8 +1021,8 @@ def test_beamform_accumulated_seeded_fuzz(case, oracle):
             check_exact_sum(c, got, dt, tag)
 
 
-@pytest.mark.parametrize("math_mode", [0, 8])
-@pytest.mark.parametrize("A,B,C,nt", [(20, 18, 3, 32), (64, 16, 2, 64), (130, 20, 2, 32), (256, 5, 1, 16)])
+@pytest.mark.parametrize("math_mode", bc.math_modes_of(bc.PARITY + "test_beamform_accumulated_non_finite_coefficients"))
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.PARITY + "test_beamform_accumulated_non_finite_coefficients"))
 def test_beamform_accumulated_non_finite_coefficients(case, oracle, A, B, C, nt, math_mode):
     """An infinite or NaN delay value makes that pair's coefficient NaN and, with it, every sample of its beam (the plane
     concerned) in the verifier's sum: NaN * 0 = NaN.  Both forms give NaN in exactly those places -- the fixed-point form,
@@ -1040,7 +1043,8 @@ def test_beamform_accumulated_non_finite_coefficients(case, oracle, A, B, C, nt,
     assert np.abs(np.where(fin, got - exp, 0)).max() <= accumulated_bound(A)
 
 
-@pytest.mark.parametrize("A,B,C,nt,depth", [(64, 16, 1280, 256, 4), (130, 20, 640, 256, 4)])
+@pytest.mark.parametrize("A,B,C,nt,depth",
+                         bc.shapes_of(bc.PARITY + "test_beamform_accumulated_non_finite_coefficients_in_every_pair_of_blocks", raw=True))
 def test_beamform_accumulated_non_finite_coefficients_in_every_pair_of_blocks(case, oracle, record_property, A, B, C, nt, depth):
     """The shapes above give every wave one sample block.  Here the launch fills the chip, so a wave has four blocks (the
     launch geometry, read from a captured graph, must prove it): the NaN rows are marked in the first pair of blocks and
@@ -1056,7 +1060,41 @@ def test_beamform_accumulated_non_finite_coefficients_in_every_pair_of_blocks(ca
     got = c.floats(dt=float(dt))
     assert np.array_equal(nan, np.isnan(got)), np.argwhere(nan != np.isnan(got))[:4]
     assert np.abs(np.where(nan, 0, got - exp)).max() <= accumulated_bound(A)
-    record_property("gridDim.x, blockDim.x, blocks proven on some wave", c.prove_depth(depth, lambda s: c.enqueue_floats(False, s)))
+    record_property("gridDim.x, blockDim.x, blocks proven on some wave", c.prove_depth(depth, lambda s: c.enqueue_floats(False, s), kind=bc.F))
+
+
+@pytest.mark.parametrize("A,B,C,nt", bc.shapes_of(bc.PARITY + "test_fp32_chain_form_with_several_blocks_per_wave"))
+def test_fp32_chain_form_with_several_blocks_per_wave(case, oracle, record_property, A, B, C, nt):
+    """The fp32 fma chain (math_mode 8) where a wave takes a second sample block.  Its launcher splits a workgroup's blocks
+    until 4096 workgroups are launched, not 1280, so every other shape of this file leaves its waves ONE block: the stores of
+    a later block (tt0 + blk * TPR + slot), the accumulators zeroed behind a block's store and the samples requested one
+    stage ahead across a block boundary run here alone -- with 1, 2 and 4 beam tiles, one chunk of antennas, three with a
+    partial last one and two whole ones (helpers/bacc_cases.py: FP32_DEEP_SHAPES; tests/test_launch_forms.py holds the list
+    to these classes).  Against the verifier's beamformer with the coefficient held, at accumulated_bound(A) and at the
+    reference's own 1e-1, every output finite, the canary behind the tensor untouched (read_beams).  The captured launch must
+    prove two blocks on some wave and be the plan's.  Then samples in which every block of a channel repeats block 0: every
+    block's floats must be block 0's, bit for bit -- and block 0's those of the first call -- which is sharp where the
+    bound is not: a sum that starts from the previous block's, or a register set of the wrong stage."""
+    from dc_sand_amd.generator import delta_times
+
+    plan = plan_of((A, B, C, nt), bc.F8)
+    assert lf.bacc_is_deep(plan), plan
+    c = case(A, B, C, nt)
+    dt = delta_times(c.bp, T_COEFF, 1)[0]
+    exp = oracle.beamform_accumulated(c.op, c.table, dt, nt, c.ant)
+    c.g.set_tuning(math_mode=8)
+    got = c.floats()
+    assert np.all(np.isfinite(got))
+    diff = np.abs(got - exp)
+    print(f"(A, B, C, nt) = {(A, B, C, nt)}: max |got - oracle| {diff.max():.3e}, bound {accumulated_bound(A):.3e}")
+    assert diff.max() <= accumulated_bound(A), diff.max()
+    assert oracle.compare(got, exp, 1e-1) == -1
+    record_property("gridDim.x, blockDim.x, blocks proven on some wave", c.prove_depth(2, lambda s: c.enqueue_floats(False, s), kind=bc.F8))
+    c.set_ant(np.ascontiguousarray(np.broadcast_to(c.ant[:, :1], c.ant.shape)))
+    rep = c.floats().view(np.uint32)
+    assert np.array_equal(rep[:, 0], got.view(np.uint32)[:, 0])
+    bad = np.argwhere(rep != rep[:, :1])
+    assert bad.size == 0, f"{bad.shape[0]} words differ from block 0's; first at [c][block][beam][sample][re, im] = {bad[0]}"
 
 
 @pytest.mark.parametrize("A,B", [(64, 16), (130, 20)])
