@@ -11,12 +11,12 @@ LIB     := dc_sand_amd/csrc/libdcs_beamformer.so
 # the companion libraries (dc_sand_amd/companions.py): each forwards to the product library through the table at the head of
 # a context or a stream (bf_ctx_ext.h, bf_stream_ext.h); libdcs_NAME.so is built from bf_NAME.cpp
 COMPANIONS := $(addprefix dc_sand_amd/csrc/libdcs_,$(addsuffix .so,stream_staging beam_weights beam_quant beam_power incoherent_beam \
-              filterbank beam_complex beam_complex_quant stokes dedisperse single_pulse correlator ddc candidates channeliser rfi))
+              filterbank beam_complex beam_complex_quant stokes dedisperse single_pulse correlator ddc candidates channeliser rfi fold))
 SRCS    := dc_sand_amd/csrc/bf_kernels.hip dc_sand_amd/csrc/bf_beamform_mfma.hip dc_sand_amd/csrc/bf_integrate.hip \
            dc_sand_amd/csrc/bf_incoherent.hip \
            dc_sand_amd/csrc/bf_filterbank.hip dc_sand_amd/csrc/bf_stokes.hip dc_sand_amd/csrc/bf_dedisperse.hip \
            dc_sand_amd/csrc/bf_single_pulse.hip dc_sand_amd/csrc/bf_correlator.hip dc_sand_amd/csrc/bf_ddc.hip \
-           dc_sand_amd/csrc/bf_candidates.hip dc_sand_amd/csrc/bf_channeliser.hip dc_sand_amd/csrc/bf_rfi.hip \
+           dc_sand_amd/csrc/bf_candidates.hip dc_sand_amd/csrc/bf_channeliser.hip dc_sand_amd/csrc/bf_rfi.hip dc_sand_amd/csrc/bf_fold.hip \
            dc_sand_amd/csrc/bf_capi.hip \
            dc_sand_amd/csrc/bf_capi_generate.hip \
            dc_sand_amd/csrc/bf_capi_beamform.hip dc_sand_amd/csrc/bf_capi_stream.hip
@@ -28,7 +28,7 @@ HDRS    := dc_sand_amd/csrc/bf_kernels.h dc_sand_amd/csrc/bf_math.h dc_sand_amd/
            include/dcs_beam_power.h include/dcs_incoherent_beam.h include/dcs_filterbank.h include/dcs_beam_complex.h \
            include/dcs_beam_complex_quant.h include/dcs_stokes.h include/dcs_dedisperse.h \
            include/dcs_single_pulse.h include/dcs_correlator.h include/dcs_ddc.h \
-           include/dcs_candidates.h include/dcs_channeliser.h include/dcs_rfi.h
+           include/dcs_candidates.h include/dcs_channeliser.h include/dcs_rfi.h include/dcs_fold.h
 # -ffp-contract=off is part of the numerical contract; keep in step with dc_sand_amd/build.py
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -fvisibility=hidden \
             -Wall -Wextra -Wno-unused-parameter

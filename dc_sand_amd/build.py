@@ -23,7 +23,7 @@ from .companions import COMPANIONS
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libdcs_beamformer.so"
 SOURCES = ["bf_kernels.hip", "bf_beamform_mfma.hip", "bf_integrate.hip", "bf_incoherent.hip", "bf_filterbank.hip", "bf_stokes.hip", "bf_dedisperse.hip",
-           "bf_single_pulse.hip", "bf_correlator.hip", "bf_ddc.hip", "bf_candidates.hip", "bf_channeliser.hip", "bf_rfi.hip", "bf_capi.hip",
+           "bf_single_pulse.hip", "bf_correlator.hip", "bf_ddc.hip", "bf_candidates.hip", "bf_channeliser.hip", "bf_rfi.hip", "bf_fold.hip", "bf_capi.hip",
            "bf_capi_generate.hip", "bf_capi_beamform.hip", "bf_capi_stream.hip"]
 HEADERS = ["bf_kernels.h", "bf_math.h", "bf_device.h", "bf_stream_ext.h", "bf_ctx_ext.h", "bf_arg_checks.h", "bf_host.h", "bf_beamform_kernel.inc",
            "bf_beamform_i8_kernel.inc", "../../include/dcs_beamformer.h",

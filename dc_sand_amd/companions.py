@@ -131,4 +131,13 @@ COMPANIONS = {
          [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, _VP, _VP, _VP, c_uint8, _VP, c_size_t, c_uint64,
           c_uint64, _VP, _VP]),
     ]),
+    # the pulsar folder: the 8-bit filterbanks folded at a phase model into exact uint32 profiles per sub-integration, channel and
+    # bin, with their hits, and the profiles' sums over frequency
+    "fold": Companion("dcs_fold.h", "bf_fold.cpp", "libdcs_fold.so", [
+        ("dcs_bf_fold_q8", c_int,
+         [_VP, _VP, c_size_t, c_uint64, c_uint64, c_uint32, c_uint32, c_uint32, c_uint32, _VP, c_size_t, _VP, c_size_t, c_uint32, _VP,
+          c_uint32, _VP, c_size_t, _VP, c_size_t, c_uint64, c_uint64, c_uint32, _VP]),
+        ("dcs_bf_fold_scrunch", c_int,
+         [_VP, _VP, c_size_t, c_uint32, c_uint64, c_uint64, c_uint32, c_uint32, _VP, c_size_t, c_uint32, _VP]),
+    ]),
 }

@@ -15,6 +15,7 @@
 #include "../../include/dcs_ddc.h"        // dcs_ddc_band
 #include "../../include/dcs_dedisperse.h" // dcs_bf_band
 #include "../../include/dcs_filterbank.h" // DCS_FB_DESCENDING
+#include "../../include/dcs_fold.h"       // dcs_bf_fold_model
 #include "../../include/dcs_rfi.h"        // dcs_bf_rfi_thresholds
 #include "../../include/dcs_stokes.h"     // DCS_BF_STOKES_I, DCS_BF_STOKES_IQUV
 
@@ -316,6 +317,28 @@ inline int rfi_clean_q8_args(dcs_bf_context *c, const uint8_t *d_filterbank, uin
                       rfi_window_ok(nr_blocks, block_len, nr_beams) &&
                       fits(first_spectrum, (uint64_t)nr_blocks * block_len, in_spectra) &&
                       fits(first_out, (uint64_t)nr_blocks * block_len, out_spectra));
+}
+
+// include/dcs_fold.h: nr_subints sub-integrations of 1 .. 2^24 spectra (no profile word wraps), 1 .. 1024 phase bins, one model
+// row per beams_per_model beams.  The window nr_subints * subint_len + max_delay is below 2^57: no sum wraps before fits().  The
+// buffer sizes are the _impl's, with those that need the context's C
+inline int fold_q8_args(dcs_bf_context *c, const uint8_t *d_filterbank, uint64_t in_spectra, uint64_t first_spectrum, uint32_t subint_len,
+                        uint32_t nr_subints, uint32_t nr_beams, uint32_t beams_per_model, const dcs_bf_fold_model *d_models,
+                        const int32_t *d_delays, uint32_t max_delay, uint32_t nbin, const uint32_t *d_profiles, const uint32_t *d_hits,
+                        uint64_t out_subints, uint64_t first_subint, uint32_t accumulate)
+{
+    return arg_status(c && d_filterbank && d_models && d_profiles && aligned(d_filterbank, 16u) && aligned(d_models, 8u) &&
+                      aligned(d_delays, 4u) && aligned(d_profiles, 4u) && aligned(d_hits, 4u) && nr_beams != 0u &&
+                      beams_per_model != 0u && nr_beams % beams_per_model == 0u && nbin >= 1u && nbin <= 1024u && subint_len >= 1u &&
+                      subint_len <= (1u << 24) && max_delay <= 0x7ffffffeu &&
+                      fits(first_spectrum, (uint64_t)nr_subints * subint_len + max_delay, in_spectra) &&
+                      fits(first_subint, nr_subints, out_subints) && accumulate <= 1u);
+}
+inline int fold_scrunch_args(dcs_bf_context *c, const uint32_t *d_profiles, uint32_t nr_beams, uint64_t out_subints, uint64_t first_subint,
+                             uint32_t nr_subints, uint32_t nbin, const uint64_t *d_scrunched, uint32_t accumulate)
+{
+    return arg_status(c && d_profiles && d_scrunched && aligned(d_profiles, 4u) && aligned(d_scrunched, 8u) && nr_beams != 0u &&
+                      nbin >= 1u && nbin <= 1024u && fits(first_subint, nr_subints, out_subints) && accumulate <= 1u);
 }
 
 #endif // BF_ARG_CHECKS_H

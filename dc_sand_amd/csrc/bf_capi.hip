@@ -102,7 +102,8 @@ const bf_ctx_ext_ops kWeightsOps = {BF_CTX_EXT_VERSION, generate_and_beamform_we
                                     ddc_tap_digits_impl, ddc_impl,
                                     find_candidates_impl,
                                     channelise_impl, channelise_q8_impl,
-                                    rfi_moments_impl, rfi_flags_impl, rfi_clean_q8_impl};
+                                    rfi_moments_impl, rfi_flags_impl, rfi_clean_q8_impl,
+                                    fold_q8_impl, fold_scrunch_impl};
 }
 
 extern "C" {
@@ -335,6 +336,7 @@ int dcs_bf_create(const dcs_bf_params *p, dcs_bf_context **out)
         if ((st = (int)bf_warm_module_candidates()) != 0) break;
         if ((st = (int)bf_warm_module_channeliser()) != 0) break;
         if ((st = (int)bf_warm_module_rfi()) != 0) break;
+        if ((st = (int)bf_warm_module_fold()) != 0) break;
         const size_t tb = (size_t)c->n_pairs * sizeof(dcs_delay_vals);
         if ((st = (int)hipMalloc((void **)&c->d_table[0], tb)) != 0) break;
         if ((st = (int)hipMalloc((void **)&c->d_table[1], tb)) != 0) break;

@@ -43,7 +43,9 @@
 // hands a foreign version above 13).
 // 16: rfi_moments, rfi_flags, rfi_clean_q8 appended (tests/test_host_abi_rfi.py hands its companion 1, 14 and 15; no older test
 // hands a foreign version above 14).
-#define BF_CTX_EXT_VERSION 16u
+// 17: fold_q8, fold_scrunch appended (tests/test_host_abi_fold.py hands its companion 1, 15 and 16; no older test hands a
+// foreign version above 15).
+#define BF_CTX_EXT_VERSION 17u
 
 struct bf_ctx_ext_ops {
     uint32_t version; // BF_CTX_EXT_VERSION
@@ -133,6 +135,11 @@ struct bf_ctx_ext_ops {
     decltype(dcs_bf_rfi_moments) *rfi_moments;
     decltype(dcs_bf_rfi_flags) *rfi_flags;
     decltype(dcs_bf_rfi_clean_q8) *rfi_clean_q8;
+    // the pulsar folder (include/dcs_fold.h): filterbanks uint8 [nr_beams][in_spectra][C], phase models [P][nr_subints] and delays
+    // int32 [P][C] (nullptr = none) -> profiles uint32 [nr_beams][out_subints][C][nbin] and hits uint32 [P][out_subints][nbin]
+    // (nullptr = not wanted); profiles -> their sums over C, uint64 [nr_beams][out_subints][nbin]
+    decltype(dcs_bf_fold_q8) *fold_q8;
+    decltype(dcs_bf_fold_scrunch) *fold_scrunch;
 };
 
 // the first member of struct dcs_bf_context

@@ -188,6 +188,8 @@ decltype(dcs_bf_channelise_q8) channelise_q8_impl;
 decltype(dcs_bf_rfi_moments) rfi_moments_impl;                               // bf_rfi.hip
 decltype(dcs_bf_rfi_flags) rfi_flags_impl;
 decltype(dcs_bf_rfi_clean_q8) rfi_clean_q8_impl;
+decltype(dcs_bf_fold_q8) fold_q8_impl;                                       // bf_fold.hip
+decltype(dcs_bf_fold_scrunch) fold_scrunch_impl;
 
 } // namespace bf_host
 

@@ -223,6 +223,7 @@ hipError_t bf_warm_module_ddc();
 hipError_t bf_warm_module_candidates();
 hipError_t bf_warm_module_channeliser();
 hipError_t bf_warm_module_rfi();
+hipError_t bf_warm_module_fold();
 hipError_t bf_warm_module_filterbank();
 
 // One coefficient per lane, one time step (reference kernel a1's shape).

@@ -259,6 +259,22 @@ def rfi_counts_bytes(nr_beams: int) -> int:
     return int(nr_beams) * 12
 
 
+def fold_profiles_bytes(params: BeamformerParameters, nr_beams: int, out_subints: int, nbin: int) -> int:
+    """Size of the profiles ``uint32 [nr_beams][out_subints][C][nbin]`` of :meth:`SteeringCoefficientGenerator.fold_q8`."""
+    return int(nr_beams) * int(out_subints) * int(params.NR_CHANNELS) * int(nbin) * 4
+
+
+def fold_hits_bytes(nr_models: int, out_subints: int, nbin: int) -> int:
+    """Size of the hits ``uint32 [nr_models][out_subints][nbin]`` of :meth:`SteeringCoefficientGenerator.fold_q8`;
+    ``nr_models`` is ``nr_beams // beams_per_model``."""
+    return int(nr_models) * int(out_subints) * int(nbin) * 4
+
+
+def fold_scrunched_bytes(nr_beams: int, out_subints: int, nbin: int) -> int:
+    """Size of the plane ``uint64 [nr_beams][out_subints][nbin]`` of :meth:`SteeringCoefficientGenerator.fold_scrunch`."""
+    return int(nr_beams) * int(out_subints) * int(nbin) * 8
+
+
 @dataclasses.dataclass(frozen=True)
 class RfiThresholds:
     """``dcs_bf_rfi_thresholds`` (include/dcs_rfi.h): an element is an outlier iff its distance from the lower median is
@@ -690,6 +706,37 @@ class SteeringCoefficientGenerator:
                                      _p_or_null(d_channel_mask), _p_or_null(d_spectrum_flags), int(fill), _p(d_out),
                                      int(out_bytes), int(out_spectra), int(first_out), _p_or_null(d_replaced), _s(stream)),
               "dcs_bf_rfi_clean_q8")
+
+    # -- the pulsar folder on the same filterbanks (include/dcs_fold.h, companion library libdcs_fold.so): d_models a device
+    #    dcs_bf_fold_model [nr_beams // beams_per_model][nr_subints] array (dc_sand_amd.fold.fold_models makes a row)
+    def fold_q8(self, d_filterbank, filterbank_bytes: int, in_spectra: int, first_spectrum: int, subint_len: int, nr_subints: int,
+                nr_beams: int, d_models, models_bytes: int, nbin: int, d_profiles, profiles_bytes: int, out_subints: int,
+                first_subint: int = 0, beams_per_model: int = 1, d_delays=None, delays_bytes: int = 0, max_delay: int = 0,
+                d_channel_mask=None, d_hits=None, hits_bytes: int = 0, accumulate: bool = False, stream=None) -> None:
+        """Per beam ``b`` and sub-integration ``s < nr_subints``: word ``[b][first_subint + s][c][j]`` of the profiles
+        (:func:`fold_profiles_bytes`) becomes (``accumulate``: grows by) the exact sum of the filterbank bytes
+        ``[first_spectrum + s * subint_len + k + d_delays[p][c]][c]`` over the ``k < subint_len`` whose phase under model
+        ``[p][s]``, ``p = b // beams_per_model``, falls into bin ``j`` of ``nbin``; ``d_hits`` (``None``, or
+        :func:`fold_hits_bytes`) counts those ``k``.  ``d_delays``: ``None``, or a device ``int32 [P][C]`` array as
+        :meth:`dm_delays` makes it; entries outside ``[0, max_delay]`` and the columns whose byte of ``d_channel_mask``
+        (``None``, or ``uint8 [C]``) is zero fold to zero."""
+        fl = _lib.companion("fold")
+        check(fl.dcs_bf_fold_q8(c_void_p(self._h), _p(d_filterbank), int(filterbank_bytes), int(in_spectra), int(first_spectrum),
+                                int(subint_len), int(nr_subints), int(nr_beams), int(beams_per_model), _p(d_models),
+                                int(models_bytes), _p_or_null(d_delays), int(delays_bytes), int(max_delay),
+                                _p_or_null(d_channel_mask), int(nbin), _p(d_profiles), int(profiles_bytes), _p_or_null(d_hits),
+                                int(hits_bytes), int(out_subints), int(first_subint), int(bool(accumulate)), _s(stream)),
+              "dcs_bf_fold_q8")
+
+    def fold_scrunch(self, d_profiles, profiles_bytes: int, nr_beams: int, out_subints: int, first_subint: int, nr_subints: int,
+                     nbin: int, d_scrunched, scrunched_bytes: int, accumulate: bool = False, stream=None) -> None:
+        """Sub-integrations ``first_subint .. first_subint + nr_subints - 1`` of the profiles summed over the channels into
+        the same sub-integrations of ``d_scrunched`` (:func:`fold_scrunched_bytes`), exactly, in 64 bits; ``accumulate`` adds."""
+        fl = _lib.companion("fold")
+        check(fl.dcs_bf_fold_scrunch(c_void_p(self._h), _p(d_profiles), int(profiles_bytes), int(nr_beams), int(out_subints),
+                                     int(first_subint), int(nr_subints), int(nbin), _p(d_scrunched), int(scrunched_bytes),
+                                     int(bool(accumulate)), _s(stream)),
+              "dcs_bf_fold_scrunch")
 
     # -- the single-pulse search on those planes (include/dcs_single_pulse.h, companion library libdcs_single_pulse.so):
     #    d_widths a device uint32 [nr_widths] array of boxcar widths, d_peaks a device uint32

@@ -68,6 +68,11 @@ the tests use.  The store-only studies need the probes build (include/dcs_probes
         turn in one process over two copies of the input: each time, its bytes' floor at 8 TB/s, its ratio to the yardstick, and
         the whole stage as a share of the dedispersion of the same spectra; --trace: a few launches only, for a counter run
                                                                                     -> profiles/r19_rfi.md
+    python tools/measure.py fold [--rounds 5] [--shapes BEAMSxSPECTRAxCHANNELS,...] [--nbins 64,256,1024] [--subint-len 8192] [--dm 100]
+        the pulsar folder per shape and nbin, with and without hits, beside fold_scrunch and dedisperse_q8 with one DM over the
+        same window, in turn in one process over two copies of the input: each time, the fold's bytes' floor at 8 TB/s (window
+        read once, profiles written once) and its ratio to the dedispersion; --trace: a few launches only
+                                                                                    -> profiles/r20_fold.md
     python tools/measure.py fbank [--rounds 5] [--trace]
         8-bit search filterbanks: the quantiser and the sums against the read probe over the same input, alternating, in one
         process, and what the three calls add to a detected-beam pipeline; --trace as for incoh -> profiles/r08_filterbank.md
@@ -1316,6 +1321,91 @@ def cmd_rfi(args):
     print(json.dumps({"rfi": rows}), flush=True)
 
 
+def cmd_fold(args):
+    """The pulsar folder (include/dcs_fold.h).  Per (shape, nbin): fold_q8 with hits on noise-like bytes -- BEAMS beams, CHANNELS
+    channels, SPECTRA spectra cut into sub-integrations of ``--subint-len``, each channel read at the delay of a DM of
+    ``--dm`` -- beside fold_q8 without hits, fold_scrunch, and dedisperse_q8 with that one DM over the same window (existing code
+    that reads the same bytes through the same gather), in turn ``--rounds`` times in one process.  The fold and the
+    dedispersion rotate over two copies of the input, so that no call finds its bytes in the Infinity Cache.  Floor: the window
+    read once plus the profiles written once at 8 TB/s."""
+    from dc_sand_amd.fold import fold_models
+    from dc_sand_amd.generator import (dm_delays_bytes, dm_time_bytes, filterbank_bytes, fold_hits_bytes, fold_profiles_bytes,
+                                       fold_scrunched_bytes)
+
+    rows = []
+    for text in args.shapes.split(","):
+        B, T, C = (int(x) for x in text.lower().split("x"))
+        L = min(args.subint_len, T)
+        S = T // L
+        assert S * L == T
+        bp = BeamformerParameters(NR_CHANNELS=C, NR_STATIONS=1, NR_BEAMS=1)
+        g = SteeringCoefficientGenerator(bp)
+        band, dms = (1500.0, -300.0 / C, 64e-6), np.full(B, args.dm, np.float64)
+        tb = dm_delays_bytes(bp, B)
+        d_dms, d_delays = device.mem_alloc(dms.nbytes), device.mem_alloc(tb)
+        device.memcpy_htod(d_dms, dms)
+        g.dm_delays(*band, d_dms, B, d_delays, tb)
+        device.synchronize()
+        table = np.empty((B, C), np.int32)
+        device.memcpy_dtoh(table, d_delays)
+        max_delay = int(table.max())
+        in_spectra = T + max_delay
+        fb = filterbank_bytes(bp, B, in_spectra)
+        bufs = [device.mem_alloc(fb) for _ in range(2)]
+        for d in bufs:
+            _noise(d, fb)
+        models = np.stack([fold_models(173.6879 + 0.01 * p, -1.7e-15, 0.125 * p, band[2], L, S) for p in range(B)])
+        d_models = device.mem_alloc(models.nbytes)
+        device.memcpy_htod(d_models, np.ascontiguousarray(models))
+        pb1 = dm_time_bytes(B, 1, T)
+        d_plane = device.mem_alloc(pb1)
+        turn = [0]
+
+        def buf():
+            turn[0] ^= 1
+            return bufs[turn[0]]
+        dedisp = lambda: g.dedisperse_q8(buf(), fb, in_spectra, 0, T, B, d_delays, 1, max_delay, d_plane, pb1, T)  # noqa: E731
+        for nbin in (int(x) for x in args.nbins.split(",")):
+            pb, hb, sb = fold_profiles_bytes(bp, B, S, nbin), fold_hits_bytes(B, S, nbin), fold_scrunched_bytes(B, S, nbin)
+            d_p, d_h, d_s = device.mem_alloc(pb), device.mem_alloc(hb), device.mem_alloc(sb)
+            kw = dict(d_delays=d_delays, delays_bytes=tb, max_delay=max_delay)
+            fold = lambda: g.fold_q8(buf(), fb, in_spectra, 0, L, S, B, d_models, models.nbytes, nbin, d_p, pb, S, d_hits=d_h,  # noqa: E731
+                                     hits_bytes=hb, **kw)
+            fold_only = lambda: g.fold_q8(buf(), fb, in_spectra, 0, L, S, B, d_models, models.nbytes, nbin, d_p, pb, S, **kw)  # noqa: E731
+            scrunch = lambda: g.fold_scrunch(d_p, pb, B, S, 0, S, nbin, d_s, sb)  # noqa: E731
+            for fn in (fold, fold_only, scrunch, dedisp):
+                fn()
+            device.synchronize()
+            if args.trace:
+                for fn in (fold, scrunch, dedisp) * 3:
+                    fn()
+                device.synchronize()
+            else:
+                t = {name: [] for name in ("fold", "fold_only", "scrunch", "dedisperse")}
+                for _ in range(args.rounds):
+                    t["fold"].append(per_launch_ms(fold))
+                    t["dedisperse"].append(per_launch_ms(dedisp))
+                    t["fold_only"].append(per_launch_ms(fold_only))
+                    t["scrunch"].append(per_launch_ms(scrunch))
+                med = {name: float(np.median(x)) for name, x in t.items()}
+                floor_us = (B * in_spectra * C + pb) / 8e12 * 1e6
+                row = {"shape": f"B={B} T={T} C={C} subint_len={L} nr_subints={S} nbin={nbin}", "max_delay": max_delay,
+                       "window_MiB": (B * in_spectra * C) >> 20, "profiles_MiB": pb >> 20,
+                       "fold_us": round(med["fold"] * 1e3, 1), "fold_without_hits_us": round(med["fold_only"] * 1e3, 1),
+                       "floor_us": round(floor_us, 1), "fold_share_of_floor": round(floor_us / (med["fold"] * 1e3), 3),
+                       "dedisperse_one_dm_us": round(med["dedisperse"] * 1e3, 1),
+                       "fold_over_dedisperse": round(med["fold"] / med["dedisperse"], 3), "scrunch_us": round(med["scrunch"] * 1e3, 1),
+                       "spreads": {k: round(max(v) / min(v) - 1.0, 4) for k, v in t.items()}}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            for d in (d_p, d_h, d_s):
+                d.free()
+        g.close()
+        for d in bufs + [d_dms, d_delays, d_models, d_plane]:
+            d.free()
+    print(json.dumps({"fold": rows}), flush=True)
+
+
 def _spectra(d_x, C, B, T):
     """Realistic float spectra [T][C][B]: x = m_cb (1 + 0.25 g), m over 2^-20 .. 2^20 (eight seeded slices repeated)."""
     rng = np.random.default_rng(0xFB)
@@ -1772,6 +1862,13 @@ def main():
     p.add_argument("--shapes", default="4x16384x4096x256,4x16384x4100x256", help="BEAMSxSPECTRAxCHANNELSxBLOCK_LEN, comma-separated")
     p.add_argument("--nr-dm", type=int, default=512, help="DMs of the dedispersion that the stage is compared with")
     p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
+    p = sub.add_parser("fold")
+    p.add_argument("--rounds", type=int, default=5, help="alternations of the fold, the one-DM dedispersion and the scrunch per shape and nbin")
+    p.add_argument("--shapes", default="4x131072x4096", help="BEAMSxSPECTRAxCHANNELS, comma-separated")
+    p.add_argument("--nbins", default="64,256,1024", help="phase bins, comma-separated")
+    p.add_argument("--subint-len", type=int, default=8192, help="spectra of a sub-integration (it divides SPECTRA)")
+    p.add_argument("--dm", type=float, default=100.0, help="the DM of the delay row of every beam")
+    p.add_argument("--trace", action="store_true", help="a few launches only (a counter run of its own)")
     p = sub.add_parser("fbank")
     p.add_argument("--rounds", type=int, default=5, help="alternations of the quantiser, the read probe and the sums per shape")
     p.add_argument("--trace", action="store_true", help="a few launches of the new kernels and the probe only (kernel trace)")
@@ -1816,7 +1913,7 @@ def main():
     device.require_device()
     device.set_device(0)
     print("device:", device.device_name(0), flush=True)
-    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "channeliser": cmd_channeliser, "rfi": cmd_rfi, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
+    {"geometry": cmd_geometry, "refshape": cmd_refshape, "fp16": cmd_fp16, "fused": cmd_fused, "bfweights": cmd_bfweights, "bfq8": cmd_bfq8, "bfpower": cmd_bfpower, "bfcomplex": cmd_bfcomplex, "bfcq8": cmd_bfcq8, "incoh": cmd_incoh, "stokes": cmd_stokes, "dedisperse": cmd_dedisperse, "single_pulse": cmd_single_pulse, "candidates": cmd_candidates, "correlator": cmd_correlator, "ddc": cmd_ddc, "channeliser": cmd_channeliser, "rfi": cmd_rfi, "fold": cmd_fold, "fbank": cmd_fbank, "mfma": cmd_mfma, "copy": cmd_copy, "bfacc": cmd_bfacc, "bfreplay": cmd_bfreplay, "stream": cmd_stream, "pmc": cmd_pmc,
      "sustained": cmd_sustained, "stores": cmd_stores, "sincos": cmd_sincos}[args.cmd](args)
 
 
